@@ -16,6 +16,12 @@ region.  value = (T * N * world_size * K) / max-over-ranks wall time.  Weak scal
 every rank owns its own 4096 envs (global env ids r*N .. (r+1)*N-1).
 Data: synthetic — the build's own LunarLander-v3 solver on fixed-seed Philox episodes,
 randomly initialised ActorCritic(8, 4, 256).
+
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+Everything else the benchmark measures — per-kernel HIP-event timers and phases inside the timed region, the roofline
+and GAE+loss figures, the frozen-policy rollout, the cpu_baseline leg, the off-policy `pieces` — runs only with --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64; the rollout slab as a
+fixed, seeded sample of its rows): same arguments, same inputs, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -84,6 +90,45 @@ def full_pass(trainer, T, N, dev, iters=5):
                 achieved_GBps=round(bw / 1e9, 1), frac=round(bw / HBM_PEAK, 4),
                 copy_GBps=round(copy_bw / 1e9, 1), frac_of_copy=round(bw / copy_bw, 4),
                 note="one launch per kernel over T*N transitions, cold caches, HIP events per launch")
+
+
+DUMP_ROWS = 1 << 16      # --dump-outputs: rows sampled from a [T*N] slab
+DUMP_LIMIT = 64 << 20    # --dump-outputs: bytes in all
+
+
+def _sample_rows(n, dev, seed=0):
+    """A fixed, seeded, sorted choice of DUMP_ROWS of n row indices (all of them when n <= DUMP_ROWS)."""
+    import numpy as np
+    if n <= DUMP_ROWS:
+        return torch.arange(n, device=dev)
+    return torch.from_numpy(np.sort(np.random.default_rng(seed).choice(n, size=DUMP_ROWS, replace=False))).to(dev)
+
+
+def _slab_sample(slabs, rows):
+    """{name: [T, N, ...] tensor} -> {name: the sampled rows of its [T*N, ...] view}."""
+    return {k: v.flatten(0, 1)[rows] for k, v in slabs.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy — float64 where the path computed it in float64, float32 otherwise
+    (integer and flag outputs included; callers pass sampled row ids as float64, exact at any slab size)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, x in arrays.items():
+        if torch.is_tensor(x):
+            x = x.detach().to(torch.float64 if x.dtype == torch.float64 else torch.float32).cpu().numpy()
+        else:
+            x = np.asarray(x, dtype=np.float64)
+        total += x.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit(f"[bench] --dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}")
+        np.save(os.path.join(dirname, name + ".npy"), x)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {dirname}", file=sys.stderr)
+
+
+def _metric_arrays(metrics):
+    return {"metric_" + k: float(v) for k, v in (metrics or {}).items()}
 
 
 def _free_port():
@@ -206,6 +251,120 @@ def _random_access_GBps(dev, entries=1 << 21, draws=1 << 22):
     return draws * 8.0 / us / 1e3, draws / us * 1e6
 
 
+def offpolicy_pieces(a, tr, cfg, dev, N, B, cap):
+    """--full, sac / rainbow: event-timed pieces of the replay memory and of the fused step at the run's own sizes and at
+    a throughput size, against this box's measured random-access rate; returns (roofline, pieces)."""
+    ra_GBps, ra_per_s = _random_access_GBps(dev)
+    mem = tr.memory
+    depth = 21                                                  # node reads of one descent through a 2^20-leaf tree
+    pieces = {}
+    if a.algo == "rainbow":
+        from gymrl_amd import ops
+        D = 4
+        row_bytes = 4 * (2 * D + 2) + 1 + 4                     # state, next_state, action, reward, flag + the index
+        for nb in sorted({B, 8192, 65536}):
+            idx = torch.empty(nb, dtype=torch.int32, device=dev)
+            pr, w = torch.empty(nb, dtype=torch.float64, device=dev), torch.empty(nb, device=dev)
+            ws = ops.per_workspace(max(8192, cap, nb), dev)
+            k = [0]
+
+            def draw():
+                k[0] += 1
+                ops.per_sample(mem.sum_tree.tree, cap, nb, mem.current_size, 0.5, ws, seed=7, counter=k[0], out=(idx, pr, w))
+            us = _event_us(draw)
+            pieces[f"per_sample B={nb}"] = dict(us=round(us, 2), draws_per_s=round(nb / us * 1e6), bytes_per_draw=8 * depth,
+                                                GBps=round(8.0 * depth * nb / us / 1e3, 2),
+                                                frac_of_random_access=round(8.0 * depth * nb / us / 1e3 / ra_GBps, 4))
+            us = _event_us(lambda: ops.replay_gather(mem.ring, idx))
+            pieces[f"ring_gather B={nb}"] = dict(us=round(us, 2), rows_per_s=round(nb / us * 1e6), bytes_per_row=row_bytes,
+                                                 GBps=round(row_bytes * nb / us / 1e3, 2), frac_hbm=round(row_bytes * nb / us / 1e3 / (HBM_PEAK / 1e9), 5))
+            td = torch.randn(nb, device=dev)
+            ws2 = ops.per_workspace(max(8192, cap, nb), dev)
+
+            def upd():
+                ops.per_update(mem.sum_tree.tree, cap, nb, ws2, idx=idx, prio=ops.per_priorities(td, mem.alpha, 0.01))
+            if nb <= 8192:
+                us = _event_us(upd)
+                pieces[f"per_update B={nb} (priorities of a sampled batch, reference order per node)"] = dict(
+                    us=round(us, 2), indices_per_s=round(nb / us * 1e6), bytes_per_index=16 * (depth - 1),
+                    GBps=round(16.0 * (depth - 1) * nb / us / 1e3, 3))
+        us = _event_us(lambda: mem.sum_tree.update_range(0, N, priority=1.0))
+        store_bytes = 16.0 * (depth - 1) * N
+        pieces[f"per_update N={N} (the new rows of one vector step)"] = dict(
+            us=round(us, 2), indices_per_s=round(N / us * 1e6), bytes_per_index=16 * (depth - 1), GBps=round(store_bytes / us / 1e3, 3))
+        roof = dict(bound="hbm", unit="GB/s", peak=HBM_PEAK / 1e9, achieved=round(store_bytes / us / 1e3, 3),
+                    frac=round(store_bytes / us / 1e3 / (HBM_PEAK / 1e9), 6), traffic=None, launch_s=us * 1e-6,
+                    kernel="gymrl_per_update over the N new rows of a vector step (csrc/per.hip per_store_leaf + per_store_ancestor): "
+                           "320 algorithmic bytes per index (20 float64 read-modify-writes).  Round 3 applied a node's additions in "
+                           "batch order (the root: one dependent chain of N float64 adds, 72-79 us); the reference stores ONE row per "
+                           "step, so the N-row store is now defined as one pairwise-summed addition per ancestor (DESIGN.md section 4, "
+                           "identical to the reference at N = 1).  Latency-bound scattered 8-byte accesses: priced against HBM as the "
+                           "contract asks, and against this box's random-access rate below",
+                    random_access_GBps_measured=round(ra_GBps, 1), random_accesses_per_s_measured=round(ra_per_s),
+                    frac_of_random_access=round(store_bytes / us / 1e3 / ra_GBps, 5))
+        # the fused step's own launches (csrc/offpolicy_step.hip), event-timed at the run's sizes
+        if tr._fused_act_ok():
+            lb = tr._loop_buffers(N, 4)
+            trk = lb["tracker"]
+            us = _event_us(lambda: tr._vector_step(lb, lb["obs"], lb["nxt"], trk.ret[0], trk.done[0]), reps=20)
+            H = cfg.hidden_dim
+            fl = 2.0 * N * (4 * H + H * H + 3 * H)
+            pieces["acting step: noisy heads + fc1, fc2, dueling argmax + CartPole + n-step push (gymrl_noisy_combine + gymrl_rainbow_act_step) "
+                   "+ the new rows' sum-tree store on the side stream"] = dict(us=round(us, 2), TFLOPs=round(fl / us / 1e6, 2))
+            upd_us = _event_us(lambda: tr.update_async(), reps=30)
+            flu = 2.0 * B * (3 * (4 * H + H * H + 3 * H) + (3 * H + H * H) + (3 * H + H * H + 4 * H))
+            cus = min(256, 3 * ((B + 15) // 16))
+            pieces[f"one update at batch {B} (proportional draw, three forwards, TD loss, backward, clip + Adam + Polyak, update_priorities)"] = dict(
+                us=round(upd_us, 2), TFLOPs=round(flu / upd_us / 1e6, 3), frac_mfma=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12), 5),
+                note=f"gymrl_rainbow_update's row kernel carries 16 rows per workgroup, three workgroups per slab: {cus} of the 256 compute units do its MFMA work")
+            if B > 256:      # SURVEY 8(d)'s throughput-sized line: the update is the dominant launch group, priced against the f32-MFMA peak
+                pieces[f"per_update N={N} (the new rows of one vector step): the small-batch line's roofline"] = roof
+                roof = dict(bound="mfma", unit="TFLOP/s", peak=MFMA_F32_PEAK / 1e12, achieved=round(flu / upd_us / 1e6, 3),
+                            frac=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12), 5), traffic=None, launch_s=upd_us * 1e-6,
+                            flops_per_launch_group=flu, compute_units_carrying_rows=cus,
+                            kernel=f"one Rainbow update at batch {B}: gymrl_rainbow_update's row-slab kernel ({3 * ((B + 15) // 16)} workgroups of 16 rows on slab-adjacent "
+                                   "1-D grids) + the weight-gradient tiles in lin.hip's 256-row slices + clip / Adam / Polyak + update_priorities "
+                                   "(sort-based passes above 512 indices)")
+    else:
+        from gymrl_amd import ops
+        D, A = 3, 1
+        row_bytes = 4 * (2 * D + A + 1) + 1 + 4
+        for nb in (B, 65536):
+            idx = ops.uniform_indices(7, 1, len(mem), min(nb, len(mem)), dev)
+            nb = idx.numel()
+            us = _event_us(lambda: ops.replay_gather(mem.ring, idx))
+            pieces[f"ring_gather B={nb}"] = dict(us=round(us, 2), rows_per_s=round(nb / us * 1e6), bytes_per_row=row_bytes,
+                                                 GBps=round(row_bytes * nb / us / 1e3, 2), frac_hbm=round(row_bytes * nb / us / 1e3 / (HBM_PEAK / 1e9), 5))
+        H = cfg.hidden_dim
+        DA = D + A
+        # algorithmic f32 flops of one update (sac_pendulum.py:213-267): actor(s'), target Q x2, Q x2 forward + input gradients,
+        # actor(s), Q x2 forward + input gradients back to the action and through the actor, every weight gradient
+        actor_f, q_f = 2.0 * B * (D * H + H * H + 2 * H * A), 2.0 * B * (DA * H + H * H + H)
+        flu = (actor_f + 2 * q_f + 2 * q_f + 2 * 2.0 * B * (H + H * H) + 2 * q_f            # P1 + critic dW
+               + actor_f + 2 * q_f + 2 * 2.0 * B * (H + H * H + DA * H) + 2.0 * B * (2 * A * H + H * H) + actor_f)   # P3 + actor dW
+        upd_us = _event_us(lambda: tr.update_async() if getattr(cfg, "use_graphs", True) else tr.update(), reps=50)
+        cus = min(256, 4 * ((B + 15) // 16))      # P1: four workgroups per 16-row slab (P3: two)
+        roof = dict(bound="mfma", unit="TFLOP/s", peak=MFMA_F32_PEAK / 1e12, achieved=round(flu / upd_us / 1e6, 3),
+                    frac=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12), 5), traffic=None, launch_s=upd_us * 1e-6,
+                    flops_per_launch_group=flu, compute_units_carrying_rows=cus,
+                    frac_of_those_units=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12 * cus / 256.0), 4),
+                    kernel=f"gymrl_sac_update: the four launches of one update at batch {B} (csrc/offpolicy_step.hip: row-slab kernels P1 / P3, "
+                           "weight-gradient + Adam tile kernels P2 / P4).  A 16-row slab's chain of layers runs on ONE compute unit, its independent "
+                           "chains on units of their own: 4 B / 16 (P1: 32 at batch 128) and 2 B / 16 (P3) workgroups carry the MFMA "
+                           "work of the row kernels (a 16 x 256 x 256 layer is 3.9 us of f32 MFMA on one compute unit, 4.6-4.9 us measured: "
+                           "tools/probe_sac_stages.py), so the figure is priced twice — against the chip's f32-MFMA peak as the contract asks "
+                           "(`frac`) and against the peak of the units that can work (`frac_of_those_units`: P1's workgroups, at most 256)")
+        pieces[f"one update at batch {B} (twin critics, actor, temperature, Adam x3 + Polyak: gymrl_sac_update, 4 launches)"] = dict(us=round(upd_us, 2))
+        if tr._fused_ok():
+            lb = tr._loop_buffers(N, D)
+            trk = lb["tracker"]
+            us = _event_us(lambda: tr._vector_step(lb, lb["obs"], lb["nxt"], trk.ret[0], trk.done[0]), reps=20)
+            fl = 2.0 * N * (D * H + H * H + 2 * H * A)
+            pieces["acting step: Actor forward + reparameterised draw + Pendulum step + replay row (gymrl_sac_act_step, 1 launch)"] = dict(
+                us=round(us, 2), TFLOPs=round(fl / us / 1e6, 2), frac_mfma=round(fl / us / 1e6 / (MFMA_F32_PEAK / 1e12), 4))
+    return roof, pieces
+
+
 def main_offpolicy(a, rank, world, local_rank):
     """BASELINE.json configs[2] (Rainbow DQN CartPole-v1, 8192 envs, PER sum tree + n-step + NoisyNet) and configs[3] (SAC
     Pendulum-v1, 4096 envs, twin Q + reparameterised sample + automatic temperature), one GPU each; with --gpus N every rank
@@ -213,7 +372,7 @@ def main_offpolicy(a, rank, world, local_rank):
     One "step" = 16 vector steps = one replay of the trainer's StepChunk graph where the trainer chunks (Rainbow), 16 passes
     of its loop otherwise: per vector step the reference loop's acting forward, env.step, n-step / ring store, proportional or
     uniform draw and ONE update (rainbow_dqn_cartpole.py:363-405, sac_pendulum.py:275-300), ring of 2^20 rows.
-    Nothing is skipped.  After the timed region rank 0 event-times the replay memory's pieces at the run's own sizes and at
+    Nothing is skipped.  With --full, after the timed region rank 0 event-times the replay memory's pieces at the run's own sizes and at
     a throughput size, against this box's measured random-access rate."""
     from gymrl_amd import dist as gdist
     dev = torch.device(f"cuda:{local_rank}")
@@ -258,115 +417,12 @@ def main_offpolicy(a, rank, world, local_rank):
         return
     sys.stdout = sys.__stdout__
     try:
-        ra_GBps, ra_per_s = _random_access_GBps(dev)
-        mem = tr.memory
+        if a.dump_outputs:
+            flats = ("flat_params", "target_flat") if a.algo == "rainbow" else ("actor_flat", "critic_flat", "critic_target_flat", "log_alpha")
+            dump_outputs(a.dump_outputs, {k: getattr(tr, k) for k in flats})
         cap = 1 << 20
-        depth = 21                                                  # node reads of one descent through a 2^20-leaf tree
-        pieces = {}
-        if a.algo == "rainbow":
-            from gymrl_amd import ops
-            D = 4
-            row_bytes = 4 * (2 * D + 2) + 1 + 4                     # state, next_state, action, reward, flag + the index
-            for nb in sorted({B, 8192, 65536}):
-                idx = torch.empty(nb, dtype=torch.int32, device=dev)
-                pr, w = torch.empty(nb, dtype=torch.float64, device=dev), torch.empty(nb, device=dev)
-                ws = ops.per_workspace(max(8192, cap, nb), dev)
-                k = [0]
-
-                def draw():
-                    k[0] += 1
-                    ops.per_sample(mem.sum_tree.tree, cap, nb, mem.current_size, 0.5, ws, seed=7, counter=k[0], out=(idx, pr, w))
-                us = _event_us(draw)
-                pieces[f"per_sample B={nb}"] = dict(us=round(us, 2), draws_per_s=round(nb / us * 1e6), bytes_per_draw=8 * depth,
-                                                    GBps=round(8.0 * depth * nb / us / 1e3, 2),
-                                                    frac_of_random_access=round(8.0 * depth * nb / us / 1e3 / ra_GBps, 4))
-                us = _event_us(lambda: ops.replay_gather(mem.ring, idx))
-                pieces[f"ring_gather B={nb}"] = dict(us=round(us, 2), rows_per_s=round(nb / us * 1e6), bytes_per_row=row_bytes,
-                                                     GBps=round(row_bytes * nb / us / 1e3, 2), frac_hbm=round(row_bytes * nb / us / 1e3 / (HBM_PEAK / 1e9), 5))
-                td = torch.randn(nb, device=dev)
-                ws2 = ops.per_workspace(max(8192, cap, nb), dev)
-
-                def upd():
-                    ops.per_update(mem.sum_tree.tree, cap, nb, ws2, idx=idx, prio=ops.per_priorities(td, mem.alpha, 0.01))
-                if nb <= 8192:
-                    us = _event_us(upd)
-                    pieces[f"per_update B={nb} (priorities of a sampled batch, reference order per node)"] = dict(
-                        us=round(us, 2), indices_per_s=round(nb / us * 1e6), bytes_per_index=16 * (depth - 1),
-                        GBps=round(16.0 * (depth - 1) * nb / us / 1e3, 3))
-            us = _event_us(lambda: mem.sum_tree.update_range(0, N, priority=1.0))
-            store_bytes = 16.0 * (depth - 1) * N
-            pieces[f"per_update N={N} (the new rows of one vector step)"] = dict(
-                us=round(us, 2), indices_per_s=round(N / us * 1e6), bytes_per_index=16 * (depth - 1), GBps=round(store_bytes / us / 1e3, 3))
-            roof = dict(bound="hbm", unit="GB/s", peak=HBM_PEAK / 1e9, achieved=round(store_bytes / us / 1e3, 3),
-                        frac=round(store_bytes / us / 1e3 / (HBM_PEAK / 1e9), 6), traffic=None, launch_s=us * 1e-6,
-                        kernel="gymrl_per_update over the N new rows of a vector step (csrc/per.hip per_store_leaf + per_store_ancestor): "
-                               "320 algorithmic bytes per index (20 float64 read-modify-writes).  Round 3 applied a node's additions in "
-                               "batch order (the root: one dependent chain of N float64 adds, 72-79 us); the reference stores ONE row per "
-                               "step, so the N-row store is now defined as one pairwise-summed addition per ancestor (DESIGN.md section 4, "
-                               "identical to the reference at N = 1).  Latency-bound scattered 8-byte accesses: priced against HBM as the "
-                               "contract asks, and against this box's random-access rate below",
-                        random_access_GBps_measured=round(ra_GBps, 1), random_accesses_per_s_measured=round(ra_per_s),
-                        frac_of_random_access=round(store_bytes / us / 1e3 / ra_GBps, 5))
-            # the fused step's own launches (csrc/offpolicy_step.hip), event-timed at the run's sizes
-            if tr._fused_act_ok():
-                lb = tr._loop_buffers(N, 4)
-                trk = lb["tracker"]
-                us = _event_us(lambda: tr._vector_step(lb, lb["obs"], lb["nxt"], trk.ret[0], trk.done[0]), reps=20)
-                H = cfg.hidden_dim
-                fl = 2.0 * N * (4 * H + H * H + 3 * H)
-                pieces["acting step: noisy heads + fc1, fc2, dueling argmax + CartPole + n-step push (gymrl_noisy_combine + gymrl_rainbow_act_step) "
-                       "+ the new rows' sum-tree store on the side stream"] = dict(us=round(us, 2), TFLOPs=round(fl / us / 1e6, 2))
-                upd_us = _event_us(lambda: tr.update_async(), reps=30)
-                flu = 2.0 * B * (3 * (4 * H + H * H + 3 * H) + (3 * H + H * H) + (3 * H + H * H + 4 * H))
-                cus = min(256, 3 * ((B + 15) // 16))
-                pieces[f"one update at batch {B} (proportional draw, three forwards, TD loss, backward, clip + Adam + Polyak, update_priorities)"] = dict(
-                    us=round(upd_us, 2), TFLOPs=round(flu / upd_us / 1e6, 3), frac_mfma=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12), 5),
-                    note=f"gymrl_rainbow_update's row kernel carries 16 rows per workgroup, three workgroups per slab: {cus} of the 256 compute units do its MFMA work")
-                if B > 256:      # SURVEY 8(d)'s throughput-sized line: the update is the dominant launch group, priced against the f32-MFMA peak
-                    pieces[f"per_update N={N} (the new rows of one vector step): the small-batch line's roofline"] = roof
-                    roof = dict(bound="mfma", unit="TFLOP/s", peak=MFMA_F32_PEAK / 1e12, achieved=round(flu / upd_us / 1e6, 3),
-                                frac=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12), 5), traffic=None, launch_s=upd_us * 1e-6,
-                                flops_per_launch_group=flu, compute_units_carrying_rows=cus,
-                                kernel=f"one Rainbow update at batch {B}: gymrl_rainbow_update's row-slab kernel ({3 * ((B + 15) // 16)} workgroups of 16 rows on slab-adjacent "
-                                       "1-D grids) + the weight-gradient tiles in lin.hip's 256-row slices + clip / Adam / Polyak + update_priorities "
-                                       "(sort-based passes above 512 indices)")
-        else:
-            from gymrl_amd import ops
-            D, A = 3, 1
-            row_bytes = 4 * (2 * D + A + 1) + 1 + 4
-            for nb in (B, 65536):
-                idx = ops.uniform_indices(7, 1, len(mem), min(nb, len(mem)), dev)
-                nb = idx.numel()
-                us = _event_us(lambda: ops.replay_gather(mem.ring, idx))
-                pieces[f"ring_gather B={nb}"] = dict(us=round(us, 2), rows_per_s=round(nb / us * 1e6), bytes_per_row=row_bytes,
-                                                     GBps=round(row_bytes * nb / us / 1e3, 2), frac_hbm=round(row_bytes * nb / us / 1e3 / (HBM_PEAK / 1e9), 5))
-            H = cfg.hidden_dim
-            DA = D + A
-            # algorithmic f32 flops of one update (sac_pendulum.py:213-267): actor(s'), target Q x2, Q x2 forward + input gradients,
-            # actor(s), Q x2 forward + input gradients back to the action and through the actor, every weight gradient
-            actor_f, q_f = 2.0 * B * (D * H + H * H + 2 * H * A), 2.0 * B * (DA * H + H * H + H)
-            flu = (actor_f + 2 * q_f + 2 * q_f + 2 * 2.0 * B * (H + H * H) + 2 * q_f            # P1 + critic dW
-                   + actor_f + 2 * q_f + 2 * 2.0 * B * (H + H * H + DA * H) + 2.0 * B * (2 * A * H + H * H) + actor_f)   # P3 + actor dW
-            upd_us = _event_us(lambda: tr.update_async() if getattr(cfg, "use_graphs", True) else tr.update(), reps=50)
-            cus = min(256, 4 * ((B + 15) // 16))      # P1: four workgroups per 16-row slab (P3: two)
-            roof = dict(bound="mfma", unit="TFLOP/s", peak=MFMA_F32_PEAK / 1e12, achieved=round(flu / upd_us / 1e6, 3),
-                        frac=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12), 5), traffic=None, launch_s=upd_us * 1e-6,
-                        flops_per_launch_group=flu, compute_units_carrying_rows=cus,
-                        frac_of_those_units=round(flu / upd_us / 1e6 / (MFMA_F32_PEAK / 1e12 * cus / 256.0), 4),
-                        kernel=f"gymrl_sac_update: the four launches of one update at batch {B} (csrc/offpolicy_step.hip: row-slab kernels P1 / P3, "
-                               "weight-gradient + Adam tile kernels P2 / P4).  A 16-row slab's chain of layers runs on ONE compute unit, its independent "
-                               "chains on units of their own: 4 B / 16 (P1: 32 at batch 128) and 2 B / 16 (P3) workgroups carry the MFMA "
-                               "work of the row kernels (a 16 x 256 x 256 layer is 3.9 us of f32 MFMA on one compute unit, 4.6-4.9 us measured: "
-                               "tools/probe_sac_stages.py), so the figure is priced twice — against the chip's f32-MFMA peak as the contract asks "
-                               "(`frac`) and against the peak of the units that can work (`frac_of_those_units`: P1's workgroups, at most 256)")
-            pieces[f"one update at batch {B} (twin critics, actor, temperature, Adam x3 + Polyak: gymrl_sac_update, 4 launches)"] = dict(us=round(upd_us, 2))
-            if tr._fused_ok():
-                lb = tr._loop_buffers(N, D)
-                trk = lb["tracker"]
-                us = _event_us(lambda: tr._vector_step(lb, lb["obs"], lb["nxt"], trk.ret[0], trk.done[0]), reps=20)
-                fl = 2.0 * N * (D * H + H * H + 2 * H * A)
-                pieces["acting step: Actor forward + reparameterised draw + Pendulum step + replay row (gymrl_sac_act_step, 1 launch)"] = dict(
-                    us=round(us, 2), TFLOPs=round(fl / us / 1e6, 2), frac_mfma=round(fl / us / 1e6 / (MFMA_F32_PEAK / 1e12), 4))
+        if a.full:
+            roof, pieces = offpolicy_pieces(a, tr, cfg, dev, N, B, cap)
         vsteps = a.steps * VS
         out = {
             "metric": f"env-steps/sec at N envs/GPU ({'Rainbow DQN CartPole' if a.algo == 'rainbow' else 'SAC Pendulum'}), 1 update per vector step + %roofline",
@@ -380,7 +436,7 @@ def main_offpolicy(a, rank, world, local_rank):
                        "envs_per_gpu": N, "vector_steps_per_step": VS, "updates_per_vector_step": 1, "batch": B, "replay_rows": cap,
                        "ms_per_vector_step": round(dt / vsteps * 1e3, 4), "updates_per_s": round(vsteps * world / dt, 1),
                        "parallelism": f"{world} independent replicas (no exchange step on this path)" if world > 1 else "single GPU"},
-            "roofline": roof, "pieces": pieces,
+            **({"roofline": roof, "pieces": pieces} if a.full else {}),
             "comm": dict(rccl_world_size=world, grad_allreduce=None, backend=_backend_name(), rank_devices=devices),
         }
         print(json.dumps(out))
@@ -412,7 +468,12 @@ def main():
                     help="ppo: HIP-event brackets around the launches of every K-th minibatch of the timed region (1: all; "
                          "the gather of the next minibatch is issued inside the previous one's bracket window either way)")
     ap.add_argument("--graphs", action="store_true", help="ppo: replay the minibatch body as a hipGraph (A/B; measured 1 % slower than the eager queue)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel timers and phases in the timed region, roofline, "
+                         "GAE+loss pass, frozen-policy rollout, cpu_baseline (ppo), replay-memory pieces (sac / rainbow)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the cpu_baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=24.0)
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help="nccl == RCCL (default); gloo only for --spawn-selftest on CPU")
     ap.add_argument("--spawn-selftest", action="store_true", help="launch + verify the ranks, all-reduce once, print one JSON line; no workload")
@@ -463,28 +524,31 @@ def main():
     sys.stdout = open(os.devnull, "w") if rank != 0 else sys.stderr       # stdout carries the JSON line only
     trainer = PPOTrainer(cfg)
     T, N = cfg.update_freq, cfg.num_envs
-    init_params = trainer.flat_params.clone()
+    init_params = trainer.flat_params.clone() if a.full else None
 
     phase_events = []
 
     def step():
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        phase_events.append(ev)
-        ev[0].record()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if a.full else None
+        if ev:
+            phase_events.append(ev)
+            ev[0].record()
         if cfg.anneal_lr:
             lr = cfg.lr * (1.0 - trainer.step_count * world / cfg.max_train_steps)
             for g in trainer.optimizer.param_groups:
                 g["lr"] = lr
         nv = trainer.collect_rollout()
-        ev[1].record()
+        if ev:
+            ev[1].record()
         m = trainer.update(nv)
-        ev[2].record()
+        if ev:
+            ev[2].record()
         return m
 
     for _ in range(a.warmup):
         step()
     phase_events.clear()
-    timers = KernelTimers(every=max(1, a.timer_every))
+    timers = KernelTimers(every=max(1, a.timer_every)) if a.full else None
     trainer._timers = timers
     gdist.barrier()
     torch.cuda.synchronize()
@@ -506,6 +570,19 @@ def main():
         return
     sys.stdout = sys.__stdout__
     try:
+        if a.dump_outputs:
+            rows = _sample_rows(T * N, dev)
+            b = trainer.buffer
+            dump_outputs(a.dump_outputs, {
+                "params": trainer.flat_params, "next_value": trainer._next_value, "gae_moments": trainer._moments,
+                **_slab_sample({"rollout_" + k: getattr(b, k) for k in ("advantages", "returns", "values", "log_probs",
+                                                                        "rewards", "actions", "dones")}, rows),
+                "rollout_states": b.states[:T].flatten(0, 1)[rows], "rollout_rows": rows.double(),
+                **_metric_arrays(metrics)})
+        if not a.full:
+            print(json.dumps(headline(a, cfg, trainer, metrics, dt, world, T, N, devices)))
+            sys.stdout.flush()
+            return
         # rollout under the initial policy (outside the timed region; the trained parameters are put back)
         trained = trainer.flat_params.clone()
         trainer.flat_params.copy_(init_params)
@@ -553,7 +630,7 @@ def main_ppo_full(a, rank, world, local_rank):
     4096 / 1024 ratio: T*N/4 rows each, accumulated over micro-batches of --micro-batch rows) with the L3 loss kernel,
     clip + Adam.  The network's rollout forward is one hand-written launch per vector step; its training pass is autograd over the
     C-ABI's HBM-bound kernels (csrc/mhc.hip, csrc/lin.hip) with the library's GEMMs for the 128-wide forward / input gradients.
-    `roofline` = the largest of those kernels, the gates backward, event-timed at the micro-batch size after the timed region."""
+    `roofline` (--full) = the largest of those kernels, the gates backward, event-timed at the micro-batch size after the timed region."""
     from gymrl_amd import dist as gdist
     from gymrl_amd.ppo_full_lunarlander import Config, PPOTrainer
     dev = torch.device(f"cuda:{local_rank}")
@@ -569,23 +646,29 @@ def main_ppo_full(a, rank, world, local_rank):
     tr = PPOTrainer(cfg)
     T, N = cfg.update_freq, cfg.num_envs
     ev_all = []
+    last = {}
 
     def step():
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ev_all.append(ev)
-        ev[0].record()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if a.full else None
+        if ev:
+            ev_all.append(ev)
+            ev[0].record()
         tr.collect_experience()
-        ev[1].record()
+        if ev:
+            ev[1].record()
         adv, ret = tr.compute_advantages()
-        ev[2].record()
+        last.update(advantages=adv, returns=ret)
+        if ev:
+            ev[2].record()
         m = tr.update_model(adv, ret)
-        ev[3].record()
+        if ev:
+            ev[3].record()
         return m
     if True:
         for _ in range(a.warmup):
             step()
         ev_all.clear()
-        tr._time_collectives = True
+        tr._time_collectives = a.full
         if tr._reducer is not None:
             tr._reducer.reset_stats()
         gdist.barrier()
@@ -603,10 +686,15 @@ def main_ppo_full(a, rank, world, local_rank):
     devices = gdist.rank_devices()
     if rank == 0:
         sys.stdout = sys.__stdout__
-        ph = [sum(e[i].elapsed_time(e[i + 1]) for e in ev_all) / a.steps for i in range(3)]
-        gae_s = ph[1] * 1e-3
+        if a.dump_outputs:
+            b = tr.buffer
+            rows = _sample_rows(T * N, dev)
+            slabs = dict(last, **{k: getattr(b, k) for k in ("values", "log_probs", "rewards", "actions", "dones", "old_entropies")})
+            dump_outputs(a.dump_outputs, {
+                "params": tr.flat_params, "next_value": b.next_value,
+                **_slab_sample({"rollout_" + k: v for k, v in slabs.items()}, rows),
+                "rollout_rows": rows.double(), **_metric_arrays(m)})
         mb = T * N // cfg.num_minibatches
-        gates = _sub_bwd_launch(min(cfg.micro_batch, mb), cfg.mhc_dim, cfg.mhc_sk_it, dev) if (cfg.mhc_rate == 2 and cfg.mhc_dim == 128) else None
         out = {
             "metric": "env-steps/sec at N envs/GPU (PPO-full LunarLander), 1/2/4/8 GPUs + %HBM roofline",
             "value": T * N * world * a.steps / dt, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
@@ -616,25 +704,58 @@ def main_ppo_full(a, rank, world, local_rank):
                        "envs_per_gpu": N, "rollout_len": T, "num_epochs": cfg.num_epochs, "num_minibatches": cfg.num_minibatches,
                        "minibatch": mb, "micro_batch": min(cfg.micro_batch, mb),
                        "optimizer_steps_per_iteration": cfg.num_epochs * cfg.num_minibatches,
-                       "parallelism": f"dp{world} (env shards + flat-gradient all-reduce)" if world > 1 else "single GPU"},
-            "roofline": ({"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK / 1e9,
-                          "kernel": "gymrl_mhc_sub_backward (csrc/mhc.hip: combine, the Linear's input gradient on f32 MFMA, read and gates "
-                                    "backward of one hyper-connection sub-block in one launch): the largest kernel of the training "
-                                    "pass, four launches per micro-batch; bound by the CU's memory pipe and 352 f32 MFMAs per 16 rows",
-                          "achieved": round(gates["bytes"] / gates["s"] / 1e9, 1), "frac": round(gates["bytes"] / gates["s"] / HBM_PEAK, 4),
-                          "traffic": None, "launch_s": gates["s"], "rows": gates["rows"], "bytes_per_row": gates["bytes_per_row"],
-                          "note": "event-timed after the timed region at the micro-batch size (cold inputs of that size: 0.9 GB)"}
-                         if gates else None),
-            "gae_pass": {"kernel": "G3: gymrl_gae_decoupled variant 2 (two carry scans + apply; both chunk maps composed in the rollout)",
-                         "GBps": round(17.0 * T * N / gae_s / 1e9, 1), "frac": round(17.0 * T * N / gae_s / HBM_PEAK, 4), "launch_s": gae_s},
-            "phases": {"rollout_ms": round(ph[0], 1), "gae_ms": round(ph[1], 3), "update_ms": round(ph[2], 1)},
+                       "parallelism": f"dp{world} (env shards + flat-gradient all-reduce)" if world > 1 else "single GPU"}}
+        if a.full:
+            ph = [sum(e[i].elapsed_time(e[i + 1]) for e in ev_all) / a.steps for i in range(3)]
+            gae_s = ph[1] * 1e-3
+            gates = _sub_bwd_launch(min(cfg.micro_batch, mb), cfg.mhc_dim, cfg.mhc_sk_it, dev) if (cfg.mhc_rate == 2 and cfg.mhc_dim == 128) else None
+            out.update({
+                "roofline": ({"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK / 1e9,
+                              "kernel": "gymrl_mhc_sub_backward (csrc/mhc.hip: combine, the Linear's input gradient on f32 MFMA, read and gates "
+                                        "backward of one hyper-connection sub-block in one launch): the largest kernel of the training "
+                                        "pass, four launches per micro-batch; bound by the CU's memory pipe and 352 f32 MFMAs per 16 rows",
+                              "achieved": round(gates["bytes"] / gates["s"] / 1e9, 1), "frac": round(gates["bytes"] / gates["s"] / HBM_PEAK, 4),
+                              "traffic": None, "launch_s": gates["s"], "rows": gates["rows"], "bytes_per_row": gates["bytes_per_row"],
+                              "note": "event-timed after the timed region at the micro-batch size (cold inputs of that size: 0.9 GB)"}
+                             if gates else None),
+                "gae_pass": {"kernel": "G3: gymrl_gae_decoupled variant 2 (two carry scans + apply; both chunk maps composed in the rollout)",
+                             "GBps": round(17.0 * T * N / gae_s / 1e9, 1), "frac": round(17.0 * T * N / gae_s / HBM_PEAK, 4), "launch_s": gae_s},
+                "phases": {"rollout_ms": round(ph[0], 1), "gae_ms": round(ph[1], 3), "update_ms": round(ph[2], 1)}})
+        out.update({
             "train_metrics": {k: float(v) for k, v in (m or {}).items()},
             "comm": dict(comm_summary(world, tr._reducer, None, dt / a.steps, a.steps), backend=_backend_name(),
-                         rank_devices=devices),
-        }
+                         rank_devices=devices)})
         print(json.dumps(out))
         sys.stdout.flush()
     gdist.shutdown()
+
+
+def headline(a, cfg, trainer, metrics, dt, world, T, N, devices, ks=None, extra=None):
+    """The PPO result line: what a plain run prints; report() (--full) adds its figures (`extra`: roofline, phases) after
+    `config`, and the all-reduce figures of its timers to `comm`."""
+    transitions = T * N
+    out = {
+        "metric": "env-steps/sec at N envs/GPU (PPO LunarLander), 1/2/4/8 GPUs + %HBM roofline",
+        "value": transitions * world * a.steps / dt,
+        "unit": "env-steps/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "PPO LunarLander-v3, 4096 vectorised envs per MI355X (BASELINE.json configs[1])",
+                   "envs_per_gpu": N, "rollout_len": T, "transitions_per_step_per_gpu": transitions,
+                   "num_epochs": cfg.num_epochs, "num_minibatches": cfg.num_minibatches,
+                   "minibatch": transitions // cfg.num_minibatches, "model": "ActorCritic 8-256-256-{256-4,256-1} tanh, 200,965 params",
+                   "parallelism": f"dp{world} (env shards + flat-gradient all-reduce)" if world > 1 else "single GPU"},
+    }
+    out.update(extra or {})
+    out.update({
+        "train_metrics": {k: float(v) for k, v in (metrics or {}).items()},
+        "avg_episode_return": (sum(trainer.episode_rewards) / len(trainer.episode_rewards)) if trainer.episode_rewards else None,
+        "comm": dict(comm_summary(world, trainer._reducer, ks, dt / a.steps, a.steps), backend=_backend_name(),
+                     rank_devices=devices),
+    })
+    return out
 
 
 def report(a, cfg, trainer, timers, phase_events, metrics, dt, world, T, N, dev, frozen_ms=None, devices=None):
@@ -738,30 +859,13 @@ def report(a, cfg, trainer, timers, phase_events, metrics, dt, world, T, N, dev,
                                      frac_at_effective_clock=round(head["frac"] * 2.4 / clk, 4),
                                      mfma_busy_share=round(sum(e["mfma_busy_share"] * e["duration_us_profiled"] for e in six) / t_us, 3))
 
-    out = {
-        "metric": "env-steps/sec at N envs/GPU (PPO LunarLander), 1/2/4/8 GPUs + %HBM roofline",
-        "value": transitions * world * a.steps / dt,
-        "unit": "env-steps/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "PPO LunarLander-v3, 4096 vectorised envs per MI355X (BASELINE.json configs[1])",
-                   "envs_per_gpu": N, "rollout_len": T, "transitions_per_step_per_gpu": transitions,
-                   "num_epochs": cfg.num_epochs, "num_minibatches": cfg.num_minibatches,
-                   "minibatch": transitions // cfg.num_minibatches, "model": "ActorCritic 8-256-256-{256-4,256-1} tanh, 200,965 params",
-                   "parallelism": f"dp{world} (env shards + flat-gradient all-reduce)" if world > 1 else "single GPU"},
+    out = headline(a, cfg, trainer, metrics, dt, world, T, N, devices, ks, extra={
         "roofline": roofline,
         "phases": {"rollout_ms": round(rollout_s * 1e3, 1), "update_ms": round(update_s * 1e3, 1),
                    "rollout_only_env_steps_per_s": round(transitions / rollout_s),
                    # one rollout under the initial (frozen) policy, outside the timed region: the in-run figure moves with
                    # what the policy has learned (contact mix), this one does not
-                   "rollout_frozen_policy_ms": frozen_ms},
-        "train_metrics": {k: float(v) for k, v in (metrics or {}).items()},
-        "avg_episode_return": (sum(trainer.episode_rewards) / len(trainer.episode_rewards)) if trainer.episode_rewards else None,
-        "comm": dict(comm_summary(world, trainer._reducer, ks, dt / a.steps, a.steps), backend=_backend_name(),
-                     rank_devices=devices),
-    }
+                   "rollout_frozen_policy_ms": frozen_ms}})
     if world == 1 and not a.no_cpu_baseline:
         from oracle.ref_ppo_cpu import time_cpu_baseline
         out["cpu_baseline"] = time_cpu_baseline(a.cpu_budget)

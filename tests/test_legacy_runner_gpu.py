@@ -126,11 +126,12 @@ def test_off_policy_buffer_contract():
 
 
 @pytest.mark.parametrize("kind", ["on", "off"])
-def test_runner_trace_matches_reference(kind):
+def test_runner_trace_matches_reference(kind, tmp_path, monkeypatch):
     """Row H1/U1: the reference utils/runner.py train() on the scripted env (tests/golden/runner_trace.npz) replayed
     by gymrl_amd.utils.runner.train() with num_envs = 1: the order of choose_action / update / save_model calls, every
     stored transition (normalised states incl. the TERMINAL observation as next state, scaled rewards, done /
     terminated flags, log-prob, V and V(next)) and the final running statistics."""
+    monkeypatch.chdir(tmp_path)                                   # the runner's metrics sink writes ./exp/<algo>_<env>_<time>
     from conftest import load_golden, rel_close
     from scripted_env import ScriptedVecEnv
     from gymrl_amd.utils.buffer import ReplayBuffer_off_policy, ReplayBuffer_on_policy

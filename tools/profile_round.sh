@@ -5,7 +5,7 @@ set -u
 OUT=/root/repo/gpurun_out/$1
 mkdir -p "$OUT"
 cd /root/repo
-timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout 200 python tools/micro_kernels.py > "$OUT/micro_kernels.json" 2> /dev/null
 timeout 200 python tools/micro_mlp.py > "$OUT/micro_mlp.json" 2> /dev/null
 timeout 200 python tools/micro_update.py > "$OUT/micro_update.json" 2> /dev/null

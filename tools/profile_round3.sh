@@ -5,9 +5,9 @@ set -u
 OUT=/root/repo/gpurun_out/$1
 mkdir -p "$OUT"
 cd /root/repo
-timeout 600 python bench.py > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_20steps.json" 2> /dev/null
-timeout 300 python bench.py --algo ppo_full --steps 3 --warmup 1 > "$OUT/bench_ppo_full.json" 2> /dev/null
+timeout 600 python bench.py --full > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_20steps.json" 2> /dev/null
+timeout 300 python bench.py --full --algo ppo_full --steps 3 --warmup 1 > "$OUT/bench_ppo_full.json" 2> /dev/null
 timeout 200 python tools/micro_update.py > "$OUT/micro_update.json" 2> /dev/null
 timeout 200 python tools/probe_rollout_balance.py 2048 > "$OUT/rollout_balance.txt" 2> /dev/null
 cd /tmp && export TMPDIR=/tmp

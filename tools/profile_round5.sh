@@ -22,13 +22,13 @@ python /root/repo/tools/pmc_gemm_summarise.py "$OUT/pmc_FETCH_SIZE_counter_colle
   "$OUT/pmc_gemm_sq.csv" "$OUT/pmc_gemm_sq_trace.csv" /root/repo/profiles/r05_pmc_summary.json "$OUT/pmc_provenance.json" > /dev/null
 cp /root/repo/profiles/r05_pmc_summary.json "$OUT/pmc_summary.json"
 popd > /dev/null
-timeout 600 python bench.py > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_20steps.json" 2> /dev/null
-timeout 300 python bench.py --algo ppo_full --steps 3 --warmup 1 > "$OUT/bench_ppo_full.json" 2> /dev/null
-timeout 300 python bench.py --algo sac > "$OUT/bench_sac.json" 2> /dev/null
-timeout 300 python bench.py --algo rainbow > "$OUT/bench_rainbow.json" 2> /dev/null
-timeout 300 python bench.py --algo sac --batch 4096 --steps 30 --warmup 30 > "$OUT/bench_sac_bigbatch.json" 2> /dev/null
-timeout 300 python bench.py --algo rainbow --batch 8192 --steps 30 --warmup 30 > "$OUT/bench_rainbow_bigbatch.json" 2> /dev/null
+timeout 600 python bench.py --full > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_20steps.json" 2> /dev/null
+timeout 300 python bench.py --full --algo ppo_full --steps 3 --warmup 1 > "$OUT/bench_ppo_full.json" 2> /dev/null
+timeout 300 python bench.py --full --algo sac > "$OUT/bench_sac.json" 2> /dev/null
+timeout 300 python bench.py --full --algo rainbow > "$OUT/bench_rainbow.json" 2> /dev/null
+timeout 300 python bench.py --full --algo sac --batch 4096 --steps 30 --warmup 30 > "$OUT/bench_sac_bigbatch.json" 2> /dev/null
+timeout 300 python bench.py --full --algo rainbow --batch 8192 --steps 30 --warmup 30 > "$OUT/bench_rainbow_bigbatch.json" 2> /dev/null
 timeout 200 python tools/micro_per.py > "$OUT/micro_per.txt" 2> /dev/null
 timeout 200 python tools/probe_rollout_balance.py 2048 > "$OUT/rollout_balance.txt" 2> /dev/null
 cd /tmp && export TMPDIR=/tmp

@@ -9,7 +9,7 @@ PROBE=$1; RUNS=$2; shift 2
 O=gpurun_out/ab_$$; mkdir -p $O
 for rep in $(seq 1 "$RUNS"); do for v in new probe; do
   if [ $v = probe ]; then export GYMRL_HIP_LIB=$PROBE; else unset GYMRL_HIP_LIB; fi
-  python bench.py "$@" --no-cpu-baseline > $O/${v}_$rep.json 2>/dev/null
+  python bench.py --full "$@" --no-cpu-baseline > $O/${v}_$rep.json 2>/dev/null
 done; done
 unset GYMRL_HIP_LIB
 for f in $O/*.json; do python - "$f" <<'PY'

@@ -15,7 +15,7 @@ NG=$(python -c 'import torch; print(torch.cuda.device_count())')
 for algo in ppo ppo_full; do
   for n in 1 2 4 8; do
     [ "$n" -le "$NG" ] || { echo "[scale] skipping $algo x$n: only $NG device(s)"; continue; }
-    timeout 1200 python bench.py --algo $algo --gpus $n --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline \
+    timeout 1200 python bench.py --full --algo $algo --gpus $n --steps "$STEPS" --warmup "$WARM" --no-cpu-baseline \
       > "$OUT/${algo}_n${n}.json" 2> "$OUT/${algo}_n${n}.err" || echo "[scale] $algo x$n failed (rc $?): see $OUT/${algo}_n${n}.err"
   done
 done
