@@ -59,8 +59,10 @@ __global__ __launch_bounds__(kBlock) void replay_gather_kernel(
 }
 
 // random.sample(buffer, B) draws B DISTINCT rows: idx[b] = the b-th element of a keyed permutation of [0, size)
-// (gymrl_device.hpp keyed_permute, tag RNG_REPLAY folded into the key) — a uniform sample without replacement
-// with no rejection loop and no bookkeeping between lanes.
+// (gymrl_device.hpp keyed_permute, tag RNG_REPLAY folded into the key) — a sample without replacement whose
+// ordered pairs and marginals tests/test_rng_distributions.py holds to the uniform law (exact Fisher-Yates for
+// size <= 16, where a Feistel network on 2-4 bits is far from uniform), with no rejection loop and no
+// bookkeeping between lanes.
 struct UniformDev { uint64_t counter; int64_t size; };
 __global__ __launch_bounds__(kBlock) void uniform_indices_kernel(uint64_t seed, uint64_t counter,
                                                                  uint32_t size, int B, int a, int bbits,

@@ -311,10 +311,13 @@ int gymrl_rnd_reward(const float* predict, const float* target, int B, int E, fl
  * obs_out f32[B,D], act_out i32[B], logp_out/adv_out/ret_out f32[B].  D <= 12.
  */
 /* P6: the epoch shuffle — ppo_lunarlander.py:262 `np.random.shuffle(indices)`.  perm_out i32[M] = a keyed
- * bijection of [0, M) evaluated per element: 6 alternating Feistel rounds on ceil(log2 M) bits with a
- * Philox4x32-10 round function keyed by (seed, counter), cycle-walked into range.  One streaming write of 4M
- * bytes instead of torch.randperm's key sort (3.3 ms per epoch at M = 2^23).  Deterministic in (seed, counter, M);
- * any uniform-looking permutation serves the algorithm, and parity runs pass the reference's own order instead. */
+ * bijection of [0, M) evaluated per element (gymrl_device.hpp keyed_permute): for M <= 16 a Fisher-Yates draw
+ * over a 4-bit table in one register (uniform over the M! orders to 2^-24 relative); above, alternating Feistel
+ * rounds on ceil(log2 M) bits with a Philox4x32-10 round function keyed by (seed, counter), cycle-walked into
+ * range — 12 rounds below 10 bits (M <= 512), 6 from there up (M >= 513).  tests/test_rng_distributions.py holds the position x value,
+ * ordered-pair and minibatch co-membership laws to the uniform permutation's.  One streaming write of 4M bytes
+ * instead of torch.randperm's key sort (3.3 ms per epoch at M = 2^23).  Deterministic in (seed, counter, M);
+ * parity runs pass the reference's own order instead. */
 int gymrl_permutation(uint64_t seed, uint64_t counter, int64_t M, int32_t* perm_out, void* stream);
 int gymrl_pack_rollout(const float* obs, const int32_t* act, const float* logp,
                        const float* adv, const float* ret, int64_t M, int obs_dim,
@@ -886,8 +889,9 @@ int gymrl_replay_gather(const float* state, const uint32_t* action, const float*
                         int D, int AW, float* state_out, void* action_out, float* reward_out,
                         float* next_state_out, float* flag_out, void* stream);
 /* random.sample(buffer, B) (dqn_cartpole.py:76) / np.random.choice(size, B, replace=False)
- * (utils/buffer.py:127): B DISTINCT uniform rows — idx[b] = the b-th element of a keyed permutation of
- * [0, size) (the Feistel/Philox bijection of gymrl_permutation, keyed by (seed, counter)); B <= size. */
+ * (utils/buffer.py:127): B DISTINCT rows — idx[b] = the b-th element of a keyed permutation of [0, size) (the
+ * bijection of gymrl_permutation, keyed by (seed, counter)), so the ordered B-tuple follows the law of a uniform
+ * sample without replacement (tests/test_rng_distributions.py); B <= size. */
 int gymrl_uniform_indices(uint64_t seed, uint64_t counter, int64_t size, int B,
                           int32_t* idx_out, const void* dev, void* stream);
 

@@ -614,13 +614,26 @@ void orc_rnd_reward(const float* predict, const float* target, int B, int E, flo
   }
 }
 
-/* P6 epoch shuffle — ppo_lunarlander.py:262: the keyed bijection gymrl_permutation evaluates (6 alternating
- * Feistel rounds with a Philox round function, cycle-walked into [0, M)). */
+/* P6 epoch shuffle — ppo_lunarlander.py:262: the keyed bijection gymrl_permutation evaluates (gymrl_device.hpp
+ * keyed_permute): M <= 16 a Fisher-Yates draw over a 16 x 4-bit table, else alternating Feistel rounds with a
+ * Philox round function (12 below 10 bits, M <= 512; 6 from 10 bits up, M >= 513), cycle-walked into [0, M). */
+static uint32_t small_permute(uint32_t i, uint32_t M, uint64_t seed, uint64_t counter) {
+  const uint32_t c2 = (uint32_t)counter, c3 = 0x60000000u | ((uint32_t)(counter >> 32) & 0x0FFFFFFFu);
+  uint64_t t = 0xFEDCBA9876543210ull;
+  uint32_t w[4];
+  for (uint32_t n = 0; n + 1u < M; ++n) {
+    if ((n & 3u) == 0u) orc_philox(seed, n >> 2, 0xFFFFFFFFu, c2, c3, w);
+    const uint32_t k = M - 1u - n, j = (uint32_t)(((uint64_t)w[n & 3u] * (k + 1u)) >> 32);
+    const uint64_t d = ((t >> (4u * k)) ^ (t >> (4u * j))) & 15u;
+    t ^= (d << (4u * k)) | (d << (4u * j));
+  }
+  return (uint32_t)(t >> (4u * i)) & 15u;
+}
 static uint32_t feistel_once(uint32_t x, int a, int b, uint64_t seed, uint64_t counter) {
-  const uint32_t mask_lo = (1u << a) - 1u, mask_hi = (1u << b) - 1u;
+  const uint32_t mask_lo = (1u << a) - 1u, mask_hi = (1u << b) - 1u, rounds = a + b < 10 ? 12u : 6u;
   uint32_t lo = x & mask_lo, hi = x >> a, o[4];
   const uint32_t c2 = (uint32_t)counter, c3 = 0x60000000u | ((uint32_t)(counter >> 32) & 0x0FFFFFFFu);
-  for (uint32_t r = 0; r < 6; ++r) {
+  for (uint32_t r = 0; r < rounds; ++r) {
     if ((r & 1u) == 0u) { orc_philox(seed, hi, r, c2, c3, o); lo ^= o[0] & mask_lo; }
     else                { orc_philox(seed, lo, r, c2, c3, o); hi ^= o[0] & mask_hi; }
   }
@@ -631,6 +644,7 @@ void orc_permutation(uint64_t seed, uint64_t counter, int64_t M, int32_t* out) {
   while (((int64_t)1 << bits) < M) ++bits;
   const int a = bits / 2, b = bits - a;
   for (int64_t i = 0; i < M; ++i) {
+    if (M <= 16) { out[i] = (int32_t)small_permute((uint32_t)i, (uint32_t)M, seed, counter); continue; }
     uint32_t x = feistel_once((uint32_t)i, a, b, seed, counter);
     while (x >= (uint32_t)M) x = feistel_once(x, a, b, seed, counter);
     out[i] = (int32_t)x;

@@ -194,12 +194,26 @@ int orc_nstep_push(float* w_state, int32_t* w_action, float* w_reward, float* w_
 }
 
 /* random.sample / np.random.choice(replace=False): the first B elements of a keyed permutation of [0, size)
- * (the bijection of orc_permutation, gymrl_oracle.c, with the replay tag folded into the key). */
+ * (the bijection of orc_permutation, gymrl_oracle.c, with the replay tag folded into the key): size <= 16 a
+ * Fisher-Yates draw over a 16 x 4-bit table, else 12 (below 10 bits, size <= 512) or 6 Feistel
+ * rounds, cycle-walked. */
+static uint32_t replay_small(uint32_t i, uint32_t M, uint64_t seed, uint64_t counter) {
+  const uint32_t c2 = (uint32_t)counter, c3 = 0x60000000u | ((uint32_t)(counter >> 32) & 0x0FFFFFFFu);
+  uint64_t t = 0xFEDCBA9876543210ull;
+  uint32_t w[4];
+  for (uint32_t n = 0; n + 1u < M; ++n) {
+    if ((n & 3u) == 0u) orc_philox(seed, n >> 2, 0xFFFFFFFFu, c2, c3, w);
+    const uint32_t k = M - 1u - n, j = (uint32_t)(((uint64_t)w[n & 3u] * (k + 1u)) >> 32);
+    const uint64_t d = ((t >> (4u * k)) ^ (t >> (4u * j))) & 15u;
+    t ^= (d << (4u * k)) | (d << (4u * j));
+  }
+  return (uint32_t)(t >> (4u * i)) & 15u;
+}
 static uint32_t replay_feistel(uint32_t x, int a, int b, uint64_t seed, uint64_t counter) {
-  const uint32_t mask_lo = (1u << a) - 1u, mask_hi = (1u << b) - 1u;
+  const uint32_t mask_lo = (1u << a) - 1u, mask_hi = (1u << b) - 1u, rounds = a + b < 10 ? 12u : 6u;
   uint32_t lo = x & mask_lo, hi = x >> a, o[4];
   const uint32_t c2 = (uint32_t)counter, c3 = 0x60000000u | ((uint32_t)(counter >> 32) & 0x0FFFFFFFu);
-  for (uint32_t r = 0; r < 6; ++r) {
+  for (uint32_t r = 0; r < rounds; ++r) {
     if ((r & 1u) == 0u) { orc_philox(seed, hi, r, c2, c3, o); lo ^= o[0] & mask_lo; }
     else                { orc_philox(seed, lo, r, c2, c3, o); hi ^= o[0] & mask_hi; }
   }
@@ -211,6 +225,7 @@ void orc_uniform_indices(uint64_t seed, uint64_t counter, int64_t size, int B, i
   const int a = bits / 2, bb = bits - a;
   const uint64_t key = seed ^ 0x5265706C61794944ull;
   for (int b = 0; b < B; ++b) {
+    if (size <= 16) { idx[b] = (int32_t)replay_small((uint32_t)b, (uint32_t)size, key, counter); continue; }
     uint32_t x = replay_feistel((uint32_t)b, a, bb, key, counter);
     while (x >= (uint32_t)size) x = replay_feistel(x, a, bb, key, counter);
     idx[b] = (int32_t)x;
