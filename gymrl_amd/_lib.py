@@ -30,6 +30,7 @@ SYMBOLS = [
     "gymrl_reduce_workspace_bytes", "gymrl_moments", "gymrl_normalize",
     "gymrl_ppo_loss_fwd_bwd", "gymrl_ppo_full_loss_fwd_bwd", "gymrl_ppo_rnn_loss_fwd_bwd",
     "gymrl_gru_cell_fwd", "gymrl_gru_cell_bwd", "gymrl_rnd_reward", "gymrl_permutation",
+    "gymrl_gru_seq_fwd", "gymrl_gru_seq_bwd", "gymrl_episode_gae", "gymrl_ppg_policy_loss_fwd_bwd", "gymrl_ppg_aux_loss_fwd_bwd",
     "gymrl_pack_rollout", "gymrl_gather_minibatch", "gymrl_gather_rows", "gymrl_loss_blocks", "gymrl_reduce_rows",
     "gymrl_sqnorm", "gymrl_adam_step", "gymrl_clip_adam_step", "gymrl_adam_bias", "gymrl_store_scalars", "gymrl_soft_update",
     "gymrl_replay_append", "gymrl_replay_gather", "gymrl_uniform_indices", "gymrl_nstep_push",
@@ -54,6 +55,18 @@ SYMBOLS = [
     "gymrl_sac_update_workspace_bytes", "gymrl_sac_args_bytes", "gymrl_sac_act_step", "gymrl_sac_update", "gymrl_sac_step", "gymrl_sac_pack_images",
     "gymrl_rainbow_update_workspace_bytes", "gymrl_rainbow_args_bytes", "gymrl_rainbow_act_step", "gymrl_rainbow_update",
 ]
+
+
+_vp, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
+_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+# argtypes of the whole-episode recurrent entry points (len / offsets are HOST arrays)
+ARGTYPES = {
+    "gymrl_gru_seq_fwd": [_vp, _vp, _vp, _vp, _i32p, _i, _i, _i, _vp, _vp, _vp],
+    "gymrl_gru_seq_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "gymrl_episode_gae": [_vp, _vp, _vp, _vp, _vp, _i64p, _i, _d, _d, _vp, _vp, _vp, _vp, _vp],
+    "gymrl_ppg_policy_loss_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64p, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
+    "gymrl_ppg_aux_loss_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i64p, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+}
 
 
 def build(force=False):
@@ -255,6 +268,8 @@ def lib():
             if name.endswith(("_bytes", "_floats")):
                 continue
             getattr(L, name).restype = C.c_int
+        for name, at in ARGTYPES.items():
+            getattr(L, name).argtypes = at
         _lib = L
     return _lib
 

@@ -7,22 +7,20 @@
 //   gymrl_rnd_reward            collect_experience's intrinsic reward  rew += mean((predict - target)^2)
 //                               (:588-590), one wave per row
 //
-// Gate order and formulas are PyTorch's:  r = s(gi_r + gh_r), z = s(gi_z + gh_z),
-// n = tanh(gi_n + r * gh_n), h' = (1 - z) * n + z * h, with s(x) = 1 / (1 + exp(-x)) on the
+// Gate order and formulas are PyTorch's (gru_cell_device.hpp, shared with gru_seq.hip):  r = s(gi_r + gh_r),
+// z = s(gi_z + gh_z), n = tanh(gi_n + r * gh_n), h' = (1 - z) * n + z * h, with s(x) = 1 / (1 + exp(-x)) on the
 // reproducible det_expf so that the CPU oracle reproduces every bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/gymrl.h"
-#include "gymrl_device.hpp"
+#include "gru_cell_device.hpp"
 
 using namespace gymrl;
 
 namespace {
 
 constexpr int kBlock = 256;
-
-__device__ __forceinline__ float det_sigmoidf(float x) { return 1.0f / (1.0f + det_expf(-x)); }
 
 __global__ __launch_bounds__(kBlock) void gru_cell_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ gh,
                                                               const float* __restrict__ h, int B, int H,
@@ -40,13 +38,7 @@ __global__ __launch_bounds__(kBlock) void gru_cell_fwd_kernel(const float* __res
                  hn = *reinterpret_cast<const float4*>(ghr + 2 * H);
     const float4 hp = *reinterpret_cast<const float4*>(h + b * H + c);
     float4 o;
-#define GRU_FWD(x)                                         \
-  {                                                        \
-    const float r = det_sigmoidf(ir.x + hr.x);             \
-    const float z = det_sigmoidf(iz.x + hz.x);             \
-    const float n = det_tanhf_sel(in.x + r * hn.x);        \
-    o.x = (1.0f - z) * n + z * hp.x;                       \
-  }
+#define GRU_FWD(x) o.x = gru_point_fwd(ir.x, iz.x, in.x, hr.x, hz.x, hn.x, hp.x);
     GRU_FWD(x) GRU_FWD(y) GRU_FWD(z) GRU_FWD(w)
 #undef GRU_FWD
     *reinterpret_cast<float4*>(h_out + b * H + c) = o;
@@ -71,20 +63,7 @@ __global__ __launch_bounds__(kBlock) void gru_cell_bwd_kernel(const float* __res
     const float4 hp = *reinterpret_cast<const float4*>(h + b * H + c);
     const float4 go = *reinterpret_cast<const float4*>(dh_out + b * H + c);
     float4 dir, diz, din, dhn, dhp;
-#define GRU_BWD(x)                                         \
-  {                                                        \
-    const float r = det_sigmoidf(ir.x + hr.x);             \
-    const float z = det_sigmoidf(iz.x + hz.x);             \
-    const float n = det_tanhf_sel(in.x + r * hn.x);        \
-    const float dn = go.x * (1.0f - z);                    \
-    const float dz = go.x * (hp.x - n);                    \
-    const float dnp = dn * (1.0f - n * n);                 \
-    din.x = dnp;                                           \
-    dhn.x = dnp * r;                                       \
-    dir.x = (dnp * hn.x) * (r * (1.0f - r));               \
-    diz.x = dz * (z * (1.0f - z));                         \
-    dhp.x = go.x * z;                                      \
-  }
+#define GRU_BWD(x) gru_point_bwd(ir.x, iz.x, in.x, hr.x, hz.x, hn.x, hp.x, go.x, dir.x, diz.x, din.x, dhn.x, dhp.x);
     GRU_BWD(x) GRU_BWD(y) GRU_BWD(z) GRU_BWD(w)
 #undef GRU_BWD
     *reinterpret_cast<float4*>(dgi + g0) = dir;

@@ -234,6 +234,129 @@ def gru_cell_bwd(gi, gh, h, dh_out):
     return dgi, dgh, dh
 
 
+def _host_i32(x):
+    vals = [int(v) for v in (x.tolist() if hasattr(x, "tolist") else x)]
+    return (C.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+def _host_i64(x):
+    vals = [int(v) for v in (x.tolist() if hasattr(x, "tolist") else x)]
+    return (C.c_int64 * max(len(vals), 1))(*vals), len(vals)
+
+
+def _need_shape(t, shape, name):
+    """The host-side lengths / offsets steer the kernels' addressing: every tensor they index must have the shape
+    they imply (a mismatch would read or write past its end)."""
+    if t is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _gru_seq_shapes(gi, W_hh, b_hh, h0, lens_len, T, B, H, **more):
+    if gi.dim() != 3 or gi.shape[2] % 3:
+        raise ValueError(f"gi: expected [T, B, 3H], got {tuple(gi.shape)}")
+    if lens_len != B:
+        raise ValueError(f"lengths has {lens_len} entries for {B} episodes")
+    _need_shape(W_hh, (3 * H, H), "W_hh")
+    _need_shape(b_hh, (3 * H,), "b_hh")
+    _need_shape(h0, (B, H), "h0")
+    for name, (t, shape) in more.items():
+        _need_shape(t, shape, name)
+
+
+def _segments(offsets, M, what):
+    offs, n1 = _host_i64(offsets)
+    if n1 < 1 or offs[n1 - 1] != M:
+        raise ValueError(f"{what}: offsets must end at the {M} stored rows (got {list(offs)[-1:] if n1 else []})")
+    return offs, n1 - 1
+
+
+def gru_seq_fwd(gi, W_hh, b_hh, lengths, h0=None, h_seq=None, h_last=None):
+    """The GRU over whole episodes in one launch (gymrl_gru_seq_fwd).  gi f32[T,B,3H] time-major, lengths: host ints [B].
+    Returns (h_seq f32[T,B,H], zero past each length; h_last f32[B,H])."""
+    T, B, H3 = gi.shape
+    H = H3 // 3
+    lens, nb = _host_i32(lengths)
+    _gru_seq_shapes(gi, W_hh, b_hh, h0, nb, T, B, H, h_seq=(h_seq, (T, B, H)), h_last=(h_last, (B, H)))
+    h_seq = torch.empty(T, B, H, dtype=torch.float32, device=gi.device) if h_seq is None else h_seq
+    h_last = torch.empty(B, H, dtype=torch.float32, device=gi.device) if h_last is None else h_last
+    check(lib().gymrl_gru_seq_fwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
+                                  _ptr(h0, torch.float32, True), lens, T, B, H, _ptr(h_seq, torch.float32),
+                                  _ptr(h_last, torch.float32), _stream()), "gymrl_gru_seq_fwd")
+    return h_seq, h_last
+
+
+def gru_seq_bwd(gi, W_hh, b_hh, h_seq, lengths, d_hseq=None, d_hlast=None, h0=None, need_dh0=True):
+    """Reverse recurrence of gru_seq_fwd (gymrl_gru_seq_bwd).  Returns (dgi, dgh f32[T,B,3H], dh0 f32[B,H] or None)."""
+    T, B, H3 = gi.shape
+    H = H3 // 3
+    lens, nb = _host_i32(lengths)
+    _gru_seq_shapes(gi, W_hh, b_hh, h0, nb, T, B, H, h_seq=(h_seq, (T, B, H)), d_hseq=(d_hseq, (T, B, H)),
+                    d_hlast=(d_hlast, (B, H)))
+    dgi, dgh = torch.empty_like(gi), torch.empty_like(gi)
+    dh0 = torch.empty(B, H, dtype=torch.float32, device=gi.device) if need_dh0 else None
+    check(lib().gymrl_gru_seq_bwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
+                                  _ptr(h0, torch.float32, True), _ptr(h_seq, torch.float32),
+                                  _ptr(d_hseq, torch.float32, True), _ptr(d_hlast, torch.float32, True), lens, T, B, H,
+                                  _ptr(dgi), _ptr(dgh), _ptr(dh0, torch.float32, True), _stream()), "gymrl_gru_seq_bwd")
+    return dgi, dgh, dh0
+
+
+def episode_gae(rew, val, next_val, done, dw, offsets, gamma, lam, want_raw=False, ep_moments=None):
+    """EpisodeBuffer.compute_advantage per episode (ppg_rnn_lunarlander.py:198-215) over episodes stored back to back;
+    offsets: host ints [E+1].  Returns (adv_norm, v_target, adv_raw or None)."""
+    M = rew.numel()
+    offs, E = _segments(offsets, M, "episode_gae")
+    for name, t in (("val", val), ("next_val", next_val), ("done", done), ("dw", dw)):
+        _need_shape(t, (M,), name)
+    _need_shape(ep_moments, (E, 2), "ep_moments")
+    n1 = E + 1
+    adv_norm, vt = torch.empty_like(rew), torch.empty_like(rew)
+    raw = torch.empty_like(rew) if want_raw else None
+    check(lib().gymrl_episode_gae(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(next_val, torch.float32),
+                                  _ptr(done, torch.uint8), _ptr(dw, torch.uint8), offs, n1 - 1, float(gamma), float(lam),
+                                  _ptr(raw, torch.float32, True), _ptr(adv_norm), _ptr(vt),
+                                  _ptr(ep_moments, torch.float64, True), _stream()), "gymrl_episode_gae")
+    return adv_norm, vt, raw
+
+
+def ppg_policy_loss_fwd_bwd(logits, value, act, old_logp, adv, v_target, offsets, clip, dual_clip, val_coef, ent_coef,
+                            metrics_sum=None):
+    """L5 (ppg_rnn_lunarlander.py:330-370) over G episodes.  Returns (dlogits, dvalue, metrics_ep f64[G,5] =
+    (loss, clip_loss, value_loss, entropy_loss, adv mean) per episode)."""
+    M, A = logits.shape
+    offs, G = _segments(offsets, M, "ppg_policy_loss_fwd_bwd")
+    for name, t in (("value", value), ("act", act), ("old_logp", old_logp), ("adv", adv), ("v_target", v_target)):
+        _need_shape(t, (M,), name)
+    _need_shape(metrics_sum, (5,), "metrics_sum")
+    dlogits, dvalue = torch.empty_like(logits), torch.empty(M, dtype=torch.float32, device=logits.device)
+    metrics_ep = torch.empty(max(G, 1), 5, dtype=torch.float64, device=logits.device)
+    check(lib().gymrl_ppg_policy_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32),
+                                              _ptr(act, torch.int32), _ptr(old_logp, torch.float32),
+                                              _ptr(adv, torch.float32), _ptr(v_target, torch.float32), offs, G, A,
+                                              clip, dual_clip, val_coef, ent_coef, _ptr(dlogits), _ptr(dvalue),
+                                              _ptr(metrics_ep), _ptr(metrics_sum, torch.float64, True), _stream()),
+          "gymrl_ppg_policy_loss_fwd_bwd")
+    return dlogits, dvalue, metrics_ep
+
+
+def ppg_aux_loss_fwd_bwd(logits, aux_value, act, old_logp, v_target, offsets, beta, metrics_sum=None):
+    """L6 (ppg_rnn_lunarlander.py:372-393) over G episodes.  Returns (dlogits, d_aux, metrics_ep f64[G,3] =
+    (aux_value_loss, clone_loss, joint) per episode)."""
+    M, A = logits.shape
+    offs, G = _segments(offsets, M, "ppg_aux_loss_fwd_bwd")
+    for name, t in (("aux_value", aux_value), ("act", act), ("old_logp", old_logp), ("v_target", v_target)):
+        _need_shape(t, (M,), name)
+    _need_shape(metrics_sum, (3,), "metrics_sum")
+    dlogits, d_aux = torch.empty_like(logits), torch.empty(M, dtype=torch.float32, device=logits.device)
+    metrics_ep = torch.empty(max(G, 1), 3, dtype=torch.float64, device=logits.device)
+    check(lib().gymrl_ppg_aux_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(aux_value, torch.float32),
+                                           _ptr(act, torch.int32), _ptr(old_logp, torch.float32),
+                                           _ptr(v_target, torch.float32), offs, G, A, beta, _ptr(dlogits), _ptr(d_aux),
+                                           _ptr(metrics_ep), _ptr(metrics_sum, torch.float64, True), _stream()),
+          "gymrl_ppg_aux_loss_fwd_bwd")
+    return dlogits, d_aux, metrics_ep
+
+
 def rnd_reward(predict, target, rew_inout=None, rnd_out=None):
     B, E = predict.shape
     check(lib().gymrl_rnd_reward(_ptr(predict, torch.float32), _ptr(target, torch.float32), C.c_int(B), C.c_int(E),

@@ -302,6 +302,55 @@ int gymrl_gru_cell_bwd(const float* gi, const float* gh, const float* h, const f
 int gymrl_rnd_reward(const float* predict, const float* target, int B, int E, float* rew_inout,
                      float* rnd_out, void* stream);
 
+/* The GRU over whole episodes — ppg_rnn_lunarlander.py:125-140 (MLPRNN: nn.GRU(256, 64) fed one unbatched [T, 256]
+ * episode per call, hidden state reset per episode :335, :377) and the same in ppo_rnn_lunarlander.py.  B episodes in
+ * one time-major batch: gi f32[T,B,3H] = x W_ih^T + b_ih (one library GEMM), W_hh f32[3H,H], b_hh f32[3H], h0 f32[B,H]
+ * or NULL (zeros), len i32[B] a HOST array with 0 <= len[b] <= T.  Gate order and cell arithmetic are
+ * gymrl_gru_cell_fwd's.  _fwd writes h_seq f32[T,B,H] (zero for t >= len[b]) and h_last f32[B,H] = h_{len[b]-1}
+ * (h0 when len[b] == 0).  _bwd runs the reverse recurrence from the stored h_seq: d_hseq f32[T,B,H] and d_hlast f32[B,H]
+ * are the incoming gradients (either may be NULL = zeros); it writes dgi, dgh f32[T,B,3H] (zero for t >= len[b]) and
+ * dh0 f32[B,H] (may be NULL).  dW_hh = sum_t dgh_t^T h_{t-1}, db_hh, dW_ih and dx are the caller's GEMMs over the
+ * flattened rows.  One launch per 768 episodes, all T steps inside; H in {16, 32, 48, 64}; W_hh, h0, h_seq 16-byte
+ * aligned.  -22 on anything else, before any HIP call. */
+int gymrl_gru_seq_fwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const int32_t* len,
+                      int T, int B, int H, float* h_seq, float* h_last, void* stream);
+int gymrl_gru_seq_bwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const float* h_seq,
+                      const float* d_hseq, const float* d_hlast, const int32_t* len, int T, int B, int H, float* dgi,
+                      float* dgh, float* dh0, void* stream);
+
+/* EpisodeBuffer.compute_advantage — ppg_rnn_lunarlander.py:198-215 (== ppo_rnn_lunarlander.py), per episode, E
+ * episodes stored back to back: episode e is rows [offsets[e], offsets[e+1]) of the flat f32 / u8 arrays; offsets
+ * i64[E+1] a HOST array, offsets[0] == 0, no empty episode.  G2's arithmetic (gymrl_gae_dw): f32 td-error
+ * (rew + gamma*next_val*(1-dw)) - val, the f32 recursion gae = (gamma*lam)*gae*(1-done) + delta; v_target = adv + val;
+ * adv_norm = (adv - mean) / (std + 1e-8) with the episode's mean and unbiased std taken in f64 (a length-1 episode has
+ * std NaN and normalises to NaN, as it does in torch).  adv_raw f32 (may be NULL) = the unnormalised adv;
+ * ep_moments f64[E][2] (may be NULL) = (mean, std).  One workgroup per episode, 255 episodes per launch. */
+int gymrl_episode_gae(const float* rew, const float* val, const float* next_val, const uint8_t* done,
+                      const uint8_t* dw, const int64_t* offsets, int E, double gamma, double lam, float* adv_raw,
+                      float* adv_norm, float* v_target, double* ep_moments, void* stream);
+
+/* L5: PPG / PPO-RNN policy phase — ppg_rnn_lunarlander.py:330-370 over G episodes (offsets as gymrl_episode_gae).
+ * logits f32[M,A] (2 <= A <= 8) of probs = softmax(logits); Categorical(probs) semantics: p / sum p, every log
+ * log(clamp(p, FLT_EPSILON, 1 - FLT_EPSILON)).  Per episode: clip_loss = -mean(where(adv < 0, max(min(r*adv,
+ * clamp(r, 1-clip, 1+clip)*adv), dual_clip*adv), min(...))), value_loss = mean((v_target - value)^2), entropy_loss =
+ * -mean(H); loss = mean over episodes of clip_loss + val_coef*value_loss + ent_coef*entropy_loss.  Writes dlogits
+ * f32[M,A], dvalue f32[M], metrics_ep f64[G][5] = (loss, clip_loss, value_loss, entropy_loss, adv mean) of each
+ * episode, and metrics_sum f64[5] (may be NULL) += their mean over the G episodes.  act must lie in [0, A): an action
+ * outside makes its log-prob NaN, and with it that episode's loss, metrics and gradients (L6 alike). */
+int gymrl_ppg_policy_loss_fwd_bwd(const float* logits, const float* value, const int32_t* act,
+                                  const float* old_logp, const float* adv, const float* v_target,
+                                  const int64_t* offsets, int G, int A, float clip, float dual_clip, float val_coef,
+                                  float ent_coef, float* dlogits, float* dvalue, double* metrics_ep,
+                                  double* metrics_sum, void* stream);
+
+/* L6: PPG aux phase — ppg_rnn_lunarlander.py:372-393.  Per episode mse(v_target, aux_value) + beta *
+ * mse(log pi(a), old_logp) with L5's clamped log; loss = mean over episodes.  Writes dlogits, d_aux, metrics_ep
+ * f64[G][3] = (aux_value_loss, clone_loss, joint) and metrics_sum f64[3] (may be NULL) += their mean. */
+int gymrl_ppg_aux_loss_fwd_bwd(const float* logits, const float* aux_value, const int32_t* act,
+                               const float* old_logp, const float* v_target, const int64_t* offsets, int G, int A,
+                               float beta, float* dlogits, float* d_aux, double* metrics_ep, double* metrics_sum,
+                               void* stream);
+
 /*
  * P6/P7: minibatch staging — ppo_lunarlander.py:238-272 (lists -> tensors, shuffled
  * index slices).  gymrl_pack_rollout writes one 64-B record per transition
