@@ -31,6 +31,7 @@ SYMBOLS = [
     "gymrl_ppo_loss_fwd_bwd", "gymrl_ppo_full_loss_fwd_bwd", "gymrl_ppo_rnn_loss_fwd_bwd",
     "gymrl_gru_cell_fwd", "gymrl_gru_cell_bwd", "gymrl_rnd_reward", "gymrl_permutation",
     "gymrl_gru_seq_fwd", "gymrl_gru_seq_bwd", "gymrl_episode_gae", "gymrl_ppg_policy_loss_fwd_bwd", "gymrl_ppg_aux_loss_fwd_bwd",
+    "gymrl_mlprnn_params_bytes", "gymrl_mlprnn_act", "gymrl_running_norm_masked", "gymrl_reward_scaling_masked",
     "gymrl_pack_rollout", "gymrl_gather_minibatch", "gymrl_gather_rows", "gymrl_loss_blocks", "gymrl_reduce_rows",
     "gymrl_sqnorm", "gymrl_adam_step", "gymrl_clip_adam_step", "gymrl_adam_bias", "gymrl_store_scalars", "gymrl_soft_update",
     "gymrl_replay_append", "gymrl_replay_gather", "gymrl_uniform_indices", "gymrl_nstep_push",
@@ -66,6 +67,10 @@ ARGTYPES = {
     "gymrl_episode_gae": [_vp, _vp, _vp, _vp, _vp, _i64p, _i, _d, _d, _vp, _vp, _vp, _vp, _vp],
     "gymrl_ppg_policy_loss_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64p, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
     "gymrl_ppg_aux_loss_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i64p, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "gymrl_mlprnn_act": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp,
+                         _vp],
+    "gymrl_running_norm_masked": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp],
+    "gymrl_reward_scaling_masked": [_vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp],
 }
 
 
@@ -225,6 +230,13 @@ class PPOFullCfg(C.Structure):
                 ("entropy_coef_dev", C.c_void_p)]
 
 
+class MlprnnParams(C.Structure):           # gymrl_mlprnn_params (include/gymrl.h), field for field
+    _fields_ = ([("pscn_w", C.c_void_p * 4), ("pscn_b", C.c_void_p * 4), ("pscn_a", C.c_void_p * 4)] +
+                [(n, C.c_void_p) for n in ("lin_w", "lin_b", "w_ih", "b_ih", "w_hh", "b_hh", "actor_w1", "actor_b1", "actor_a",
+                                          "actor_w2", "actor_b2", "critic_w1", "critic_b1", "critic_a", "critic_w2",
+                                          "critic_b2")])
+
+
 def lib():
     """The loaded C-ABI library.  Raises (never falls back) when it is absent."""
     global _lib
@@ -256,6 +268,10 @@ def lib():
         L.gymrl_sac_args_bytes.restype = C.c_size_t
         L.gymrl_rainbow_update_workspace_bytes.restype = C.c_size_t
         L.gymrl_rainbow_args_bytes.restype = C.c_size_t
+        L.gymrl_mlprnn_params_bytes.restype = C.c_size_t
+        if L.gymrl_mlprnn_params_bytes() != C.sizeof(MlprnnParams):
+            raise RuntimeError("gymrl_amd/_lib.py: MlprnnParams does not mirror include/gymrl.h "
+                               f"({C.sizeof(MlprnnParams)} bytes here, {L.gymrl_mlprnn_params_bytes()} in the library)")
         if L.gymrl_rainbow_args_bytes(0) != C.sizeof(RainbowActArgs) or L.gymrl_rainbow_args_bytes(1) != C.sizeof(RainbowUpdateArgs):
             raise RuntimeError("gymrl_amd/_lib.py: RainbowActArgs / RainbowUpdateArgs do not mirror include/gymrl.h "
                                f"({C.sizeof(RainbowActArgs)} / {C.sizeof(RainbowUpdateArgs)} bytes here, "

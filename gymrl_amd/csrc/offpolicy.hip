@@ -267,8 +267,9 @@ __global__ void sac_alpha_step_kernel(double* __restrict__ log_alpha, double* __
 
 // ---------------------------------------------------------------- N1-N3 ------
 // One lane per feature; the N rows are consumed in order (the reference's single stream).
-__global__ void running_norm_kernel(const float* __restrict__ x, int N, int D, double* __restrict__ stats,
-                                    int update, float* __restrict__ y) {
+// live (may be NULL = all): rows with live == 0 are skipped — no update, no output (gymrl_running_norm_masked)
+__global__ void running_norm_kernel(const float* __restrict__ x, const uint8_t* __restrict__ live, int N, int D,
+                                    double* __restrict__ stats, int update, float* __restrict__ y) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   const bool valid = k < D;
   double n = stats[0];
@@ -276,6 +277,7 @@ __global__ void running_norm_kernel(const float* __restrict__ x, int N, int D, d
   double S = valid ? stats[2 + D + k] : 0.0;
   double std = valid ? stats[2 + 2 * D + k] : 0.0;
   for (int i = 0; valid && i < N; ++i) {
+    if (live && !live[i]) continue;
     const float xv = x[(size_t)i * D + k];
     if (update) {
       n += 1.0;
@@ -294,14 +296,15 @@ __global__ void running_norm_kernel(const float* __restrict__ x, int N, int D, d
   if (k == 0) stats[0] = n;
 }
 
-__global__ void reward_scaling_kernel(const float* __restrict__ r, const uint8_t* __restrict__ done, int N,
-                                      double gamma, double* __restrict__ R, double* __restrict__ stats,
-                                      float* __restrict__ y) {
+__global__ void reward_scaling_kernel(const float* __restrict__ r, const uint8_t* __restrict__ done,
+                                      const uint8_t* __restrict__ live, int N, double gamma, double* __restrict__ R,
+                                      double* __restrict__ stats, float* __restrict__ y) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double n = stats[0];
   float mean = (float)stats[2];
   double S = stats[3], std = stats[4];
   for (int i = 0; i < N; ++i) {
+    if (live && !live[i]) continue;
     const double rv = (double)r[i];
     R[i] = gamma * R[i] + rv;                                                 // :46
     const float xv = (float)R[i];                                             // update() casts to float32 (:13)
@@ -572,23 +575,33 @@ int gymrl_sac_alpha_step(double* log_alpha, double* m, double* v, const double* 
   return 0;
 }
 
-int gymrl_running_norm(const float* x, int N, int D, double* stats, int update, float* y_out, void* stream_) {
+int gymrl_running_norm_masked(const float* x, const uint8_t* live, int N, int D, double* stats, int update, float* y_out,
+                              void* stream_) {
   if (!x || !stats || !y_out || N < 0 || D <= 0 || D > 1024) return -22;
   if (N == 0) return 0;
-  hipLaunchKernelGGL(running_norm_kernel, dim3(1), dim3(((D + 63) / 64) * 64), 0, (hipStream_t)stream_, x, N, D,
+  hipLaunchKernelGGL(running_norm_kernel, dim3(1), dim3(((D + 63) / 64) * 64), 0, (hipStream_t)stream_, x, live, N, D,
                      stats, update, y_out);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+int gymrl_running_norm(const float* x, int N, int D, double* stats, int update, float* y_out, void* stream_) {
+  return gymrl_running_norm_masked(x, nullptr, N, D, stats, update, y_out, stream_);
+}
+
+int gymrl_reward_scaling_masked(const float* r, const uint8_t* done, const uint8_t* live, int N, double gamma, double* R,
+                                double* stats, float* y_out, void* stream_) {
+  if (!r || !R || !stats || !y_out || N < 0) return -22;
+  if (N == 0) return 0;
+  hipLaunchKernelGGL(reward_scaling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, r, done, live, N, gamma, R,
+                     stats, y_out);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
 
 int gymrl_reward_scaling(const float* r, const uint8_t* done, int N, double gamma, double* R, double* stats,
                          float* y_out, void* stream_) {
-  if (!r || !R || !stats || !y_out || N < 0) return -22;
-  if (N == 0) return 0;
-  hipLaunchKernelGGL(reward_scaling_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, r, done, N, gamma, R,
-                     stats, y_out);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
+  return gymrl_reward_scaling_masked(r, done, nullptr, N, gamma, R, stats, y_out, stream_);
 }
 
 int gymrl_noisy_action(const float* mu, const double* eps, uint64_t seed, uint64_t counter, int64_t n, int mode,

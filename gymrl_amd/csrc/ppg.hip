@@ -8,7 +8,8 @@
 //   gymrl_ppg_aux_loss_fwd_bwd     L6, the aux phase (:372-393): mse(v_target, aux) + beta * mse(log pi(a), old_logp)
 //
 // The policy is torch's Categorical(probs) over probs = softmax(logits): probs are renormalised p / sum(p) and every log is
-// log(clamp(p, eps, 1 - eps)) with eps = FLT_EPSILON (log_prob and entropy alike).  clamp passes the gradient on its closed
+// log(clamp(p, eps, 1 - eps)) with eps = FLT_EPSILON (log_prob and entropy alike; clamped_policy_device.hpp, shared with
+// the acting step gymrl_mlprnn_act).  clamp passes the gradient on its closed
 // interval and blocks it outside, so a saturated probability gets no gradient through its log (a log-softmax form would).
 // torch.min / torch.max ties split the gradient in half, as in the L1 kernel (policy_device.hpp ppo_loss_row).
 // A minibatch of G episodes has loss = mean over episodes of each episode's mean: at G = 1 the reference's loss exactly.
@@ -18,7 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/gymrl.h"
-#include "gymrl_device.hpp"
+#include "clamped_policy_device.hpp"
 
 using namespace gymrl;
 
@@ -106,34 +107,7 @@ struct LossCfg {
   float inv_G;
 };
 
-constexpr float kEps = 1.1920928955078125e-07f;       // torch.finfo(torch.float32).eps
-constexpr float kOneMinusEps = 0.99999988079071044921875f;
-
-// Categorical(softmax(z)) as torch builds it from probs.  p: softmax, S = sum p, p2 = p / S, L = log(clamp(p2, eps, 1 - eps)).
-template <int A>
-__device__ __forceinline__ void clamped_policy(const float (&z)[A], float (&p)[A], float& S, float (&p2)[A], float (&L)[A],
-                                               float (&c)[A], bool (&inb)[A]) {
-  float m = z[0];
-#pragma unroll
-  for (int k = 1; k < A; ++k) m = fmaxf(m, z[k]);
-  float s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < A; ++k) { p[k] = det_expf(z[k] - m); s += p[k]; }
-#pragma unroll
-  for (int k = 0; k < A; ++k) p[k] = p[k] / s;
-  S = 0.0f;
-#pragma unroll
-  for (int k = 0; k < A; ++k) S += p[k];
-#pragma unroll
-  for (int k = 0; k < A; ++k) {
-    p2[k] = p[k] / S;
-    inb[k] = p2[k] >= kEps && p2[k] <= kOneMinusEps;
-    c[k] = fminf(fmaxf(p2[k], kEps), kOneMinusEps);
-    L[k] = det_logf(c[k]);
-  }
-}
-
-// gradients wrt (L, p2 directly) -> wrt the logits
+// gradients wrt (L, p2 directly) -> wrt the logits; the forward half is clamped_policy (clamped_policy_device.hpp)
 template <int A>
 __device__ __forceinline__ void clamped_policy_bwd(const float (&p)[A], float S, const float (&c)[A], const bool (&inb)[A],
                                                    const float (&gL)[A], const float (&gp2d)[A], float (&gz)[A]) {

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, GaeOnline,
-                   MlpDesc, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    check, lib)
 
 _vp = C.c_void_p
@@ -355,6 +355,52 @@ def ppg_aux_loss_fwd_bwd(logits, aux_value, act, old_logp, v_target, offsets, be
                                            _ptr(metrics_ep), _ptr(metrics_sum, torch.float64, True), _stream()),
           "gymrl_ppg_aux_loss_fwd_bwd")
     return dlogits, d_aux, metrics_ep
+
+
+def mlprnn_params(net):
+    """gymrl_mlprnn_params of a PSCN -> MLPRNN -> actor_fc / critic_fc network (ppg_rnn_lunarlander.py:143-176): the
+    parameters' own device addresses.  They are views of the flat buffer the optimiser updates in place, so one descriptor
+    serves the whole run.  The float4-read weights must be 16-byte aligned (flatten_module aligns every view)."""
+    P = MlprnnParams()
+    for i, layer in enumerate(net.fc_head.layers):
+        lin, act = layer.mlp[0], layer.mlp[1]
+        P.pscn_w[i], P.pscn_b[i], P.pscn_a[i] = _addr(lin.weight), _addr(lin.bias), _addr(act.weight)
+    P.lin_w, P.lin_b = _addr(net.rnn.rnn_linear.mlp[0].weight), _addr(net.rnn.rnn_linear.mlp[0].bias)
+    g = net.rnn.rnn
+    P.w_ih, P.b_ih, P.w_hh, P.b_hh = (_addr(t) for t in (g.weight_ih_l0, g.bias_ih_l0, g.weight_hh_l0, g.bias_hh_l0))
+    a, c = net.actor_fc.mlp, net.critic_fc.mlp
+    P.actor_w1, P.actor_b1, P.actor_a, P.actor_w2, P.actor_b2 = (_addr(t) for t in (a[0].weight, a[0].bias, a[1].weight,
+                                                                                  a[2].weight, a[2].bias))
+    P.critic_w1, P.critic_b1, P.critic_a, P.critic_w2, P.critic_b2 = (_addr(t) for t in (c[0].weight, c[0].bias, c[1].weight,
+                                                                                       c[2].weight, c[2].bias))
+    for t in [p for p in net.parameters()]:
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("mlprnn_params: every parameter must be a contiguous f32 device tensor")
+    return P
+
+
+def mlprnn_act(x, h_in, params, A, live=None, noise_exp=None, seed=0, counter=0, env_id0=0, deterministic=False,
+               h_out=None, act_out=None, logp_out=None, value_out=None, probs_out=None):
+    """gymrl_mlprnn_act: the network's single-step forward for N envs + the Categorical draw, one launch
+    (ppg_rnn_lunarlander.py:311-328).  x f32[N,D], h_in f32[N,64]; h_out may be h_in.  Returns (act i32[N], logp f32[N],
+    value f32[N], h_out f32[N,64], probs f32[N,A] or None).  Rows with live == 0 are not written."""
+    N, D = x.shape
+    dev = x.device
+    _need_shape(h_in, (N, 64), "h_in")
+    for name, t, shape in (("live", live, (N,)), ("noise_exp", noise_exp, (N, A)), ("h_out", h_out, (N, 64)),
+                           ("act_out", act_out, (N,)), ("logp_out", logp_out, (N,)), ("value_out", value_out, (N,)),
+                           ("probs_out", probs_out, (N, A))):
+        _need_shape(t, shape, name)
+    h_out = torch.empty_like(h_in) if h_out is None else h_out
+    act_out = torch.empty(N, dtype=torch.int32, device=dev) if act_out is None else act_out
+    logp_out = torch.empty(N, dtype=torch.float32, device=dev) if logp_out is None else logp_out
+    value_out = torch.empty(N, dtype=torch.float32, device=dev) if value_out is None else value_out
+    check(lib().gymrl_mlprnn_act(_ptr(x, torch.float32), _ptr(h_in, torch.float32), C.byref(params), N, D, int(A),
+                                 _ptr(live, torch.uint8, True), _ptr(noise_exp, torch.float32, True), seed, counter, env_id0,
+                                 int(bool(deterministic)), _ptr(h_out, torch.float32), _ptr(act_out, torch.int32),
+                                 _ptr(logp_out, torch.float32), _ptr(value_out, torch.float32),
+                                 _ptr(probs_out, torch.float32, True), _stream()), "gymrl_mlprnn_act")
+    return act_out, logp_out, value_out, h_out, probs_out
 
 
 def rnd_reward(predict, target, rew_inout=None, rnd_out=None):
@@ -780,6 +826,26 @@ def running_norm(x, stats, update=True, out=None):
     out = torch.empty_like(x) if out is None else out
     check(lib().gymrl_running_norm(_ptr(x, torch.float32), C.c_int(N), C.c_int(D), _ptr(stats, torch.float64),
                                    C.c_int(int(update)), _ptr(out, torch.float32), _stream()), "gymrl_running_norm")
+    return out
+
+
+def running_norm_masked(x, live, stats, update=True, out=None):
+    """running_norm over the rows with live != 0 only, in row order; dead rows of `out` are left as they are."""
+    N, D = x.shape
+    _need_shape(live, (N,), "live")
+    out = torch.empty_like(x) if out is None else out
+    check(lib().gymrl_running_norm_masked(_ptr(x, torch.float32), _ptr(live, torch.uint8), N, D, _ptr(stats, torch.float64),
+                                          int(update), _ptr(out, torch.float32), _stream()), "gymrl_running_norm_masked")
+    return out
+
+
+def reward_scaling_masked(r, live, gamma, R, stats, done=None, out=None):
+    """reward_scaling over the rows with live != 0 only (R of a dead row is left as it is)."""
+    _need_shape(live, (r.numel(),), "live")
+    out = torch.empty_like(r) if out is None else out
+    check(lib().gymrl_reward_scaling_masked(_ptr(r, torch.float32), _ptr(done, torch.uint8, True), _ptr(live, torch.uint8),
+                                            r.numel(), float(gamma), _ptr(R, torch.float64), _ptr(stats, torch.float64),
+                                            _ptr(out, torch.float32), _stream()), "gymrl_reward_scaling_masked")
     return out
 
 

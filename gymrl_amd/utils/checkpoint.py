@@ -20,12 +20,18 @@ def _offsets(model):
     return [(p, (p.data_ptr() - flat.data_ptr()) // 4, p.numel()) for p in model.parameters()]
 
 
-def adam_state_dict(model, opt):
-    """FusedAdam -> torch.optim.Adam.state_dict() layout (parameters in model.parameters() order)."""
+def adam_state_dict(model, opt, steps=None):
+    """FusedAdam -> torch.optim.Adam.state_dict() layout (parameters in model.parameters() order).  steps (optional): the
+    step count of every parameter, for optimisers that skip some parameters in some steps (torch.optim.Adam keeps no
+    state for a parameter it has never stepped); None: all share opt.step_count."""
     state = {}
-    if opt.step_count > 0:
+    if steps is None:
+        steps = [opt.step_count] * len(list(model.parameters()))
+    if max(steps, default=0) > 0:
         for i, (p, off, n) in enumerate(_offsets(model)):
-            state[i] = {"step": torch.tensor(float(opt.step_count)),
+            if steps[i] <= 0:
+                continue
+            state[i] = {"step": torch.tensor(float(steps[i])),
                         "exp_avg": opt.m[off:off + n].view(p.shape).detach().cpu().clone(),
                         "exp_avg_sq": opt.v[off:off + n].view(p.shape).detach().cpu().clone()}
     g = opt.param_groups[0]
@@ -35,20 +41,26 @@ def adam_state_dict(model, opt):
     return {"state": state, "param_groups": [group]}
 
 
-def load_adam_state_dict(model, opt, sd):
-    """torch.optim.Adam-format dict -> FusedAdam's flat moments (all parameters share one step)."""
+def load_adam_state_dict(model, opt, sd, per_param=False):
+    """torch.optim.Adam-format dict -> FusedAdam's flat moments (all parameters share one step).  per_param=True: the
+    step counts may differ; they are returned (model.parameters() order, 0 where there is no state) and opt.step_count
+    is left alone."""
     g = sd["param_groups"][0]
     opt.param_groups[0].update(lr=float(g["lr"]), betas=tuple(g["betas"]), eps=float(g["eps"]))
     steps = set()
+    per = []
     opt.m.zero_()
     opt.v.zero_()
     for i, (p, off, n) in enumerate(_offsets(model)):
         st = sd["state"].get(i)
+        per.append(0 if st is None else int(float(st["step"])))
         if st is None:
             continue
         steps.add(int(float(st["step"])))
         opt.m[off:off + n].copy_(st["exp_avg"].reshape(-1).to(opt.m.device, torch.float32))
         opt.v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1).to(opt.v.device, torch.float32))
+    if per_param:
+        return per
     if len(steps) > 1:
         raise ValueError(f"parameters with different Adam step counts {sorted(steps)} cannot share a fused step")
     opt.step_count = steps.pop() if steps else 0

@@ -351,6 +351,47 @@ int gymrl_ppg_aux_loss_fwd_bwd(const float* logits, const float* aux_value, cons
                                float beta, float* dlogits, float* d_aux, double* metrics_ep, double* metrics_sum,
                                void* stream);
 
+/* The acting step of the PPG / PPO-RNN trainers — ppg_rnn_lunarlander.py:311-328 (choose_action / evaluate_action) over
+ * ActorCriticPPG.forward :165-176 for N envs in ONE launch: PSCN(D, 256) (:92-122: four Linear -> PReLU layers 256, 128,
+ * 64, 32 wide, each layer's first half kept, its second half fed on), MLPRNN(256, 256) (:125-140: cat(rnn_linear(x), one
+ * nn.GRU(256, 64) step)), actor_fc MLP([256, 64, A]) and critic_fc MLP([256, 32, 1]) (:156-157; one PReLU slope per MLP),
+ * probs = softmax(logits).  Every pointer of gymrl_mlprnn_params is the nn.Module parameter in its torch layout (Linear
+ * weights [out, in] row-major, PReLU slopes f32[1], GRU weights in gate order r, z, n); the weights marked (16) are read
+ * with 16-byte loads and must be 16-byte aligned.  Exact f32 throughout (MFMA f32 products, no reduced precision).
+ *   x f32[N,D] (1 <= D <= 16), h_in f32[N,64]; h_out f32[N,64] (may be h_in) = the GRU cell of gymrl_gru_cell_fwd on
+ *   the step's gi, gh; value f32[N]; probs f32[N,A] (may be NULL) = softmax; act i32[N]: with deterministic, the first
+ *   maximum of probs (evaluate_action); otherwise Categorical(probs).sample() = argmax_k p_k / q_k over p / sum p with
+ *   q ~ Exp(1) from noise_exp f32[N,A] (may be NULL) or Philox keyed (seed, counter, env_id0 + row) as in
+ *   gymrl_categorical_sample; logp f32[N] = log(clamp(p_a / sum p, FLT_EPSILON, 1 - FLT_EPSILON)), the expression of
+ *   L5 / L6.  live u8[N] (may be NULL = all): rows with live == 0 write nothing.  2 <= A <= 8, 0 <= N <= 2^24; -22 on
+ *   anything else (NULL required pointers, misaligned weights) before any HIP call.  One workgroup per 16 envs. */
+typedef struct gymrl_mlprnn_params {
+  const float* pscn_w[4];   /* fc_head.layers.i.mlp.0.weight: [256,D], [128,128] (16), [64,64] (16), [32,32] (16) */
+  const float* pscn_b[4];
+  const float* pscn_a[4];   /* fc_head.layers.i.mlp.1.weight (PReLU) */
+  const float* lin_w;       /* rnn.rnn_linear.mlp.0.weight [192,256] (16) */
+  const float* lin_b;
+  const float* w_ih;        /* rnn.rnn.weight_ih_l0 [192,256] (16) */
+  const float* b_ih;
+  const float* w_hh;        /* rnn.rnn.weight_hh_l0 [192,64] (16) */
+  const float* b_hh;
+  const float* actor_w1;    /* actor_fc.mlp.0.weight [64,256] (16) */
+  const float* actor_b1;
+  const float* actor_a;     /* actor_fc.mlp.1.weight */
+  const float* actor_w2;    /* actor_fc.mlp.2.weight [A,64] */
+  const float* actor_b2;
+  const float* critic_w1;   /* critic_fc.mlp.0.weight [32,256] (16) */
+  const float* critic_b1;
+  const float* critic_a;
+  const float* critic_w2;   /* critic_fc.mlp.2.weight [1,32] */
+  const float* critic_b2;
+} gymrl_mlprnn_params;
+size_t gymrl_mlprnn_params_bytes(void);   /* sizeof(gymrl_mlprnn_params): a binding checks its mirror */
+int gymrl_mlprnn_act(const float* x, const float* h_in, const gymrl_mlprnn_params* params, int N, int D, int A,
+                     const uint8_t* live, const float* noise_exp, uint64_t seed, uint64_t counter, int64_t env_id0,
+                     int deterministic, float* h_out, int32_t* act, float* logp, float* value, float* probs,
+                     void* stream);
+
 /*
  * P6/P7: minibatch staging — ppo_lunarlander.py:238-272 (lists -> tensors, shuffled
  * index slices).  gymrl_pack_rollout writes one 64-B record per transition
@@ -1136,6 +1177,12 @@ int gymrl_running_norm(const float* x, int N, int D, double* stats, int update, 
                        void* stream);
 int gymrl_reward_scaling(const float* r, const uint8_t* done, int N, double gamma, double* R,
                          double* stats, float* y_out, void* stream);
+/* The same over the rows with live u8[N] != 0 only (the PPG / PPO-RNN trainers' finished envs of a round, which the
+ * reference never steps): dead rows neither update the statistics nor R, and their outputs are not written. */
+int gymrl_running_norm_masked(const float* x, const uint8_t* live, int N, int D, double* stats, int update,
+                              float* y_out, void* stream);
+int gymrl_reward_scaling_masked(const float* r, const uint8_t* done, const uint8_t* live, int N, double gamma,
+                                double* R, double* stats, float* y_out, void* stream);
 
 /* ============================================ fused off-policy vector step ===== */
 /*
