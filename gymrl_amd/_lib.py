@@ -20,60 +20,6 @@ ABI_VERSION = 3      # == GYMRL_ABI_VERSION of the include/gymrl.h this front-en
 
 _lib = None
 
-# every symbol include/gymrl.h declares (tests/test_abi.py checks the export table)
-SYMBOLS = [
-    "gymrl_abi_version", "gymrl_device_ok",
-    "gymrl_env_obs_dim", "gymrl_env_act_dim", "gymrl_env_is_discrete", "gymrl_env_max_steps",
-    "gymrl_env_state_bytes", "gymrl_env_reset", "gymrl_env_step", "gymrl_env_refill", "gymrl_env_abandon",
-    "gymrl_categorical_sample",
-    "gymrl_gae_workspace_bytes", "gymrl_gae", "gymrl_gae_online_flush", "gymrl_gae_chunk", "gymrl_gae_dw", "gymrl_gae_decoupled", "gymrl_gae_decoupled_workspace_bytes",
-    "gymrl_reduce_workspace_bytes", "gymrl_moments", "gymrl_normalize",
-    "gymrl_ppo_loss_fwd_bwd", "gymrl_ppo_full_loss_fwd_bwd", "gymrl_ppo_rnn_loss_fwd_bwd",
-    "gymrl_gru_cell_fwd", "gymrl_gru_cell_bwd", "gymrl_rnd_reward", "gymrl_permutation",
-    "gymrl_gru_seq_fwd", "gymrl_gru_seq_bwd", "gymrl_episode_gae", "gymrl_ppg_policy_loss_fwd_bwd", "gymrl_ppg_aux_loss_fwd_bwd",
-    "gymrl_mlprnn_params_bytes", "gymrl_mlprnn_act", "gymrl_running_norm_masked", "gymrl_reward_scaling_masked",
-    "gymrl_pack_rollout", "gymrl_gather_minibatch", "gymrl_gather_rows", "gymrl_loss_blocks", "gymrl_reduce_rows",
-    "gymrl_sqnorm", "gymrl_adam_step", "gymrl_clip_adam_step", "gymrl_adam_bias", "gymrl_store_scalars", "gymrl_soft_update",
-    "gymrl_replay_append", "gymrl_replay_gather", "gymrl_uniform_indices", "gymrl_nstep_push",
-    "gymrl_per_workspace_bytes", "gymrl_per_update", "gymrl_per_max_leaf", "gymrl_per_priorities", "gymrl_per_update_td",
-    "gymrl_per_sample", "gymrl_noisy_noise", "gymrl_epsilon_greedy", "gymrl_dqn_td_loss",
-    "gymrl_sac_sample_fwd", "gymrl_sac_sample_bwd", "gymrl_sac_target", "gymrl_sac_critic_loss",
-    "gymrl_sac_actor_loss", "gymrl_sac_alpha_step", "gymrl_running_norm", "gymrl_reward_scaling",
-    "gymrl_noisy_action", "gymrl_mse_loss", "gymrl_neg_mean_loss",
-    "gymrl_dsac_target", "gymrl_dsac_critic_loss", "gymrl_dsac_actor_loss", "gymrl_dsac_alpha_step",
-    "gymrl_mlp_packed_floats", "gymrl_mlp_pack", "gymrl_mlp_forward",
-    "gymrl_mlp_train_workspace_bytes", "gymrl_linear_tanh_smallk", "gymrl_linear_smallk", "gymrl_tanh_inplace", "gymrl_tanh_bwd_colsum",
-    "gymrl_linear_smallk_bwd", "gymrl_heads_fwd_tanh", "gymrl_heads_bwd", "gymrl_rollout_lunar", "gymrl_rollout_cartpole",
-    "gymrl_gemm_workspace_bytes", "gymrl_linear_fwd", "gymrl_linear_bwd_input", "gymrl_linear_bwd_input_add",
-    "gymrl_linear_bwd_weight_geometry", "gymrl_linear_bwd_weight",
-    "gymrl_heads_loss_blocks", "gymrl_heads_loss_fwd_bwd", "gymrl_update_finalize",
-    "gymrl_lin_workspace_bytes", "gymrl_lin_fwd", "gymrl_lin_bwd_input", "gymrl_lin_bwd_weight",
-    "gymrl_noisy_combine", "gymrl_noisy_combine_images", "gymrl_noisy_split", "gymrl_dueling_bwd",
-    "gymrl_mhc_gates", "gymrl_mhc_combine", "gymrl_rmsnorm", "gymrl_sinkhorn",
-    "gymrl_mhc_read_fwd", "gymrl_mhc_read_bwd", "gymrl_mhc_combine_bwd",
-    "gymrl_mhc_gates_bwd_workspace_bytes", "gymrl_mhc_gates_bwd", "gymrl_rmsnorm_bwd_workspace_bytes", "gymrl_rmsnorm_bwd", "gymrl_rmsnorm_sum_bwd", "gymrl_norm_proj_fwd", "gymrl_norm_proj_bwd_workspace_bytes", "gymrl_norm_proj_bwd",
-    "gymrl_mhc_policy_forward", "gymrl_mhc_policy_image_floats", "gymrl_mhc_policy_pack", "gymrl_mhc_sub_forward", "gymrl_mhc_sub_backward", "gymrl_rollout_lunar_mhc",
-    "gymrl_sac_update_workspace_bytes", "gymrl_sac_args_bytes", "gymrl_sac_act_step", "gymrl_sac_update", "gymrl_sac_step", "gymrl_sac_pack_images",
-    "gymrl_rainbow_update_workspace_bytes", "gymrl_rainbow_args_bytes", "gymrl_rainbow_act_step", "gymrl_rainbow_update",
-]
-
-
-_vp, _f, _i, _d = C.c_void_p, C.c_float, C.c_int, C.c_double
-_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-# argtypes of the whole-episode recurrent entry points (len / offsets are HOST arrays)
-ARGTYPES = {
-    "gymrl_gru_seq_fwd": [_vp, _vp, _vp, _vp, _i32p, _i, _i, _i, _vp, _vp, _vp],
-    "gymrl_gru_seq_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "gymrl_episode_gae": [_vp, _vp, _vp, _vp, _vp, _i64p, _i, _d, _d, _vp, _vp, _vp, _vp, _vp],
-    "gymrl_ppg_policy_loss_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64p, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
-    "gymrl_ppg_aux_loss_fwd_bwd": [_vp, _vp, _vp, _vp, _vp, _i64p, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "gymrl_mlprnn_act": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, C.c_uint64, C.c_uint64, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp,
-                         _vp],
-    "gymrl_running_norm_masked": [_vp, _vp, _i, _i, _vp, _i, _vp, _vp],
-    "gymrl_reward_scaling_masked": [_vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp],
-}
-
-
 def build(force=False):
     """Compile the HIP library in-tree (cross-compiles without a GPU)."""
     if force:
@@ -83,13 +29,13 @@ def build(force=False):
 
 
 class LinItem(C.Structure):
-    """gymrl_lin_item (include/gymrl.h)."""
+    _c_name_ = "gymrl_lin_item"
     _fields_ = ([(n, C.c_void_p) for n in ("x", "x2", "w", "b", "y", "dy", "dx", "dx2", "dw", "db")] +
                 [("act", C.c_int), ("lo", C.c_float), ("hi", C.c_float), ("argmax", C.c_void_p)])
 
 
 class NoisyLayer(C.Structure):
-    """gymrl_noisy_layer (include/gymrl.h)."""
+    _c_name_ = "gymrl_noisy_layer"
     _fields_ = ([(n, C.c_void_p) for n in ("w_mu", "w_sigma", "w_eps", "b_mu", "b_sigma", "b_eps", "w_eps_copy", "b_eps_copy",
                                           "dw_mu", "dw_sigma", "db_mu", "db_sigma")] +
                 [("seed", C.c_uint64), ("counter", C.c_uint64), ("counter_dev", C.c_void_p), ("draw", C.c_int),
@@ -97,29 +43,31 @@ class NoisyLayer(C.Structure):
 
 
 class MhcSub(C.Structure):
-    """gymrl_mhc_sub (include/gymrl.h)."""
+    _c_name_ = "gymrl_mhc_sub"
     _fields_ = [(n, C.c_void_p) for n in ("norm_w", "w", "alpha", "beta", "lin_w", "lin_b")]
 
 
 class MhcHead(C.Structure):
-    """gymrl_mhc_head (include/gymrl.h)."""
+    _c_name_ = "gymrl_mhc_head"
     _fields_ = [("w1", C.c_void_p), ("b1", C.c_void_p), ("norm_w", C.c_void_p), ("norm_eps", C.c_float), ("w2", C.c_void_p),
                 ("b2", C.c_void_p)]
 
 
 class MhcPolicy(C.Structure):
-    """gymrl_mhc_policy (include/gymrl.h)."""
+    _c_name_ = "gymrl_mhc_policy"
     _fields_ = [("obs_dim", C.c_int), ("n_sub", C.c_int), ("n_act", C.c_int), ("sk_it", C.c_int), ("in_w", C.c_void_p),
                 ("in_b", C.c_void_p), ("sub", MhcSub * 8), ("final_norm_w", C.c_void_p), ("final_norm_eps", C.c_float),
                 ("head", MhcHead * 2), ("image", C.c_void_p)]
 
 
 class PPOCfg(C.Structure):
+    _c_name_ = "gymrl_ppo_cfg"
     _fields_ = [("clip_eps", C.c_float), ("dual_clip", C.c_float), ("value_coef", C.c_float),
                 ("entropy_coef", C.c_float)]
 
 
 class GaeOnline(C.Structure):
+    _c_name_ = "gymrl_gae_online"
     _fields_ = [("rew_prev", C.c_void_p), ("done_prev", C.c_void_p), ("val_prev", C.c_void_p),
                 ("running", C.c_void_p), ("gae_workspace", C.c_void_p), ("t_prev", C.c_int), ("T", C.c_int),
                 ("gamma", C.c_double), ("lam", C.c_double), ("lam2", C.c_double), ("running2", C.c_void_p)]
@@ -130,15 +78,18 @@ ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2
 
 
 class MlpStage(C.Structure):
+    _c_name_ = "gymrl_mlp_stage"
     _fields_ = [("W", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("in_dim", C.c_int),
                 ("out_dim", C.c_int), ("act", C.c_int), ("src", C.c_int), ("dst", C.c_int), ("out_stride", C.c_int)]
 
 
 class MlpDesc(C.Structure):
+    _c_name_ = "gymrl_mlp_desc"
     _fields_ = [("n_stages", C.c_int), ("stage", MlpStage * MLP_MAX_STAGES)]
 
 
 class RolloutLunarArgs(C.Structure):
+    _c_name_ = "gymrl_rollout_lunar_args"
     _fields_ = [("env_state", C.c_void_p), ("n_envs", C.c_int), ("seed", C.c_uint64), ("env_id0", C.c_int64),
                 ("counter0", C.c_uint64), ("obs", C.c_void_p), ("act", C.c_void_p), ("logp", C.c_void_p),
                 ("val", C.c_void_p), ("rew", C.c_void_p), ("done", C.c_void_p), ("ep_ret", C.c_void_p),
@@ -149,15 +100,18 @@ class RolloutLunarArgs(C.Structure):
                 ("refill", C.c_int), ("gae_carry", C.c_int)]
 
 
-class SacActorParams(C.Structure):        # gymrl_sac_actor_params: fc1, fc2, mean, log_std
+class SacActorParams(C.Structure):
+    _c_name_ = "gymrl_sac_actor_params"   # fc1, fc2, mean, log_std
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
 
 
-class SacCriticParams(C.Structure):       # gymrl_sac_critic_params: fc1..fc6
+class SacCriticParams(C.Structure):
+    _c_name_ = "gymrl_sac_critic_params"   # fc1..fc6
     _fields_ = [("w", C.c_void_p * 6), ("b", C.c_void_p * 6)]
 
 
-class SacActArgs(C.Structure):            # gymrl_sac_act_args (include/gymrl.h), field for field
+class SacActArgs(C.Structure):
+    _c_name_ = "gymrl_sac_act_args"
     _fields_ = [("N", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("env_kind", C.c_int),
                 ("env_state", C.c_void_p), ("env_seed", C.c_uint64), ("env_id0", C.c_int64),
                 ("obs", C.c_void_p), ("obs_out", C.c_void_p), ("eps", C.c_void_p),
@@ -170,7 +124,8 @@ class SacActArgs(C.Structure):            # gymrl_sac_act_args (include/gymrl.h)
                 ("ep_stats", C.c_void_p), ("images", C.c_void_p)]
 
 
-class SacUpdateArgs(C.Structure):         # gymrl_sac_update_args (include/gymrl.h), field for field
+class SacUpdateArgs(C.Structure):
+    _c_name_ = "gymrl_sac_update_args"
     _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int),
                 ("gamma", C.c_float), ("bound", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
                 ("target_entropy", C.c_float), ("tau", C.c_double),
@@ -191,7 +146,8 @@ class SacUpdateArgs(C.Structure):         # gymrl_sac_update_args (include/gymrl
                 ("sums", C.c_void_p), ("alpha_loss", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
 
 
-class RainbowActArgs(C.Structure):        # gymrl_rainbow_act_args (include/gymrl.h), field for field
+class RainbowActArgs(C.Structure):
+    _c_name_ = "gymrl_rainbow_act_args"
     _fields_ = [("N", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("env_kind", C.c_int),
                 ("env_state", C.c_void_p), ("env_seed", C.c_uint64), ("env_id0", C.c_int64),
                 ("obs", C.c_void_p), ("obs_out", C.c_void_p),
@@ -206,7 +162,8 @@ class RainbowActArgs(C.Structure):        # gymrl_rainbow_act_args (include/gymr
                 ("ep_stats", C.c_void_p), ("fc2_img", C.c_void_p)]
 
 
-class RainbowUpdateArgs(C.Structure):     # gymrl_rainbow_update_args (include/gymrl.h), field for field
+class RainbowUpdateArgs(C.Structure):
+    _c_name_ = "gymrl_rainbow_update_args"
     _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("gamma_n", C.c_float),
                 ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
                 ("r_flag", C.c_void_p), ("idx", C.c_void_p), ("is_weight", C.c_void_p),
@@ -220,25 +177,181 @@ class RainbowUpdateArgs(C.Structure):     # gymrl_rainbow_update_args (include/g
                 ("p_fc2_img_f", C.c_void_p), ("p_fc2_img_b", C.c_void_p), ("t_fc2_img_f", C.c_void_p)]
 
 
-class WeightImage(C.Structure):           # gymrl_weight_image
+class WeightImage(C.Structure):
+    _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
 
 
 class PPOFullCfg(C.Structure):
+    _c_name_ = "gymrl_ppo_full_cfg"
     _fields_ = [("clip_eps_min", C.c_float), ("clip_eps_max", C.c_float), ("dual_clip", C.c_float),
                 ("erc_beta_low", C.c_float), ("erc_beta_high", C.c_float), ("entropy_coef", C.c_float),
                 ("entropy_coef_dev", C.c_void_p)]
 
 
-class MlprnnParams(C.Structure):           # gymrl_mlprnn_params (include/gymrl.h), field for field
+class MlprnnParams(C.Structure):
+    _c_name_ = "gymrl_mlprnn_params"
     _fields_ = ([("pscn_w", C.c_void_p * 4), ("pscn_b", C.c_void_p * 4), ("pscn_a", C.c_void_p * 4)] +
                 [(n, C.c_void_p) for n in ("lin_w", "lin_b", "w_ih", "b_ih", "w_hh", "b_hh", "actor_w1", "actor_b1", "actor_a",
                                           "actor_w2", "actor_b2", "critic_w1", "critic_b1", "critic_a", "critic_w2",
                                           "critic_b2")])
 
 
+_vp, _i, _i64, _u64, _f, _d, _sz, _P = (C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t,
+                                        C.POINTER)
+# Every entry point of include/gymrl.h, in its order: name -> (restype, argtypes).  lib() applies it, so ctypes converts
+# plain Python ints and floats and refuses an argument of another type; tests/test_abi.py holds each line to the header.
+# A pointer to device memory or a stream is _vp; a HOST array the caller passes as a ctypes array is _P(<scalar>); a
+# `const gymrl_x*` is _P(<its mirror above>), or _vp where callers also hand in an untyped NULL (gymrl_mhc_policy_pack,
+# gymrl_mhc_policy_forward, gymrl_sac_step).
+SIGNATURES = {
+    "gymrl_abi_version": (_i, []),
+    "gymrl_device_ok": (_i, []),
+    "gymrl_env_obs_dim": (_i, [_i]),
+    "gymrl_env_act_dim": (_i, [_i]),
+    "gymrl_env_is_discrete": (_i, [_i]),
+    "gymrl_env_max_steps": (_i, [_i]),
+    "gymrl_env_state_bytes": (_sz, [_i, _i]),
+    "gymrl_env_reset": (_i, [_i, _vp, _i, _u64, _i64, _vp, _vp]),
+    "gymrl_env_step": (_i, [_i, _vp, _i, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_env_abandon": (_i, [_i, _vp, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_env_refill": (_i, [_i, _vp, _i, _u64, _i64, _vp]),
+    "gymrl_categorical_sample": (_i, [_vp, _vp, _vp, _u64, _u64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _P(GaeOnline), _vp]),
+    "gymrl_gae_online_flush": (_i, [_P(GaeOnline), _vp, _i, _vp]),
+    "gymrl_gae_chunk": (_i, []),
+    "gymrl_gae_workspace_bytes": (_sz, [_i, _i]),
+    "gymrl_gae": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp, _i, _vp, _vp]),
+    "gymrl_gae_dw": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_gae_decoupled_workspace_bytes": (_sz, [_i, _i]),
+    "gymrl_gae_decoupled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _d, _d, _d, _vp, _vp, _i, _vp, _vp]),
+    "gymrl_reduce_workspace_bytes": (_sz, []),
+    "gymrl_moments": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "gymrl_normalize": (_i, [_vp, _i64, _vp, _i, _d, _vp]),
+    "gymrl_ppo_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(PPOCfg), _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_loss_blocks": (_i, [_i]),
+    "gymrl_reduce_rows": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "gymrl_ppo_full_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(PPOFullCfg), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_ppo_rnn_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(PPOFullCfg), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_gru_cell_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "gymrl_gru_cell_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_rnd_reward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "gymrl_gru_seq_fwd": (_i, [_vp, _vp, _vp, _vp, _P(C.c_int32), _i, _i, _i, _vp, _vp, _vp]),
+    "gymrl_gru_seq_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_int32), _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_episode_gae": (_i, [_vp, _vp, _vp, _vp, _vp, _P(_i64), _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_ppg_policy_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _P(_i64), _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_ppg_aux_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _P(_i64), _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_mlprnn_params_bytes": (_sz, []),
+    "gymrl_mlprnn_act": (_i, [_vp, _vp, _P(MlprnnParams), _i, _i, _i, _vp, _vp, _u64, _u64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_permutation": (_i, [_u64, _u64, _i64, _vp, _vp]),
+    "gymrl_pack_rollout": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "gymrl_gather_minibatch": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_gather_rows": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "gymrl_sqnorm": (_i, [_vp, _i64, _f, _vp, _vp, _vp]),
+    "gymrl_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _d, _d, _d, _i64, _vp, _f, _f, _vp, _f, _i, _vp, _d, _vp]),
+    "gymrl_clip_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _d, _d, _d, _i64, _vp, _f, _f, _vp, _f, _i, _vp, _d, _vp, _vp]),
+    "gymrl_adam_bias": (_i, [_d, _d, _d, _i64, _P(_f)]),
+    "gymrl_store_scalars": (_i, [_vp, _vp, _i, _vp]),
+    "gymrl_soft_update": (_i, [_vp, _vp, _i64, _d, _vp]),
+    "gymrl_mlp_packed_floats": (_sz, [_i, _i]),
+    "gymrl_mlp_pack": (_i, [_vp, _i, _i, _vp, _vp]),
+    "gymrl_mlp_forward": (_i, [_vp, _i, _i, _P(MlpDesc), _vp]),
+    "gymrl_rollout_lunar": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
+    "gymrl_rollout_cartpole": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
+    "gymrl_rollout_lunar_mhc": (_i, [_P(RolloutLunarArgs), _P(MhcPolicy), _vp]),
+    "gymrl_lin_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_lin_fwd": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gymrl_lin_bwd_input": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gymrl_lin_bwd_weight": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gymrl_noisy_combine": (_i, [_P(NoisyLayer), _i, _i, _i, _vp, _vp, _vp]),
+    "gymrl_noisy_split": (_i, [_P(NoisyLayer), _i, _i, _i, _vp, _vp, _i, _vp]),
+    "gymrl_noisy_combine_images": (_i, [_P(NoisyLayer), _i, _i, _i, _vp, _vp, _P(WeightImage), _i, _vp]),
+    "gymrl_dueling_bwd": (_i, [_vp, _i, _i, _vp, _vp]),
+    "gymrl_mhc_gates": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_mhc_combine": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "gymrl_rmsnorm": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "gymrl_rmsnorm_bwd_workspace_bytes": (_sz, [_i]),
+    "gymrl_rmsnorm_bwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_rmsnorm_sum_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_norm_proj_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "gymrl_norm_proj_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "gymrl_norm_proj_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_sinkhorn": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gymrl_mhc_gates_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "gymrl_mhc_gates_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_mhc_read_fwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "gymrl_mhc_read_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "gymrl_mhc_combine_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_mhc_sub_forward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_mhc_sub_backward": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "gymrl_mhc_policy_image_floats": (_sz, [_i]),
+    "gymrl_mhc_policy_pack": (_i, [_vp, _vp, _vp]),
+    "gymrl_mhc_policy_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "gymrl_mlp_train_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gymrl_linear_tanh_smallk": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "gymrl_linear_smallk": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "gymrl_tanh_inplace": (_i, [_vp, _i64, _vp, _i, _vp]),
+    "gymrl_tanh_bwd_colsum": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "gymrl_linear_smallk_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_heads_fwd_tanh": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "gymrl_heads_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "gymrl_heads_loss_blocks": (_i, [_i64, _i]),
+    "gymrl_heads_loss_fwd_bwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PPOCfg), _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
+    "gymrl_gemm_workspace_bytes": (_sz, []),
+    "gymrl_linear_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
+    "gymrl_linear_bwd_input": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "gymrl_linear_bwd_input_add": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "gymrl_linear_bwd_weight_geometry": (_i, [_i64, _i, _P(_i), _P(_i64)]),
+    "gymrl_linear_bwd_weight": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_update_finalize": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_replay_append": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_replay_gather": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_uniform_indices": (_i, [_u64, _u64, _i64, _i, _vp, _vp, _vp]),
+    "gymrl_nstep_push": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                              _vp, _vp, _i, _vp]),
+    "gymrl_per_workspace_bytes": (_sz, [_i]),
+    "gymrl_per_update": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _d, _i, _vp, _vp, _vp]),
+    "gymrl_per_max_leaf": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "gymrl_per_priorities": (_i, [_vp, _i, _d, _d, _d, _vp, _vp]),
+    "gymrl_per_update_td": (_i, [_vp, _i64, _vp, _vp, _i, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    "gymrl_per_sample": (_i, [_vp, _i64, _vp, _u64, _u64, _i, _i64, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_noisy_noise": (_i, [_vp, _vp, _u64, _u64, _i, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_epsilon_greedy": (_i, [_vp, _vp, _u64, _u64, _i64, _i, _i, _f, _vp, _vp]),
+    "gymrl_dqn_td_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_sac_sample_fwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "gymrl_sac_sample_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "gymrl_sac_target": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp]),
+    "gymrl_sac_critic_loss": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_sac_actor_loss": (_i, [_vp, _vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_sac_alpha_step": (_i, [_vp, _vp, _vp, _vp, _i, _d, _d, _d, _d, _i64, _vp, _vp, _vp]),
+    "gymrl_noisy_action": (_i, [_vp, _vp, _u64, _u64, _i64, _i, _d, _d, _d, _vp, _vp]),
+    "gymrl_mse_loss": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_neg_mean_loss": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_dsac_target": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp]),
+    "gymrl_dsac_critic_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_dsac_actor_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_dsac_alpha_step": (_i, [_vp, _vp, _vp, _vp, _i, _d, _d, _d, _d, _d, _i64, _vp, _vp, _vp]),
+    "gymrl_running_norm": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "gymrl_reward_scaling": (_i, [_vp, _vp, _i, _d, _vp, _vp, _vp, _vp]),
+    "gymrl_running_norm_masked": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "gymrl_reward_scaling_masked": (_i, [_vp, _vp, _vp, _i, _d, _vp, _vp, _vp, _vp]),
+    "gymrl_sac_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_sac_pack_images": (_i, [_P(SacUpdateArgs), _vp]),
+    "gymrl_sac_args_bytes": (_sz, [_i]),
+    "gymrl_sac_act_step": (_i, [_P(SacActArgs), _vp]),
+    "gymrl_sac_update": (_i, [_P(SacUpdateArgs), _vp]),
+    "gymrl_sac_step": (_i, [_vp, _vp, _vp]),
+    "gymrl_rainbow_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_rainbow_args_bytes": (_sz, [_i]),
+    "gymrl_rainbow_act_step": (_i, [_P(RainbowActArgs), _vp]),
+    "gymrl_rainbow_update": (_i, [_P(RainbowUpdateArgs), _i, _vp]),
+}
+SYMBOLS = list(SIGNATURES)
+
+
 def lib():
-    """The loaded C-ABI library.  Raises (never falls back) when it is absent."""
+    """The loaded C-ABI library, every function typed by SIGNATURES.  Raises (never falls back) when it is absent."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -246,46 +359,13 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `make -C {CSRC}` (or __graft_entry__.build()). "
                 "gymrl_amd has no CPU fallback.")
         L = C.CDLL(LIB_PATH)
-        L.gymrl_abi_version.restype = C.c_int
         got = L.gymrl_abi_version()
         if got != ABI_VERSION:       # a stale .so would take mis-aligned arguments silently
             raise RuntimeError(f"{LIB_PATH} reports ABI version {got}, this package needs {ABI_VERSION}: rebuild it "
                                f"with `make -C {CSRC}`")
-        L.gymrl_env_state_bytes.restype = C.c_size_t
-        L.gymrl_gae_workspace_bytes.restype = C.c_size_t
-        L.gymrl_gae_decoupled_workspace_bytes.restype = C.c_size_t
-        L.gymrl_reduce_workspace_bytes.restype = C.c_size_t
-        L.gymrl_per_workspace_bytes.restype = C.c_size_t
-        L.gymrl_mlp_packed_floats.restype = C.c_size_t
-        L.gymrl_mhc_policy_image_floats.restype = C.c_size_t
-        L.gymrl_mlp_train_workspace_bytes.restype = C.c_size_t
-        L.gymrl_gemm_workspace_bytes.restype = C.c_size_t
-        L.gymrl_lin_workspace_bytes.restype = C.c_size_t
-        L.gymrl_mhc_gates_bwd_workspace_bytes.restype = C.c_size_t
-        L.gymrl_rmsnorm_bwd_workspace_bytes.restype = C.c_size_t
-        L.gymrl_norm_proj_bwd_workspace_bytes.restype = C.c_size_t
-        L.gymrl_sac_update_workspace_bytes.restype = C.c_size_t
-        L.gymrl_sac_args_bytes.restype = C.c_size_t
-        L.gymrl_rainbow_update_workspace_bytes.restype = C.c_size_t
-        L.gymrl_rainbow_args_bytes.restype = C.c_size_t
-        L.gymrl_mlprnn_params_bytes.restype = C.c_size_t
-        if L.gymrl_mlprnn_params_bytes() != C.sizeof(MlprnnParams):
-            raise RuntimeError("gymrl_amd/_lib.py: MlprnnParams does not mirror include/gymrl.h "
-                               f"({C.sizeof(MlprnnParams)} bytes here, {L.gymrl_mlprnn_params_bytes()} in the library)")
-        if L.gymrl_rainbow_args_bytes(0) != C.sizeof(RainbowActArgs) or L.gymrl_rainbow_args_bytes(1) != C.sizeof(RainbowUpdateArgs):
-            raise RuntimeError("gymrl_amd/_lib.py: RainbowActArgs / RainbowUpdateArgs do not mirror include/gymrl.h "
-                               f"({C.sizeof(RainbowActArgs)} / {C.sizeof(RainbowUpdateArgs)} bytes here, "
-                               f"{L.gymrl_rainbow_args_bytes(0)} / {L.gymrl_rainbow_args_bytes(1)} in the library)")
-        if L.gymrl_sac_args_bytes(0) != C.sizeof(SacActArgs) or L.gymrl_sac_args_bytes(1) != C.sizeof(SacUpdateArgs):
-            raise RuntimeError("gymrl_amd/_lib.py: SacActArgs / SacUpdateArgs do not mirror include/gymrl.h "
-                               f"({C.sizeof(SacActArgs)} / {C.sizeof(SacUpdateArgs)} bytes here, "
-                               f"{L.gymrl_sac_args_bytes(0)} / {L.gymrl_sac_args_bytes(1)} in the library)")
-        for name in SYMBOLS:
-            if name.endswith(("_bytes", "_floats")):
-                continue
-            getattr(L, name).restype = C.c_int
-        for name, at in ARGTYPES.items():
-            getattr(L, name).argtypes = at
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

@@ -40,7 +40,7 @@ def device_ok():
 
 # ------------------------------------------------------------------ GAE -----
 def gae_workspace(T, N, device):
-    nbytes = lib().gymrl_gae_workspace_bytes(C.c_int(T), C.c_int(N))
+    nbytes = lib().gymrl_gae_workspace_bytes(T, N)
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
@@ -56,10 +56,8 @@ def gae(rew, val, done, next_val, gamma, lam, adv_out=None, ret_out=None, moment
     ret_out = torch.empty_like(rew) if ret_out is None else ret_out
     if workspace is None and (variant == 1 or moments_out is not None):
         workspace = gae_workspace(T, N, rew.device)
-    check(lib().gymrl_gae(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(done, torch.uint8),
-                          _ptr(next_val, torch.float32), C.c_int(T), C.c_int(N), C.c_double(gamma),
-                          C.c_double(lam), _ptr(adv_out, torch.float32), _ptr(ret_out, torch.float32),
-                          _ptr(moments_out, torch.float64, True), C.c_int(variant),
+    check(lib().gymrl_gae(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(done, torch.uint8), _ptr(next_val, torch.float32), T, N, gamma,
+                          lam, _ptr(adv_out, torch.float32), _ptr(ret_out, torch.float32), _ptr(moments_out, torch.float64, True), variant,
                           _ptr(workspace, None, True), _stream()), "gymrl_gae")
     return adv_out, ret_out
 
@@ -70,16 +68,14 @@ def gae_dw(rew, val, next_val, done, dw, gamma, lam, moments_out=None, workspace
     adv, vt = torch.empty_like(rew), torch.empty_like(rew)
     if workspace is None and moments_out is not None:
         workspace = gae_workspace(T, N, rew.device)
-    check(lib().gymrl_gae_dw(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(next_val, torch.float32),
-                             _ptr(done, torch.uint8), _ptr(dw, torch.uint8), C.c_int(T), C.c_int(N),
-                             C.c_double(gamma), C.c_double(lam), _ptr(adv), _ptr(vt),
-                             _ptr(moments_out, torch.float64, True), _ptr(workspace, None, True), _stream()),
-          "gymrl_gae_dw")
+    check(lib().gymrl_gae_dw(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(next_val, torch.float32), _ptr(done, torch.uint8),
+                             _ptr(dw, torch.uint8), T, N, gamma, lam, _ptr(adv), _ptr(vt), _ptr(moments_out, torch.float64, True),
+                             _ptr(workspace, None, True), _stream()), "gymrl_gae_dw")
     return adv, vt
 
 
 def gae_decoupled_workspace(T, N, device):
-    nbytes = lib().gymrl_gae_decoupled_workspace_bytes(C.c_int(T), C.c_int(N))
+    nbytes = lib().gymrl_gae_decoupled_workspace_bytes(T, N)
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
@@ -92,24 +88,21 @@ def gae_decoupled(rew, val, done, next_val, gamma, lam_actor, lam_critic, varian
     ret = torch.empty_like(rew) if ret_out is None else ret_out
     if variant and workspace is None:
         workspace = gae_decoupled_workspace(T, N, rew.device)
-    check(lib().gymrl_gae_decoupled(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(done, torch.uint8),
-                                    _ptr(next_val, torch.float32), C.c_int(T), C.c_int(N), C.c_double(gamma),
-                                    C.c_double(lam_actor), C.c_double(lam_critic), _ptr(adv), _ptr(ret),
-                                    C.c_int(variant), _ptr(workspace, None, True), _stream()), "gymrl_gae_decoupled")
+    check(lib().gymrl_gae_decoupled(_ptr(rew, torch.float32), _ptr(val, torch.float32), _ptr(done, torch.uint8), _ptr(next_val, torch.float32), T, N,
+                                    gamma, lam_actor, lam_critic, _ptr(adv), _ptr(ret), variant, _ptr(workspace, None, True), _stream()),
+          "gymrl_gae_decoupled")
     return adv, ret
 
 
 def moments(x, out=None, workspace=None):
     out = torch.empty(3, dtype=torch.float64, device=x.device) if out is None else out
     workspace = reduce_workspace(x.device) if workspace is None else workspace
-    check(lib().gymrl_moments(_ptr(x, torch.float32), C.c_int64(x.numel()), _ptr(out, torch.float64),
-                              _ptr(workspace), _stream()), "gymrl_moments")
+    check(lib().gymrl_moments(_ptr(x, torch.float32), x.numel(), _ptr(out, torch.float64), _ptr(workspace), _stream()), "gymrl_moments")
     return out
 
 
 def normalize_(x, mom, ddof=0, eps=1e-8):
-    check(lib().gymrl_normalize(_ptr(x, torch.float32), C.c_int64(x.numel()), _ptr(mom, torch.float64),
-                                C.c_int(ddof), C.c_double(eps), _stream()), "gymrl_normalize")
+    check(lib().gymrl_normalize(_ptr(x, torch.float32), x.numel(), _ptr(mom, torch.float64), ddof, eps, _stream()), "gymrl_normalize")
     return x
 
 
@@ -123,8 +116,7 @@ def gae_online(rew_prev, done_prev, val_prev, running, workspace, t_prev, T, gam
 
 
 def gae_online_flush(online, val_cur):
-    check(lib().gymrl_gae_online_flush(C.byref(online), _ptr(val_cur, torch.float32), C.c_int(val_cur.numel()),
-                                       _stream()), "gymrl_gae_online_flush")
+    check(lib().gymrl_gae_online_flush(C.byref(online), _ptr(val_cur, torch.float32), val_cur.numel(), _stream()), "gymrl_gae_online_flush")
 
 
 def categorical_sample(logits, value=None, noise_exp=None, seed=0, counter=0, env_id0=0, deterministic=False,
@@ -137,13 +129,10 @@ def categorical_sample(logits, value=None, noise_exp=None, seed=0, counter=0, en
     ent_out = torch.empty(n, dtype=torch.float32, device=dev) if ent_out is None else ent_out
     if value is not None and value_out is None:
         value_out = torch.empty(n, dtype=torch.float32, device=dev)
-    check(lib().gymrl_categorical_sample(_ptr(logits, torch.float32), _ptr(value, torch.float32, True),
-                                         _ptr(noise_exp, torch.float32, True), C.c_uint64(seed),
-                                         C.c_uint64(counter), C.c_int64(env_id0), C.c_int(n), C.c_int(A),
-                                         C.c_int(int(deterministic)), _ptr(act_out, torch.int32), _ptr(logp_out),
-                                         _ptr(ent_out, None, True), _ptr(value_out, None, True),
-                                         C.byref(online) if online is not None else None, _stream()),
-          "gymrl_categorical_sample")
+    check(lib().gymrl_categorical_sample(_ptr(logits, torch.float32), _ptr(value, torch.float32, True), _ptr(noise_exp, torch.float32, True), seed,
+                                         counter, env_id0, n, A, int(deterministic), _ptr(act_out, torch.int32), _ptr(logp_out),
+                                         _ptr(ent_out, None, True), _ptr(value_out, None, True), C.byref(online) if online is not None else None,
+                                         _stream()), "gymrl_categorical_sample")
     return act_out, logp_out, ent_out, value_out
 
 
@@ -167,14 +156,10 @@ def ppo_loss_fwd_bwd(logits, value, act, logp_old, adv, ret, cfg, idx=None, adv_
     c = PPOCfg(*cfg)
     if metrics_sum is not None and workspace is None:
         workspace = _reduce_ws(logits.device)
-    check(lib().gymrl_ppo_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32),
-                                       _ptr(idx, torch.int32, True), _ptr(act, torch.int32),
-                                       _ptr(logp_old, torch.float32), _ptr(adv, torch.float32),
-                                       _ptr(ret, torch.float32), _ptr(adv_moments, torch.float64, True),
-                                       C.c_int(B), C.c_int(A), C.byref(c), _ptr(dlogits_out), _ptr(dvalue_out),
-                                       _ptr(metrics_sum, torch.float64, True), _ptr(workspace, None, True),
-                                       _stream()),
-          "gymrl_ppo_loss_fwd_bwd")
+    check(lib().gymrl_ppo_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32), _ptr(idx, torch.int32, True), _ptr(act, torch.int32),
+                                       _ptr(logp_old, torch.float32), _ptr(adv, torch.float32), _ptr(ret, torch.float32),
+                                       _ptr(adv_moments, torch.float64, True), B, A, C.byref(c), _ptr(dlogits_out), _ptr(dvalue_out),
+                                       _ptr(metrics_sum, torch.float64, True), _ptr(workspace, None, True), _stream()), "gymrl_ppo_loss_fwd_bwd")
     return dlogits_out, dvalue_out
 
 
@@ -189,14 +174,11 @@ def ppo_full_loss_fwd_bwd(logits, value, act, logp_old, ent_old, adv, ret, cfg, 
     c.entropy_coef_dev = None if entropy_coef_dev is None else _ptr(entropy_coef_dev, torch.float32).value
     if metrics_sum is not None and workspace is None:
         workspace = _reduce_ws(logits.device)
-    check(lib().gymrl_ppo_full_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32),
-                                            _ptr(idx, torch.int32, True), _ptr(act, torch.int32),
-                                            _ptr(logp_old, torch.float32), _ptr(ent_old, torch.float32),
-                                            _ptr(adv, torch.float32), _ptr(ret, torch.float32), C.c_int(B),
-                                            C.c_int(A), C.byref(c), _ptr(corr_mul, torch.float32, True), _ptr(dlogits_out),
-                                            _ptr(dvalue_out), _ptr(metrics_sum, torch.float64, True),
-                                            _ptr(workspace, None, True), _stream()),
-          "gymrl_ppo_full_loss_fwd_bwd")
+    check(lib().gymrl_ppo_full_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32), _ptr(idx, torch.int32, True),
+                                            _ptr(act, torch.int32), _ptr(logp_old, torch.float32), _ptr(ent_old, torch.float32),
+                                            _ptr(adv, torch.float32), _ptr(ret, torch.float32), B, A, C.byref(c), _ptr(corr_mul, torch.float32, True),
+                                            _ptr(dlogits_out), _ptr(dvalue_out), _ptr(metrics_sum, torch.float64, True), _ptr(workspace, None, True),
+                                            _stream()), "gymrl_ppo_full_loss_fwd_bwd")
     return dlogits_out, dvalue_out
 
 
@@ -206,13 +188,10 @@ def ppo_rnn_loss_fwd_bwd(logits, value, act, logp_old, ent_old, val_old, adv, re
     B, A = logits.shape
     dlogits, dvalue = torch.empty_like(logits), torch.empty(B, dtype=torch.float32, device=logits.device)
     c = PPOFullCfg(*cfg)
-    check(lib().gymrl_ppo_rnn_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32),
-                                           _ptr(idx, torch.int32, True), _ptr(act, torch.int32),
-                                           _ptr(logp_old, torch.float32), _ptr(ent_old, torch.float32),
-                                           _ptr(val_old, torch.float32), _ptr(adv, torch.float32),
-                                           _ptr(ret, torch.float32), C.c_int(B), C.c_int(A), C.byref(c),
-                                           _ptr(corr_mul, torch.float32, True), _ptr(dlogits),
-                                           _ptr(dvalue), _ptr(metrics_sum, torch.float64, True),
+    check(lib().gymrl_ppo_rnn_loss_fwd_bwd(_ptr(logits, torch.float32), _ptr(value, torch.float32), _ptr(idx, torch.int32, True),
+                                           _ptr(act, torch.int32), _ptr(logp_old, torch.float32), _ptr(ent_old, torch.float32),
+                                           _ptr(val_old, torch.float32), _ptr(adv, torch.float32), _ptr(ret, torch.float32), B, A, C.byref(c),
+                                           _ptr(corr_mul, torch.float32, True), _ptr(dlogits), _ptr(dvalue), _ptr(metrics_sum, torch.float64, True),
                                            _ptr(_reduce_ws(logits.device)), _stream()), "gymrl_ppo_rnn_loss_fwd_bwd")
     return dlogits, dvalue
 
@@ -220,17 +199,16 @@ def ppo_rnn_loss_fwd_bwd(logits, value, act, logp_old, ent_old, val_old, adv, re
 def gru_cell_fwd(gi, gh, h, out=None):
     B, H = h.shape
     out = torch.empty_like(h) if out is None else out
-    check(lib().gymrl_gru_cell_fwd(_ptr(gi, torch.float32), _ptr(gh, torch.float32), _ptr(h, torch.float32), C.c_int(B),
-                                   C.c_int(H), _ptr(out, torch.float32), _stream()), "gymrl_gru_cell_fwd")
+    check(lib().gymrl_gru_cell_fwd(_ptr(gi, torch.float32), _ptr(gh, torch.float32), _ptr(h, torch.float32), B, H, _ptr(out, torch.float32), _stream()),
+          "gymrl_gru_cell_fwd")
     return out
 
 
 def gru_cell_bwd(gi, gh, h, dh_out):
     B, H = h.shape
     dgi, dgh, dh = torch.empty_like(gi), torch.empty_like(gh), torch.empty_like(h)
-    check(lib().gymrl_gru_cell_bwd(_ptr(gi, torch.float32), _ptr(gh, torch.float32), _ptr(h, torch.float32),
-                                   _ptr(dh_out, torch.float32), C.c_int(B), C.c_int(H), _ptr(dgi), _ptr(dgh), _ptr(dh),
-                                   _stream()), "gymrl_gru_cell_bwd")
+    check(lib().gymrl_gru_cell_bwd(_ptr(gi, torch.float32), _ptr(gh, torch.float32), _ptr(h, torch.float32), _ptr(dh_out, torch.float32), B, H,
+                                   _ptr(dgi), _ptr(dgh), _ptr(dh), _stream()), "gymrl_gru_cell_bwd")
     return dgi, dgh, dh
 
 
@@ -405,28 +383,25 @@ def mlprnn_act(x, h_in, params, A, live=None, noise_exp=None, seed=0, counter=0,
 
 def rnd_reward(predict, target, rew_inout=None, rnd_out=None):
     B, E = predict.shape
-    check(lib().gymrl_rnd_reward(_ptr(predict, torch.float32), _ptr(target, torch.float32), C.c_int(B), C.c_int(E),
-                                 _ptr(rew_inout, torch.float32, True), _ptr(rnd_out, torch.float32, True), _stream()),
-          "gymrl_rnd_reward")
+    check(lib().gymrl_rnd_reward(_ptr(predict, torch.float32), _ptr(target, torch.float32), B, E, _ptr(rew_inout, torch.float32, True),
+                                 _ptr(rnd_out, torch.float32, True), _stream()), "gymrl_rnd_reward")
 
 
 def loss_blocks(B):
-    return int(lib().gymrl_loss_blocks(C.c_int(B)))
+    return int(lib().gymrl_loss_blocks(B))
 
 
 def reduce_rows(partials, rows, blocks_per_row, K):
     """[rows, blocks_per_row, K] f64 block partials -> [rows, K] sums (one launch)."""
     out = torch.empty(rows, K, dtype=torch.float64, device=partials.device)
-    check(lib().gymrl_reduce_rows(_ptr(partials, torch.float64), C.c_int(rows), C.c_int(blocks_per_row), C.c_int(K),
-                                  _ptr(out), _stream()), "gymrl_reduce_rows")
+    check(lib().gymrl_reduce_rows(_ptr(partials, torch.float64), rows, blocks_per_row, K, _ptr(out), _stream()), "gymrl_reduce_rows")
     return out
 
 
 def permutation(seed, counter, M, device, out=None):
     """P6 epoch shuffle: i32[M] keyed bijection of [0, M) (gymrl_permutation)."""
     out = torch.empty(M, dtype=torch.int32, device=device) if out is None else out
-    check(lib().gymrl_permutation(C.c_uint64(seed), C.c_uint64(counter), C.c_int64(M), _ptr(out, torch.int32), _stream()),
-          "gymrl_permutation")
+    check(lib().gymrl_permutation(seed, counter, M, _ptr(out, torch.int32), _stream()), "gymrl_permutation")
     return out
 
 
@@ -434,9 +409,8 @@ def pack_rollout(obs, act, logp, adv, ret, packed=None):
     """P6: one 64-B record per transition (ppo_lunarlander.py:238-250).  obs [M, D]."""
     M, D = obs.shape
     packed = torch.empty(M, 16, dtype=torch.float32, device=obs.device) if packed is None else packed
-    check(lib().gymrl_pack_rollout(_ptr(obs, torch.float32), _ptr(act, torch.int32), _ptr(logp, torch.float32),
-                                   _ptr(adv, torch.float32), _ptr(ret, torch.float32), C.c_int64(M), C.c_int(D),
-                                   _ptr(packed, torch.float32), _stream()), "gymrl_pack_rollout")
+    check(lib().gymrl_pack_rollout(_ptr(obs, torch.float32), _ptr(act, torch.int32), _ptr(logp, torch.float32), _ptr(adv, torch.float32),
+                                   _ptr(ret, torch.float32), M, D, _ptr(packed, torch.float32), _stream()), "gymrl_pack_rollout")
     return packed
 
 
@@ -444,8 +418,7 @@ def gather_rows(src, idx, out=None):
     """gymrl_gather_rows: src[idx] for a 2-D float32 `src` whose rows are a multiple of 16 bytes (idx int32)."""
     B, D = idx.numel(), src.shape[1]
     out = torch.empty(B, D, device=src.device) if out is None else out
-    check(lib().gymrl_gather_rows(_ptr(src, torch.float32), _ptr(idx, torch.int32), C.c_int(B), C.c_int(D), _ptr(out, torch.float32),
-                                  _stream()), "gymrl_gather_rows")
+    check(lib().gymrl_gather_rows(_ptr(src, torch.float32), _ptr(idx, torch.int32), B, D, _ptr(out, torch.float32), _stream()), "gymrl_gather_rows")
     return out
 
 
@@ -456,48 +429,40 @@ def gather_minibatch(packed, idx, obs_dim, out=None):
         out = (torch.empty(B, obs_dim, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
                torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(B, device=dev))
     obs, act, logp, adv, ret = out
-    check(lib().gymrl_gather_minibatch(_ptr(packed, torch.float32), _ptr(idx, torch.int32), C.c_int(B),
-                                       C.c_int(obs_dim), _ptr(obs, torch.float32), _ptr(act, torch.int32),
-                                       _ptr(logp, torch.float32), _ptr(adv, torch.float32),
-                                       _ptr(ret, torch.float32), _stream()), "gymrl_gather_minibatch")
+    check(lib().gymrl_gather_minibatch(_ptr(packed, torch.float32), _ptr(idx, torch.int32), B, obs_dim, _ptr(obs, torch.float32),
+                                       _ptr(act, torch.int32), _ptr(logp, torch.float32), _ptr(adv, torch.float32), _ptr(ret, torch.float32),
+                                       _stream()), "gymrl_gather_minibatch")
     return out
 
 
 # -------------------------------------------------------------- optimiser ---
 def sqnorm(g, out, workspace, grad_scale=1.0):
-    check(lib().gymrl_sqnorm(_ptr(g, torch.float32), C.c_int64(g.numel()), C.c_float(grad_scale),
-                             _ptr(out, torch.float64), _ptr(workspace), _stream()), "gymrl_sqnorm")
+    check(lib().gymrl_sqnorm(_ptr(g, torch.float32), g.numel(), grad_scale, _ptr(out, torch.float64), _ptr(workspace), _stream()), "gymrl_sqnorm")
     return out
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, max_grad_norm=0.0, sqnorm_buf=None,
               clamp_abs=0.0, zero_grad=True, lr_dev=None, bias_dev=None, polyak_target=None, tau=0.0):
     """O1: Adam on one flat buffer (ppo_lunarlander.py:302-307); call sqnorm() first when clipping."""
-    check(lib().gymrl_adam_step(_ptr(p, torch.float32), _ptr(g, torch.float32), _ptr(m, torch.float32),
-                                _ptr(v, torch.float32), C.c_int64(p.numel()), C.c_double(lr),
-                                _ptr(lr_dev, torch.float32, True), C.c_double(beta1), C.c_double(beta2),
-                                C.c_double(eps), C.c_int64(step), _ptr(bias_dev, torch.float32, True),
-                                C.c_float(grad_scale),
-                                C.c_float(max_grad_norm), _ptr(sqnorm_buf, torch.float64, True),
-                                C.c_float(clamp_abs), C.c_int(int(zero_grad)), _ptr(polyak_target, torch.float32, True),
-                                C.c_double(tau), _stream()), "gymrl_adam_step")
+    check(lib().gymrl_adam_step(_ptr(p, torch.float32), _ptr(g, torch.float32), _ptr(m, torch.float32), _ptr(v, torch.float32), p.numel(), lr,
+                                _ptr(lr_dev, torch.float32, True), beta1, beta2, eps, step, _ptr(bias_dev, torch.float32, True), grad_scale,
+                                max_grad_norm, _ptr(sqnorm_buf, torch.float64, True), clamp_abs, int(zero_grad),
+                                _ptr(polyak_target, torch.float32, True), tau, _stream()), "gymrl_adam_step")
 
 
 def clip_adam_step(p, g, m, v, lr, beta1, beta2, eps, step, max_grad_norm, workspace, grad_scale=1.0, sqnorm_out=None,
                    clamp_abs=0.0, zero_grad=True, lr_dev=None, bias_dev=None, polyak_target=None, tau=0.0):
     """gymrl_clip_adam_step: sqnorm() + adam_step() as two launches instead of three (same bits)."""
-    check(lib().gymrl_clip_adam_step(_ptr(p, torch.float32), _ptr(g, torch.float32), _ptr(m, torch.float32), _ptr(v, torch.float32),
-                                     C.c_int64(p.numel()), C.c_double(lr), _ptr(lr_dev, torch.float32, True), C.c_double(beta1),
-                                     C.c_double(beta2), C.c_double(eps), C.c_int64(step), _ptr(bias_dev, torch.float32, True),
-                                     C.c_float(grad_scale), C.c_float(max_grad_norm), _ptr(sqnorm_out, torch.float64, True),
-                                     C.c_float(clamp_abs), C.c_int(int(zero_grad)), _ptr(polyak_target, torch.float32, True),
-                                     C.c_double(tau), _ptr(workspace), _stream()), "gymrl_clip_adam_step")
+    check(lib().gymrl_clip_adam_step(_ptr(p, torch.float32), _ptr(g, torch.float32), _ptr(m, torch.float32), _ptr(v, torch.float32), p.numel(), lr,
+                                     _ptr(lr_dev, torch.float32, True), beta1, beta2, eps, step, _ptr(bias_dev, torch.float32, True), grad_scale,
+                                     max_grad_norm, _ptr(sqnorm_out, torch.float64, True), clamp_abs, int(zero_grad),
+                                     _ptr(polyak_target, torch.float32, True), tau, _ptr(workspace), _stream()), "gymrl_clip_adam_step")
 
 
 def adam_bias(lr, beta1, beta2, step):
     """Host arithmetic of Adam's step-dependent scalars -> 4 float32 (gymrl_adam_bias)."""
     out = (C.c_float * 4)()
-    check(lib().gymrl_adam_bias(C.c_double(lr), C.c_double(beta1), C.c_double(beta2), C.c_int64(step), out), "gymrl_adam_bias")
+    check(lib().gymrl_adam_bias(lr, beta1, beta2, step, out), "gymrl_adam_bias")
     return bytes(out)
 
 
@@ -506,12 +471,11 @@ def store_scalars(dst, payload):
     if len(payload) > dst.numel() * dst.element_size():
         raise ValueError("payload larger than the destination block")
     buf = C.create_string_buffer(payload, len(payload))
-    check(lib().gymrl_store_scalars(_ptr(dst), buf, C.c_int(len(payload)), _stream()), "gymrl_store_scalars")
+    check(lib().gymrl_store_scalars(_ptr(dst), buf, len(payload), _stream()), "gymrl_store_scalars")
 
 
 def soft_update(target, source, tau):
-    check(lib().gymrl_soft_update(_ptr(target, torch.float32), _ptr(source, torch.float32),
-                                  C.c_int64(target.numel()), C.c_double(tau), _stream()), "gymrl_soft_update")
+    check(lib().gymrl_soft_update(_ptr(target, torch.float32), _ptr(source, torch.float32), target.numel(), tau, _stream()), "gymrl_soft_update")
 
 
 # -------------------------------------------------------------------- env ---
@@ -526,41 +490,36 @@ def env_dims(kind):
 
 
 def env_state(kind, n, device):
-    nbytes = int(lib().gymrl_env_state_bytes(C.c_int(kind), C.c_int(n)))
+    nbytes = int(lib().gymrl_env_state_bytes(kind, n))
     if nbytes == 0:
         raise RuntimeError(f"env kind {kind} unavailable")
     return torch.zeros(nbytes, dtype=torch.uint8, device=device)
 
 
 def env_reset(kind, state, n, seed, env_id0, obs_out):
-    check(lib().gymrl_env_reset(C.c_int(kind), _ptr(state), C.c_int(n), C.c_uint64(seed), C.c_int64(env_id0),
-                                _ptr(obs_out, torch.float32), _stream()), "gymrl_env_reset")
+    check(lib().gymrl_env_reset(kind, _ptr(state), n, seed, env_id0, _ptr(obs_out, torch.float32), _stream()), "gymrl_env_reset")
 
 
 def env_refill(kind, state, n, seed, env_id0, stream=None):
     st = _stream() if stream is None else _vp(stream.cuda_stream)
-    check(lib().gymrl_env_refill(C.c_int(kind), _ptr(state), C.c_int(n), C.c_uint64(seed), C.c_int64(env_id0), st),
-          "gymrl_env_refill")
+    check(lib().gymrl_env_refill(kind, _ptr(state), n, seed, env_id0, st), "gymrl_env_refill")
 
 
 def env_step(kind, state, n, seed, env_id0, action, obs_out, rew_out, terminated_out, truncated_out,
              term_obs_out=None, done_out=None, ep_ret_out=None, ep_len_out=None, ep_stats=None):
-    check(lib().gymrl_env_step(C.c_int(kind), _ptr(state), C.c_int(n), C.c_uint64(seed), C.c_int64(env_id0),
-                               _ptr(action), _ptr(obs_out, torch.float32), _ptr(term_obs_out, torch.float32, True),
-                               _ptr(rew_out, torch.float32), _ptr(terminated_out, torch.uint8),
-                               _ptr(truncated_out, torch.uint8), _ptr(done_out, torch.uint8, True),
-                               _ptr(ep_ret_out, torch.float32, True), _ptr(ep_len_out, torch.int32, True),
-                               _ptr(ep_stats, torch.float64, True), _stream()), "gymrl_env_step")
+    check(lib().gymrl_env_step(kind, _ptr(state), n, seed, env_id0, _ptr(action), _ptr(obs_out, torch.float32),
+                               _ptr(term_obs_out, torch.float32, True), _ptr(rew_out, torch.float32), _ptr(terminated_out, torch.uint8),
+                               _ptr(truncated_out, torch.uint8), _ptr(done_out, torch.uint8, True), _ptr(ep_ret_out, torch.float32, True),
+                               _ptr(ep_len_out, torch.int32, True), _ptr(ep_stats, torch.float64, True), _stream()), "gymrl_env_step")
 
 
 # ============================================================== off-policy ===
 def env_abandon(kind, state, n, seed, env_id0, cap, obs_inout, flag_inout=None, ep_ret_out=None, ep_len_out=None,
                 ep_stats=None):
     """Start the next episode of every env whose running episode reached `cap` steps (include/gymrl.h)."""
-    check(lib().gymrl_env_abandon(C.c_int(kind), _ptr(state), C.c_int(n), C.c_uint64(seed), C.c_int64(env_id0), C.c_int(cap),
-                                  _ptr(obs_inout, torch.float32), _ptr(flag_inout, torch.uint8, True),
-                                  _ptr(ep_ret_out, torch.float32, True), _ptr(ep_len_out, torch.int32, True),
-                                  _ptr(ep_stats, torch.float64, True), _stream()), "gymrl_env_abandon")
+    check(lib().gymrl_env_abandon(kind, _ptr(state), n, seed, env_id0, cap, _ptr(obs_inout, torch.float32), _ptr(flag_inout, torch.uint8, True),
+                                  _ptr(ep_ret_out, torch.float32, True), _ptr(ep_len_out, torch.int32, True), _ptr(ep_stats, torch.float64, True),
+                                  _stream()), "gymrl_env_abandon")
 
 
 def _dev(t):
@@ -574,12 +533,10 @@ def replay_append(ring, cursor, src_state, src_action, src_reward, src_next_stat
     cap, D = state.shape
     AW = action.shape[1]
     n = src_reward.numel()
-    check(lib().gymrl_replay_append(_ptr(state, torch.float32), _ptr(action), _ptr(reward, torch.float32),
-                                    _ptr(next_state, torch.float32), _ptr(flag, torch.uint8), C.c_int64(cap),
-                                    C.c_int64(cursor), C.c_int(D), C.c_int(AW), C.c_int(n),
-                                    _ptr(src_state, torch.float32), _ptr(src_action), _ptr(src_reward, torch.float32),
-                                    _ptr(src_next_state, torch.float32), _ptr(src_flag, torch.uint8), _dev(cursor_dev),
-                                    _stream()), "gymrl_replay_append")
+    check(lib().gymrl_replay_append(_ptr(state, torch.float32), _ptr(action), _ptr(reward, torch.float32), _ptr(next_state, torch.float32),
+                                    _ptr(flag, torch.uint8), cap, cursor, D, AW, n, _ptr(src_state, torch.float32), _ptr(src_action),
+                                    _ptr(src_reward, torch.float32), _ptr(src_next_state, torch.float32), _ptr(src_flag, torch.uint8),
+                                    _dev(cursor_dev), _stream()), "gymrl_replay_append")
 
 
 def replay_gather(ring, idx, action_dtype=torch.int32):
@@ -590,17 +547,15 @@ def replay_gather(ring, idx, action_dtype=torch.int32):
     B, dev = idx.numel(), state.device
     out = (torch.empty(B, D, device=dev), torch.empty(B, AW, dtype=action_dtype, device=dev),
            torch.empty(B, device=dev), torch.empty(B, D, device=dev), torch.empty(B, device=dev))
-    check(lib().gymrl_replay_gather(_ptr(state, torch.float32), _ptr(action), _ptr(reward, torch.float32),
-                                    _ptr(next_state, torch.float32), _ptr(flag, torch.uint8), _ptr(idx, torch.int32),
-                                    C.c_int(B), C.c_int(D), C.c_int(AW), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
-                                    _ptr(out[3]), _ptr(out[4]), _stream()), "gymrl_replay_gather")
+    check(lib().gymrl_replay_gather(_ptr(state, torch.float32), _ptr(action), _ptr(reward, torch.float32), _ptr(next_state, torch.float32),
+                                    _ptr(flag, torch.uint8), _ptr(idx, torch.int32), B, D, AW, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                                    _ptr(out[4]), _stream()), "gymrl_replay_gather")
     return out
 
 
 def uniform_indices(seed, counter, size, B, device, out=None, dev=None):
     idx = torch.empty(B, dtype=torch.int32, device=device) if out is None else out
-    check(lib().gymrl_uniform_indices(C.c_uint64(seed), C.c_uint64(counter), C.c_int64(size), C.c_int(B),
-                                      _ptr(idx), _dev(dev), _stream()), "gymrl_uniform_indices")
+    check(lib().gymrl_uniform_indices(seed, counter, size, B, _ptr(idx), _dev(dev), _stream()), "gymrl_uniform_indices")
     return idx
 
 
@@ -611,42 +566,37 @@ def nstep_push(win, n_steps, pushes, gamma, obs, action, reward, next_obs, termi
     w_state, w_action, w_reward, w_next, w_term, w_done = win
     state, act_w, rew, nxt, flag = ring
     N, D = obs.shape
-    rc = lib().gymrl_nstep_push(_ptr(w_state, torch.float32), _ptr(w_action, torch.int32), _ptr(w_reward, torch.float32),
-                                _ptr(w_next, torch.float32), _ptr(w_term, torch.uint8), _ptr(w_done, torch.uint8),
-                                C.c_int(n_steps), C.c_int64(pushes), C.c_int(N), C.c_int(D), C.c_double(gamma),
-                                _ptr(obs, torch.float32), _ptr(action, torch.int32), _ptr(reward, torch.float32),
-                                _ptr(next_obs, torch.float32), _ptr(terminal, torch.uint8, True), _ptr(done, torch.uint8),
-                                _ptr(state, torch.float32), _ptr(act_w), _ptr(rew, torch.float32),
-                                _ptr(nxt, torch.float32), _ptr(flag, torch.uint8), C.c_int64(state.shape[0]),
-                                C.c_int64(cursor), _dev(dev), _ptr(ep_len, torch.int32, True), C.c_int(max_episode_steps),
-                                _stream())
+    rc = lib().gymrl_nstep_push(_ptr(w_state, torch.float32), _ptr(w_action, torch.int32), _ptr(w_reward, torch.float32), _ptr(w_next, torch.float32),
+                                _ptr(w_term, torch.uint8), _ptr(w_done, torch.uint8), n_steps, pushes, N, D, gamma, _ptr(obs, torch.float32),
+                                _ptr(action, torch.int32), _ptr(reward, torch.float32), _ptr(next_obs, torch.float32),
+                                _ptr(terminal, torch.uint8, True), _ptr(done, torch.uint8), _ptr(state, torch.float32), _ptr(act_w),
+                                _ptr(rew, torch.float32), _ptr(nxt, torch.float32), _ptr(flag, torch.uint8), state.shape[0], cursor, _dev(dev),
+                                _ptr(ep_len, torch.int32, True), max_episode_steps, _stream())
     if rc < 0:
         check(rc, "gymrl_nstep_push")
     return rc == 1
 
 
 def per_workspace(B, device):
-    return torch.empty(int(lib().gymrl_per_workspace_bytes(C.c_int(B))), dtype=torch.uint8, device=device)
+    return torch.empty(int(lib().gymrl_per_workspace_bytes(B)), dtype=torch.uint8, device=device)
 
 
 def per_update(tree, cap, B, workspace, idx=None, idx_start=0, idx_is_tree=False, prio=None, prio_scalar_dev=None,
                prio_scalar=0.0, idx_start_dev=None):
-    check(lib().gymrl_per_update(_ptr(tree, torch.float64), C.c_int64(cap), _ptr(idx, torch.int32, True),
-                                 C.c_int64(idx_start), C.c_int(int(idx_is_tree)), _ptr(prio, torch.float64, True),
-                                 _ptr(prio_scalar_dev, torch.float64, True), C.c_double(prio_scalar), C.c_int(B),
-                                 _dev(idx_start_dev), _ptr(workspace), _stream()), "gymrl_per_update")
+    check(lib().gymrl_per_update(_ptr(tree, torch.float64), cap, _ptr(idx, torch.int32, True), idx_start, int(idx_is_tree),
+                                 _ptr(prio, torch.float64, True), _ptr(prio_scalar_dev, torch.float64, True), prio_scalar, B, _dev(idx_start_dev),
+                                 _ptr(workspace), _stream()), "gymrl_per_update")
 
 
 def per_max_leaf(tree, cap, out, workspace):
-    check(lib().gymrl_per_max_leaf(_ptr(tree, torch.float64), C.c_int64(cap), _ptr(out, torch.float64),
-                                   _ptr(workspace), _stream()), "gymrl_per_max_leaf")
+    check(lib().gymrl_per_max_leaf(_ptr(tree, torch.float64), cap, _ptr(out, torch.float64), _ptr(workspace), _stream()), "gymrl_per_max_leaf")
     return out
 
 
 def per_priorities(td, alpha, eps, clip=0.0, out=None):
     out = torch.empty(td.numel(), dtype=torch.float64, device=td.device) if out is None else out
-    check(lib().gymrl_per_priorities(_ptr(td, torch.float32), C.c_int(td.numel()), C.c_double(alpha), C.c_double(eps),
-                                     C.c_double(clip), _ptr(out, torch.float64), _stream()), "gymrl_per_priorities")
+    check(lib().gymrl_per_priorities(_ptr(td, torch.float32), td.numel(), alpha, eps, clip, _ptr(out, torch.float64), _stream()),
+          "gymrl_per_priorities")
     return out
 
 
@@ -656,10 +606,9 @@ PER_TD_MAX_BATCH = 512
 def per_update_td(tree, cap, idx, td, alpha, eps, workspace, clip=0.0, max_out=None, ticket=None):
     """gymrl_per_update_td: update_priorities of a sampled batch straight from the TD errors (B <= 512, cap < 2^30); with
     max_out f64[1] + ticket i32[1] (zero) the maximum over the leaves after the update comes out of the same two launches."""
-    check(lib().gymrl_per_update_td(_ptr(tree, torch.float64), C.c_int64(cap), _ptr(idx, torch.int32), _ptr(td, torch.float32),
-                                    C.c_int(idx.numel()), C.c_double(alpha), C.c_double(eps), C.c_double(clip),
-                                    _ptr(max_out, torch.float64, True), _ptr(ticket, torch.int32, True), _ptr(workspace),
-                                    _stream()), "gymrl_per_update_td")
+    check(lib().gymrl_per_update_td(_ptr(tree, torch.float64), cap, _ptr(idx, torch.int32), _ptr(td, torch.float32), idx.numel(), alpha, eps, clip,
+                                    _ptr(max_out, torch.float64, True), _ptr(ticket, torch.int32, True), _ptr(workspace), _stream()),
+          "gymrl_per_update_td")
 
 
 def per_sample(tree, cap, B, size, beta, workspace, u=None, seed=0, counter=0, variant_b=False, out=None, dev=None):
@@ -669,26 +618,21 @@ def per_sample(tree, cap, B, size, beta, workspace, u=None, seed=0, counter=0, v
         w = torch.empty(B, dtype=torch.float32, device=tree.device)
     else:
         idx, prio, w = out
-    check(lib().gymrl_per_sample(_ptr(tree, torch.float64), C.c_int64(cap), _ptr(u, torch.float64, True),
-                                 C.c_uint64(seed), C.c_uint64(counter), C.c_int(B), C.c_int64(size), C.c_double(beta),
-                                 C.c_int(int(variant_b)), _ptr(idx), _ptr(prio), _ptr(w), _dev(dev), _ptr(workspace),
-                                 _stream()), "gymrl_per_sample")
+    check(lib().gymrl_per_sample(_ptr(tree, torch.float64), cap, _ptr(u, torch.float64, True), seed, counter, B, size, beta, int(variant_b),
+                                 _ptr(idx), _ptr(prio), _ptr(w), _dev(dev), _ptr(workspace), _stream()), "gymrl_per_sample")
     return idx, prio, w
 
 
 def noisy_noise(nin, nout, w_eps, b_eps, eps_in=None, eps_out=None, seed=0, counter=0, counter_dev=None):
-    check(lib().gymrl_noisy_noise(_ptr(eps_in, torch.float32, True), _ptr(eps_out, torch.float32, True),
-                                  C.c_uint64(seed), C.c_uint64(counter), C.c_int(nin), C.c_int(nout),
-                                  _ptr(w_eps, torch.float32), _ptr(b_eps, torch.float32), _dev(counter_dev), _stream()),
-          "gymrl_noisy_noise")
+    check(lib().gymrl_noisy_noise(_ptr(eps_in, torch.float32, True), _ptr(eps_out, torch.float32, True), seed, counter, nin, nout,
+                                  _ptr(w_eps, torch.float32), _ptr(b_eps, torch.float32), _dev(counter_dev), _stream()), "gymrl_noisy_noise")
 
 
 def epsilon_greedy(q, epsilon, u=None, seed=0, counter=0, env_id0=0, act_out=None):
     n, A = q.shape
     act_out = torch.empty(n, dtype=torch.int32, device=q.device) if act_out is None else act_out
-    check(lib().gymrl_epsilon_greedy(_ptr(q, torch.float32), _ptr(u, torch.float32, True), C.c_uint64(seed),
-                                     C.c_uint64(counter), C.c_int64(env_id0), C.c_int(n), C.c_int(A),
-                                     C.c_float(epsilon), _ptr(act_out, torch.int32), _stream()), "gymrl_epsilon_greedy")
+    check(lib().gymrl_epsilon_greedy(_ptr(q, torch.float32), _ptr(u, torch.float32, True), seed, counter, env_id0, n, A, epsilon,
+                                     _ptr(act_out, torch.int32), _stream()), "gymrl_epsilon_greedy")
     return act_out
 
 
@@ -697,11 +641,10 @@ def dqn_td_loss(q, q_next_target, act, rew, flag, gamma_n, q_next_online=None, w
     td = torch.empty(B, device=q.device)
     dq = torch.empty_like(q)
     ws = _reduce_ws(q.device) if loss_sum is not None else None
-    check(lib().gymrl_dqn_td_loss(_ptr(q, torch.float32), _ptr(q_next_online, torch.float32, True),
-                                  _ptr(q_next_target, torch.float32), _ptr(act, torch.int32), _ptr(rew, torch.float32),
-                                  _ptr(flag, torch.float32), _ptr(w, torch.float32, True), C.c_int(B), C.c_int(A),
-                                  C.c_double(gamma_n), _ptr(td), _ptr(dq), _ptr(loss_sum, torch.float64, True),
-                                  _ptr(ws, None, True), _stream()), "gymrl_dqn_td_loss")
+    check(lib().gymrl_dqn_td_loss(_ptr(q, torch.float32), _ptr(q_next_online, torch.float32, True), _ptr(q_next_target, torch.float32),
+                                  _ptr(act, torch.int32), _ptr(rew, torch.float32), _ptr(flag, torch.float32), _ptr(w, torch.float32, True), B, A,
+                                  gamma_n, _ptr(td), _ptr(dq), _ptr(loss_sum, torch.float64, True), _ptr(ws, None, True), _stream()),
+          "gymrl_dqn_td_loss")
     return td, dq
 
 
@@ -709,44 +652,40 @@ def noisy_action(mu, std, bound, eps=None, mode=0, noise_clip=0.0, seed=0, count
     """gymrl_noisy_action: Gaussian exploration noise (mode 0, numpy-float64 semantics) or TD3 target-policy
     smoothing (mode 1, torch-float32 semantics) on an action tensor; eps = explicit f64 N(0,1) draws."""
     out = torch.empty_like(mu) if out is None else out
-    check(lib().gymrl_noisy_action(_ptr(mu, torch.float32), _ptr(eps, torch.float64, True), C.c_uint64(seed),
-                                   C.c_uint64(counter), C.c_int64(mu.numel()), C.c_int(mode), C.c_double(std),
-                                   C.c_double(noise_clip), C.c_double(bound), _ptr(out, torch.float32), _stream()),
-          "gymrl_noisy_action")
+    check(lib().gymrl_noisy_action(_ptr(mu, torch.float32), _ptr(eps, torch.float64, True), seed, counter, mu.numel(), mode, std, noise_clip, bound,
+                                   _ptr(out, torch.float32), _stream()), "gymrl_noisy_action")
     return out
 
 
 def mse_loss(q, y, sum_out):
     """One critic's F.mse_loss forward+backward: returns dq; sum_out (f64[1]) += sum (q - y)^2."""
     dq = torch.empty_like(q)
-    check(lib().gymrl_mse_loss(_ptr(q, torch.float32), _ptr(y, torch.float32), C.c_int(q.numel()), _ptr(dq),
-                               _ptr(sum_out, torch.float64), _ptr(_reduce_ws(q.device)), _stream()), "gymrl_mse_loss")
+    check(lib().gymrl_mse_loss(_ptr(q, torch.float32), _ptr(y, torch.float32), q.numel(), _ptr(dq), _ptr(sum_out, torch.float64),
+                               _ptr(_reduce_ws(q.device)), _stream()), "gymrl_mse_loss")
     return dq
 
 
 def neg_mean_loss(q, sum_out):
     """Actor loss -mean(q): returns dq = -1/B; sum_out (f64[1]) += sum q."""
     dq = torch.empty_like(q)
-    check(lib().gymrl_neg_mean_loss(_ptr(q, torch.float32), C.c_int(q.numel()), _ptr(dq), _ptr(sum_out, torch.float64),
-                                    _ptr(_reduce_ws(q.device)), _stream()), "gymrl_neg_mean_loss")
+    check(lib().gymrl_neg_mean_loss(_ptr(q, torch.float32), q.numel(), _ptr(dq), _ptr(sum_out, torch.float64), _ptr(_reduce_ws(q.device)), _stream()),
+          "gymrl_neg_mean_loss")
     return dq
 
 
 def dsac_target(probs_n, q1n, q2n, rew, done, log_alpha, gamma):
     y = torch.empty_like(rew)
     B, A = probs_n.shape
-    check(lib().gymrl_dsac_target(_ptr(probs_n, torch.float32), _ptr(q1n, torch.float32), _ptr(q2n, torch.float32),
-                                  _ptr(rew, torch.float32), _ptr(done, torch.float32), _ptr(log_alpha, torch.float32),
-                                  C.c_int(B), C.c_int(A), C.c_double(gamma), _ptr(y), _stream()), "gymrl_dsac_target")
+    check(lib().gymrl_dsac_target(_ptr(probs_n, torch.float32), _ptr(q1n, torch.float32), _ptr(q2n, torch.float32), _ptr(rew, torch.float32),
+                                  _ptr(done, torch.float32), _ptr(log_alpha, torch.float32), B, A, gamma, _ptr(y), _stream()), "gymrl_dsac_target")
     return y
 
 
 def dsac_critic_loss(q1, q2, act, y, sums):
     B, A = q1.shape
     d1, d2 = torch.empty_like(q1), torch.empty_like(q2)
-    check(lib().gymrl_dsac_critic_loss(_ptr(q1, torch.float32), _ptr(q2, torch.float32), _ptr(act, torch.int32),
-                                       _ptr(y, torch.float32), C.c_int(B), C.c_int(A), _ptr(d1), _ptr(d2),
-                                       _ptr(sums, torch.float64), _ptr(_reduce_ws(q1.device)), _stream()),
+    check(lib().gymrl_dsac_critic_loss(_ptr(q1, torch.float32), _ptr(q2, torch.float32), _ptr(act, torch.int32), _ptr(y, torch.float32), B, A,
+                                       _ptr(d1), _ptr(d2), _ptr(sums, torch.float64), _ptr(_reduce_ws(q1.device)), _stream()),
           "gymrl_dsac_critic_loss")
     return d1, d2
 
@@ -754,28 +693,23 @@ def dsac_critic_loss(q1, q2, act, y, sums):
 def dsac_actor_loss(probs, q1, q2, log_alpha, sums):
     B, A = probs.shape
     dp = torch.empty_like(probs)
-    check(lib().gymrl_dsac_actor_loss(_ptr(probs, torch.float32), _ptr(q1, torch.float32), _ptr(q2, torch.float32),
-                                      _ptr(log_alpha, torch.float32), C.c_int(B), C.c_int(A), _ptr(dp),
-                                      _ptr(sums, torch.float64), _ptr(_reduce_ws(probs.device)), _stream()),
-          "gymrl_dsac_actor_loss")
+    check(lib().gymrl_dsac_actor_loss(_ptr(probs, torch.float32), _ptr(q1, torch.float32), _ptr(q2, torch.float32), _ptr(log_alpha, torch.float32), B,
+                                      A, _ptr(dp), _ptr(sums, torch.float64), _ptr(_reduce_ws(probs.device)), _stream()), "gymrl_dsac_actor_loss")
     return dp
 
 
 def dsac_alpha_step(log_alpha, m, v, sums, B, target_entropy, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, loss_out=None,
                     bias_dev=None):
-    check(lib().gymrl_dsac_alpha_step(_ptr(log_alpha, torch.float32), _ptr(m, torch.float32), _ptr(v, torch.float32),
-                                      _ptr(sums, torch.float64), C.c_int(B), C.c_double(target_entropy), C.c_double(lr),
-                                      C.c_double(beta1), C.c_double(beta2), C.c_double(eps), C.c_int64(step),
-                                      _ptr(bias_dev, torch.float64, True), _ptr(loss_out, torch.float64, True), _stream()),
-          "gymrl_dsac_alpha_step")
+    check(lib().gymrl_dsac_alpha_step(_ptr(log_alpha, torch.float32), _ptr(m, torch.float32), _ptr(v, torch.float32), _ptr(sums, torch.float64), B,
+                                      target_entropy, lr, beta1, beta2, eps, step, _ptr(bias_dev, torch.float64, True),
+                                      _ptr(loss_out, torch.float64, True), _stream()), "gymrl_dsac_alpha_step")
 
 
 def sac_sample_fwd(mean, log_std, eps, bound):
     B, A = mean.shape
     action, logp = torch.empty_like(mean), torch.empty(B, device=mean.device)
-    check(lib().gymrl_sac_sample_fwd(_ptr(mean, torch.float32), _ptr(log_std, torch.float32), _ptr(eps, torch.float32),
-                                     C.c_int(B), C.c_int(A), C.c_float(bound), _ptr(action), _ptr(logp), _stream()),
-          "gymrl_sac_sample_fwd")
+    check(lib().gymrl_sac_sample_fwd(_ptr(mean, torch.float32), _ptr(log_std, torch.float32), _ptr(eps, torch.float32), B, A, bound, _ptr(action),
+                                     _ptr(logp), _stream()), "gymrl_sac_sample_fwd")
     return action, logp
 
 
@@ -783,49 +717,45 @@ def sac_sample_bwd(mean, log_std, eps, d_action, d_logp, bound):
     B, A = mean.shape
     dm, ds = torch.empty_like(mean), torch.empty_like(mean)
     check(lib().gymrl_sac_sample_bwd(_ptr(mean, torch.float32), _ptr(log_std, torch.float32), _ptr(eps, torch.float32),
-                                     _ptr(d_action, torch.float32, True), _ptr(d_logp, torch.float32, True), C.c_int(B),
-                                     C.c_int(A), C.c_float(bound), _ptr(dm), _ptr(ds), _stream()), "gymrl_sac_sample_bwd")
+                                     _ptr(d_action, torch.float32, True), _ptr(d_logp, torch.float32, True), B, A, bound, _ptr(dm), _ptr(ds),
+                                     _stream()), "gymrl_sac_sample_bwd")
     return dm, ds
 
 
 def sac_target(rew, done, q1n, q2n, logp_n, log_alpha, gamma):
     y = torch.empty_like(rew)
-    check(lib().gymrl_sac_target(_ptr(rew, torch.float32), _ptr(done, torch.float32), _ptr(q1n, torch.float32),
-                                 _ptr(q2n, torch.float32), _ptr(logp_n, torch.float32), _ptr(log_alpha, torch.float64),
-                                 C.c_int(rew.numel()), C.c_double(gamma), _ptr(y), _stream()), "gymrl_sac_target")
+    check(lib().gymrl_sac_target(_ptr(rew, torch.float32), _ptr(done, torch.float32), _ptr(q1n, torch.float32), _ptr(q2n, torch.float32),
+                                 _ptr(logp_n, torch.float32), _ptr(log_alpha, torch.float64), rew.numel(), gamma, _ptr(y), _stream()),
+          "gymrl_sac_target")
     return y
 
 
 def sac_critic_loss(q1, q2, y, sums):
     d1, d2 = torch.empty_like(q1), torch.empty_like(q2)
-    check(lib().gymrl_sac_critic_loss(_ptr(q1, torch.float32), _ptr(q2, torch.float32), _ptr(y, torch.float32),
-                                      C.c_int(q1.numel()), _ptr(d1), _ptr(d2), _ptr(sums, torch.float64),
-                                      _ptr(_reduce_ws(q1.device)), _stream()), "gymrl_sac_critic_loss")
+    check(lib().gymrl_sac_critic_loss(_ptr(q1, torch.float32), _ptr(q2, torch.float32), _ptr(y, torch.float32), q1.numel(), _ptr(d1), _ptr(d2),
+                                      _ptr(sums, torch.float64), _ptr(_reduce_ws(q1.device)), _stream()), "gymrl_sac_critic_loss")
     return d1, d2
 
 
 def sac_actor_loss(logp, q1, q2, log_alpha, target_entropy, sums):
     dl, d1, d2 = torch.empty_like(logp), torch.empty_like(q1), torch.empty_like(q2)
-    check(lib().gymrl_sac_actor_loss(_ptr(logp, torch.float32), _ptr(q1, torch.float32), _ptr(q2, torch.float32),
-                                     _ptr(log_alpha, torch.float64), C.c_int(logp.numel()), C.c_double(target_entropy),
-                                     _ptr(dl), _ptr(d1), _ptr(d2), _ptr(sums, torch.float64),
+    check(lib().gymrl_sac_actor_loss(_ptr(logp, torch.float32), _ptr(q1, torch.float32), _ptr(q2, torch.float32), _ptr(log_alpha, torch.float64),
+                                     logp.numel(), target_entropy, _ptr(dl), _ptr(d1), _ptr(d2), _ptr(sums, torch.float64),
                                      _ptr(_reduce_ws(q1.device)), _stream()), "gymrl_sac_actor_loss")
     return dl, d1, d2
 
 
 def sac_alpha_step(log_alpha, m, v, sums, B, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, loss_out=None, bias_dev=None):
-    check(lib().gymrl_sac_alpha_step(_ptr(log_alpha, torch.float64), _ptr(m, torch.float64), _ptr(v, torch.float64),
-                                     _ptr(sums, torch.float64), C.c_int(B), C.c_double(lr), C.c_double(beta1),
-                                     C.c_double(beta2), C.c_double(eps), C.c_int64(step),
-                                     _ptr(bias_dev, torch.float64, True), _ptr(loss_out, torch.float64, True), _stream()),
+    check(lib().gymrl_sac_alpha_step(_ptr(log_alpha, torch.float64), _ptr(m, torch.float64), _ptr(v, torch.float64), _ptr(sums, torch.float64), B, lr,
+                                     beta1, beta2, eps, step, _ptr(bias_dev, torch.float64, True), _ptr(loss_out, torch.float64, True), _stream()),
           "gymrl_sac_alpha_step")
 
 
 def running_norm(x, stats, update=True, out=None):
     N, D = x.shape
     out = torch.empty_like(x) if out is None else out
-    check(lib().gymrl_running_norm(_ptr(x, torch.float32), C.c_int(N), C.c_int(D), _ptr(stats, torch.float64),
-                                   C.c_int(int(update)), _ptr(out, torch.float32), _stream()), "gymrl_running_norm")
+    check(lib().gymrl_running_norm(_ptr(x, torch.float32), N, D, _ptr(stats, torch.float64), int(update), _ptr(out, torch.float32), _stream()),
+          "gymrl_running_norm")
     return out
 
 
@@ -851,9 +781,8 @@ def reward_scaling_masked(r, live, gamma, R, stats, done=None, out=None):
 
 def reward_scaling(r, done, gamma, R, stats, out=None):
     out = torch.empty_like(r) if out is None else out
-    check(lib().gymrl_reward_scaling(_ptr(r, torch.float32), _ptr(done, torch.uint8, True), C.c_int(r.numel()),
-                                     C.c_double(gamma), _ptr(R, torch.float64), _ptr(stats, torch.float64),
-                                     _ptr(out, torch.float32), _stream()), "gymrl_reward_scaling")
+    check(lib().gymrl_reward_scaling(_ptr(r, torch.float32), _ptr(done, torch.uint8, True), r.numel(), gamma, _ptr(R, torch.float64),
+                                     _ptr(stats, torch.float64), _ptr(out, torch.float32), _stream()), "gymrl_reward_scaling")
     return out
 
 
@@ -861,13 +790,12 @@ def reward_scaling(r, done, gamma, R, stats, out=None):
 def mlp_pack(W, packed=None):
     """gymrl_mlp_pack: nn.Linear weight [out, in] -> MFMA B-operand image (f32 1-D).  Reuses `packed`."""
     out_dim, in_dim = W.shape
-    n = lib().gymrl_mlp_packed_floats(C.c_int(out_dim), C.c_int(in_dim))
+    n = lib().gymrl_mlp_packed_floats(out_dim, in_dim)
     if packed is None:
         packed = torch.empty(n, dtype=torch.float32, device=W.device)
     elif packed.numel() != n:
         raise ValueError("packed buffer has the wrong size")
-    check(lib().gymrl_mlp_pack(_ptr(W, torch.float32), C.c_int(out_dim), C.c_int(in_dim), _ptr(packed, torch.float32),
-                               _stream()), "gymrl_mlp_pack")
+    check(lib().gymrl_mlp_pack(_ptr(W, torch.float32), out_dim, in_dim, _ptr(packed, torch.float32), _stream()), "gymrl_mlp_pack")
     return packed
 
 
@@ -897,47 +825,42 @@ def mlp_forward(x, desc):
     """gymrl_mlp_forward: the whole Linear(+Tanh|ReLU) chain on x [n_rows, in_dim] in one launch; outputs
     go to the `out` tensors named in the descriptor."""
     n, in_dim = x.shape
-    check(lib().gymrl_mlp_forward(_ptr(x, torch.float32), C.c_int(n), C.c_int(in_dim), C.byref(desc), _stream()),
-          "gymrl_mlp_forward")
+    check(lib().gymrl_mlp_forward(_ptr(x, torch.float32), n, in_dim, C.byref(desc), _stream()), "gymrl_mlp_forward")
 
 
 # ------------------------------------------------------ MLP update passes ---
 def mlp_train_workspace(C_, D, A, device):
-    n = lib().gymrl_mlp_train_workspace_bytes(C.c_int(C_), C.c_int(D), C.c_int(A))
+    n = lib().gymrl_mlp_train_workspace_bytes(C_, D, A)
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
 def linear_tanh_smallk(x, W, b, out):
     """out = tanh(x W^T + b) for a first layer with in_features in {2,3,4,8} (shared.0 + Tanh)."""
     B, D = x.shape
-    check(lib().gymrl_linear_tanh_smallk(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True),
-                                         C.c_int64(B), C.c_int(D), C.c_int(W.shape[0]), _ptr(out, torch.float32),
-                                         _stream()), "gymrl_linear_tanh_smallk")
+    check(lib().gymrl_linear_tanh_smallk(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True), B, D, W.shape[0],
+                                         _ptr(out, torch.float32), _stream()), "gymrl_linear_tanh_smallk")
     return out
 
 
 def linear_smallk(x, W, b, out):
     """out = x W^T + b for a first layer with in_features in {2,3,4,8} and a power-of-two width (no activation)."""
     B, D = x.shape
-    check(lib().gymrl_linear_smallk(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True),
-                                    C.c_int64(B), C.c_int(D), C.c_int(W.shape[0]), _ptr(out, torch.float32), _stream()),
-          "gymrl_linear_smallk")
+    check(lib().gymrl_linear_smallk(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True), B, D, W.shape[0],
+                                    _ptr(out, torch.float32), _stream()), "gymrl_linear_smallk")
     return out
 
 
 def tanh_inplace(z, bias=None):
     """z <- tanh(z + bias) in place; bias [C] broadcasts over the rows of z [..., C]."""
-    check(lib().gymrl_tanh_inplace(_ptr(z, torch.float32), C.c_int64(z.numel()), _ptr(bias, torch.float32, True),
-                                   C.c_int(z.shape[-1]), _stream()), "gymrl_tanh_inplace")
+    check(lib().gymrl_tanh_inplace(_ptr(z, torch.float32), z.numel(), _ptr(bias, torch.float32, True), z.shape[-1], _stream()), "gymrl_tanh_inplace")
     return z
 
 
 def tanh_bwd_colsum(dH, H, colsum_out, workspace):
     """dH <- dH * (1 - H^2) in place; colsum_out[c] = sum_r dH[r, c]."""
     B, Cc = dH.shape
-    check(lib().gymrl_tanh_bwd_colsum(_ptr(dH, torch.float32), _ptr(H, torch.float32), C.c_int64(B), C.c_int(Cc),
-                                      _ptr(colsum_out, torch.float32), _ptr(workspace), _stream()),
-          "gymrl_tanh_bwd_colsum")
+    check(lib().gymrl_tanh_bwd_colsum(_ptr(dH, torch.float32), _ptr(H, torch.float32), B, Cc, _ptr(colsum_out, torch.float32), _ptr(workspace),
+                                      _stream()), "gymrl_tanh_bwd_colsum")
     return dH
 
 
@@ -946,34 +869,30 @@ def linear_smallk_bwd(dH, H, x, dW, db, workspace, W=None, b=None):
     (W, b) the kernel recomputes H = tanh(x W^T + b) instead of reading it (H may then be None).  dW = db = None: the
     block partials only (they stay in `workspace` for update_finalize)."""
     B, Cc = dH.shape
-    check(lib().gymrl_linear_smallk_bwd(_ptr(dH, torch.float32), _ptr(H, torch.float32, True), _ptr(x, torch.float32),
-                                        C.c_int64(B), C.c_int(x.shape[1]), C.c_int(Cc), _ptr(dW, torch.float32, True),
-                                        _ptr(db, torch.float32, True), _ptr(W, torch.float32, True), _ptr(b, torch.float32, True),
-                                        _ptr(workspace), _stream()), "gymrl_linear_smallk_bwd")
+    check(lib().gymrl_linear_smallk_bwd(_ptr(dH, torch.float32), _ptr(H, torch.float32, True), _ptr(x, torch.float32), B, x.shape[1], Cc,
+                                        _ptr(dW, torch.float32, True), _ptr(db, torch.float32, True), _ptr(W, torch.float32, True),
+                                        _ptr(b, torch.float32, True), _ptr(workspace), _stream()), "gymrl_linear_smallk_bwd")
 
 
 def heads_fwd_tanh(Zac, Wa2, ba2, Wc2, bc2, logits, value, bac=None, store_h=True):
     """Zac [B, 2C] -> tanh in place + logits [B, A] + value [B] (include/gymrl.h gymrl_heads_fwd_tanh)."""
     B, C2 = Zac.shape
-    check(lib().gymrl_heads_fwd_tanh(_ptr(Zac, torch.float32), C.c_int64(B), C.c_int(C2 // 2), C.c_int(Wa2.shape[0]),
-                                     _ptr(bac, torch.float32, True), _ptr(Wa2, torch.float32), _ptr(ba2, torch.float32, True), _ptr(Wc2, torch.float32),
-                                     _ptr(bc2, torch.float32, True), _ptr(logits, torch.float32),
-                                     _ptr(value, torch.float32), C.c_int(int(store_h)), _stream()), "gymrl_heads_fwd_tanh")
+    check(lib().gymrl_heads_fwd_tanh(_ptr(Zac, torch.float32), B, C2 // 2, Wa2.shape[0], _ptr(bac, torch.float32, True), _ptr(Wa2, torch.float32),
+                                     _ptr(ba2, torch.float32, True), _ptr(Wc2, torch.float32), _ptr(bc2, torch.float32, True),
+                                     _ptr(logits, torch.float32), _ptr(value, torch.float32), int(store_h), _stream()), "gymrl_heads_fwd_tanh")
 
 
 def heads_bwd(Hac, dlogits, dv, Wa2, Wc2, dZac, dbac, dWa2, dba2, dWc2, dbc2, workspace, pre_activation=False, bac=None):
     """Backward of both heads in one pass over Hac = [Ha | Hc] (include/gymrl.h gymrl_heads_bwd)."""
     B, C2 = Hac.shape
-    check(lib().gymrl_heads_bwd(_ptr(Hac, torch.float32), _ptr(dlogits, torch.float32), _ptr(dv, torch.float32),
-                                C.c_int64(B), C.c_int(C2 // 2), C.c_int(dlogits.shape[1]), _ptr(Wa2, torch.float32),
-                                _ptr(Wc2, torch.float32), _ptr(dZac, torch.float32), _ptr(dbac, torch.float32),
-                                _ptr(dWa2, torch.float32), _ptr(dba2, torch.float32), _ptr(dWc2, torch.float32),
-                                _ptr(dbc2, torch.float32), C.c_int(int(pre_activation)), _ptr(bac, torch.float32, True),
-                                _ptr(workspace), _stream()), "gymrl_heads_bwd")
+    check(lib().gymrl_heads_bwd(_ptr(Hac, torch.float32), _ptr(dlogits, torch.float32), _ptr(dv, torch.float32), B, C2 // 2, dlogits.shape[1],
+                                _ptr(Wa2, torch.float32), _ptr(Wc2, torch.float32), _ptr(dZac, torch.float32), _ptr(dbac, torch.float32),
+                                _ptr(dWa2, torch.float32), _ptr(dba2, torch.float32), _ptr(dWc2, torch.float32), _ptr(dbc2, torch.float32),
+                                int(pre_activation), _ptr(bac, torch.float32, True), _ptr(workspace), _stream()), "gymrl_heads_bwd")
 
 
 def heads_loss_blocks(B, C_=256):
-    return int(lib().gymrl_heads_loss_blocks(C.c_int64(B), C.c_int(C_)))
+    return int(lib().gymrl_heads_loss_blocks(B, C_))
 
 
 def heads_loss_fwd_bwd(Zac, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, cfg, adv_moments, dbac, dWa2, dba2, dWc2,
@@ -982,13 +901,13 @@ def heads_loss_fwd_bwd(Zac, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, cf
     outputs None: the block partials only (they stay in `workspace` for update_finalize)."""
     B, C2 = Zac.shape
     c = PPOCfg(*[float(v) for v in cfg])
-    check(lib().gymrl_heads_loss_fwd_bwd(
-        _ptr(Zac, torch.float32), C.c_int64(B), C.c_int(C2 // 2), C.c_int(Wa2.shape[0]), _ptr(bac, torch.float32, True),
-        _ptr(Wa2, torch.float32), _ptr(ba2, torch.float32, True), _ptr(Wc2, torch.float32), _ptr(bc2, torch.float32, True),
-        _ptr(act, torch.int32), _ptr(logp_old, torch.float32), _ptr(adv, torch.float32), _ptr(ret, torch.float32),
-        _ptr(adv_moments, torch.float64, True), C.byref(c), _ptr(dbac, torch.float32, True), _ptr(dWa2, torch.float32, True),
-        _ptr(dba2, torch.float32, True), _ptr(dWc2, torch.float32, True), _ptr(dbc2, torch.float32, True), _ptr(metric_parts, torch.float64),
-        _ptr(workspace), _stream()), "gymrl_heads_loss_fwd_bwd")
+    check(lib().gymrl_heads_loss_fwd_bwd(_ptr(Zac, torch.float32), B, C2 // 2, Wa2.shape[0], _ptr(bac, torch.float32, True), _ptr(Wa2, torch.float32),
+                                         _ptr(ba2, torch.float32, True), _ptr(Wc2, torch.float32), _ptr(bc2, torch.float32, True),
+                                         _ptr(act, torch.int32), _ptr(logp_old, torch.float32), _ptr(adv, torch.float32), _ptr(ret, torch.float32),
+                                         _ptr(adv_moments, torch.float64, True), C.byref(c), _ptr(dbac, torch.float32, True),
+                                         _ptr(dWa2, torch.float32, True), _ptr(dba2, torch.float32, True), _ptr(dWc2, torch.float32, True),
+                                         _ptr(dbc2, torch.float32, True), _ptr(metric_parts, torch.float64), _ptr(workspace), _stream()),
+          "gymrl_heads_loss_fwd_bwd")
 
 
 # ------------------------------------------------------ update-path GEMMs ---
@@ -1002,7 +921,7 @@ def gemm_config(key, value):
     L = lib()
     if not hasattr(L, "gymrl_gemm_config"):
         raise RuntimeError("gymrl_gemm_config exists in the probe build only (make -C gymrl_amd/csrc prof)")
-    check(L.gymrl_gemm_config(C.c_int(key), C.c_int(value)), "gymrl_gemm_config")
+    check(L.gymrl_gemm_config(key, value), "gymrl_gemm_config")
 
 
 def linear_shape_ok(K, N):
@@ -1014,18 +933,16 @@ def linear_shape_ok(K, N):
 def linear_fwd(x, W, b, out, act=True):
     """out [B, N] = tanh(x [B, K] W[N, K]^T + b) (act=False: no tanh; b None: no bias) — exact-f32 MFMA, fused epilogue."""
     B, K = x.shape
-    check(lib().gymrl_linear_fwd(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True),
-                                 C.c_int64(B), C.c_int(K), C.c_int(W.shape[0]), C.c_int(int(act)), _ptr(out, torch.float32),
-                                 _stream()), "gymrl_linear_fwd")
+    check(lib().gymrl_linear_fwd(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True), B, K, W.shape[0], int(act),
+                                 _ptr(out, torch.float32), _stream()), "gymrl_linear_fwd")
     return out
 
 
 def linear_bwd_input(dy, W, H, dx):
     """dx [B, K] = (dy [B, N] W[N, K]) * (1 - H^2)  (H None: no factor)."""
     B, N = dy.shape
-    check(lib().gymrl_linear_bwd_input(_ptr(dy, torch.float32), _ptr(W, torch.float32), _ptr(H, torch.float32, True),
-                                       C.c_int64(B), C.c_int(N), C.c_int(W.shape[1]), _ptr(dx, torch.float32), _stream()),
-          "gymrl_linear_bwd_input")
+    check(lib().gymrl_linear_bwd_input(_ptr(dy, torch.float32), _ptr(W, torch.float32), _ptr(H, torch.float32, True), B, N, W.shape[1],
+                                       _ptr(dx, torch.float32), _stream()), "gymrl_linear_bwd_input")
     return dx
 
 
@@ -1034,16 +951,14 @@ def linear_bwd_input_add(dy, W, g, dx):
     B, N = dy.shape
     if g.shape != dx.shape or g.data_ptr() == dx.data_ptr():
         raise ValueError("linear_bwd_input_add: g and dx are two tensors of one shape")
-    check(lib().gymrl_linear_bwd_input_add(_ptr(dy, torch.float32), _ptr(W, torch.float32), _ptr(g, torch.float32),
-                                           C.c_int64(B), C.c_int(N), C.c_int(W.shape[1]), _ptr(dx, torch.float32), _stream()),
-          "gymrl_linear_bwd_input_add")
+    check(lib().gymrl_linear_bwd_input_add(_ptr(dy, torch.float32), _ptr(W, torch.float32), _ptr(g, torch.float32), B, N, W.shape[1],
+                                           _ptr(dx, torch.float32), _stream()), "gymrl_linear_bwd_input_add")
     return dx
 
 
 def linear_bwd_weight_geometry(B, N):
     s, r = C.c_int(0), C.c_int64(0)
-    check(lib().gymrl_linear_bwd_weight_geometry(C.c_int64(B), C.c_int(N), C.byref(s), C.byref(r)),
-          "gymrl_linear_bwd_weight_geometry")
+    check(lib().gymrl_linear_bwd_weight_geometry(B, N, C.byref(s), C.byref(r)), "gymrl_linear_bwd_weight_geometry")
     return s.value, r.value
 
 
@@ -1055,8 +970,7 @@ def linear_bwd_weight(dy, x, dW, workspace, db=None, partials_db=False):
         db_arg = _ptr(workspace)                       # a non-NULL flag: nothing is written through it in this mode
     else:
         db_arg = _ptr(db, torch.float32, True)
-    check(lib().gymrl_linear_bwd_weight(_ptr(dy, torch.float32), _ptr(x, torch.float32), C.c_int64(B), C.c_int(N),
-                                        C.c_int(x.shape[1]), _ptr(dW, torch.float32, True), db_arg,
+    check(lib().gymrl_linear_bwd_weight(_ptr(dy, torch.float32), _ptr(x, torch.float32), B, N, x.shape[1], _ptr(dW, torch.float32, True), db_arg,
                                         _ptr(workspace), _stream()), "gymrl_linear_bwd_weight")
     return dW
 
@@ -1065,9 +979,8 @@ def update_finalize(B, C_, A, D, ws_dw_ac, dWac, ws_dw_2, dW2, db2, ws_heads, db
     """gymrl_update_finalize: the second halves of a minibatch's five batch reductions (both 256-deep weight gradients, the
     heads' and the first layer's gradients) as ONE launch, from the partials their producers left in their workspaces."""
     f = lambda t: _ptr(t, torch.float32)        # noqa: E731
-    check(lib().gymrl_update_finalize(C.c_int64(B), C.c_int(C_), C.c_int(A), C.c_int(D), _ptr(ws_dw_ac), f(dWac), _ptr(ws_dw_2),
-                                      f(dW2), f(db2), _ptr(ws_heads), f(dbac), f(dWa2), f(dba2), f(dWc2), f(dbc2), _ptr(ws_smallk),
-                                      f(dW1), f(db1), _stream()), "gymrl_update_finalize")
+    check(lib().gymrl_update_finalize(B, C_, A, D, _ptr(ws_dw_ac), f(dWac), _ptr(ws_dw_2), f(dW2), f(db2), _ptr(ws_heads), f(dbac), f(dWa2), f(dba2),
+                                      f(dWc2), f(dbc2), _ptr(ws_smallk), f(dW1), f(db1), _stream()), "gymrl_update_finalize")
 
 
 # ------------------------------------------------------ persistent rollout ---
@@ -1167,7 +1080,7 @@ def _same(vals, what):
 
 
 def lin_workspace(B, N, K, n_items, device):
-    n = lib().gymrl_lin_workspace_bytes(C.c_int(B), C.c_int(N), C.c_int(K), C.c_int(n_items))
+    n = lib().gymrl_lin_workspace_bytes(B, N, K, n_items)
     return torch.empty(max(n // 4, 1), dtype=torch.float32, device=device) if n else None
 
 
@@ -1193,9 +1106,8 @@ def lin_fwd(x, w, b, act=0, x2=None, out=None, lo=0.0, hi=0.0, argmax=None):
                       b=[None if t is None else _ptr(t, torch.float32).value for t in bs], y=py,
                       act=acts, lo=_as_items(lo, n), hi=_as_items(hi, n),
                       argmax=[None if t is None else _ptr(t, torch.int32).value for t in _as_items(argmax, n)])
-    check(lib().gymrl_lin_fwd(items, C.c_int(n), C.c_int(B), C.c_int(K), C.c_int(K1), C.c_int(N),
-                              C.c_int(_same(ldx, "a row stride")), C.c_int(_same(ldx2, "a row stride")),
-                              C.c_int(_same(ldy, "a row stride")), _stream()), "gymrl_lin_fwd")
+    check(lib().gymrl_lin_fwd(items, n, B, K, K1, N, _same(ldx, "a row stride"), _same(ldx2, "a row stride"), _same(ldy, "a row stride"), _stream()),
+          "gymrl_lin_fwd")
     return outs if multi else outs[0]
 
 
@@ -1228,10 +1140,8 @@ def lin_bwd_input(dy, y, w, act=0, K1=None, dx=None, dx2=None, want=(True, True)
     pdx2, lddx2 = zip(*(_rows(t, True) for t in dx2s))
     items = _lin_pack(n, dy=pdy, y=py, w=[_ptr(t, torch.float32).value for t in ws], dx=pdx, dx2=pdx2,
                       act=acts, lo=_as_items(lo, n), hi=_as_items(hi, n))
-    check(lib().gymrl_lin_bwd_input(items, C.c_int(n), C.c_int(B), C.c_int(N), C.c_int(K), C.c_int(K1),
-                                    C.c_int(_same(ldy, "a row stride")), C.c_int(_same(lddx, "a row stride")),
-                                    C.c_int(_same(lddx2, "a row stride")), C.c_int(int(accumulate)),
-                                    C.c_int(int(sum_items)), _stream()), "gymrl_lin_bwd_input")
+    check(lib().gymrl_lin_bwd_input(items, n, B, N, K, K1, _same(ldy, "a row stride"), _same(lddx, "a row stride"), _same(lddx2, "a row stride"),
+                                    int(accumulate), int(sum_items), _stream()), "gymrl_lin_bwd_input")
     if sum_items:
         return dxs[0], dx2s[0]
     return (dxs, dx2s) if multi else (dxs[0], dx2s[0])
@@ -1258,11 +1168,8 @@ def lin_bwd_weight(dy, y, x, dw, db=None, act=0, x2=None, lo=0.0, hi=0.0, accumu
     items = _lin_pack(n, dy=pdy, y=py, x=px, x2=px2, dw=[_ptr(t, torch.float32).value for t in dws],
                       db=[None if t is None else _ptr(t, torch.float32).value for t in dbs],
                       act=acts, lo=_as_items(lo, n), hi=_as_items(hi, n))
-    check(lib().gymrl_lin_bwd_weight(items, C.c_int(n), C.c_int(B), C.c_int(N), C.c_int(K), C.c_int(K1),
-                                     C.c_int(_same(ldy, "a row stride")), C.c_int(_same(ldx, "a row stride")),
-                                     C.c_int(_same(ldx2, "a row stride")), C.c_int(int(accumulate)),
-                                     _ptr(workspace, torch.float32, True), _stream()),
-          "gymrl_lin_bwd_weight")
+    check(lib().gymrl_lin_bwd_weight(items, n, B, N, K, K1, _same(ldy, "a row stride"), _same(ldx, "a row stride"), _same(ldx2, "a row stride"),
+                                     int(accumulate), _ptr(workspace, torch.float32, True), _stream()), "gymrl_lin_bwd_weight")
     return dw
 
 
@@ -1305,11 +1212,10 @@ def noisy_combine(layers, training=True, images=None):
                 raise ValueError("noisy_combine: an image needs a contiguous square weight and H * H floats per image")
             ims[i].W, ims[i].H = _ptr(w, torch.float32).value, H
             ims[i].img_fwd, ims[i].img_bwd = (None if t is None else _ptr(t, torch.float32).value for t in (f, bw))
-        check(lib().gymrl_noisy_combine_images(arr, C.c_int(len(layers)), C.c_int(K), C.c_int(int(training)), _ptr(W), _ptr(b),
-                                               ims, C.c_int(len(images)), _stream()), "gymrl_noisy_combine_images")
+        check(lib().gymrl_noisy_combine_images(arr, len(layers), K, int(training), _ptr(W), _ptr(b), ims, len(images), _stream()),
+              "gymrl_noisy_combine_images")
         return W, b
-    check(lib().gymrl_noisy_combine(arr, C.c_int(len(layers)), C.c_int(K), C.c_int(int(training)), _ptr(W), _ptr(b), _stream()),
-          "gymrl_noisy_combine")
+    check(lib().gymrl_noisy_combine(arr, len(layers), K, int(training), _ptr(W), _ptr(b), _stream()), "gymrl_noisy_combine")
     return W, b
 
 
@@ -1318,15 +1224,15 @@ def noisy_split(layers, dW, db, training=True, accumulate=False):
     arr, K, rows = _noisy_layers(layers)
     if tuple(dW.shape) != (rows, K):
         raise ValueError("noisy_split: stacked gradient shape mismatch")
-    check(lib().gymrl_noisy_split(arr, C.c_int(len(layers)), C.c_int(K), C.c_int(int(training)), _ptr(dW, torch.float32),
-                                  _ptr(db, torch.float32), C.c_int(int(accumulate)), _stream()), "gymrl_noisy_split")
+    check(lib().gymrl_noisy_split(arr, len(layers), K, int(training), _ptr(dW, torch.float32), _ptr(db, torch.float32), int(accumulate), _stream()),
+          "gymrl_noisy_split")
 
 
 def dueling_bwd(dq):
     """gymrl_dueling_bwd: dq [B, A] -> dS [B, A + 1] (advantage columns, then the value column)."""
     B, A = dq.shape
     dS = torch.empty(B, A + 1, dtype=torch.float32, device=dq.device)
-    check(lib().gymrl_dueling_bwd(_ptr(dq, torch.float32), C.c_int(B), C.c_int(A), _ptr(dS), _stream()), "gymrl_dueling_bwd")
+    check(lib().gymrl_dueling_bwd(_ptr(dq, torch.float32), B, A, _ptr(dS), _stream()), "gymrl_dueling_bwd")
     return dS
 
 
@@ -1340,10 +1246,9 @@ def mhc_gates(h, norm_w, w, alpha, beta, sk_it, stats=False):
     pre, post = torch.empty(B, n, device=dev), torch.empty(B, n, device=dev)
     mix, read = torch.empty(B, n, n, device=dev), torch.empty(B, D, device=dev)
     st = torch.empty(B, n * n + 2 * n + 1, device=dev) if stats else None
-    check(lib().gymrl_mhc_gates(_ptr(h, torch.float32), _ptr(norm_w, torch.float32), _ptr(w, torch.float32),
-                                _ptr(alpha, torch.float32), _ptr(beta, torch.float32), C.c_int(B), C.c_int(n), C.c_int(D),
-                                C.c_int(sk_it), _ptr(pre), _ptr(post), _ptr(mix), _ptr(read), None if st is None else _ptr(st),
-                                _stream()), "gymrl_mhc_gates")
+    check(lib().gymrl_mhc_gates(_ptr(h, torch.float32), _ptr(norm_w, torch.float32), _ptr(w, torch.float32), _ptr(alpha, torch.float32),
+                                _ptr(beta, torch.float32), B, n, D, sk_it, _ptr(pre), _ptr(post), _ptr(mix), _ptr(read),
+                                None if st is None else _ptr(st), _stream()), "gymrl_mhc_gates")
     return (pre, post, mix, read, st) if stats else (pre, post, mix, read)
 
 
@@ -1351,9 +1256,8 @@ def mhc_combine(post, mix, out, h, act=0):
     """gymrl_mhc_combine: h'[b, i] = post[b, i] act(out[b]) + sum_j mix[b, i, j] h[b, j]; act = 0 or LIN_ACT["silu"]."""
     B, n, D = h.shape
     h_out = torch.empty_like(h)
-    check(lib().gymrl_mhc_combine(_ptr(post, torch.float32), _ptr(mix, torch.float32), _ptr(out, torch.float32),
-                                  _ptr(h, torch.float32), C.c_int(B), C.c_int(n), C.c_int(D), C.c_int(act), _ptr(h_out),
-                                  _stream()), "gymrl_mhc_combine")
+    check(lib().gymrl_mhc_combine(_ptr(post, torch.float32), _ptr(mix, torch.float32), _ptr(out, torch.float32), _ptr(h, torch.float32), B, n, D, act,
+                                  _ptr(h_out), _stream()), "gymrl_mhc_combine")
     return h_out
 
 
@@ -1361,8 +1265,7 @@ def rmsnorm(x, w, eps, n_sum=1, act=0):
     """gymrl_rmsnorm: x [B, n_sum * D] (or [B, n_sum, D]) -> y [B, D] = s rsqrt(mean(s^2) + eps) w, s = act(the sum of the blocks)."""
     B, D = x.shape[0], w.numel()
     y = torch.empty(B, D, device=x.device)
-    check(lib().gymrl_rmsnorm(_ptr(x, torch.float32), _ptr(w, torch.float32), C.c_int(B), C.c_int(D), C.c_int(n_sum),
-                              C.c_float(eps), C.c_int(act), _ptr(y), _stream()), "gymrl_rmsnorm")
+    check(lib().gymrl_rmsnorm(_ptr(x, torch.float32), _ptr(w, torch.float32), B, D, n_sum, eps, act, _ptr(y), _stream()), "gymrl_rmsnorm")
     return y
 
 
@@ -1396,11 +1299,10 @@ def rmsnorm_bwd(g, x, w, eps, act=0, n_sum=1):
     """gymrl_rmsnorm_bwd / gymrl_rmsnorm_sum_bwd: (dL/dx [B, D], dL/dw [D]) of y = rmsnorm(x, w, eps, act=act); D <= 512.
     n_sum > 1: x is [B, n_sum, D] and the norm is of the blocks' sum — dL/dx [B, D] is every block's gradient."""
     B, D = x.shape[0], w.numel()
-    ws = _scratch("rmsnorm_bwd", D, lib().gymrl_rmsnorm_bwd_workspace_bytes(C.c_int(D)), x.device)
+    ws = _scratch("rmsnorm_bwd", D, lib().gymrl_rmsnorm_bwd_workspace_bytes(D), x.device)
     d_x, d_w = torch.empty(B, D, device=x.device), torch.empty_like(w)
-    check(lib().gymrl_rmsnorm_sum_bwd(_ptr(g, torch.float32), _ptr(x, torch.float32), _ptr(w, torch.float32), C.c_int(B), C.c_int(D),
-                                      C.c_int(n_sum), C.c_float(eps), C.c_int(act), _ptr(d_x), _ptr(d_w), _ptr(ws), _stream()),
-          "gymrl_rmsnorm_sum_bwd")
+    check(lib().gymrl_rmsnorm_sum_bwd(_ptr(g, torch.float32), _ptr(x, torch.float32), _ptr(w, torch.float32), B, D, n_sum, eps, act, _ptr(d_x),
+                                      _ptr(d_w), _ptr(ws), _stream()), "gymrl_rmsnorm_sum_bwd")
     return d_x, d_w
 
 
@@ -1422,8 +1324,8 @@ def norm_proj_fwd(x, norm_w, eps, W2, b2):
         x, norm_w, W2 = _al16(x), _al16(norm_w), _al16(W2)
     out = torch.empty(B, W2.shape[0], device=x.device)
     f = torch.float32
-    check(lib().gymrl_norm_proj_fwd(_ptr(x, f), _ptr(norm_w, f), _ptr(W2, f), _ptr(b2, f, True), C.c_int(B), C.c_int(D),
-                                    C.c_int(W2.shape[0]), C.c_float(eps), _ptr(out), _stream()), "gymrl_norm_proj_fwd")
+    check(lib().gymrl_norm_proj_fwd(_ptr(x, f), _ptr(norm_w, f), _ptr(W2, f), _ptr(b2, f, True), B, D, W2.shape[0], eps, _ptr(out), _stream()),
+          "gymrl_norm_proj_fwd")
     return out
 
 
@@ -1433,13 +1335,12 @@ def norm_proj_bwd(d_out, x, norm_w, eps, W2):
     n_out = W2.shape[0]
     if D == 256:
         x, norm_w, W2 = _al16(x), _al16(norm_w), _al16(W2)
-    ws = _scratch("norm_proj_bwd", (D, n_out), lib().gymrl_norm_proj_bwd_workspace_bytes(C.c_int(D), C.c_int(n_out)), x.device)
+    ws = _scratch("norm_proj_bwd", (D, n_out), lib().gymrl_norm_proj_bwd_workspace_bytes(D, n_out), x.device)
     d_x, d_nw, d_W2 = torch.empty_like(x), torch.empty_like(norm_w), torch.empty_like(W2)
     d_b2 = torch.empty(n_out, device=x.device)
     f = torch.float32
-    check(lib().gymrl_norm_proj_bwd(_ptr(d_out, f), _ptr(x, f), _ptr(norm_w, f), _ptr(W2, f), C.c_int(B), C.c_int(D), C.c_int(n_out),
-                                    C.c_float(eps), _ptr(d_x), _ptr(d_nw), _ptr(d_W2), _ptr(d_b2), _ptr(ws), _stream()),
-          "gymrl_norm_proj_bwd")
+    check(lib().gymrl_norm_proj_bwd(_ptr(d_out, f), _ptr(x, f), _ptr(norm_w, f), _ptr(W2, f), B, D, n_out, eps, _ptr(d_x), _ptr(d_nw), _ptr(d_W2),
+                                    _ptr(d_b2), _ptr(ws), _stream()), "gymrl_norm_proj_bwd")
     return d_x, d_nw, d_W2, d_b2
 
 
@@ -1452,9 +1353,9 @@ def mhc_sub_forward(h, norm_w, w, alpha, beta, lin_w, lin_b, sk_it):
     stats, read, z = torch.empty(B, n * n + 2 * n + 1, device=dev), torch.empty(B, D, device=dev), torch.empty(B, D, device=dev)
     h_out = torch.empty(B, n, D, device=dev)
     f = torch.float32
-    check(lib().gymrl_mhc_sub_forward(_ptr(h, f), C.c_int(h.dim() == 2), _ptr(norm_w, f), _ptr(w, f), _ptr(alpha, f), _ptr(beta, f), _ptr(lin_w, f),
-                                      _ptr(lin_b, f), C.c_int(B), C.c_int(n), C.c_int(D), C.c_int(sk_it), _ptr(pre), _ptr(post),
-                                      _ptr(mix), _ptr(stats), _ptr(read), _ptr(z), _ptr(h_out), _stream()), "gymrl_mhc_sub_forward")
+    check(lib().gymrl_mhc_sub_forward(_ptr(h, f), h.dim() == 2, _ptr(norm_w, f), _ptr(w, f), _ptr(alpha, f), _ptr(beta, f), _ptr(lin_w, f),
+                                      _ptr(lin_b, f), B, n, D, sk_it, _ptr(pre), _ptr(post), _ptr(mix), _ptr(stats), _ptr(read), _ptr(z), _ptr(h_out),
+                                      _stream()), "gymrl_mhc_sub_forward")
     return pre, post, mix, stats, read, z, h_out
 
 
@@ -1468,17 +1369,16 @@ def mhc_sub_backward(g, h, z, pre, post, mix, stats, norm_w, w, alpha, lin_w, su
     for t, nm in ((g, "g"), (h, "h")):
         if t.shape not in ((B, 2, D), (B, D)) or not t.is_contiguous():
             raise ValueError(f"{nm}: expected a contiguous [B, 2, D] or [B, D] tensor")
-    ws = _scratch("mhc_gates_bwd", (2, D), lib().gymrl_mhc_gates_bwd_workspace_bytes(C.c_int(2), C.c_int(D)), dev)
+    ws = _scratch("mhc_gates_bwd", (2, D), lib().gymrl_mhc_gates_bwd_workspace_bytes(2, D), dev)
     Bp = (B + 15) // 16 * 16                               # the kernel writes whole 16-row tiles
     d_z = torch.empty(Bp, D, device=dev)[:B]
     d_h = (torch.empty(Bp, D, device=dev) if sum_branches else torch.empty(Bp, 2, D, device=dev))[:B]
     d_nw, d_w = torch.empty_like(norm_w), torch.empty_like(w)
     d_alpha, d_beta = torch.empty(3, device=dev), torch.empty(w.shape[1], device=dev)
-    check(lib().gymrl_mhc_sub_backward(_ptr(g, f), C.c_int(g.dim() == 2), _ptr(h, f), C.c_int(h.dim() == 2), _ptr(z, f),
-                                       _ptr(pre, f), _ptr(post, f), _ptr(mix, f), _ptr(stats, f), _ptr(norm_w, f), _ptr(w, f),
-                                       _ptr(alpha, f), _ptr(lin_w, f), C.c_int(B), C.c_int(2), C.c_int(D), _ptr(d_z), _ptr(d_h),
-                                       C.c_int(bool(sum_branches)), _ptr(d_nw), _ptr(d_w), _ptr(d_alpha), _ptr(d_beta), _ptr(ws),
-                                       _stream()), "gymrl_mhc_sub_backward")
+    check(lib().gymrl_mhc_sub_backward(_ptr(g, f), g.dim() == 2, _ptr(h, f), h.dim() == 2, _ptr(z, f), _ptr(pre, f), _ptr(post, f), _ptr(mix, f),
+                                       _ptr(stats, f), _ptr(norm_w, f), _ptr(w, f), _ptr(alpha, f), _ptr(lin_w, f), B, 2, D, _ptr(d_z), _ptr(d_h),
+                                       bool(sum_branches), _ptr(d_nw), _ptr(d_w), _ptr(d_alpha), _ptr(d_beta), _ptr(ws), _stream()),
+          "gymrl_mhc_sub_backward")
     return d_z, d_h, d_nw, d_w, d_alpha, d_beta
 
 
@@ -1488,8 +1388,8 @@ def mhc_policy(desc, obs, logits_out=None, value_out=None):
     B = obs.shape[0]
     logits = torch.empty(B, desc.n_act, device=obs.device) if logits_out is None else logits_out
     value = torch.empty(B, device=obs.device) if value_out is None else value_out
-    check(lib().gymrl_mhc_policy_forward(C.byref(desc), _ptr(obs, torch.float32), C.c_int(B), _ptr(logits, torch.float32),
-                                         _ptr(value, torch.float32), _stream()), "gymrl_mhc_policy_forward")
+    check(lib().gymrl_mhc_policy_forward(C.byref(desc), _ptr(obs, torch.float32), B, _ptr(logits, torch.float32), _ptr(value, torch.float32),
+                                         _stream()), "gymrl_mhc_policy_forward")
     return logits, value
 
 
@@ -1497,7 +1397,7 @@ def mhc_policy_pack(desc, image=None):
     """gymrl_mhc_policy_pack: the image of desc's wide operands (the sub-blocks' Linears and gate weights, the heads' first
     Linears) in the order the one-launch forward's lanes read them; returns the buffer (desc.image is the caller's to set —
     and to refresh: the image does not follow the parameters)."""
-    n = int(lib().gymrl_mhc_policy_image_floats(C.c_int(desc.n_sub)))
+    n = int(lib().gymrl_mhc_policy_image_floats(desc.n_sub))
     if image is None or image.numel() != n:
         image = torch.empty(n, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
     check(lib().gymrl_mhc_policy_pack(C.byref(desc), _ptr(image, torch.float32), _stream()), "gymrl_mhc_policy_pack")
@@ -1508,16 +1408,14 @@ def sinkhorn(A, sk_it):
     """gymrl_sinkhorn: A [B, n, n] -> (u [B, n], v [B, n])."""
     B, n, _ = A.shape
     u, v = torch.empty(B, n, device=A.device), torch.empty(B, n, device=A.device)
-    check(lib().gymrl_sinkhorn(_ptr(A, torch.float32), C.c_int(B), C.c_int(n), C.c_int(sk_it), _ptr(u), _ptr(v), _stream()),
-          "gymrl_sinkhorn")
+    check(lib().gymrl_sinkhorn(_ptr(A, torch.float32), B, n, sk_it, _ptr(u), _ptr(v), _stream()), "gymrl_sinkhorn")
     return u, v
 
 
 def mhc_read_fwd(pre, h):
     B, n, D = h.shape
     read = torch.empty(B, D, device=h.device)
-    check(lib().gymrl_mhc_read_fwd(_ptr(pre, torch.float32), _ptr(h, torch.float32), C.c_int(B), C.c_int(n), C.c_int(D), _ptr(read),
-                                   _stream()), "gymrl_mhc_read_fwd")
+    check(lib().gymrl_mhc_read_fwd(_ptr(pre, torch.float32), _ptr(h, torch.float32), B, n, D, _ptr(read), _stream()), "gymrl_mhc_read_fwd")
     return read
 
 
@@ -1526,9 +1424,8 @@ def mhc_read_bwd(g, pre, h, want_dh=True):
     B, n, D = h.shape
     d_pre = torch.empty(B, n, device=h.device)
     d_h = torch.empty_like(h) if want_dh else None
-    check(lib().gymrl_mhc_read_bwd(_ptr(g, torch.float32), _ptr(pre, torch.float32), _ptr(h, torch.float32), C.c_int(B), C.c_int(n),
-                                   C.c_int(D), _ptr(d_pre), None if d_h is None else _ptr(d_h), C.c_int(0), _stream()),
-          "gymrl_mhc_read_bwd")
+    check(lib().gymrl_mhc_read_bwd(_ptr(g, torch.float32), _ptr(pre, torch.float32), _ptr(h, torch.float32), B, n, D, _ptr(d_pre),
+                                   None if d_h is None else _ptr(d_h), 0, _stream()), "gymrl_mhc_read_bwd")
     return d_pre, d_h
 
 
@@ -1540,10 +1437,9 @@ def mhc_combine_bwd(g, post, mix, out, h, act=0, want_dh=True):
     d_post, d_mix = torch.empty(B, n, device=dev), torch.empty(B, n, n, device=dev)
     d_out = torch.empty(B, D, device=dev)
     d_h = torch.empty_like(h) if want_dh else None
-    check(lib().gymrl_mhc_combine_bwd(_ptr(g, torch.float32), _ptr(post, torch.float32), _ptr(mix, torch.float32),
-                                      _ptr(out, torch.float32), _ptr(h, torch.float32), C.c_int(B), C.c_int(n), C.c_int(D),
-                                      C.c_int(act), _ptr(d_post), _ptr(d_mix), _ptr(d_out), None if d_h is None else _ptr(d_h),
-                                      _stream()), "gymrl_mhc_combine_bwd")
+    check(lib().gymrl_mhc_combine_bwd(_ptr(g, torch.float32), _ptr(post, torch.float32), _ptr(mix, torch.float32), _ptr(out, torch.float32),
+                                      _ptr(h, torch.float32), B, n, D, act, _ptr(d_post), _ptr(d_mix), _ptr(d_out),
+                                      None if d_h is None else _ptr(d_h), _stream()), "gymrl_mhc_combine_bwd")
     return d_post, d_mix, d_out, d_h
 
 
@@ -1552,16 +1448,14 @@ def mhc_gates_bwd(h, norm_w, w, alpha, pre, post, mix, stats, d_pre, d_post, d_m
     g_out [B, n, D]: the read's and the combine's gradient paths into h, folded into d_h in the same pass."""
     B, n, D = h.shape
     dev = h.device
-    ws = _scratch("mhc_gates_bwd", (n, D), lib().gymrl_mhc_gates_bwd_workspace_bytes(C.c_int(n), C.c_int(D)), dev)
+    ws = _scratch("mhc_gates_bwd", (n, D), lib().gymrl_mhc_gates_bwd_workspace_bytes(n, D), dev)
     d_h, d_nw, d_w = torch.empty_like(h), torch.empty_like(norm_w), torch.empty_like(w)
     d_alpha, d_beta = torch.empty(3, device=dev), torch.empty(w.shape[1], device=dev)
     opt = lambda t: None if t is None else _ptr(t, torch.float32)   # noqa: E731
-    check(lib().gymrl_mhc_gates_bwd(_ptr(h, torch.float32), _ptr(norm_w, torch.float32), _ptr(w, torch.float32),
-                                    _ptr(alpha, torch.float32), _ptr(pre, torch.float32), _ptr(post, torch.float32),
-                                    _ptr(mix, torch.float32), _ptr(stats, torch.float32), _ptr(d_pre, torch.float32),
-                                    _ptr(d_post, torch.float32), _ptr(d_mix, torch.float32), opt(d_read), opt(g_out),
-                                    C.c_int(B), C.c_int(n), C.c_int(D), _ptr(d_h), _ptr(d_nw), _ptr(d_w), _ptr(d_alpha),
-                                    _ptr(d_beta), _ptr(ws), _stream()), "gymrl_mhc_gates_bwd")
+    check(lib().gymrl_mhc_gates_bwd(_ptr(h, torch.float32), _ptr(norm_w, torch.float32), _ptr(w, torch.float32), _ptr(alpha, torch.float32),
+                                    _ptr(pre, torch.float32), _ptr(post, torch.float32), _ptr(mix, torch.float32), _ptr(stats, torch.float32),
+                                    _ptr(d_pre, torch.float32), _ptr(d_post, torch.float32), _ptr(d_mix, torch.float32), opt(d_read), opt(g_out), B,
+                                    n, D, _ptr(d_h), _ptr(d_nw), _ptr(d_w), _ptr(d_alpha), _ptr(d_beta), _ptr(ws), _stream()), "gymrl_mhc_gates_bwd")
     return d_h, d_nw, d_w, d_alpha, d_beta
 
 
@@ -1581,8 +1475,7 @@ def sac_fused_shape_ok(B, D, A, H):
 def sac_update_workspace(B, D, A, H, device):
     # zeroed: the hand-off flags between the row phases' workgroups and gymrl_sac_step's phase counters live in it (zero before
     # the first launch, left zero)
-    return torch.zeros(int(lib().gymrl_sac_update_workspace_bytes(C.c_int(B), C.c_int(D), C.c_int(A), C.c_int(H))),
-                       dtype=torch.uint8, device=device)
+    return torch.zeros(int(lib().gymrl_sac_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
 
 
 def _sac_actor_params(dst, actor):
@@ -1688,8 +1581,7 @@ def rainbow_fused_shape_ok(B, D, A, H):
 
 def rainbow_update_workspace(B, D, A, H, device):
     # zeroed: the hand-off flags between gymrl_rainbow_update's three workgroups per slab live in it (zero before the first launch, left zero)
-    return torch.zeros(int(lib().gymrl_rainbow_update_workspace_bytes(C.c_int(B), C.c_int(D), C.c_int(A), C.c_int(H))),
-                       dtype=torch.uint8, device=device)
+    return torch.zeros(int(lib().gymrl_rainbow_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
 
 
 def rainbow_act_args(env, net, win, ring, cap, n_steps, gamma, max_episode_steps):
@@ -1748,5 +1640,5 @@ def rainbow_update(a, idx, is_weight, head_w, head_b, td_out, split=None, phase=
         for l, (wm, wsg, bm, bsg, we, be) in enumerate(split):
             a.dw_mu[l], a.dw_sigma[l], a.db_mu[l], a.db_sigma[l] = _addr(wm), _addr(wsg), _addr(bm), _addr(bsg)
             a.w_eps[l], a.b_eps[l] = _addr(we), _addr(be)
-    check(lib().gymrl_rainbow_update(C.byref(a), C.c_int(phase), _stream()), "gymrl_rainbow_update")
+    check(lib().gymrl_rainbow_update(C.byref(a), phase, _stream()), "gymrl_rainbow_update")
 

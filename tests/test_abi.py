@@ -1,17 +1,114 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports
-every symbol include/gymrl.h declares; no compute is launched (no GPU here)."""
+every symbol include/gymrl.h declares, and the ctypes binding (gymrl_amd/_lib.py: one SIGNATURES line per entry
+point, one Structure per struct) says what the header says; no compute is launched (no GPU here)."""
 import ctypes
 import os
 import re
 
+import pytest
+
 from conftest import ROOT
 
 
-def _declared_symbols():
+def _header_text():
     hdr = open(os.path.join(ROOT, "include", "gymrl.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    hdr = re.sub(r"#ifdef GYMRL_PROF_BUILD.*?#endif", "", hdr, flags=re.S)      # probe-build-only declarations
-    return sorted(set(re.findall(r"\b(gymrl_[a-z0-9_]+)\s*\(", hdr)))
+    return re.sub(r"#ifdef GYMRL_PROF_BUILD.*?#endif", "", hdr, flags=re.S)      # probe-build-only declarations
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(gymrl_[a-z0-9_]+)\s*\(", _header_text())))
+
+
+def _c_type(decl, what):
+    """'const float* x[4]' -> (('float', 1, '4'), 'x'): base type, pointer depth, array length (0: not an array)."""
+    m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[\s*(\w+)\s*\])?", decl.strip(), flags=re.S)
+    assert m and m.group(1).strip(), f"{what}: cannot parse `{' '.join(decl.split())}`"
+    base = " ".join(t for t in m.group(1).replace("*", " ").split() if t != "const")
+    return (base, m.group(1).count("*"), m.group(3) or 0), m.group(2)
+
+
+def _parse_header():
+    """include/gymrl.h as (functions, structs): name -> (return type, [parameter types]) in the header's order, and typedef
+    name -> [(field, type)]; a type is (base, pointer depth, array length), a struct named by its tag reads as its typedef.
+    Anything between the structs, enums and forward declarations that is not a prototype fails here, by name."""
+    hdr = _header_text()
+    consts = {k: int(v) for k, v in re.findall(r"^#define\s+(\w+)\s+(\d+)\s*$", hdr, flags=re.M)}
+    hdr = re.sub(r"^\s*#.*$", "", hdr, flags=re.M)
+    hdr = re.sub(r'extern\s+"C"\s*\{', "", hdr)
+    structs, tags = {}, {}
+
+    def take_struct(m):
+        tag, body, name = m.groups()
+        assert "{" not in body, f"struct {name}: nested braces"
+        if tag:
+            tags["struct " + tag] = name
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = decl.split(",")
+            (base, ptr, arr), fname = _c_type(first, f"struct {name}")
+            fields.append((fname, (base, ptr, arr)))
+            for extra in more:        # `double gamma, lam;`: the declarators after the first carry no base type
+                (_, ptr2, arr2), fname2 = _c_type(base + " " + extra, f"struct {name}")
+                fields.append((fname2, (base, ptr2, arr2)))
+        structs[name] = []
+        for fname, (base, ptr, arr) in fields:
+            arr = consts.get(arr, arr)
+            assert isinstance(arr, int) or arr.isdigit(), f"struct {name}.{fname}: unknown array length {arr}"
+            structs[name].append((fname, (base, ptr, int(arr))))
+        return ""
+
+    hdr = re.sub(r"typedef\s+struct\s*(\w+)?\s*\{(.*?)\}\s*(\w+)\s*;", take_struct, hdr, flags=re.S)
+    hdr = re.sub(r"\benum\s*\{.*?\}\s*;", "", hdr, flags=re.S)
+    hdr = re.sub(r"\bstruct\s+\w+\s*;", "", hdr)                                 # forward declarations
+    functions = {}
+    for decl in filter(None, (d.strip() for d in hdr.split(";"))):
+        if decl == "}":                                                           # closes extern "C"
+            continue
+        m = re.fullmatch(r"(.*?)\b(gymrl_\w+)\s*\((.*)\)", decl, flags=re.S)
+        assert m, f"include/gymrl.h: cannot parse the declaration `{' '.join(decl.split())}`"
+        ret, name, params = m.groups()
+        assert name not in functions, f"{name} is declared twice"
+        types = [_c_type(ret + " _", name)[0]]
+        types += [] if params.strip() == "void" else [_c_type(p, name)[0] for p in params.split(",")]
+        for base, ptr, arr in types:
+            assert not arr and ptr <= 1, f"{name}: array or pointer-to-pointer in a prototype"
+        types = [(tags.get(base, base), ptr, arr) for base, ptr, arr in types]
+        functions[name] = (types[0], types[1:])
+    return functions, structs
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "unsigned int": ctypes.c_uint,
+            "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "unsigned long long": ctypes.c_ulonglong,
+            "uint8_t": ctypes.c_uint8, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+# typedef structs of the header the binding never builds: name -> why (none today)
+_NOT_MIRRORED = {}
+
+
+def _mirrors():
+    from gymrl_amd import _lib
+    classes = [c for c in vars(_lib).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure]
+    for c in classes:
+        assert getattr(c, "_c_name_", None), f"_lib.{c.__name__} does not name its header struct (_c_name_)"
+    by_name = {c._c_name_: c for c in classes}
+    assert len(by_name) == len(classes), "two mirrors name one header struct"
+    return by_name
+
+
+def _agrees(ct, htype, mirrors):
+    """Does the ctypes type say what the header type says?  Scalars and structs by value: the exact type.  A pointer:
+    c_void_p, or POINTER of the exact pointee (void has none).  An array: the length and the element."""
+    base, ptr, arr = htype
+    if arr:
+        return issubclass(ct, ctypes.Array) and ct._length_ == arr and _agrees(ct._type_, (base, ptr, 0), mirrors)
+    exact = _SCALARS.get(base) or mirrors.get(base)
+    if ptr:
+        return ct is ctypes.c_void_p or (exact is not None and ct is ctypes.POINTER(exact))
+    return exact is not None and ct is exact
+
+
+def _spell(ct):
+    return getattr(ct, "__name__", repr(ct))
 
 
 def test_library_exports_every_declared_symbol():
@@ -27,10 +124,71 @@ def test_library_exports_every_declared_symbol():
     assert not hasattr(L, "gymrl_gemm_config")
 
 
+def test_signature_table_says_what_the_header_says():
+    """Every SIGNATURES line against its prototype: arity, return type, every parameter."""
+    from gymrl_amd import _lib
+    functions, _ = _parse_header()
+    mirrors = _mirrors()
+    assert list(_lib.SIGNATURES) == list(functions), "gymrl_amd/_lib.py SIGNATURES: not the header's names in the header's order"
+    assert _lib.SYMBOLS == list(_lib.SIGNATURES)
+    for name, (ret, params) in functions.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert ret[1] == 0 and restype is _SCALARS[ret[0]], f"{name}: returns {ret[0]}, the table says {_spell(restype)}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters in the header, {len(argtypes)} in the table"
+        for i, (ct, htype) in enumerate(zip(argtypes, params)):
+            assert _agrees(ct, htype, mirrors), f"{name}: parameter {i} is {htype[0]}{'*' * htype[1]}, the table says {_spell(ct)}"
+
+
+def test_struct_mirrors_say_what_the_header_says():
+    """Every ctypes.Structure of _lib.py against its typedef struct, field by field: name, order, type, array length."""
+    from gymrl_amd import _lib
+    _, structs = _parse_header()
+    mirrors = _mirrors()
+    assert len(structs) >= 19
+    assert set(mirrors) <= set(structs), f"mirrors of no header struct: {sorted(set(mirrors) - set(structs))}"
+    assert set(structs) - set(mirrors) == set(_NOT_MIRRORED), "a header struct without a mirror is listed in _NOT_MIRRORED, with a reason"
+    for cname, cls in mirrors.items():
+        fields = structs[cname]
+        assert [f for f, _ in cls._fields_] == [f for f, _ in fields], f"{cname} ({cls.__name__}): field names or their order differ"
+        for (fname, ct), (_, htype) in zip(cls._fields_, fields):
+            assert _agrees(ct, htype, mirrors), (f"{cname}.{fname} is {htype[0]}{'*' * htype[1]}{'[%d]' % htype[2] if htype[2] else ''}, "
+                                                 f"{cls.__name__} says {_spell(ct)}")
+    # the layouts the library itself reports (the size queries stay exported)
+    L = _lib.lib()
+    assert L.gymrl_mlprnn_params_bytes() == ctypes.sizeof(_lib.MlprnnParams) == 28 * 8
+    assert (L.gymrl_sac_args_bytes(0), L.gymrl_sac_args_bytes(1)) == (ctypes.sizeof(_lib.SacActArgs), ctypes.sizeof(_lib.SacUpdateArgs))
+    assert (L.gymrl_rainbow_args_bytes(0), L.gymrl_rainbow_args_bytes(1)) == (ctypes.sizeof(_lib.RainbowActArgs),
+                                                                               ctypes.sizeof(_lib.RainbowUpdateArgs))
+
+
+def test_lib_applies_the_table_and_refuses_a_wrong_type():
+    """lib() types every exported function, so a wrongly typed argument raises before it reaches the library."""
+    from gymrl_amd import _lib
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    null = ctypes.c_void_p(None)
+    with pytest.raises(ctypes.ArgumentError):
+        L.gymrl_env_obs_dim(ctypes.c_int64(0))                                  # int64 object for an int
+    with pytest.raises(ctypes.ArgumentError):
+        L.gymrl_gae_workspace_bytes(2048, 4096.0)                               # float for an int
+    with pytest.raises(ctypes.ArgumentError):
+        L.gymrl_soft_update(null, null, 8, ctypes.c_float(0.005), null)         # float object for a double
+    with pytest.raises(ctypes.ArgumentError):
+        L.gymrl_soft_update(null, null, ctypes.c_int(8), 0.005, null)           # int object for an int64_t
+    with pytest.raises(ctypes.ArgumentError):
+        L.gymrl_rollout_lunar(ctypes.byref(_lib.MlpDesc()), ctypes.byref(_lib.MlpDesc()), null)   # another struct's pointer
+    with pytest.raises(ctypes.ArgumentError):
+        L.gymrl_gru_seq_fwd(null, null, null, null, (ctypes.c_int64 * 2)(), 1, 2, 16, null, null, null)   # i64 host array for i32
+    with pytest.raises(TypeError):
+        L.gymrl_env_state_bytes(0)                                              # a missing argument
+    assert L.gymrl_soft_update(null, null, 8, 0.005, null) == -22               # plain Python scalars convert
+
+
 def test_stale_library_is_refused(tmp_path, monkeypatch):
     """_lib.lib() compares the library's ABI version with the one this front-end was written against."""
     from gymrl_amd import _lib
-    import pytest
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "ABI_VERSION", 999)
     with pytest.raises(RuntimeError, match="ABI version"):
