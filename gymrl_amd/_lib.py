@@ -177,6 +177,46 @@ class RainbowUpdateArgs(C.Structure):
                 ("p_fc2_img_f", C.c_void_p), ("p_fc2_img_b", C.c_void_p), ("t_fc2_img_f", C.c_void_p)]
 
 
+class Td3ActorParams(C.Structure):
+    _c_name_ = "gymrl_td3_actor_params"   # fc1, fc2, fc3
+    _fields_ = [("w", C.c_void_p * 3), ("b", C.c_void_p * 3)]
+
+
+class Td3ActArgs(C.Structure):
+    _c_name_ = "gymrl_td3_act_args"
+    _fields_ = [("N", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("env_kind", C.c_int),
+                ("env_state", C.c_void_p), ("env_seed", C.c_uint64), ("env_id0", C.c_int64),
+                ("obs", C.c_void_p), ("obs_out", C.c_void_p), ("eps", C.c_void_p),
+                ("noise_seed", C.c_uint64), ("noise_counter", C.c_uint64), ("noise_counter_dev", C.c_void_p),
+                ("bound", C.c_float), ("noise_std", C.c_double),
+                ("actor", Td3ActorParams),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p), ("cap", C.c_int64), ("cursor", C.c_int64), ("cursor_dev", C.c_void_p),
+                ("action_out", C.c_void_p), ("rew_out", C.c_void_p), ("done_out", C.c_void_p), ("ep_ret_out", C.c_void_p),
+                ("ep_stats", C.c_void_p), ("images", C.c_void_p)]
+
+
+class Td3UpdateArgs(C.Structure):
+    _c_name_ = "gymrl_td3_update_args"
+    _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("n_critics", C.c_int),
+                ("gamma", C.c_float), ("bound", C.c_float), ("noise_clip", C.c_float),
+                ("policy_noise", C.c_double), ("tau", C.c_double),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p),
+                ("idx", C.c_void_p), ("idx_seed", C.c_uint64), ("idx_counter", C.c_uint64), ("idx_size", C.c_int64),
+                ("idx_dev", C.c_void_p), ("eps", C.c_void_p),
+                ("noise_seed", C.c_uint64), ("noise_counter", C.c_uint64), ("noise_counter_dev", C.c_void_p),
+                ("delayed", C.c_int), ("delayed_dev", C.c_void_p),
+                ("actor", Td3ActorParams), ("actor_target", Td3ActorParams),
+                ("critic", SacCriticParams), ("critic_target", SacCriticParams),
+                ("actor_p", C.c_void_p), ("actor_m", C.c_void_p), ("actor_v", C.c_void_p),
+                ("critic_p", C.c_void_p), ("critic_m", C.c_void_p), ("critic_v", C.c_void_p),
+                ("adam_critic", C.c_float * 4), ("adam_actor", C.c_float * 4),
+                ("adam_critic_dev", C.c_void_p), ("adam_actor_dev", C.c_void_p),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps_adam", C.c_double),
+                ("sums", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
+
+
 class WeightImage(C.Structure):
     _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
@@ -346,6 +386,11 @@ SIGNATURES = {
     "gymrl_rainbow_args_bytes": (_sz, [_i]),
     "gymrl_rainbow_act_step": (_i, [_P(RainbowActArgs), _vp]),
     "gymrl_rainbow_update": (_i, [_P(RainbowUpdateArgs), _i, _vp]),
+    "gymrl_td3_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_td3_pack_images": (_i, [_P(Td3UpdateArgs), _vp]),
+    "gymrl_td3_args_bytes": (_sz, [_i]),
+    "gymrl_td3_act_step": (_i, [_P(Td3ActArgs), _vp]),
+    "gymrl_td3_update": (_i, [_P(Td3UpdateArgs), _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

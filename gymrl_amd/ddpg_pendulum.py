@@ -31,6 +31,8 @@ class Config:
         # --- vectorised-engine additions ---
         self.num_envs = 1
         self.updates_per_step = 1
+        self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/offpolicy_step.hip): opt-in
+        self.fused_images = True       # ... with weight images of the H x H layers (H % 16 == 0)
 
 
 class Critic(nn.Module):
@@ -45,6 +47,8 @@ class Critic(nn.Module):
 
 
 class DDPGTrainer(_ActorCriticBase):
+    N_CRITICS = 1
+
     def __init__(self, config):
         self._setup(config, Critic)
 
@@ -58,6 +62,10 @@ class DDPGTrainer(_ActorCriticBase):
             return 0.0, 0.0
         if indices is None and self._parity_updates is not None:
             indices = next(self._parity_updates)
+        if self._fused_update_ok() and (indices is None or indices.numel() == cfg.batch_size):
+            self._update_fused(indices)
+            s = self._sums.tolist()
+            return -s[1] / cfg.batch_size, s[0] / cfg.batch_size
         if indices is None:
             indices = self.memory.draw_indices(cfg.batch_size)
         B = self._update_body(indices)
@@ -67,6 +75,7 @@ class DDPGTrainer(_ActorCriticBase):
         """Everything after the index draw; biases = device views of the (critic, actor) Adams' step scalars when the
         body runs inside / ahead of a hipGraph."""
         cfg = self.cfg
+        self._img_versions = None             # this path writes the parameters without the fused step's weight images
         bc, ba = biases if biases is not None else (None, None)
         states, actions, rewards, next_states, dones = self.memory.gather(indices)
         B = states.shape[0]
@@ -94,6 +103,9 @@ class DDPGTrainer(_ActorCriticBase):
         """update() without the host round trip, replayed as a captured hipGraph (gymrl_amd/graphs.py)."""
         cfg = self.cfg
         if len(self.memory) < cfg.batch_size:
+            return
+        if self._fused_update_ok():        # four launches: nothing left for a graph to save
+            self._update_fused()
             return
         if self._graph is None:
             from .graphs import GraphedUpdate

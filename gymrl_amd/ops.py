@@ -11,7 +11,7 @@ import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, GaeOnline,
                    MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
-                   check, lib)
+                   Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
 
@@ -1572,6 +1572,123 @@ def sac_step(act, upd):
     """gymrl_sac_step: the acting step and the update whose arguments sac_act_step(..., launch=False) and
     sac_update(..., launch=False) have filled in, as ONE launch."""
     check(lib().gymrl_sac_step(C.byref(act), C.byref(upd), _stream()), "gymrl_sac_step")
+
+
+# ------------------------------------------ fused TD3 / DDPG vector step ---
+TD3_FUSED_MAX_BATCH = 256      # one grid of at most 16 slabs per row phase (offpolicy_step.hip kTd3MaxBatch)
+
+
+def td3_fused_shape_ok(B, D, A, H):
+    """Shapes gymrl_td3_act_step / gymrl_td3_update take (include/gymrl.h): everything else runs layer by layer."""
+    return 0 < B <= TD3_FUSED_MAX_BATCH and 0 < D <= 8 and 0 < A <= 4 and 4 <= H <= 256 and H % 4 == 0
+
+
+def td3_update_workspace(B, D, A, H, device):
+    return torch.zeros(int(lib().gymrl_td3_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
+
+
+def _td3_actor_params(dst, actor):
+    for k, layer in enumerate((actor.fc1, actor.fc2, actor.fc3)):
+        dst.w[k], dst.b[k] = _addr(layer.weight), _addr(layer.bias)
+
+
+def _td3_critic_params(dst, critic):
+    """TD3's twin module fills fc1..fc6, DDPG's single Q network fc1..fc3 (the rest stays NULL)."""
+    for k, name in enumerate(("fc1", "fc2", "fc3", "fc4", "fc5", "fc6")):
+        layer = getattr(critic, name, None)
+        if layer is not None:
+            dst.w[k], dst.b[k] = _addr(layer.weight), _addr(layer.bias)
+
+
+def td3_images(H, device):
+    """The nine weight images of the H x H layers (gymrl_td3_update_args.images), or None when H % 16 != 0."""
+    return torch.zeros(9 * H * H, device=device) if H % 16 == 0 else None
+
+
+def td3_pack_images(a):
+    """gymrl_td3_pack_images: rebuild every image from the parameters as they are now."""
+    check(lib().gymrl_td3_pack_images(C.byref(a), _stream()), "gymrl_td3_pack_images")
+
+
+def td3_act_args(env, actor, ring, cap, bound, noise_std, images=None):
+    """A gymrl_td3_act_args with everything that does not change from step to step filled in.  noise_std: the exploration
+    std select_action() passes to noisy_action (exploration noise times the action bound)."""
+    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (env.act_dim,):
+        raise ValueError(f"td3_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
+    a = Td3ActArgs()
+    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, actor.fc1.weight.shape[0]
+    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    a.bound, a.noise_std = float(bound), float(noise_std)
+    _td3_actor_params(a.actor, actor)
+    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    a.cap = cap
+    a.images = _addr(images)
+    return a
+
+
+def td3_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, eps=None, noise_seed=0, noise_counter=0, noise_counter_dev=None,
+                 action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None):
+    """gymrl_td3_act_step: actor forward on obs [N, D], exploration noise (noisy_action mode 0; eps = f64[N, A] or None:
+    Philox (noise_seed, noise_counter)), env step with auto-reset, replay rows at (cursor + env) % cap — ONE launch."""
+    if tuple(obs.shape) != (a.N, a.D) or tuple(obs_out.shape) != (a.N, a.D):
+        raise ValueError(f"td3_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
+    if eps is not None and (eps.dtype != torch.float64 or eps.numel() != a.N * a.A):
+        raise ValueError("td3_act_step: eps must be float64 [N, A]")
+    a.env_seed = env.seed                              # reset(seed=...) may have moved it
+    a.obs, a.obs_out = _ptr(obs, torch.float32).value, _ptr(obs_out, torch.float32).value
+    a.eps = None if eps is None else _ptr(eps, torch.float64).value
+    a.noise_seed, a.noise_counter, a.noise_counter_dev = noise_seed, noise_counter, _addr(noise_counter_dev)
+    a.cursor, a.cursor_dev = cursor, _addr(cursor_dev)
+    a.action_out, a.rew_out, a.done_out, a.ep_ret_out, a.ep_stats = (_addr(t) for t in (action_out, rew_out, done_out, ep_ret_out, ep_stats))
+    check(lib().gymrl_td3_act_step(C.byref(a), _stream()), "gymrl_td3_act_step")
+
+
+def td3_update_args(B, D, A, n_critics, actor, actor_target, critic, critic_target, actor_opt, critic_opt, ring, cfg_scalars, sums,
+                    workspace, images=None):
+    """A gymrl_td3_update_args with the per-trainer constants filled in.  cfg_scalars = (gamma, tau, bound, policy_noise,
+    noise_clip); sums: f64[2] (critic loss sum, sum of Q(s, actor(s)))."""
+    if sums.dtype != torch.float64 or sums.numel() != 2 or not sums.is_contiguous():
+        raise ValueError("td3_update_args: sums must be a contiguous float64[2]")
+    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (A,):
+        raise ValueError(f"td3_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., {A}]")
+    a = Td3UpdateArgs()
+    a.B, a.D, a.A, a.H, a.n_critics = B, D, A, actor.fc1.weight.shape[0], n_critics
+    gamma, tau, bound, policy_noise, noise_clip = cfg_scalars
+    a.gamma, a.tau, a.bound, a.policy_noise, a.noise_clip = float(gamma), float(tau), float(bound), float(policy_noise), float(noise_clip)
+    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    _td3_actor_params(a.actor, actor)
+    _td3_actor_params(a.actor_target, actor_target)
+    _td3_critic_params(a.critic, critic)
+    _td3_critic_params(a.critic_target, critic_target)
+    a.actor_p, a.actor_m, a.actor_v = _addr(actor_opt.p), _addr(actor_opt.m), _addr(actor_opt.v)
+    a.critic_p, a.critic_m, a.critic_v = _addr(critic_opt.p), _addr(critic_opt.m), _addr(critic_opt.v)
+    g = critic_opt.param_groups[0]
+    a.beta1, a.beta2, a.eps_adam = g["betas"][0], g["betas"][1], g["eps"]
+    a.sums, a.workspace, a.images = _addr(sums), _addr(workspace), _addr(images)
+    return a
+
+
+def td3_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None, eps=None, noise_seed=0, noise_counter=0,
+               noise_counter_dev=None, delayed=1, delayed_dev=None, adam_critic=None, adam_actor=None, adam_critic_dev=None,
+               adam_actor_dev=None):
+    """gymrl_td3_update: TD3Trainer.update() / DDPGTrainer.update() as at most four launches.  idx: i32[B] rows or None (the
+    keyed draw); eps: f64[B, A] smoothing draws or None (Philox); delayed / delayed_dev (i32[1]): whether the actor phases run;
+    adam_critic / adam_actor: the 16-byte blocks of adam_bias() (host) or device views of them."""
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != a.B):
+        raise ValueError(f"td3_update: idx must be int32 [{a.B}]")
+    if eps is not None and (eps.dtype != torch.float64 or eps.numel() != a.B * a.A):
+        raise ValueError(f"td3_update: eps must be float64 [{a.B}, {a.A}]")
+    a.idx, a.idx_seed, a.idx_counter, a.idx_size, a.idx_dev = _addr(idx), idx_seed, idx_counter, idx_size, _addr(idx_dev)
+    a.eps = _addr(eps)
+    a.noise_seed, a.noise_counter, a.noise_counter_dev = noise_seed, noise_counter, _addr(noise_counter_dev)
+    a.delayed, a.delayed_dev = int(bool(delayed)), _addr(delayed_dev)
+    for dst, blk in ((a.adam_critic, adam_critic), (a.adam_actor, adam_actor)):
+        if blk is not None:
+            vals = (C.c_float * 4).from_buffer_copy(blk)
+            for k in range(4):
+                dst[k] = vals[k]
+    a.adam_critic_dev, a.adam_actor_dev = _addr(adam_critic_dev), _addr(adam_actor_dev)
+    check(lib().gymrl_td3_update(C.byref(a), _stream()), "gymrl_td3_update")
 
 
 # --------------------------------------------- fused Rainbow vector step ---

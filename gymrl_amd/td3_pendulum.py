@@ -3,6 +3,9 @@ reference's algorithms/td3_pendulum.py surface: Config :28-45, Actor :48-61, Cri
 networks in one module + q1()), ReplayBuffer :95-116, TD3Trainer :120-329 (soft_update :149-154,
 select_action :156-169, update :171-228, train / eval / test).
 
+With Config.fused_step the vector step is gymrl_td3_act_step + gymrl_td3_update (csrc/offpolicy_step.hip: one launch to act,
+at most four to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described next.
+
 Underneath: Pendulum instances step on the GPU; replay ring, exploration and smoothing noise
 (`gymrl_noisy_action`), the Bellman target (`gymrl_sac_target` with zero log-prob), the twin-critic
 loss (`gymrl_sac_critic_loss`), the actor loss (`gymrl_neg_mean_loss`), the fused Adam steps and
@@ -43,6 +46,8 @@ class Config:
         # --- vectorised-engine additions ---
         self.num_envs = 1
         self.updates_per_step = 1
+        self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/offpolicy_step.hip): opt-in
+        self.fused_images = True       # ... with weight images of the H x H layers (H % 16 == 0)
 
 
 class Actor(nn.Module):
@@ -107,17 +112,194 @@ class _ActorCriticBase:
         self.memory = ReplayBuffer(config.memory_capacity, state_dim, action_dim, self.device, seed=self.base_seed)
         self.episode_rewards = deque(maxlen=100)
         d64 = dict(dtype=torch.float64, device=self.device)
-        self._sum_c, self._sum_a = torch.zeros(1, **d64), torch.zeros(1, **d64)
+        self._sums = torch.zeros(2, **d64)           # critic loss sum, sum of Q(s, actor(s)): one buffer, so that the fused
+        self._sum_c, self._sum_a = self._sums[0:1], self._sums[1:2]      # update writes what the loss kernels write
         self._log_alpha0 = torch.zeros(1, **d64)     # alpha * 0 log-prob: the SAC target kernel as a plain TD target
         self._act_counter = 0
         self._noise_counter = 0
         self._parity_eps = None        # tests: iterator of f64[N, A] N(0,1) draws for select_action
         self._parity_updates = None    # tests: iterator of per-update tuples (see update())
         self._graph = None             # hipGraph of the update (trainers that define update_async)
+        self._fused = None             # (act args, update args, workspace, env, weight images) of the fused step, built on first use
+        self._img_versions = None      # versions of the flat buffers the weight images were last rebuilt from
 
     def soft_update(self, target_flat, source_flat):
         """:149-154 on the flat parameter buffers."""
         ops.soft_update(target_flat, source_flat, self.cfg.tau)
+        self._img_versions = None      # a raw-pointer write: the fused step's weight images of the target are stale
+
+    # ------------------------------------------------------------ fused vector step (csrc/offpolicy_step.hip) --
+    N_CRITICS = 2                      # TD3's twin module; DDPGTrainer: 1
+    CHUNK = 16                         # vector steps per StepChunk replay (= the episode tracker's flush period)
+
+    def _smoothing(self):
+        """(policy_noise, noise_clip) of the target-policy smoothing; DDPG has none."""
+        return 0.0, 0.0
+
+    def _count_update(self):
+        """The host counters one update() advances before its kernels run -> is this a delayed (actor) step?"""
+        return True
+
+    def _fused_update_ok(self):
+        """update() as gymrl_td3_update: opt-in (cfg.fused_step) and a matter of shapes."""
+        cfg, m = self.cfg, self.memory
+        return (bool(getattr(cfg, "fused_step", False))
+                and ops.td3_fused_shape_ok(cfg.batch_size, m.ring[0].shape[1], m.ring[1].shape[1], cfg.hidden_dim))
+
+    def _fused_ok(self):
+        """The whole vector step fused: the update AND acting + env step + replay row (gymrl_td3_act_step steps Pendulum itself)."""
+        cfg, env = self.cfg, self.env
+        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind == ops.PENDULUM
+                and cfg.max_steps >= env.max_steps and self.memory.capacity >= env.n)
+
+    def _fused_args(self):
+        if self._fused is None or self._fused[3] is not self.env:
+            cfg, env, m = self.cfg, self.env, self.memory
+            D, A = m.ring[0].shape[1], m.ring[1].shape[1]
+            img = ops.td3_images(cfg.hidden_dim, self.device) if getattr(cfg, "fused_images", True) else None
+            act = (ops.td3_act_args(env, self.actor, m.ring, m.capacity, self.action_bound, self._exploration_std() * self.action_bound, img)
+                   if isinstance(env, VecEnv) and env.kind == ops.PENDULUM else None)
+            ws = ops.td3_update_workspace(cfg.batch_size, D, A, cfg.hidden_dim, self.device)       # zeroed once
+            upd = ops.td3_update_args(cfg.batch_size, D, A, self.N_CRITICS, self.actor, self.actor_target, self.critic, self.critic_target,
+                                      self.actor_optimizer, self.critic_optimizer, m.ring,
+                                      (cfg.gamma, cfg.tau, self.action_bound) + tuple(self._smoothing()), self._sums, ws, img)
+            self._fused = (act, upd, ws, env, img)
+            self._img_versions = None
+        # the weight images follow the parameters as long as only the fused update writes them; anything that went through
+        # torch (load_state_dict: the parameters' version counters move) or around it (soft_update(), the layer-by-layer
+        # update: they reset _img_versions) makes them stale: rebuild (one launch) before the next fused call
+        if self._fused[4] is not None:
+            ps = getattr(self, "_img_params", None)
+            if ps is None:
+                ps = self._img_params = tuple([f] + list(net.parameters()) for f, net in (
+                    (self.actor_flat, self.actor), (self.critic_flat, self.critic),
+                    (self.actor_target_flat, self.actor_target), (self.critic_target_flat, self.critic_target)))
+            v = tuple(sum([t._version for t in group]) for group in ps)
+            if v != self._img_versions:
+                ops.td3_pack_images(self._fused[1])
+                self._img_versions = v
+        return self._fused
+
+    def _update_fused(self, indices=None, eps=None, dev=None):
+        """update() as gymrl_td3_update's launches -> delayed (host mode).  dev = (draw, adam_c, adam_a, noise, delayed) device
+        records of a StepChunk replay; None: this call's scalars travel as arguments and the host counters advance here."""
+        m = self.memory
+        upd = self._fused_args()[1]
+        if dev is not None:
+            ops.td3_update(upd, idx_seed=m.seed, idx_dev=dev[0], idx_size=m.capacity, adam_critic_dev=dev[1], adam_actor_dev=dev[2],
+                           noise_seed=self.base_seed + 1, noise_counter_dev=dev[3], delayed_dev=dev[4])
+            return None
+        if indices is None:
+            counter, size = m.draws, m.size
+            m.draws += 1
+        else:
+            counter, size = 0, 0
+        delayed = self._count_update()
+        ops.td3_update(upd, idx=indices, idx_seed=m.seed, idx_counter=counter, idx_size=size, eps=eps, noise_seed=self.base_seed + 1,
+                       noise_counter=self._noise_counter, delayed=delayed, adam_critic=self.critic_optimizer.next_bias(),
+                       adam_actor=self.actor_optimizer.next_bias() if delayed else None)
+        return delayed
+
+    def _next_parity_update(self):
+        """(indices, eps) of the next update from the tests' iterator, (None, None) without one."""
+        if self._parity_updates is None:
+            return None, None
+        item = next(self._parity_updates)
+        return item if isinstance(item, tuple) else (item, None)
+
+    def _act_fused(self, lb, obs, nxt, ep_ret, done, cursor_dev=None, noise_dev=None):
+        """Acting + env step + replay row of one vector step: one launch (select_action + env.step + memory.push)."""
+        env, m = self.env, self.memory
+        eps = None if self._parity_eps is None else next(self._parity_eps)
+        if cursor_dev is None:
+            self._act_counter += 1
+        ops.td3_act_step(self._fused_args()[0], env, obs, nxt, cursor=m.cursor, cursor_dev=cursor_dev, eps=eps,
+                         noise_seed=self.base_seed, noise_counter=self._act_counter, noise_counter_dev=noise_dev,
+                         rew_out=lb["rew"], done_out=done, ep_ret_out=ep_ret, ep_stats=env.ep_stats)
+        if cursor_dev is None:
+            m.advance(env.n)
+
+    def _loop_buffers(self, N, D):
+        """Step buffers that outlive one train() call: the captured StepChunk graph holds their addresses."""
+        lb = getattr(self, "_loop", None)
+        if lb is None or lb["N"] != N:
+            d = self.device
+            lb = self._loop = dict(N=N, obs=torch.empty(N, D, device=d), nxt=torch.empty(N, D, device=d), rew=torch.empty(N, device=d),
+                                   tracker=EpisodeTracker(N, d, flush_every=1 if N == 1 else self.CHUNK))
+        lb["tracker"].k, lb["tracker"].episodes = 0, 0
+        return lb
+
+    def _chunk_body(self, lb, j):
+        """Vector step j of a StepChunk capture: the act launch and the update's, every per-step scalar read from record j."""
+        ch, tr = self._chunk, lb["tracker"]
+        obs, nxt = (lb["obs"], lb["nxt"]) if j % 2 == 0 else (lb["nxt"], lb["obs"])
+        self._act_fused(lb, obs, nxt, tr.ret[j], tr.done[j], cursor_dev=ch.view(j, "push"), noise_dev=ch.view(j, "noise_a"))
+        self._update_fused(dev=(ch.view(j, "draw"), ch.view(j, "adam_c", torch.float32), ch.view(j, "adam_a", torch.float32),
+                                ch.view(j, "noise_u"), ch.view(j, "delayed", torch.int32)))
+
+    def _stage_chunk(self):
+        """The host's bookkeeping of the next CHUNK vector steps, in the eager loop's order, written into the records."""
+        ch, m, N = self._chunk, self.memory, self.env.n
+        for j in range(ch.K):
+            ch.set(j, "push", m.cursor)
+            m.advance(N)
+            self._act_counter += 1
+            ch.set(j, "noise_a", self._act_counter)
+            ch.set(j, "draw", m.draws, m.size)
+            m.draws += 1
+            delayed = self._count_update()
+            ch.set(j, "noise_u", self._noise_counter)
+            ch.set(j, "delayed", int(delayed))
+            ch.set_bytes(j, "adam_c", self.critic_optimizer.next_bias())
+            if delayed:                   # (the actor's step count moves on the delayed steps only)
+                ch.set_bytes(j, "adam_a", self.actor_optimizer.next_bias())
+        ch.flush()
+
+    def _train_fused(self, max_vector_steps=None):
+        """_train on the fused step.  With hipGraphs on, CHUNK whole vector steps replay as one graph (graphs.StepChunk);
+        while the ring holds fewer rows than a batch — and for what a chunk cannot take — the loop is eager: the act launch,
+        then the update's, no host round trip (the loss sums stay on the device)."""
+        cfg, env, m = self.cfg, self.env, self.memory
+        N, D = env.n, env.obs_dim
+        lb = self._loop_buffers(N, D)
+        obs, nxt, tracker = lb["obs"], lb["nxt"], lb["tracker"]
+        env.reset(obs)
+        step = 0
+        pending = None            # drain_async() token of the last chunk, collected one chunk later
+        graphed = bool(getattr(cfg, "use_graphs", True)) and self._parity_updates is None
+        chunked = graphed and N > 1 and cfg.updates_per_step == 1 and self._parity_eps is None
+        limit = max_vector_steps or (cfg.max_episodes * cfg.max_steps // N + 1)
+        while tracker.episodes < cfg.max_episodes and step < limit:
+            if chunked and tracker.k == 0 and limit - step >= self.CHUNK and obs is lb["obs"] and len(m) >= cfg.batch_size:
+                if getattr(self, "_chunk", None) is None:
+                    from .graphs import StepChunk
+                    self._chunk = StepChunk(self.device, self.CHUNK, [("push", "q"), ("draw", "Qq"), ("adam_c", "4f"), ("adam_a", "4f"),
+                                                                      ("noise_a", "Q"), ("noise_u", "Q"), ("delayed", "i")])
+                self._fused_args()             # weight images rebuilt (if stale) BEFORE the capture, not inside it
+                self._stage_chunk()
+                self._chunk.run(lambda j: self._chunk_body(lb, j), key=(id(env), env.state.data_ptr()))
+                step += self.CHUNK
+                tracker.k = self.CHUNK
+                token = tracker.drain_async()      # the chunk's episode returns come back one chunk late: the host goes on staging
+                tracker.collect(pending, self.episode_rewards)
+                pending = token
+                if cfg.max_episodes - tracker.episodes <= N * self.CHUNK:      # within reach of the episode budget: no lag
+                    tracker.collect(pending, self.episode_rewards)
+                    pending = None
+                continue
+            tracker.collect(pending, self.episode_rewards)
+            pending = None
+            ep_ret, done = tracker.slot()
+            self._act_fused(lb, obs, nxt, ep_ret, done)
+            for _ in range(cfg.updates_per_step):
+                if len(m) >= cfg.batch_size:
+                    self._update_fused(*self._next_parity_update())
+            obs, nxt = nxt, obs
+            step += 1
+            tracker.advance(self.episode_rewards)
+        tracker.collect(pending, self.episode_rewards)
+        tracker.flush(self.episode_rewards)
+        self.env.close()
 
     @torch.no_grad()
     def select_action(self, state, deterministic=False, eps=None):
@@ -138,14 +320,17 @@ class _ActorCriticBase:
     def _train(self, max_vector_steps=None):
         """The reference's episode loop with N lock-stepped envs: act, step, push, update every step."""
         cfg, env = self.cfg, self.env
+        if self._fused_ok():
+            return self._train_fused(max_vector_steps)
         N, D = env.n, env.obs_dim
         obs, nxt, tobs = (torch.empty(N, D, device=self.device) for _ in range(3))
         rew = torch.empty(N, device=self.device)
         tracker = EpisodeTracker(N, self.device, flush_every=1 if N == 1 else 16)
         env.reset(obs)
         step = 0
-        # DDPG replays its update as a captured hipGraph; TD3's update draws its target-smoothing noise from a host
-        # counter and alternates between two bodies (policy delay), and stays eager
+        # (the layer-by-layer path; cfg.fused_step: _train_fused above)  DDPG replays its update as a captured hipGraph; TD3's
+        # layer-by-layer update draws its target-smoothing noise from a host counter and alternates between two bodies
+        # (policy delay), and stays eager
         graphed = (bool(getattr(cfg, "use_graphs", True)) and self._parity_updates is None and hasattr(self, "update_async"))
         limit = max_vector_steps or (cfg.max_episodes * cfg.max_steps // N + 1)
         while tracker.episodes < cfg.max_episodes and step < limit:
@@ -196,14 +381,27 @@ class TD3Trainer(_ActorCriticBase):
     def _exploration_std(self):
         return self.cfg.exploration_noise
 
+    def _smoothing(self):
+        return self.cfg.policy_noise, self.cfg.noise_clip
+
+    def _count_update(self):
+        self.total_updates += 1
+        self._noise_counter += 1
+        return self.total_updates % self.cfg.policy_freq == 0
+
     def update(self, indices=None, eps=None):
         """:171-228 -> (actor_loss, critic_loss) python floats (actor_loss 0.0 on the skipped policy steps)."""
         cfg = self.cfg
         if len(self.memory) < cfg.batch_size:
             return 0.0, 0.0
-        self.total_updates += 1
         if indices is None and self._parity_updates is not None:
             indices, eps = next(self._parity_updates)
+        if self._fused_update_ok() and (indices is None or indices.numel() == cfg.batch_size):
+            delayed = self._update_fused(indices, eps)
+            s = self._sums.tolist()
+            return (-s[1] / cfg.batch_size if delayed else 0.0), s[0] / cfg.batch_size
+        self.total_updates += 1
+        self._img_versions = None             # this path writes the parameters without the fused step's weight images
         states, actions, rewards, next_states, dones = self.memory.sample(cfg.batch_size, indices)
         B = states.shape[0]
         with torch.no_grad():                                          # :191-199

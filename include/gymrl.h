@@ -1328,6 +1328,75 @@ size_t gymrl_rainbow_args_bytes(int which);  /* sizeof(gymrl_rainbow_act_args) (
 int gymrl_rainbow_act_step(const gymrl_rainbow_act_args* args, void* stream);
 int gymrl_rainbow_update(const gymrl_rainbow_update_args* args, int phase, void* stream);   /* phase 0: both launches; 1: rows (td_out is complete after it: update_priorities may start); 2: tiles */
 
+/*
+ * TD3's and DDPG's Pendulum vector step on the same row-slab kernels (csrc/offpolicy_step.hip): td3_pendulum.py's train loop
+ * :230-262 / update :171-228 and ddpg_pendulum.py's :196-228 / :150-194.  SAC's step with a deterministic tanh actor (:48-61),
+ * clipped Gaussian noise in place of the reparameterised sample, no temperature, and a delayed actor phase:
+ *   gymrl_td3_act_step   ONE launch: actor forward on the N observations (fc1, fc2 ReLU, fc3 tanh, times bound; :158-163),
+ *                        exploration noise by gymrl_noisy_action mode 0's float64 expression (:164-168; explicit f64 eps or Philox
+ *                        (noise_seed, noise_counter, stream 2, element)), Pendulum step with auto-reset, replay row (obs, action,
+ *                        reward, TERMINAL next obs, done) at (cursor + env) % cap, the episode bookkeeping outputs
+ *   gymrl_td3_update     update(), at most four launches, n_critics = 2 (TD3) or 1 (DDPG):
+ *     R1 rows   index draw (gymrl_uniform_indices' permutation, or idx) + ring gather; actor_target(s') (:191); the smoothing noise
+ *               by gymrl_noisy_action mode 1's float32 expression (:192-196; none when policy_noise == 0 or n_critics == 1);
+ *               the target critic(s) (:197); y by gymrl_sac_target's expression with a zero log-prob (:198-199); critic(s) on
+ *               (s, a) (:201); gymrl_sac_critic_loss's / gymrl_mse_loss's gradient (:203-204); the critics' input-gradient chain
+ *     T2 tiles  critic weight / bias gradient tiles (gymrl_lin_bwd_weight's order) + Adam (:206-208); the critic target's Polyak
+ *               update only on a DELAYED step (:223 sits inside the policy_freq branch; DDPG :190: every step); critic loss sum
+ *     R3 rows   actor(s); critic.q1(s, actor(s)) of the UPDATED critic (:213; DDPG's single critic :185); gymrl_neg_mean_loss's
+ *               gradient back through the critic to the action, through bound and tanh, through the actor
+ *     T4 tiles  actor weight gradients + Adam (:215-217), the actor target's Polyak update (:222-224), actor loss sum
+ *   Whether a step is delayed is ONE word: `delayed`, or delayed_dev[0] when that pointer is set, so that one captured hipGraph
+ *   serves every step.  On a step that is not, every workgroup of R3 and T4 returns at once and T2 leaves the target alone; the
+ *   decision is uniform over each grid and no workgroup waits for another anywhere in these kernels (one workgroup carries a
+ *   slab through all of a row phase).
+ * Results are the layer-by-layer path's bits (tests/test_td3_fused_step_gpu.py).  Limits: H % 4 == 0, H <= 256, D <= 8, A <= 4,
+ * B <= 256 (-22 otherwise: the trainers stay on the layer path); Pendulum-v1 for the act step.
+ */
+typedef struct { float* w[3]; float* b[3]; } gymrl_td3_actor_params;     /* fc1, fc2, fc3 (td3_pendulum.py:52-54) */
+typedef struct {
+  int N, D, A, H;
+  int env_kind;                            /* GYMRL_ENV_PENDULUM */
+  void* env_state; uint64_t env_seed; int64_t env_id0;
+  const float* obs; float* obs_out;        /* f32[N, D] in / next observations out (post-reset where an episode ended) */
+  const double* eps;                       /* f64[N, A] N(0,1) draws, or NULL: Philox (noise_seed, noise_counter, stream 2, env * A + j) */
+  uint64_t noise_seed, noise_counter; const uint64_t* noise_counter_dev;
+  float bound; double noise_std;           /* action bound; exploration std (already times the bound, as select_action passes it) */
+  gymrl_td3_actor_params actor;
+  float* r_state; uint32_t* r_action; float* r_reward; float* r_next; uint8_t* r_flag; int64_t cap, cursor;
+  const int64_t* cursor_dev;
+  float* action_out; float* rew_out; uint8_t* done_out; float* ep_ret_out; double* ep_stats;     /* any may be NULL */
+  const float* images;                     /* gymrl_td3_update_args.images of the same trainer, or NULL (reads actor.fc2 in place) */
+} gymrl_td3_act_args;
+typedef struct {
+  int B, D, A, H;
+  int n_critics;                           /* 2: TD3 (critic.fc1-3 = Q1, fc4-6 = Q2), 1: DDPG (fc1-3 only) */
+  float gamma, bound, noise_clip;
+  double policy_noise, tau;
+  const float* r_state; const uint32_t* r_action; const float* r_reward; const float* r_next; const uint8_t* r_flag;
+  const int32_t* idx;                      /* i32[B] explicit rows, or NULL: the keyed permutation of gymrl_uniform_indices */
+  uint64_t idx_seed, idx_counter; int64_t idx_size; const void* idx_dev;     /* idx_dev: {uint64 counter; int64 size} */
+  const double* eps;                       /* f64[B, A] smoothing draws, or NULL: Philox (noise_seed, noise_counter, stream 2, row * A + j) */
+  uint64_t noise_seed, noise_counter; const uint64_t* noise_counter_dev;
+  int delayed; const int32_t* delayed_dev; /* != 0: the actor phases run and the critic target moves (total_updates % policy_freq == 0) */
+  gymrl_td3_actor_params actor, actor_target; gymrl_sac_critic_params critic, critic_target;
+  float* actor_p; float* actor_m; float* actor_v; float* critic_p; float* critic_m; float* critic_v;
+  float adam_critic[4], adam_actor[4];
+  const float* adam_critic_dev; const float* adam_actor_dev;
+  double beta1, beta2, eps_adam;
+  double* sums;                            /* f64[2] out: critic loss sum; sum of Q(s, actor(s)) (written on delayed steps only) */
+  void* workspace;                         /* >= gymrl_td3_update_workspace_bytes(B, D, A, H) */
+  /* Weight images of the H x H layers (H % 16 == 0), f32[9][H*H], or NULL: forward actor.fc2, critic.fc2 / fc5,
+   * critic_target.fc2 / fc5, actor_target.fc2; input gradient actor.fc2, critic.fc2 / fc5.  gymrl_td3_update keeps them equal to
+   * the parameters it writes; gymrl_td3_pack_images rebuilds them after anything else did. */
+  float* images;
+} gymrl_td3_update_args;
+size_t gymrl_td3_update_workspace_bytes(int B, int D, int A, int H);
+int gymrl_td3_pack_images(const gymrl_td3_update_args* args, void* stream);
+size_t gymrl_td3_args_bytes(int which);      /* sizeof(gymrl_td3_act_args) (0) / sizeof(gymrl_td3_update_args) (1) */
+int gymrl_td3_act_step(const gymrl_td3_act_args* args, void* stream);
+int gymrl_td3_update(const gymrl_td3_update_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
