@@ -2,7 +2,7 @@
 //
 // The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1").step()/reset() (gymnasium classic_control, third-party:
 // SURVEY.md 8c.2) for one env = one lane.  Shared by the stand-alone steppers (env_classic.hip: gymrl_env_step) and the
-// fused acting kernels (offpolicy_step.hip: forward + draw + env step + ring append in one launch), so both produce the
+// fused acting kernels (offpolicy_step.hip, rainbow_step.hip, td3_step.hip: forward + draw + env step + ring append in one launch), so both produce the
 // same bits.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
 #pragma once
 #include "env_common.hpp"

@@ -3,7 +3,7 @@
 // lin.hip runs every Linear(+activation) of the DQN / Rainbow / SAC / TD3 / DDPG networks as one launch per layer and
 // direction: a wavefront owns a 16 x 16 output tile and walks the whole reduction with v_mfma_f32_16x16x4_f32.  At the
 // reference's batch sizes (128 / 256 rows) such a launch is ~1 us of work behind ~4-7 us of dispatch, first-load latency
-// and drain, and a SAC update is ~50 of them.  The fused step kernels (offpolicy_step.hip) keep a 16-row slab of the
+// and drain, and a SAC update is ~50 of them.  The fused step kernels (slab_step_device.hpp) keep a 16-row slab of the
 // batch in ONE workgroup's LDS through a whole chain of layers — rows never interact in a forward or input-gradient
 // pass — so a layer costs its tile's MFMA chain and a workgroup barrier instead of a launch.  The tile bodies below are
 // what both use: the SAME sequence of MFMAs on the SAME operands in the SAME order (documented in lin.hip's header), so
@@ -438,7 +438,7 @@ __device__ __forceinline__ f32x4 tile_bwd_weight(const float* __restrict__ dZ, i
 // rows_per_slice rows (a multiple of 32) whose partial tiles lin_slice_reduce_kernel adds in eight groups — group g the slices
 // g * each .. (g + 1) * each - 1 one after another from +0, then the groups in turn.  B >= 16384 on 64-aligned shapes takes the
 // 64 x 64-block kernels (another order: not restated here, the fused step stops at 8192 rows).  The fused step's weight-gradient
-// tiles (offpolicy_step.hip sac_dw_body) follow the same cut: one wave per slice, the last one to arrive adds them in this order.
+// tiles (slab_step_device.hpp sac_dw_body) follow the same cut: one wave per slice, the last one to arrive adds them in this order.
 __host__ __device__ __forceinline__ bool bwd_weight_big_shape(int B, int N, int K) { return B >= 16384 && N % 64 == 0 && K % 64 == 0; }
 __host__ __device__ __forceinline__ int bwd_weight_slices(int B, int N, int K) {
   if (B <= 512) return 1;

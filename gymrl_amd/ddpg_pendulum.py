@@ -31,7 +31,7 @@ class Config:
         # --- vectorised-engine additions ---
         self.num_envs = 1
         self.updates_per_step = 1
-        self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/offpolicy_step.hip): opt-in
+        self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/td3_step.hip): opt-in
         self.fused_images = True       # ... with weight images of the H x H layers (H % 16 == 0)
 
 

@@ -1464,7 +1464,7 @@ def _addr(t):
     return None if t is None else _ptr(t).value
 
 
-FUSED_MAX_BATCH = 8192     # row-slab kernels: B <= 256 as resident 2-D grids, above that slab-adjacent 1-D grids (offpolicy_step.hip slab_grid)
+FUSED_MAX_BATCH = 8192     # row-slab kernels: B <= 256 as resident 2-D grids, above that slab-adjacent 1-D grids (slab_step_device.hpp slab_grid)
 
 
 def sac_fused_shape_ok(B, D, A, H):
@@ -1575,7 +1575,7 @@ def sac_step(act, upd):
 
 
 # ------------------------------------------ fused TD3 / DDPG vector step ---
-TD3_FUSED_MAX_BATCH = 256      # one grid of at most 16 slabs per row phase (offpolicy_step.hip kTd3MaxBatch)
+TD3_FUSED_MAX_BATCH = 256      # one grid of at most 16 slabs per row phase (td3_step.hip kTd3MaxBatch)
 
 
 def td3_fused_shape_ok(B, D, A, H):

@@ -48,7 +48,7 @@ class Config:
         self.updates_per_step = 1
         self.use_graphs = True             # replay the update as one captured hipGraph (train(); update() stays eager)
         self.fused_step = True             # acting + env + n-step push in ONE launch, the update's ~20 Linear / loss launches in TWO
-        #                                    (csrc/offpolicy_step.hip; bit-identical to the layer-by-layer path, which remains for
+        #                                    (csrc/rainbow_step.hip; bit-identical to the layer-by-layer path, which remains for
         #                                    other shapes and custom envs)
         self.fused_images = True           # fused step: fc2 (hidden x hidden, hidden % 16 == 0) is streamed from MFMA-operand images
         #                                    that the step's NoisyLinear launch rebuilds from the parameters (same values, same
@@ -443,7 +443,7 @@ class RainbowDQNTrainer:
         self._parity_u = None          # tests: iterator of f64[B] PER uniforms for update()
         self._graph = None             # hipGraph of the update, captured on first use (update_async)
 
-    # ------------------------------------------------------------ fused vector step (csrc/offpolicy_step.hip) --
+    # ------------------------------------------------------------ fused vector step (csrc/rainbow_step.hip) ----
     def _fused_update_ok(self):
         cfg = self.cfg
         return (bool(getattr(cfg, "fused_step", True)) and gnn.FUSED_LINEAR

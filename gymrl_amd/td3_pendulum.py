@@ -3,7 +3,7 @@ reference's algorithms/td3_pendulum.py surface: Config :28-45, Actor :48-61, Cri
 networks in one module + q1()), ReplayBuffer :95-116, TD3Trainer :120-329 (soft_update :149-154,
 select_action :156-169, update :171-228, train / eval / test).
 
-With Config.fused_step the vector step is gymrl_td3_act_step + gymrl_td3_update (csrc/offpolicy_step.hip: one launch to act,
+With Config.fused_step the vector step is gymrl_td3_act_step + gymrl_td3_update (csrc/td3_step.hip: one launch to act,
 at most four to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described next.
 
 Underneath: Pendulum instances step on the GPU; replay ring, exploration and smoothing noise
@@ -46,7 +46,7 @@ class Config:
         # --- vectorised-engine additions ---
         self.num_envs = 1
         self.updates_per_step = 1
-        self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/offpolicy_step.hip): opt-in
+        self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/td3_step.hip): opt-in
         self.fused_images = True       # ... with weight images of the H x H layers (H % 16 == 0)
 
 
@@ -128,7 +128,7 @@ class _ActorCriticBase:
         ops.soft_update(target_flat, source_flat, self.cfg.tau)
         self._img_versions = None      # a raw-pointer write: the fused step's weight images of the target are stale
 
-    # ------------------------------------------------------------ fused vector step (csrc/offpolicy_step.hip) --
+    # ------------------------------------------------------------ fused vector step (csrc/td3_step.hip) --------
     N_CRITICS = 2                      # TD3's twin module; DDPGTrainer: 1
     CHUNK = 16                         # vector steps per StepChunk replay (= the episode tracker's flush period)
 

@@ -1,7 +1,8 @@
 """The fused SAC vector step (csrc/offpolicy_step.hip: acting + env + replay row in one launch, update() in four) against the
 layer-by-layer path it replaces (gymrl_lin_* launches + the stand-alone loss / optimiser / replay / env kernels, which
 tests/test_trainers_gpu.py pins against the reference's own update() and train()): same noise, same index draws ->
-every parameter, Adam moment, the target network, the float64 temperature and the replay ring equal BIT FOR BIT."""
+every parameter, Adam moment, the target network, the float64 temperature and the replay ring equal BIT FOR BIT.
+Rainbow's fused step (csrc/rainbow_step.hip) against its layer-by-layer path likewise."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""The fused TD3 / DDPG vector step (csrc/offpolicy_step.hip: acting + env + replay row in one launch, update() in at most
+"""The fused TD3 / DDPG vector step (csrc/td3_step.hip: acting + env + replay row in one launch, update() in at most
 four) against the layer-by-layer path it replaces (gymrl_lin_* launches + the stand-alone noise / loss / optimiser / replay /
 env kernels, which tests/test_trainers_gpu.py pins against the reference's own update()): same noise, same index draws ->
 every parameter, Adam moment, both target networks, the loss sums and the replay ring equal BIT FOR BIT."""
