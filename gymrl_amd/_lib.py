@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GYMRL_HIP_LIB") or os.path.join(_HERE, "libgymrl_hip.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 3      # == GYMRL_ABI_VERSION of the include/gymrl.h this front-end was written against
+ABI_VERSION = 4      # == GYMRL_ABI_VERSION of the include/gymrl.h this front-end was written against
 
 _lib = None
 
@@ -243,7 +243,7 @@ _vp, _i, _i64, _u64, _f, _d, _sz, _P = (C.c_void_p, C.c_int, C.c_int64, C.c_uint
 # plain Python ints and floats and refuses an argument of another type; tests/test_abi.py holds each line to the header.
 # A pointer to device memory or a stream is _vp; a HOST array the caller passes as a ctypes array is _P(<scalar>); a
 # `const gymrl_x*` is _P(<its mirror above>), or _vp where callers also hand in an untyped NULL (gymrl_mhc_policy_pack,
-# gymrl_mhc_policy_forward, gymrl_sac_step).
+# gymrl_mhc_policy_forward).
 SIGNATURES = {
     "gymrl_abi_version": (_i, []),
     "gymrl_device_ok": (_i, []),
@@ -381,7 +381,6 @@ SIGNATURES = {
     "gymrl_sac_args_bytes": (_sz, [_i]),
     "gymrl_sac_act_step": (_i, [_P(SacActArgs), _vp]),
     "gymrl_sac_update": (_i, [_P(SacUpdateArgs), _vp]),
-    "gymrl_sac_step": (_i, [_vp, _vp, _vp]),
     "gymrl_rainbow_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_rainbow_args_bytes": (_sz, [_i]),
     "gymrl_rainbow_act_step": (_i, [_P(RainbowActArgs), _vp]),

@@ -1,4 +1,4 @@
-// offpolicy_step.hip — a whole SAC vector step (sac_pendulum.py:269-310) in five launches, or in one (gymrl_sac_step).
+// offpolicy_step.hip — a whole SAC vector step (sac_pendulum.py:269-310) in five launches.
 //
 // Round 3's step was ~60 launches of 4-14 us each (profiles/r03_sac_kernel_stats.csv: 0.325 ms per vector step, the acting
 // forward at 0.03 of the f32-MFMA peak): every Linear of a 128-row batch is ~1 us of MFMA work behind a dispatch, a first
@@ -74,11 +74,12 @@ struct Images {
 //          the time it would otherwise wait.
 // All workgroups of every slab are resident (4 * B / 16 <= 64 of 256 CUs) and the producers wait for nobody: no deadlock.
 // Every flag has one writer and one reader, who clears it.  Same layers, same order per element as the per-layer path.
-// ring_ready / ring_n (the one-launch step): the acting workgroups of the same launch that must have written their replay rows
-// before this workgroup gathers (its index draw does not wait for them)
+//
+// Each kernel of this file is a __forceinline__ body and the __global__ function that calls it, on purpose: with the body written
+// into the kernel, where the argument struct is the by-value parameter itself and not a reference to it, hipcc gives the kernels
+// scratch (sac_p1 / sac_p3 <256>: 0 -> 80 bytes per lane, sac_act: 56 -> 128; profiles/sac_one_launch_removal_ab.txt)
 template <int HC>
-__device__ __forceinline__ void sac_p1_body(const gymrl_sac_update_args& a, const SacWs& ws, float* lds, const int bx, const int role, const int S,
-                                            const unsigned int* ring_ready, unsigned int ring_n) {
+__device__ __forceinline__ void sac_p1_body(const gymrl_sac_update_args& a, const SacWs& ws, float* lds, const int bx, const int role, const int S) {
   const Lds L;
   const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);      // HC: the hidden width this instance is built for (0: any)
   const int X0 = L.big, X1 = X0 + 16 * ld, H1a = X1 + 16 * ld, H1b = H1a + 16 * ld, H2a = H1b + 16 * ld, H2b = H2a + 16 * ld;
@@ -115,7 +116,6 @@ __device__ __forceinline__ void sac_p1_body(const gymrl_sac_update_args& a, cons
   int64_t row = 0;
   if (t < nrows) row = replay_draw_row(a, row0 + t);
   sg.commit();
-  phase_wait(ring_ready, ring_n);
   if (t < 16) {
     const int b = row0 + t;
     const bool ok = t < nrows;
@@ -261,8 +261,8 @@ template <int HC>
 __global__ __launch_bounds__(kThreads) void sac_p1_kernel(const gymrl_sac_update_args a, const SacWs ws) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int order[4] = {0, 1, 2, 3};                 // the two target chains wait for nobody; the critic chains wait for them
-  const SlabGrid g = slab_grid<4>(ws.sync + 8, order);
-  sac_p1_body<HC>(a, ws, lds, g.slab, g.role, g.slabs, nullptr, 0u);
+  const SlabGrid g = slab_grid<4>(ws.sync, order);
+  sac_p1_body<HC>(a, ws, lds, g.slab, g.role, g.slabs);
   slab_grid_done(g);
 }
 
@@ -272,11 +272,8 @@ __global__ __launch_bounds__(kThreads) void sac_p1_kernel(const gymrl_sac_update
 // the two Q columns (both ways: the min's tie rule needs both) and the helper's half of d action (1 -> 0): d action is ONE
 // accumulator chain over both networks in the per-layer path (Q1's terms, then Q2's), so the helper runs Q1's half and
 // workgroup 0 goes on from its 16 x A partial sums.
-// rows_ready / critic_ready (the one-launch step): P1's and P2's phase counters — the saved sample and slabs are P1's, the
-// critic's parameters P2's; what does not need the updated critic is loaded before the second wait
 template <int HC>
-__device__ __forceinline__ void sac_p3_body(const gymrl_sac_update_args& a, const SacWs& ws, float* lds, const int bx, const int by, const int S,
-                                            const unsigned int* rows_ready, unsigned int rows_n, const unsigned int* critic_ready, unsigned int critic_n) {
+__device__ __forceinline__ void sac_p3_body(const gymrl_sac_update_args& a, const SacWs& ws, float* lds, const int bx, const int by, const int S) {
   const Lds L;
   const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);      // HC: the hidden width this instance is built for (0: any)
   const int X0 = L.big, X1 = X0 + 16 * ld, H1a = X1 + 16 * ld, H1b = H1a + 16 * ld, H2a = H1b + 16 * ld, H2b = H2a + 16 * ld;
@@ -289,7 +286,6 @@ __device__ __forceinline__ void sac_p3_body(const gymrl_sac_update_args& a, cons
   const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD, kA = kMaxA;
   const Images im(a.images, H);
   if (!helper) STEP_MARK(1, 0);
-  phase_wait(rows_ready, rows_n);
   // the batch's states and the actor step's sample (a, logp, mean, log_std, eps: P1 computed them); workgroup 0 also takes the
   // actor's two activation slabs back for the way home
   if (t < 16) {
@@ -311,7 +307,6 @@ __device__ __forceinline__ void sac_p3_body(const gymrl_sac_update_args& a, cons
       lds[AH2 + rr * ld + c] = ok ? ws.aH2[(size_t)(row0 + rr) * H + c] : 0.0f;
     }
   }
-  phase_wait(critic_ready, critic_n);
   // the narrow layers' parameters into a slab this workgroup leaves free (Stager): its Q network's fc1 and fc3 — forward, and
   // fc1 again as the d action chain's operand — and, for the way home, the actor's heads
   const int n = helper ? 0 : 1;
@@ -430,8 +425,8 @@ template <int HC>
 __global__ __launch_bounds__(kThreads) void sac_p3_kernel(const gymrl_sac_update_args a, const SacWs ws) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int order[2] = {0, 1};                       // they exchange both ways: case (b) of slab_grid's comment
-  const SlabGrid g = slab_grid<2>(ws.sync + 10, order);
-  sac_p3_body<HC>(a, ws, lds, g.slab, g.role, g.slabs, nullptr, 0u, nullptr, 0u);
+  const SlabGrid g = slab_grid<2>(ws.sync + 2, order);
+  sac_p3_body<HC>(a, ws, lds, g.slab, g.role, g.slabs);
   slab_grid_done(g);
 }
 
@@ -488,75 +483,6 @@ template <int HC>
 __global__ __launch_bounds__(kThreads) void sac_act_kernel(const gymrl_sac_act_args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   sac_act_body<HC>(a, lds, blockIdx.x);
-}
-
-// ======================================================================================== the step as ONE launch =====
-// gymrl_sac_step: acting + env step + replay rows, then the whole update, in one grid.  Block ranges are the five phases in
-// order (acting | P1: 4 per slab | P2: critic tiles | P3: 2 per slab | P4: actor tiles); a phase that needs an earlier one
-// complete spins on that phase's counter (phase_wait) — a launch boundary's 3-4 us become ~1 us, and what a phase can do
-// before it needs its predecessor (P1's index draw: 6 Philox-keyed Feistel rounds; P3's loads of the saved sample and the
-// actor's slabs) is hidden behind it.  No deadlock: the acting blocks wait for nobody, every wait is on an earlier range, and
-// the blocks that can wait (at most 4 + 2 per slab + the tile blocks: < 150 at B = 256) are fewer than the 256 compute units,
-// so whatever order the dispatcher takes, the blocks a waiter needs get a unit.  The last block to finish (a ticket) clears
-// the counters: the workspace is as zero after the launch as before it.
-struct SacStepArgs {
-  gymrl_sac_act_args act; gymrl_sac_update_args upd; SacWs ws; DwArgs c, p;
-  int n_act, slabs, c_blocks, p_blocks;
-};
-static_assert(sizeof(SacStepArgs) <= 4096, "kernel arguments");
-
-template <int HC>
-__global__ __launch_bounds__(kThreads) void sac_step_kernel(const SacStepArgs by_value) {
-  // read in place from the kernel-argument segment (the struct is the first argument): as a by-value object the dynamic
-  // indices into its pointer tables made hipcc copy all of it into every lane's scratch (3.5 KB per lane)
-  const SacStepArgs& s = *(const SacStepArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  __shared__ double sm[3][4];
-  unsigned int* const sync = s.ws.sync;
-  const int S = s.slabs;
-  // the block's place in the launch is the order in which it STARTED (a ticket), not blockIdx: every phase_wait / flag_wait
-  // below waits for places lower than its own or — P1's / P3's pairs — for a place at most 3 S (48) higher, whose
-  // workgroups start as the earlier ones finish (slab_grid's argument: the started places are always a prefix)
-  __shared__ unsigned int place;
-  if (threadIdx.x == 0) place = __hip_atomic_fetch_add(sync + 6, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  int b = (int)__builtin_amdgcn_readfirstlane(place);
-  if (b < s.n_act) {
-    sac_act_body<HC>(s.act, lds, b);
-    phase_done(sync + 0);
-  } else if ((b -= s.n_act) < 4 * S) {
-    const int role = b / S;
-    sac_p1_body<HC>(s.upd, s.ws, lds, b - role * S, role, S, sync + 0, (unsigned)s.n_act);
-    if (role >= 2) phase_done(sync + 1);
-  } else if ((b -= 4 * S) < s.c_blocks) {
-    [[maybe_unused]] const int bx = b;                 // (probe build: stamps of the group's first block)
-    STEP_MARK(2, 16);
-    phase_wait(sync + 1, 2u * S);
-    STEP_MARK(2, 17);
-    sac_dw_body(s.c, b, s.c_blocks, sm);
-    phase_done(sync + 2);
-    STEP_MARK(2, 18);
-  } else if ((b -= s.c_blocks) < 2 * S) {
-    const int by = b / S;
-    sac_p3_body<HC>(s.upd, s.ws, lds, b - by * S, by, S, sync + 1, 2u * S, sync + 2, (unsigned)s.c_blocks);
-    if (by == 0) phase_done(sync + 3);
-  } else {
-    b -= 2 * S;
-    [[maybe_unused]] const int bx = b;
-    STEP_MARK(2, 19);
-    phase_wait(sync + 3, (unsigned)S);
-    STEP_MARK(2, 20);
-    sac_dw_body(s.p, b, s.p_blocks, sm);
-    STEP_MARK(2, 21);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (__hip_atomic_fetch_add(sync + 7, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-      for (int k = 0; k < 4; ++k) __hip_atomic_store(sync + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(sync + 6, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(sync + 7, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
 }
 
 inline bool sac_shape_ok(int B, int D, int A, int H) {
@@ -622,8 +548,8 @@ static bool sac_update_args_ok(const gymrl_sac_update_args& a) {
 static int sac_set_lds_attr() {
   static bool attr_set = false;
   if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)sac_p1_kernel<0>, (const void*)sac_p1_kernel<256>, (const void*)sac_p3_kernel<0>, (const void*)sac_p3_kernel<256>,
-                                    (const void*)sac_step_kernel<0>, (const void*)sac_step_kernel<256>}, (int)lds_bytes(256, 8)))
+    if (const int rc = set_max_lds({(const void*)sac_p1_kernel<0>, (const void*)sac_p1_kernel<256>, (const void*)sac_p3_kernel<0>, (const void*)sac_p3_kernel<256>},
+                                   (int)lds_bytes(256, 8)))
       return rc;
     attr_set = true;
   }
@@ -681,24 +607,6 @@ int gymrl_sac_update(const gymrl_sac_update_args* args, void* stream_) {
   launch_dw(c, stream);
   hipLaunchKernelGGL(H == 256 ? sac_p3_kernel<256> : sac_p3_kernel<0>, slab_launch_grid(slabs, 2), dim3(kThreads), lds_bytes(H, 8), stream, a, ws);   // y / role: the actor + Q2, then Q1
   launch_dw(p, stream);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
-}
-
-int gymrl_sac_step(const gymrl_sac_act_args* act_args, const gymrl_sac_update_args* upd_args, void* stream_) {
-  if (!act_args || !upd_args) return -22;
-  const gymrl_sac_act_args& a = *act_args;
-  const gymrl_sac_update_args& u = *upd_args;
-  if (!sac_act_args_ok(a) || !sac_update_args_ok(u) || a.H != u.H || u.B > 256) return -22;   // one grid: every waiting block must be resident
-  if (const int rc = sac_set_lds_attr()) return rc;
-  SacStepArgs s;
-  s.act = a; s.upd = u;
-  SacWs::carve(&s.ws, align256(u.workspace), u.B, u.D, u.A, u.H);
-  sac_build_dw(u, s.ws, s.c, s.p);
-  s.n_act = (a.N + 15) / 16; s.slabs = (u.B + 15) / 16;
-  s.c_blocks = (s.c.total_waves + kWaves - 1) / kWaves + 1; s.p_blocks = (s.p.total_waves + kWaves - 1) / kWaves + 1;
-  const int blocks = s.n_act + 6 * s.slabs + s.c_blocks + s.p_blocks;
-  hipLaunchKernelGGL(u.H == 256 ? sac_step_kernel<256> : sac_step_kernel<0>, dim3(blocks), dim3(kThreads), lds_bytes(u.H, 8), (hipStream_t)stream_, s);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

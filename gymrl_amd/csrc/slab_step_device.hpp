@@ -2,8 +2,8 @@
 //
 // offpolicy_step.hip (SAC), rainbow_step.hip (Rainbow) and td3_step.hip (TD3 / DDPG) carry a 16-row slab of the batch through
 // a chain of layers in ONE workgroup of 16 waves (offpolicy_step.hip's header has the argument).  Here: the stages (fwd_stage /
-// bwd_stage over FwdItem / BwdItem), the LDS layout (Lds), the narrow layers' staging (Stager), the hand-off flags and phase
-// counters, the grid shapes and their deadlock argument (slab_grid), SAC's and TD3's hand-off workspace (SacWs), the
+// bwd_stage over FwdItem / BwdItem), the LDS layout (Lds), the narrow layers' staging (Stager), the hand-off flags,
+// the grid shapes and their deadlock argument (slab_grid), SAC's and TD3's hand-off workspace (SacWs), the
 // weight-gradient tile kernel (DwArgs / sac_dw_body / sac_dw_kernel) with its host-side list builder (DwBuilder), and the
 // blocks that the algorithms had each carried a copy of: the replay index draw, the Pendulum acting tail, the weight-image
 // packing and the small host helpers.  Everything is __forceinline__ device code or inline host code inside an anonymous
@@ -57,8 +57,8 @@ struct SacWs {
   double* terms2;                     // [B]: the second Q network's critic term (its workgroup's share of terms[.][0])
   float *xtq[2], *xmisc;              // P1: the two target networks' Q(s', a') columns [16 S] and {reward, done, logp'} [16 S][4], from the
                                       // target-chain workgroups to the critic-chain workgroups (each forms y itself)
-  unsigned int* sync;                 // [16]: gymrl_sac_step's phase counters (0 acting, 1 P1, 2 P2, 3 P3 done; 6 next ticket, 7 finished workgroups);
-                                      // the large-batch row kernels' tickets (slab_grid: 8 / 9 P1's, 10 / 11 P3's) — all zero between launches
+  unsigned int* sync;                 // [16]: the large-batch row kernels' tickets (slab_grid: 0 / 1 P1's, 2 / 3 P3's), zero between launches;
+                                      // the other twelve words are unused and keep the workspace's layout
   unsigned int* flag;                 // [8][ceil(B / 16)]: hand-off flags (1 = waiting to be consumed; zero before the first launch, left zero):
                                       //   P1: 0 / 1 target network 1 -> critic workgroup 1 / 2, 5 / 6 target network 2 -> critic workgroup 1 / 2;
                                       //   P3: 2 / 3 Q1 / Q2, 4 the second network's dZ1 slab
@@ -273,29 +273,6 @@ __device__ __forceinline__ void flag_wait(unsigned int* f) {
 __device__ __forceinline__ void flag_clear(unsigned int* f) { __hip_atomic_store(f, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float xload(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void xstore(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// phase counters of the one-launch step (gymrl_sac_step): a workgroup that has finished a phase adds one with a release, after
-// every wave has waited for its own global stores and a workgroup barrier; a workgroup of a later phase spins until the
-// count is complete (acquire: what it then reads with plain loads is what the producers wrote), thread 0 for everybody
-__device__ __forceinline__ void phase_done(unsigned int* c) {
-  // __syncthreads() alone waits for LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier): every wave first waits until its OWN
-  // global stores have reached the L2 (vmcnt(0)), then the barrier, then thread 0's release writes the L2 back and publishes
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void phase_wait(const unsigned int* c, unsigned int n) {
-  if (c) {
-    if (threadIdx.x == 0) {
-      unsigned int polls = 0;
-      while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++polls > kSpinLimit) __builtin_trap();
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-  }
-}
 
 // Grid shapes of the row kernels, and why a waiting workgroup's producer is always running.
 //   B <= 256 (the reference's batch sizes): dim3(slabs, R), y = role — at most 64 workgroups of one per compute unit, every one

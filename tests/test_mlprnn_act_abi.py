@@ -25,7 +25,7 @@ def test_symbols_and_descriptor():
     for name in ("gymrl_mlprnn_params_bytes", "gymrl_mlprnn_act", "gymrl_running_norm_masked", "gymrl_reward_scaling_masked"):
         assert name in _lib.SYMBOLS and hasattr(L, name), name
     assert L.gymrl_mlprnn_params_bytes() == ctypes.sizeof(_lib.MlprnnParams) == 28 * 8
-    assert L.gymrl_abi_version() == 3
+    assert L.gymrl_abi_version() == 4
 
 
 def test_mlprnn_act_validates_arguments_without_gpu():

@@ -19,7 +19,7 @@ def test_symbols_are_declared_and_loaded():
     for name in ("gymrl_gru_seq_fwd", "gymrl_gru_seq_bwd", "gymrl_episode_gae", "gymrl_ppg_policy_loss_fwd_bwd",
                  "gymrl_ppg_aux_loss_fwd_bwd"):
         assert name in _lib.SYMBOLS and hasattr(L, name), name
-    assert L.gymrl_abi_version() == 3
+    assert L.gymrl_abi_version() == 4
 
 
 def test_gru_seq_validates_arguments_without_gpu():

@@ -176,14 +176,21 @@ def _train(mod, cls, steps, **over):
     return tr
 
 
-def test_sac_chunked_vector_steps_equal_eager():
+# (64 / 128 / 256: the default shape; 256 / 128 / 256: sixteen full acting workgroups; 4100 / 256 / 256: a partial last acting
+#  workgroup, a full set of slabs at B = 256, and the ring wraps; 40 / 24 / 32: a hidden width without weight images and
+#  without the 256-wide instances.  Updates start once the ring holds a batch — after ceil(B / N) <= 2 vector steps here)
+@pytest.mark.parametrize("N,B,hidden,steps", [(64, 128, 256, 70), (256, 128, 256, 64), (4100, 256, 256, 64), (40, 24, 32, 64)])
+def test_sac_chunked_vector_steps_equal_eager(N, B, hidden, steps):
     from gymrl_amd import sac_pendulum
-    eager = _train(sac_pendulum, "SACTrainer", 70, use_graphs=False)
-    chunk = _train(sac_pendulum, "SACTrainer", 70, use_graphs=True, chunk_steps=16)
-    assert chunk._chunk.graph is not None                                        # 3 chunks of 16 replayed
-    assert chunk.critic_optimizer.step_count == eager.critic_optimizer.step_count > 60
-    for name in ("actor_flat", "critic_flat", "critic_target_flat", "log_alpha", "_alpha_m", "_alpha_v"):
-        assert torch.equal(getattr(eager, name), getattr(chunk, name)), name
+    shape = dict(num_envs=N, batch_size=B, hidden_dim=hidden, memory_capacity=1 << 14)
+    eager = _train(sac_pendulum, "SACTrainer", steps, use_graphs=False, **shape)
+    chunk = _train(sac_pendulum, "SACTrainer", steps, use_graphs=True, chunk_steps=16, **shape)
+    assert eager._fused_ok() and chunk._fused_ok()
+    assert chunk._chunk.graph is not None and getattr(eager, "_chunk", None) is None      # 3-4 chunks of 16 replayed
+    assert chunk.critic_optimizer.step_count == eager.critic_optimizer.step_count > steps - 10 >= 48
+    for name in ("actor_flat", "critic_flat", "critic_target_flat", "log_alpha", "_alpha_m", "_alpha_v", "_sums"):
+        assert torch.equal(getattr(eager, name), getattr(chunk, name)), (N, B, hidden, name)
+    assert all(torch.isfinite(getattr(chunk, n)).all() for n in ("actor_flat", "critic_flat", "log_alpha"))
     for a, b in zip(eager.memory.ring, chunk.memory.ring):
         assert torch.equal(a, b)
     assert (eager.memory.cursor, eager.memory.size, eager.memory.draws) == (chunk.memory.cursor, chunk.memory.size, chunk.memory.draws)
