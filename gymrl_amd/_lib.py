@@ -217,6 +217,41 @@ class Td3UpdateArgs(C.Structure):
                 ("sums", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
 
 
+class DsacActArgs(C.Structure):
+    _c_name_ = "gymrl_dsac_act_args"
+    _fields_ = [("N", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("env_kind", C.c_int),
+                ("env_state", C.c_void_p), ("env_seed", C.c_uint64), ("env_id0", C.c_int64),
+                ("obs", C.c_void_p), ("obs_out", C.c_void_p), ("noise_exp", C.c_void_p),
+                ("seed", C.c_uint64), ("counter", C.c_uint64), ("counter_dev", C.c_void_p),
+                ("actor", Td3ActorParams),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p), ("cap", C.c_int64), ("cursor", C.c_int64), ("cursor_dev", C.c_void_p),
+                ("action_out", C.c_void_p), ("rew_out", C.c_void_p), ("done_out", C.c_void_p), ("ep_ret_out", C.c_void_p),
+                ("ep_stats", C.c_void_p), ("images", C.c_void_p)]
+
+
+class DsacUpdateArgs(C.Structure):
+    _c_name_ = "gymrl_dsac_update_args"
+    _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int),
+                ("gamma", C.c_float), ("target_entropy", C.c_float), ("tau", C.c_double),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p),
+                ("idx", C.c_void_p), ("idx_seed", C.c_uint64), ("idx_counter", C.c_uint64), ("idx_size", C.c_int64),
+                ("idx_dev", C.c_void_p),
+                ("actor", Td3ActorParams), ("critic1", Td3ActorParams), ("critic2", Td3ActorParams),
+                ("critic1_target", Td3ActorParams), ("critic2_target", Td3ActorParams),
+                ("actor_p", C.c_void_p), ("actor_m", C.c_void_p), ("actor_v", C.c_void_p),
+                ("critic1_p", C.c_void_p), ("critic1_m", C.c_void_p), ("critic1_v", C.c_void_p),
+                ("critic2_p", C.c_void_p), ("critic2_m", C.c_void_p), ("critic2_v", C.c_void_p),
+                ("adam_critic1", C.c_float * 4), ("adam_critic2", C.c_float * 4), ("adam_actor", C.c_float * 4),
+                ("adam_critic1_dev", C.c_void_p), ("adam_critic2_dev", C.c_void_p), ("adam_actor_dev", C.c_void_p),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps_adam", C.c_double),
+                ("log_alpha", C.c_void_p), ("alpha_m", C.c_void_p), ("alpha_v", C.c_void_p),
+                ("lr_alpha", C.c_double), ("alpha_beta1", C.c_double), ("alpha_beta2", C.c_double), ("alpha_eps", C.c_double),
+                ("alpha_t", C.c_int64), ("alpha_bias_dev", C.c_void_p),
+                ("sums", C.c_void_p), ("alpha_loss", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
+
+
 class WeightImage(C.Structure):
     _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
@@ -390,6 +425,13 @@ SIGNATURES = {
     "gymrl_td3_args_bytes": (_sz, [_i]),
     "gymrl_td3_act_step": (_i, [_P(Td3ActArgs), _vp]),
     "gymrl_td3_update": (_i, [_P(Td3UpdateArgs), _vp]),
+    "gymrl_dsac_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_dsac_pack_images": (_i, [_P(DsacUpdateArgs), _vp]),
+    "gymrl_dsac_args_bytes": (_sz, [_i]),
+    "gymrl_dsac_act_step": (_i, [_P(DsacActArgs), _vp]),
+    "gymrl_dsac_update": (_i, [_P(DsacUpdateArgs), _vp]),
+    "gymrl_softmax_rows_fwd": (_i, [_vp, _i, _i, _vp, _vp]),
+    "gymrl_softmax_rows_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -1,11 +1,11 @@
 // slab_step_device.hpp — what the row-slab step kernels of every off-policy algorithm share.
 //
-// offpolicy_step.hip (SAC), rainbow_step.hip (Rainbow) and td3_step.hip (TD3 / DDPG) carry a 16-row slab of the batch through
+// offpolicy_step.hip (SAC), rainbow_step.hip (Rainbow), td3_step.hip (TD3 / DDPG) and dsac_step.hip (discrete SAC) carry a 16-row slab of the batch through
 // a chain of layers in ONE workgroup of 16 waves (offpolicy_step.hip's header has the argument).  Here: the stages (fwd_stage /
 // bwd_stage over FwdItem / BwdItem), the LDS layout (Lds), the narrow layers' staging (Stager), the hand-off flags,
 // the grid shapes and their deadlock argument (slab_grid), SAC's and TD3's hand-off workspace (SacWs), the
 // weight-gradient tile kernel (DwArgs / sac_dw_body / sac_dw_kernel) with its host-side list builder (DwBuilder), and the
-// blocks that the algorithms had each carried a copy of: the replay index draw, the Pendulum acting tail, the weight-image
+// blocks that the algorithms had each carried a copy of: the replay index draw, the Pendulum / CartPole acting tails, the weight-image
 // packing and the small host helpers.  Everything is __forceinline__ device code or inline host code inside an anonymous
 // namespace: every translation unit that includes this header has its own file-local kernels and the library exports none of it.
 #pragma once
@@ -348,6 +348,10 @@ struct DwArgs {
   int alpha_step;
   double* log_alpha; double* alpha_m; double* alpha_v; double lr_alpha, abeta1, abeta2, aeps; double alpha_bias[2];
   const double* alpha_bias_dev; double* alpha_loss;
+  // alpha_step == 2: discrete SAC's float32 temperature (offpolicy.hip dsac_alpha_kernel) — its scalar and moments, the target
+  // entropy and the step count the bias corrections are formed from when alpha_bias_dev is null; lr_alpha / abeta1 / abeta2 /
+  // aeps hold that kernel's float32 arguments
+  float* log_alpha_f; float* alpha_m_f; float* alpha_v_f; float target_entropy_f; int64_t alpha_t;
 };
 
 // One wave per 16 x 16 tile of a weight gradient + its Adam step; the last block of the group sums the loss terms (its first
@@ -404,6 +408,24 @@ __device__ __forceinline__ void sac_dw_body(const DwArgs& a, const int block, co
     }
     if (!a.alpha_step) return;
     __syncthreads();
+    if (a.alpha_step == 2) {              // offpolicy.hip dsac_alpha_kernel on fin[1] = the entropy sum (float32 arithmetic)
+      if (threadIdx.x == 0) {
+        const float lr = (float)a.lr_alpha, b1 = (float)a.abeta1, b2 = (float)a.abeta2, eps = (float)a.aeps;
+        const float alpha = det_expf(a.log_alpha_f[0]);
+        const float mean_gap = (float)((0.0 + fin[1]) / (double)a.B) - a.target_entropy_f;
+        if (a.alpha_loss) a.alpha_loss[0] = (double)(alpha * mean_gap);
+        const float g = alpha * mean_gap;
+        const float mm = b1 * a.alpha_m_f[0] + (1.0f - b1) * g;
+        const float vv = b2 * a.alpha_v_f[0] + (1.0f - b2) * g * g;
+        a.alpha_m_f[0] = mm; a.alpha_v_f[0] = vv;
+        const double bc1 = a.alpha_bias_dev ? a.alpha_bias_dev[0] : 1.0 - pow((double)b1, (double)a.alpha_t);
+        const double bc2 = a.alpha_bias_dev ? a.alpha_bias_dev[1] : 1.0 - pow((double)b2, (double)a.alpha_t);
+        const float step_size = (float)((double)lr / bc1);
+        const float denom = (float)(sqrt((double)vv) / sqrt(bc2)) + eps;
+        a.log_alpha_f[0] = a.log_alpha_f[0] - step_size * (mm / denom);
+      }
+      return;
+    }
     if (threadIdx.x == 0) {               // offpolicy.hip sac_alpha_step_kernel
       double bc1 = a.alpha_bias[0], bc2_sqrt = sqrt(a.alpha_bias[1]);
       if (a.alpha_bias_dev) { bc1 = a.alpha_bias_dev[0]; bc2_sqrt = sqrt(a.alpha_bias_dev[1]); }
@@ -593,6 +615,37 @@ __device__ __forceinline__ void pendulum_act_tail(const Args& a, const float* ld
     }
     a.r_reward[row] = r.reward;
     a.r_flag[row] = r.done;                             // done = terminated or truncated
+    if (a.rew_out) a.rew_out[i] = r.reward;
+    if (a.done_out) a.done_out[i] = r.done;
+    if (r.done && a.ep_ret_out) a.ep_ret_out[i] = (float)r.ret;
+  }
+  accumulate_ep_stats(a.ep_stats, r.done && ok, r.ret, r.len);
+}
+
+// The same tail for CartPole under a discrete action: the step with auto-reset, the ring row {state, int32 action word, reward,
+// TERMINAL observation, done} at (cursor + i) % cap, the outputs env.step(..., done_out, term_obs_out, ep_ret_out) + memory.push
+// write.  (Rainbow's tail pushes into an n-step window between the step and the ring row and keeps its own copy.)
+template <class Args>
+__device__ __forceinline__ void cartpole_act_tail(const Args& a, const float* lds, const Lds& L, int t, int row0, int nrows, int act) {
+  const bool ok = t < nrows;
+  const int D = a.D;
+  ClassicStep<4> r;
+  r.done = false; r.ret = 0.0; r.len = 0;
+  if (ok) {
+    const int i = row0 + t;
+    const CartPoleState st(a.env_state, a.N);
+    cartpole_step_one(st, i, a.env_seed, a.env_id0, act, r);
+    const int64_t cursor = a.cursor_dev ? a.cursor_dev[0] : a.cursor;
+    const int64_t row = (cursor + i) % a.cap;
+    for (int k = 0; k < D; ++k) {
+      a.r_state[row * D + k] = lds[L.S + t * kMaxD + k];
+      a.r_next[row * D + k] = r.o_term[k];
+      a.obs_out[(size_t)i * D + k] = r.o_next[k];
+    }
+    a.r_action[row] = (uint32_t)act;
+    a.r_reward[row] = r.reward;
+    a.r_flag[row] = r.done;
+    if (a.action_out) a.action_out[i] = act;
     if (a.rew_out) a.rew_out[i] = r.reward;
     if (a.done_out) a.done_out[i] = r.done;
     if (r.done && a.ep_ret_out) a.ep_ret_out[i] = (float)r.ret;

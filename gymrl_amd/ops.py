@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -1679,6 +1679,136 @@ def td3_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None,
                 dst[k] = vals[k]
     a.adam_critic_dev, a.adam_actor_dev = _addr(adam_critic_dev), _addr(adam_actor_dev)
     check(lib().gymrl_td3_update(C.byref(a), _stream()), "gymrl_td3_update")
+
+
+# --------------------------------------- fused discrete-SAC vector step ---
+DSAC_FUSED_MAX_BATCH = 256     # one grid of at most 16 slabs per row phase (dsac_step.hip kDsacMaxBatch)
+
+
+def dsac_fused_shape_ok(B, D, A, H):
+    """Shapes gymrl_dsac_act_step / gymrl_dsac_update take (include/gymrl.h): everything else runs layer by layer."""
+    return 0 < B <= DSAC_FUSED_MAX_BATCH and 0 < D <= 8 and 0 < A <= 4 and 4 <= H <= 256 and H % 4 == 0
+
+
+class _SoftmaxRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z):
+        z = z.contiguous()
+        B, A = z.shape
+        p = torch.empty_like(z)
+        check(lib().gymrl_softmax_rows_fwd(_ptr(z, torch.float32), B, A, _ptr(p), _stream()), "gymrl_softmax_rows_fwd")
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    def backward(ctx, g):
+        p, = ctx.saved_tensors
+        g = g.contiguous()
+        B, A = p.shape
+        dz = torch.empty_like(p)
+        check(lib().gymrl_softmax_rows_bwd(_ptr(p, torch.float32), _ptr(g, torch.float32), B, A, _ptr(dz), _stream()), "gymrl_softmax_rows_bwd")
+        return dz
+
+
+def softmax_rows(z):
+    """softmax over the last dimension of z f32[B, A] (A <= 8) with csrc/softmax_device.hpp's arithmetic, forward and
+    backward: the bits the fused discrete-SAC step produces (F.softmax's belong to torch)."""
+    if z.dim() != 2 or not 0 < z.shape[1] <= 8:
+        raise ValueError(f"softmax_rows: expected [B, A <= 8], got {tuple(z.shape)}")
+    return _SoftmaxRows.apply(z)
+
+
+def dsac_update_workspace(B, D, A, H, device):
+    return torch.zeros(int(lib().gymrl_dsac_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
+
+
+def dsac_images(H, device):
+    """The eight weight images of the H x H layers (gymrl_dsac_update_args.images), or None when H % 16 != 0."""
+    return torch.zeros(8 * H * H, device=device) if H % 16 == 0 else None
+
+
+def dsac_pack_images(a):
+    """gymrl_dsac_pack_images: rebuild every image from the parameters as they are now."""
+    check(lib().gymrl_dsac_pack_images(C.byref(a), _stream()), "gymrl_dsac_pack_images")
+
+
+def dsac_act_args(env, actor, ring, cap, images=None):
+    """A gymrl_dsac_act_args with everything that does not change from step to step filled in."""
+    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"dsac_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
+    a = DsacActArgs()
+    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, actor.fc1.weight.shape[0]
+    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    _td3_actor_params(a.actor, actor)
+    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    a.cap = cap
+    a.images = _addr(images)
+    return a
+
+
+def dsac_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, noise_exp=None, seed=0, counter=0, counter_dev=None,
+                  action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None):
+    """gymrl_dsac_act_step: actor logits on obs [N, D], the categorical draw (noise_exp = f32[N, A] Exp(1) draws or None:
+    gymrl_categorical_sample's Philox keys under (seed, counter)), CartPole step with auto-reset, replay rows at
+    (cursor + env) % cap — ONE launch."""
+    if tuple(obs.shape) != (a.N, a.D) or tuple(obs_out.shape) != (a.N, a.D):
+        raise ValueError(f"dsac_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
+    if noise_exp is not None and (noise_exp.dtype != torch.float32 or noise_exp.numel() != a.N * a.A):
+        raise ValueError("dsac_act_step: noise_exp must be float32 [N, A]")
+    if action_out is not None and (action_out.dtype != torch.int32 or action_out.numel() != a.N):
+        raise ValueError("dsac_act_step: action_out must be int32 [N]")
+    a.env_seed = env.seed                              # reset(seed=...) may have moved it
+    a.obs, a.obs_out = _ptr(obs, torch.float32).value, _ptr(obs_out, torch.float32).value
+    a.noise_exp = _addr(noise_exp)
+    a.seed, a.counter, a.counter_dev = seed, counter, _addr(counter_dev)
+    a.cursor, a.cursor_dev = cursor, _addr(cursor_dev)
+    a.action_out, a.rew_out, a.done_out, a.ep_ret_out, a.ep_stats = (_addr(t) for t in (action_out, rew_out, done_out, ep_ret_out, ep_stats))
+    check(lib().gymrl_dsac_act_step(C.byref(a), _stream()), "gymrl_dsac_act_step")
+
+
+def dsac_update_args(B, D, A, actor, critic1, critic2, critic1_target, critic2_target, actor_opt, critic1_opt, critic2_opt, ring,
+                     cfg_scalars, log_alpha, alpha_m, alpha_v, sums, alpha_loss, workspace, images=None):
+    """A gymrl_dsac_update_args with the per-trainer constants filled in.  cfg_scalars = (gamma, tau, target_entropy,
+    lr_alpha); sums: f64[4] (critic1, critic2 loss sums, actor loss sum, entropy sum)."""
+    if sums.dtype != torch.float64 or sums.numel() != 4 or not sums.is_contiguous():
+        raise ValueError("dsac_update_args: sums must be a contiguous float64[4]")
+    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"dsac_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
+    a = DsacUpdateArgs()
+    a.B, a.D, a.A, a.H = B, D, A, actor.fc1.weight.shape[0]
+    gamma, tau, tent, lr_alpha = cfg_scalars
+    a.gamma, a.tau, a.target_entropy = float(gamma), float(tau), float(tent)
+    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    for dst, net in ((a.actor, actor), (a.critic1, critic1), (a.critic2, critic2), (a.critic1_target, critic1_target),
+                     (a.critic2_target, critic2_target)):
+        _td3_actor_params(dst, net)
+    a.actor_p, a.actor_m, a.actor_v = _addr(actor_opt.p), _addr(actor_opt.m), _addr(actor_opt.v)
+    a.critic1_p, a.critic1_m, a.critic1_v = _addr(critic1_opt.p), _addr(critic1_opt.m), _addr(critic1_opt.v)
+    a.critic2_p, a.critic2_m, a.critic2_v = _addr(critic2_opt.p), _addr(critic2_opt.m), _addr(critic2_opt.v)
+    g = critic1_opt.param_groups[0]
+    a.beta1, a.beta2, a.eps_adam = g["betas"][0], g["betas"][1], g["eps"]
+    a.log_alpha, a.alpha_m, a.alpha_v = (_ptr(t, torch.float32).value for t in (log_alpha, alpha_m, alpha_v))
+    a.lr_alpha, a.alpha_beta1, a.alpha_beta2, a.alpha_eps = float(lr_alpha), 0.9, 0.999, 1e-8      # dsac_alpha_step's defaults
+    a.sums, a.alpha_loss, a.workspace, a.images = _addr(sums), _addr(alpha_loss), _addr(workspace), _addr(images)
+    return a
+
+
+def dsac_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None, adam_critic1=None, adam_critic2=None, adam_actor=None,
+                adam_critic1_dev=None, adam_critic2_dev=None, adam_actor_dev=None, alpha_t=0, alpha_bias_dev=None):
+    """gymrl_dsac_update: sac_cartpole.SACTrainer.update() as four launches.  idx: i32[B] rows or None (the keyed draw);
+    adam_*: the 16-byte blocks of adam_bias() (host) or device views of them; alpha_t: the temperature's step count, or
+    alpha_bias_dev = f64[2] {1 - b1^t, 1 - b2^t} on the device."""
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != a.B):
+        raise ValueError(f"dsac_update: idx must be int32 [{a.B}]")
+    a.idx, a.idx_seed, a.idx_counter, a.idx_size, a.idx_dev = _addr(idx), idx_seed, idx_counter, idx_size, _addr(idx_dev)
+    for dst, blk in ((a.adam_critic1, adam_critic1), (a.adam_critic2, adam_critic2), (a.adam_actor, adam_actor)):
+        if blk is not None:
+            vals = (C.c_float * 4).from_buffer_copy(blk)
+            for k in range(4):
+                dst[k] = vals[k]
+    a.adam_critic1_dev, a.adam_critic2_dev, a.adam_actor_dev = _addr(adam_critic1_dev), _addr(adam_critic2_dev), _addr(adam_actor_dev)
+    a.alpha_t, a.alpha_bias_dev = int(alpha_t), _addr(alpha_bias_dev)
+    check(lib().gymrl_dsac_update(C.byref(a), _stream()), "gymrl_dsac_update")
 
 
 # --------------------------------------------- fused Rainbow vector step ---

@@ -3,6 +3,9 @@ MI355X engine behind the reference's algorithms/sac_cartpole.py surface: Config 
 Actor :70-80 (softmax output), Critic :83-93 (Q per action), SACTrainer :96-329 (select_action :127-138,
 soft_update :140-145, update :148-227, train / eval / test).
 
+With Config.fused_step the vector step is gymrl_dsac_act_step + gymrl_dsac_update (csrc/dsac_step.hip: one launch to act,
+four to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described next.
+
 Underneath: CartPole instances step on the GPU; replay ring, categorical draw, soft-Bellman target, both
 critic losses, the actor loss's forward + dL/dprobs, the float32 log_alpha Adam step, three fused Adam steps
 and the Polyak updates are HIP kernels behind the C-ABI; Linear layers and the softmax run through PyTorch-ROCm.
@@ -43,6 +46,11 @@ class Config:
         self.num_envs = 1
         self.updates_per_step = 1
         self.use_graphs = True             # replay the update as one captured hipGraph (train(); update() stays eager)
+        self.fused_step = False            # the vector step as gymrl_dsac_act_step + gymrl_dsac_update (csrc/dsac_step.hip): opt-in
+        self.fused_images = True           # ... with weight images of the H x H layers (H % 16 == 0)
+        self.kernel_softmax = False        # Actor.forward through ops.softmax_rows (csrc/softmax_device.hpp) instead of F.softmax;
+                                           # fused_step implies it (read when the trainer is built), so that the layer path and
+                                           # the fused path of one run produce the same bits and the run can change paths
 
 
 class Actor(nn.Module):
@@ -51,12 +59,14 @@ class Actor(nn.Module):
         self.fc1 = SmallLinear(state_dim, hidden_dim, act="relu")
         self.fc2 = SmallLinear(hidden_dim, hidden_dim, act="relu")
         self.fc3 = SmallLinear(hidden_dim, action_dim)
+        self.kernel_softmax = False        # SACTrainer sets it from its Config
 
     def logits(self, x):
         return self.fc3(self.fc2(self.fc1(x)))
 
     def forward(self, x):
-        return F.softmax(self.logits(x), dim=-1)
+        z = self.logits(x)
+        return ops.softmax_rows(z) if self.kernel_softmax else F.softmax(z, dim=-1)
 
 
 class Critic(nn.Module):
@@ -83,6 +93,7 @@ class SACTrainer:
         g = torch.random.get_rng_state()
         torch.manual_seed(self.base_seed)
         self.actor = Actor(state_dim, action_dim, config.hidden_dim)
+        self.actor.kernel_softmax = bool(getattr(config, "kernel_softmax", False) or getattr(config, "fused_step", False))
         self.critic1 = Critic(state_dim, action_dim, config.hidden_dim)
         self.critic2 = Critic(state_dim, action_dim, config.hidden_dim)
         torch.random.set_rng_state(g)
@@ -101,13 +112,17 @@ class SACTrainer:
         self._alpha_m, self._alpha_v = torch.zeros(1, **f32), torch.zeros(1, **f32)
         self._alpha_steps = 0
         d64 = dict(dtype=torch.float64, device=self.device)
-        self._sums_c, self._sums_a, self._alpha_loss = torch.zeros(2, **d64), torch.zeros(2, **d64), torch.zeros(1, **d64)
+        self._sums = torch.zeros(4, **d64)           # critic1, critic2 loss sums | actor loss sum, entropy sum: one buffer, so that
+        self._sums_c, self._sums_a = self._sums[0:2], self._sums[2:4]    # the fused update writes what the loss kernels write
+        self._alpha_loss = torch.zeros(1, **d64)
         self.memory = ReplayBuffer(config.memory_capacity, state_dim, self.device, seed=self.base_seed)
         self.episode_rewards = deque(maxlen=100)
         self._act_counter = 0
         self._parity_noise = None      # tests: iterator of f32[N, A] Exp(1) draws for select_action
         self._parity_indices = None    # tests: iterator of i32[B] replay indices for update()
         self._graph = None             # hipGraph of the update, captured on first use (update_async)
+        self._fused = None             # (act args, update args, workspace, env, weight images) of the fused step, built on first use
+        self._img_versions = None      # versions of the flat buffers the weight images were last rebuilt from
 
     @torch.no_grad()
     def select_action(self, state, deterministic=False, noise_exp=None):
@@ -123,6 +138,167 @@ class SACTrainer:
     def soft_update(self, target_flat, source_flat):
         """:140-145 on the flat parameter buffers."""
         ops.soft_update(target_flat, source_flat, self.cfg.tau)
+        self._img_versions = None      # a raw-pointer write: the fused step's weight images of the target are stale
+
+    # ------------------------------------------------------------ fused vector step (csrc/dsac_step.hip) -------
+    CHUNK = 16                         # vector steps per StepChunk replay (= the episode tracker's flush period)
+
+    def _fused_update_ok(self):
+        """update() as gymrl_dsac_update: opt-in (cfg.fused_step) and a matter of shapes."""
+        cfg, m = self.cfg, self.memory
+        return (bool(getattr(cfg, "fused_step", False))
+                and ops.dsac_fused_shape_ok(cfg.batch_size, m.ring[0].shape[1], self.action_dim, cfg.hidden_dim))
+
+    def _fused_ok(self):
+        """The whole vector step fused: the update AND acting + env step + replay row (gymrl_dsac_act_step steps CartPole
+        itself and has no `abandon`: the trainer's own step cap must not cut an episode short)."""
+        cfg, env = self.cfg, self.env
+        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind == ops.CARTPOLE
+                and cfg.max_steps >= env.max_steps and self.memory.capacity >= env.n)
+
+    def _fused_args(self):
+        if self._fused is None or self._fused[3] is not self.env:
+            cfg, env, m = self.cfg, self.env, self.memory
+            D, A = m.ring[0].shape[1], self.action_dim
+            img = ops.dsac_images(cfg.hidden_dim, self.device) if getattr(cfg, "fused_images", True) else None
+            act = (ops.dsac_act_args(env, self.actor, m.ring, m.capacity, img)
+                   if isinstance(env, VecEnv) and env.kind == ops.CARTPOLE else None)
+            ws = ops.dsac_update_workspace(cfg.batch_size, D, A, cfg.hidden_dim, self.device)
+            upd = ops.dsac_update_args(cfg.batch_size, D, A, self.actor, self.critic1, self.critic2, self.critic1_target,
+                                       self.critic2_target, self.actor_optim, self.critic1_optim, self.critic2_optim, m.ring,
+                                       (cfg.gamma, cfg.tau, cfg.target_entropy, cfg.lr_alpha), self.log_alpha, self._alpha_m,
+                                       self._alpha_v, self._sums, self._alpha_loss, ws, img)
+            self._fused = (act, upd, ws, env, img)
+            self._img_versions = None
+        # the weight images follow the parameters as long as only the fused update writes them; anything that went through
+        # torch (load_state_dict, a checkpoint: the parameters' version counters move) or around it (soft_update(), the
+        # layer-by-layer update, load_checkpoint(): they reset _img_versions) makes them stale: rebuild (one launch)
+        if self._fused[4] is not None:
+            ps = getattr(self, "_img_params", None)
+            if ps is None:
+                ps = self._img_params = tuple([f] + list(net.parameters()) for f, net in (
+                    (self.actor_flat, self.actor), (self.c1_flat, self.critic1), (self.c2_flat, self.critic2),
+                    (self.c1_target_flat, self.critic1_target), (self.c2_target_flat, self.critic2_target)))
+            v = tuple(sum([t._version for t in group]) for group in ps)
+            if v != self._img_versions:
+                ops.dsac_pack_images(self._fused[1])
+                self._img_versions = v
+        return self._fused
+
+    def _update_fused(self, indices=None, dev=None):
+        """update() as gymrl_dsac_update's four launches.  dev = (draw, adam_c1, adam_c2, adam_a, alpha) device records of a
+        StepChunk replay; None: this call's scalars travel as arguments and the host counters advance here."""
+        m = self.memory
+        upd = self._fused_args()[1]
+        if dev is not None:
+            ops.dsac_update(upd, idx_seed=m.seed, idx_dev=dev[0], idx_size=m.capacity, adam_critic1_dev=dev[1], adam_critic2_dev=dev[2],
+                            adam_actor_dev=dev[3], alpha_bias_dev=dev[4])
+            return
+        if indices is None:
+            counter, size = m.draws, m.size
+            m.draws += 1
+        else:
+            counter, size = 0, 0
+            if indices.dtype != torch.int32:
+                indices = indices.to(torch.int32)
+        self._alpha_steps += 1
+        ops.dsac_update(upd, idx=indices, idx_seed=m.seed, idx_counter=counter, idx_size=size,
+                        adam_critic1=self.critic1_optim.next_bias(), adam_critic2=self.critic2_optim.next_bias(),
+                        adam_actor=self.actor_optim.next_bias(), alpha_t=self._alpha_steps)
+
+    def _act_fused(self, lb, obs, nxt, ep_ret, done, cursor_dev=None, counter_dev=None):
+        """Acting + env step + replay row of one vector step: one launch (select_action + env.step + memory.push)."""
+        env, m = self.env, self.memory
+        noise = None if self._parity_noise is None else next(self._parity_noise)
+        if cursor_dev is None:
+            self._act_counter += 1
+        ops.dsac_act_step(self._fused_args()[0], env, obs, nxt, cursor=m.cursor, cursor_dev=cursor_dev, noise_exp=noise,
+                          seed=self.base_seed, counter=self._act_counter, counter_dev=counter_dev,
+                          rew_out=lb["rew"], done_out=done, ep_ret_out=ep_ret, ep_stats=env.ep_stats)
+        if cursor_dev is None:
+            m.advance(env.n)
+
+    def _loop_buffers(self, N, D):
+        """Step buffers that outlive one train() call: the captured StepChunk graph holds their addresses."""
+        lb = getattr(self, "_loop", None)
+        if lb is None or lb["N"] != N:
+            d = self.device
+            lb = self._loop = dict(N=N, obs=torch.empty(N, D, device=d), nxt=torch.empty(N, D, device=d), rew=torch.empty(N, device=d),
+                                   tracker=EpisodeTracker(N, d, flush_every=1 if N == 1 else self.CHUNK))
+        lb["tracker"].k, lb["tracker"].episodes = 0, 0
+        return lb
+
+    def _chunk_body(self, lb, j):
+        """Vector step j of a StepChunk capture: the act launch and the update's, every per-step scalar read from record j."""
+        ch, tr = self._chunk, lb["tracker"]
+        obs, nxt = (lb["obs"], lb["nxt"]) if j % 2 == 0 else (lb["nxt"], lb["obs"])
+        self._act_fused(lb, obs, nxt, tr.ret[j], tr.done[j], cursor_dev=ch.view(j, "push"), counter_dev=ch.view(j, "act"))
+        self._update_fused(dev=(ch.view(j, "draw"), ch.view(j, "adam_c1", torch.float32), ch.view(j, "adam_c2", torch.float32),
+                                ch.view(j, "adam_a", torch.float32), ch.view(j, "alpha", torch.float64)))
+
+    def _stage_chunk(self):
+        """The host's bookkeeping of the next CHUNK vector steps, in the eager loop's order, written into the records."""
+        ch, m, N = self._chunk, self.memory, self.env.n
+        b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))              # the kernel's float32 betas, as doubles
+        for j in range(ch.K):
+            ch.set(j, "push", m.cursor)
+            m.advance(N)
+            self._act_counter += 1
+            ch.set(j, "act", self._act_counter)
+            ch.set(j, "draw", m.draws, m.size)
+            m.draws += 1
+            self._alpha_steps += 1
+            ch.set(j, "alpha", 1.0 - b1 ** self._alpha_steps, 1.0 - b2 ** self._alpha_steps)
+            ch.set_bytes(j, "adam_c1", self.critic1_optim.next_bias())
+            ch.set_bytes(j, "adam_c2", self.critic2_optim.next_bias())
+            ch.set_bytes(j, "adam_a", self.actor_optim.next_bias())
+        ch.flush()
+
+    def _train_fused(self, max_vector_steps=None):
+        """_train on the fused step.  With hipGraphs on, CHUNK whole vector steps replay as one graph (graphs.StepChunk);
+        while the ring holds fewer rows than a batch — and for what a chunk cannot take — the loop is eager: the act launch,
+        then the update's, no host round trip (the loss sums stay on the device)."""
+        cfg, env, m = self.cfg, self.env, self.memory
+        N, D = env.n, env.obs_dim
+        lb = self._loop_buffers(N, D)
+        obs, nxt, tracker = lb["obs"], lb["nxt"], lb["tracker"]
+        env.reset(obs)
+        step = 0
+        pending = None            # drain_async() token of the last chunk, collected one chunk later
+        graphed = bool(getattr(cfg, "use_graphs", True)) and self._parity_indices is None
+        chunked = graphed and N > 1 and cfg.updates_per_step == 1 and self._parity_noise is None
+        limit = max_vector_steps or (cfg.max_episodes * cfg.max_steps // N + 1)
+        while tracker.episodes < cfg.max_episodes and step < limit:
+            if chunked and tracker.k == 0 and limit - step >= self.CHUNK and obs is lb["obs"] and len(m) >= cfg.batch_size:
+                if getattr(self, "_chunk", None) is None:
+                    from .graphs import StepChunk
+                    self._chunk = StepChunk(self.device, self.CHUNK, [("push", "q"), ("draw", "Qq"), ("adam_c1", "4f"), ("adam_c2", "4f"),
+                                                                      ("adam_a", "4f"), ("alpha", "2d"), ("act", "Q")])
+                self._fused_args()             # weight images rebuilt (if stale) BEFORE the capture, not inside it
+                self._stage_chunk()
+                self._chunk.run(lambda j: self._chunk_body(lb, j), key=(id(env), env.state.data_ptr()))
+                step += self.CHUNK
+                tracker.k = self.CHUNK
+                token = tracker.drain_async()      # the chunk's episode returns come back one chunk late: the host goes on staging
+                tracker.collect(pending, self.episode_rewards)
+                pending = token
+                if cfg.max_episodes - tracker.episodes <= N * self.CHUNK:      # within reach of the episode budget: no lag
+                    tracker.collect(pending, self.episode_rewards)
+                    pending = None
+                continue
+            tracker.collect(pending, self.episode_rewards)
+            pending = None
+            ep_ret, done = tracker.slot()
+            self._act_fused(lb, obs, nxt, ep_ret, done)
+            for _ in range(cfg.updates_per_step):
+                if len(m) >= cfg.batch_size:
+                    self._update_fused(None if self._parity_indices is None else next(self._parity_indices))
+            obs, nxt = nxt, obs
+            step += 1
+            tracker.advance(self.episode_rewards)
+        tracker.collect(pending, self.episode_rewards)
+        tracker.flush(self.episode_rewards)
+        self.env.close()
 
     def update(self, indices=None):
         """:148-227 -> (actor_loss, critic1_loss, critic2_loss, alpha_loss) python floats."""
@@ -131,6 +307,10 @@ class SACTrainer:
             return 0.0, 0.0, 0.0, 0.0
         if indices is None and self._parity_indices is not None:
             indices = next(self._parity_indices)
+        if self._fused_update_ok() and (indices is None or indices.numel() == cfg.batch_size):
+            self._update_fused(indices)
+            s = self._sums.tolist()
+            return s[2] / cfg.batch_size, s[0] / cfg.batch_size, s[1] / cfg.batch_size, float(self._alpha_loss.item())
         if indices is None:
             indices = self.memory.draw_indices(cfg.batch_size)
         B = self._update_body(indices)
@@ -141,6 +321,7 @@ class SACTrainer:
         """Everything after the index draw; biases = device views of the three Adams' step scalars (critic1, critic2,
         actor) and alpha_bias the temperature's, when the body runs inside / ahead of a hipGraph."""
         cfg = self.cfg
+        self._img_versions = None             # this path writes the parameters without the fused step's weight images
         bc1, bc2, ba = biases if biases is not None else (None, None, None)
         states, actions, rewards, next_states, dones = self.memory.gather(indices)
         B = states.shape[0]
@@ -177,13 +358,45 @@ class SACTrainer:
         cfg = self.cfg
         if len(self.memory) < cfg.batch_size:
             return
+        if self._fused_update_ok():        # four launches: nothing left for a graph to save
+            return self._update_fused()
         if self._graph is None:
             from .graphs import GraphedUpdate
             b1, b2 = float(np.float32(0.9)), float(np.float32(0.999))          # the kernel's float32 betas, as doubles
             self._graph = GraphedUpdate(self.device, cfg.batch_size, [self.critic1_optim, self.critic2_optim, self.actor_optim],
                                         lambda idx, biases, ab: self._update_body(idx, biases, ab),
                                         alpha=(self, "_alpha_steps", b1, b2))
+        self._img_versions = None             # (a replay runs no Python: _update_body's own reset is not enough)
         self._graph(self.memory, cfg.batch_size)
+
+    def save_checkpoint(self, path, include_memory=True):
+        """ModelLoader-style dict: five networks, the three optimisers in torch.optim.Adam's layout, the
+        float32 temperature with its Adam state, the host counters and — unlike the reference, which skips `memory` — the
+        replay ring."""
+        from .utils import checkpoint
+        extra = {"memory_state_dict": self.memory.state_dict()} if include_memory else {}
+        return checkpoint.save_agent(path, {k: getattr(self, k) for k in ("actor", "critic1", "critic2", "critic1_target", "critic2_target")},
+                                     {"actor_optim": (self.actor, self.actor_optim), "critic1_optim": (self.critic1, self.critic1_optim),
+                                      "critic2_optim": (self.critic2, self.critic2_optim)},
+                                     log_alpha=self.log_alpha.detach().cpu(), alpha_m=self._alpha_m.cpu(), alpha_v=self._alpha_v.cpu(),
+                                     alpha_steps=self._alpha_steps, _act_counter=self._act_counter,
+                                     episode_rewards=list(self.episode_rewards), **extra)
+
+    def load_checkpoint(self, path):
+        from .utils import checkpoint
+        rest = checkpoint.load_agent(path, {k: getattr(self, k) for k in ("actor", "critic1", "critic2", "critic1_target", "critic2_target")},
+                                     {"actor_optim": (self.actor, self.actor_optim), "critic1_optim": (self.critic1, self.critic1_optim),
+                                      "critic2_optim": (self.critic2, self.critic2_optim)})
+        self._img_versions = None             # the fused step's weight images are rebuilt from the loaded parameters
+        self.log_alpha.copy_(rest["log_alpha"].to(self.device))
+        self._alpha_m.copy_(rest["alpha_m"].to(self.device))
+        self._alpha_v.copy_(rest["alpha_v"].to(self.device))
+        self._alpha_steps, self._act_counter = int(rest["alpha_steps"]), int(rest["_act_counter"])
+        self.episode_rewards.clear()
+        self.episode_rewards.extend(rest.get("episode_rewards", []))
+        if "memory_state_dict" in rest:
+            self.memory.load_state_dict(rest["memory_state_dict"])
+        return rest
 
     def train(self, max_vector_steps=None):
         """The reference's train() loop (every Linear of the update and of acting is a gymrl_lin_* launch: gymrl_amd/nn.py)."""
@@ -192,6 +405,8 @@ class SACTrainer:
     def _train(self, max_vector_steps=None):
         """:229-262 with N lock-stepped envs."""
         cfg, env = self.cfg, self.env
+        if self._fused_ok():
+            return self._train_fused(max_vector_steps)
         N, D = env.n, env.obs_dim
         obs, nxt, tobs = (torch.empty(N, D, device=self.device) for _ in range(3))
         rew = torch.empty(N, device=self.device)

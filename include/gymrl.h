@@ -1392,6 +1392,79 @@ size_t gymrl_td3_args_bytes(int which);      /* sizeof(gymrl_td3_act_args) (0) /
 int gymrl_td3_act_step(const gymrl_td3_act_args* args, void* stream);
 int gymrl_td3_update(const gymrl_td3_update_args* args, void* stream);
 
+/*
+ * Discrete SAC's CartPole vector step on the same row-slab kernels (csrc/dsac_step.hip): sac_cartpole.py's select_action
+ * :127-138 with the env step and memory.push of its train loop, and update :148-227.  TD3's scheme (one workgroup carries a
+ * 16-row slab through a whole row phase, nothing waits for another workgroup) with three-layer networks that end in A
+ * columns, an expectation over the actions in place of a sampled one, two critics with separate flat buffers and optimisers,
+ * no actor target and a float32 temperature:
+ *   gymrl_dsac_act_step  ONE launch (:127-138 + env.step + memory.push): actor logits on the N observations (fc1, fc2 ReLU, fc3),
+ *                        gymrl_categorical_sample's draw under its keys (seed, counter, env_id0 + env; or the explicit
+ *                        noise_exp rows), CartPole step with auto-reset, replay row (obs, int32 action word, reward, TERMINAL
+ *                        next obs, done) at (cursor + env) % cap, the episode bookkeeping outputs
+ *   gymrl_dsac_update    update() (:148-227), four launches:
+ *     R1 rows   index draw (gymrl_uniform_indices' permutation, or idx) + ring gather; actor(s'), critic1_target(s'),
+ *               critic2_target(s') (:173, :177-178); the softmax of csrc/softmax_device.hpp; y by gymrl_dsac_target's expression
+ *               (:174-183); critic1(s), critic2(s) (:185-186); gymrl_dsac_critic_loss's gradient (:187-188); both critics'
+ *               input-gradient chains
+ *     T2 tiles  both critics' weight / bias gradient tiles (gymrl_lin_bwd_weight's order) + Adam (:190-196) + the Polyak
+ *               update of their targets (:219-220), each over its own flat buffer; the two critic loss sums
+ *     R3 rows   actor(s) + softmax; critic1(s), critic2(s) of the UPDATED critics, forward only (:198-203);
+ *               gymrl_dsac_actor_loss's two terms and dL/dprobs (:204-205); the softmax backward; the actor's chain
+ *     T4 tiles  actor weight gradients + Adam (:207-209); actor loss and entropy sums; gymrl_dsac_alpha_step's float32
+ *               temperature step on the finished entropy sum (:211-217)
+ * Results are the layer-by-layer path's bits when that path runs its softmax through gymrl_softmax_rows_fwd / _bwd
+ * (tests/test_dsac_fused_step_gpu.py).  Limits: H % 4 == 0, H <= 256, D <= 8, A <= 4, B <= 256 (-22 otherwise, before any
+ * launch: the trainer stays on the layer path); CartPole-v1 (D = 4, A = 2) for the act step.
+ */
+typedef struct {
+  int N, D, A, H;
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE */
+  void* env_state; uint64_t env_seed; int64_t env_id0;
+  const float* obs; float* obs_out;        /* f32[N, D] in / next observations out (post-reset where an episode ended) */
+  const float* noise_exp;                  /* f32[N, A] Exp(1) draws, or NULL: gymrl_categorical_sample's Philox keys */
+  uint64_t seed, counter; const uint64_t* counter_dev;     /* select_action's (base seed, _act_counter) */
+  gymrl_td3_actor_params actor;            /* fc1, fc2, fc3: the logits */
+  float* r_state; uint32_t* r_action; float* r_reward; float* r_next; uint8_t* r_flag; int64_t cap, cursor;
+  const int64_t* cursor_dev;
+  int32_t* action_out; float* rew_out; uint8_t* done_out; float* ep_ret_out; double* ep_stats;     /* any may be NULL */
+  const float* images;                     /* gymrl_dsac_update_args.images of the same trainer, or NULL (reads actor.fc2 in place) */
+} gymrl_dsac_act_args;
+typedef struct {
+  int B, D, A, H;
+  float gamma, target_entropy;
+  double tau;
+  const float* r_state; const uint32_t* r_action; const float* r_reward; const float* r_next; const uint8_t* r_flag;
+  const int32_t* idx;                      /* i32[B] explicit rows, or NULL: the keyed permutation of gymrl_uniform_indices */
+  uint64_t idx_seed, idx_counter; int64_t idx_size; const void* idx_dev;     /* idx_dev: {uint64 counter; int64 size} */
+  gymrl_td3_actor_params actor, critic1, critic2, critic1_target, critic2_target;     /* fc1, fc2, fc3 each */
+  /* flat parameter buffers and their Adam moments, one set per optimiser */
+  float* actor_p; float* actor_m; float* actor_v; float* critic1_p; float* critic1_m; float* critic1_v;
+  float* critic2_p; float* critic2_m; float* critic2_v;
+  float adam_critic1[4], adam_critic2[4], adam_actor[4];     /* gymrl_adam_bias' blocks */
+  const float* adam_critic1_dev; const float* adam_critic2_dev; const float* adam_actor_dev;
+  double beta1, beta2, eps_adam;           /* the critics' optimisers' (the actor's are the same defaults) */
+  float* log_alpha; float* alpha_m; float* alpha_v;        /* the float32 temperature and its Adam moments */
+  double lr_alpha, alpha_beta1, alpha_beta2, alpha_eps;    /* gymrl_dsac_alpha_step's arguments (rounded to float32 there) */
+  int64_t alpha_t; const double* alpha_bias_dev;           /* its step count, or {1 - b1^t, 1 - b2^t} from the device */
+  double* sums;                            /* f64[4] out: critic1, critic2 loss sums; actor loss sum, entropy sum */
+  double* alpha_loss;                      /* f64[1] out or NULL */
+  void* workspace;                         /* >= gymrl_dsac_update_workspace_bytes(B, D, A, H) */
+  /* Weight images of the H x H layers (H % 16 == 0), f32[8][H*H], or NULL: forward actor.fc2, critic1.fc2, critic2.fc2,
+   * critic1_target.fc2, critic2_target.fc2; input gradient actor.fc2, critic1.fc2, critic2.fc2.  gymrl_dsac_update keeps them
+   * equal to the parameters it writes; gymrl_dsac_pack_images rebuilds them after anything else did. */
+  float* images;
+} gymrl_dsac_update_args;
+size_t gymrl_dsac_update_workspace_bytes(int B, int D, int A, int H);
+int gymrl_dsac_pack_images(const gymrl_dsac_update_args* args, void* stream);
+size_t gymrl_dsac_args_bytes(int which);     /* sizeof(gymrl_dsac_act_args) (0) / sizeof(gymrl_dsac_update_args) (1) */
+int gymrl_dsac_act_step(const gymrl_dsac_act_args* args, void* stream);
+int gymrl_dsac_update(const gymrl_dsac_update_args* args, void* stream);
+/* The softmax of csrc/softmax_device.hpp over the rows of z f32[B, A] (A <= 8) and its backward dz = p (g - sum g p): what
+ * ops.softmax_rows runs in place of F.softmax (sac_cartpole.py:70-80) under Config.kernel_softmax. */
+int gymrl_softmax_rows_fwd(const float* z, int B, int A, float* p_out, void* stream);
+int gymrl_softmax_rows_bwd(const float* p, const float* g, int B, int A, float* dz_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
