@@ -21,13 +21,17 @@ using namespace gymrl;
 using namespace gymrl::slab;
 
 constexpr int kDsacMaxBatch = 256;     // (ops.DSAC_FUSED_MAX_BATCH) one grid of at most 16 slabs per row phase
-struct DsacImages {                    // gymrl_dsac_update_args.images, f32[8][H*H]; all null without images or H % 16 != 0
+struct DsacImages {                    // gymrl_dsac_update_args.images, f32[8][H*H]: five forward images, then three input-gradient images
   const float *af, *cf[2], *tf[2], *ab, *cb[2];
   __host__ __device__ DsacImages(const float* base, int H) {
-    const bool on = base && (H & 15) == 0;
-    const size_t n = (size_t)H * H;
-    auto at = [&](int k) { return on ? base + k * n : nullptr; };
+    const ImageSlots at(base, H);
     af = at(0); cf[0] = at(1); cf[1] = at(2); tf[0] = at(3); tf[1] = at(4); ab = at(5); cb[0] = at(6); cb[1] = at(7);
+  }
+  // the same slots as the layers they are packed from
+  static constexpr int kCount = 8;
+  static PackTable sources(const gymrl_dsac_update_args& a) {
+    return PackTable{{a.actor.w[1], a.critic1.w[1], a.critic2.w[1], a.critic1_target.w[1], a.critic2_target.w[1],
+                      a.actor.w[1], a.critic1.w[1], a.critic2.w[1], nullptr}, 5};
   }
 };
 
@@ -295,14 +299,6 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float* __re
   if (b < B) softmax_row_bwd(p + (size_t)b * A, g + (size_t)b * A, A, dz + (size_t)b * A);
 }
 
-inline bool dsac_shape_ok(int B, int D, int A, int H) {
-  return B > 0 && B <= kDsacMaxBatch && D > 0 && D <= kMaxD && A > 0 && A <= kMaxA && H >= 4 && H <= 256 && (H & 3) == 0;
-}
-inline bool net_ok(const gymrl_td3_actor_params& n) {
-  for (int k = 0; k < 3; ++k) if (!n.w[k] || !n.b[k]) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -311,22 +307,15 @@ size_t gymrl_dsac_update_workspace_bytes(int B, int D, int A, int H) { return wo
 size_t gymrl_dsac_args_bytes(int which) { return which == 0 ? sizeof(gymrl_dsac_act_args) : which == 1 ? sizeof(gymrl_dsac_update_args) : 0; }
 
 static int dsac_set_lds_attr() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)dsac_r1_kernel<0>, (const void*)dsac_r1_kernel<256>, (const void*)dsac_r3_kernel<0>, (const void*)dsac_r3_kernel<256>,
-                                    (const void*)dsac_act_kernel<0>, (const void*)dsac_act_kernel<256>}, (int)lds_bytes(256, 6)))
-      return rc;
-    attr_set = true;
-  }
-  return 0;
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)dsac_r1_kernel<0>, (const void*)dsac_r1_kernel<256>, (const void*)dsac_r3_kernel<0>, (const void*)dsac_r3_kernel<256>,
+                                 (const void*)dsac_act_kernel<0>, (const void*)dsac_act_kernel<256>}, (int)lds_bytes(256, 6));
 }
 
 int gymrl_dsac_act_step(const gymrl_dsac_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_dsac_act_args& a = *args;
-  if (a.N <= 0 || !dsac_shape_ok(1, a.D, a.A, a.H) || a.env_kind != GYMRL_ENV_CARTPOLE || a.D != 4 || a.A != 2) return -22;
-  if (!a.env_state || !a.obs || !a.obs_out || !a.r_state || !a.r_action || !a.r_reward || !a.r_next || !a.r_flag || a.cap < a.N || a.cursor < 0) return -22;
-  if (!net_ok(a.actor)) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
   if (const int rc = dsac_set_lds_attr()) return rc;
   hipLaunchKernelGGL(a.H == 256 ? dsac_act_kernel<256> : dsac_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
   GYMRL_CHECK_LAUNCH();
@@ -334,10 +323,10 @@ int gymrl_dsac_act_step(const gymrl_dsac_act_args* args, void* stream_) {
 }
 
 static bool dsac_update_args_ok(const gymrl_dsac_update_args& a) {
-  if (!dsac_shape_ok(a.B, a.D, a.A, a.H)) return false;
-  if (!a.r_state || !a.r_action || !a.r_reward || !a.r_next || !a.r_flag || !a.workspace || !a.sums || !a.actor_p || !a.actor_m || !a.actor_v ||
-      !a.critic1_p || !a.critic1_m || !a.critic1_v || !a.critic2_p || !a.critic2_m || !a.critic2_v || !a.log_alpha || !a.alpha_m || !a.alpha_v ||
-      (!a.idx && !a.idx_dev && a.idx_size < a.B) || (!a.alpha_bias_dev && a.alpha_t <= 0))
+  if (!slab_shape_ok(a.B, kDsacMaxBatch, a.D, a.A, a.H)) return false;
+  if (!ring_ok(a) || !all_set({a.workspace, a.sums, a.actor_p, a.actor_m, a.actor_v, a.critic1_p, a.critic1_m, a.critic1_v, a.critic2_p, a.critic2_m,
+                               a.critic2_v, a.log_alpha, a.alpha_m, a.alpha_v}) ||
+      !draw_ok(a, /*idx_dev_counts=*/true) || (!a.alpha_bias_dev && a.alpha_t <= 0))
     return false;
   return net_ok(a.actor) && net_ok(a.critic1) && net_ok(a.critic2) && net_ok(a.critic1_target) && net_ok(a.critic2_target);
 }
@@ -345,11 +334,8 @@ static bool dsac_update_args_ok(const gymrl_dsac_update_args& a) {
 int gymrl_dsac_pack_images(const gymrl_dsac_update_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_dsac_update_args& a = *args;
-  if (!a.images || a.H <= 0 || (a.H & 15) != 0 || a.H > 256) return -22;
-  if (!a.actor.w[1] || !a.critic1.w[1] || !a.critic2.w[1] || !a.critic1_target.w[1] || !a.critic2_target.w[1]) return -22;
-  const PackTable tb{{a.actor.w[1], a.critic1.w[1], a.critic2.w[1], a.critic1_target.w[1], a.critic2_target.w[1],
-                      a.actor.w[1], a.critic1.w[1], a.critic2.w[1], nullptr}, 5};
-  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, 8), dim3(256), 0, (hipStream_t)stream_, tb, a.images, a.H);
+  if (!pack_args_ok(a) || !all_set({a.actor.w[1], a.critic1.w[1], a.critic2.w[1], a.critic1_target.w[1], a.critic2_target.w[1]})) return -22;
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, DsacImages::kCount), dim3(256), 0, (hipStream_t)stream_, DsacImages::sources(a), a.images, a.H);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
@@ -363,16 +349,8 @@ int gymrl_dsac_update(const gymrl_dsac_update_args* args, void* stream_) {
   DsacWs ws;
   DsacWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
   const int B = a.B, D = a.D, A = a.A, H = a.H, slabs = (B + 15) / 16;
-  const bool use_img = a.images && (H & 15) == 0;
-  const size_t hh = (size_t)H * H;
-  auto img = [&](int k) { return use_img ? a.images + k * hh : nullptr; };
-  auto finish = [&](DwBuilder& bd, float* p, float* m, float* v, const float (&adam)[4], const float* adam_dev, int term0, int nterms, double* sums) {
-    bd.finish(nullptr);                     // (at most 256 rows: no slice partials)
-    bd.optimiser(p, m, v, adam, adam_dev, a.beta1, a.beta2, a.eps_adam);
-    DwArgs& d = bd.d;
-    d.tau = (float)a.tau; d.omt = (float)(1.0 - a.tau);
-    d.terms = ws.terms; d.terms_b = nullptr; d.term0 = term0; d.nterms = nterms; d.sums = sums; d.alpha_step = 0;
-  };
+  const DsacImages im(a.images, H);
+  const float tau = (float)a.tau, omt = (float)(1.0 - a.tau);
   // the tile lists of T2 (critic1, critic2) and T4 (actor)
   Dw2 c{};
   const gymrl_td3_actor_params* cn[2] = {&a.critic1, &a.critic2};
@@ -380,20 +358,21 @@ int gymrl_dsac_update(const gymrl_dsac_update_args* args, void* stream_) {
   for (int i = 0; i < 2; ++i) {
     DwBuilder cb{c.d[i], B};
     cb.seg(ws.Z1[i], H, H, ws.s, D, nullptr, 0, D, D, cn[i]->w[0], cn[i]->b[0], tn[i]->w[0], tn[i]->b[0]);
-    cb.seg(ws.Z2[i], H, H, ws.H1[i], H, nullptr, 0, H, H, cn[i]->w[1], cn[i]->b[1], tn[i]->w[1], tn[i]->b[1], img(1 + i), img(6 + i), img(3 + i));
+    cb.seg(ws.Z2[i], H, H, ws.H1[i], H, nullptr, 0, H, H, cn[i]->w[1], cn[i]->b[1], tn[i]->w[1], tn[i]->b[1], im.cf[i], im.cb[i], im.tf[i]);
     cb.seg(ws.dq[i], A, A, ws.H2[i], H, nullptr, 0, H, H, cn[i]->w[2], cn[i]->b[2], tn[i]->w[2], tn[i]->b[2]);
-    if (i == 0) finish(cb, a.critic1_p, a.critic1_m, a.critic1_v, a.adam_critic1, a.adam_critic1_dev, 0, 1, a.sums);
-    else finish(cb, a.critic2_p, a.critic2_m, a.critic2_v, a.adam_critic2, a.adam_critic2_dev, 1, 1, a.sums);
+    // (at most 256 rows: no slice partials)
+    if (i == 0) cb.close(a, nullptr, a.critic1_p, a.critic1_m, a.critic1_v, a.adam_critic1, a.adam_critic1_dev, tau, omt, ws.terms, nullptr, 0, 1, a.sums);
+    else cb.close(a, nullptr, a.critic2_p, a.critic2_m, a.critic2_v, a.adam_critic2, a.adam_critic2_dev, tau, omt, ws.terms, nullptr, 1, 1, a.sums);
   }
   const int nb0 = (c.d[0].total_waves + 3) / 4 + 1, nb1 = (c.d[1].total_waves + 3) / 4 + 1;
   c.na = nb0;
   DwArgs p{};
   DwBuilder pb{p, B};
   pb.seg(ws.aZ1, H, H, ws.s, D, nullptr, 0, D, D, a.actor.w[0], a.actor.b[0]);
-  pb.seg(ws.aZ2, H, H, ws.aH1, H, nullptr, 0, H, H, a.actor.w[1], a.actor.b[1], nullptr, nullptr, img(0), img(5), nullptr);
+  pb.seg(ws.aZ2, H, H, ws.aH1, H, nullptr, 0, H, H, a.actor.w[1], a.actor.b[1], nullptr, nullptr, im.af, im.ab);
   pb.seg(ws.dlogit, A, A, ws.aH2, H, nullptr, 0, H, H, a.actor.w[2], a.actor.b[2]);
   // (R3's terms sit in columns 1, 2 and go to sums[2], sums[3]: the body writes sums[term0 + k])
-  finish(pb, a.actor_p, a.actor_m, a.actor_v, a.adam_actor, a.adam_actor_dev, 1, 2, a.sums + 1);
+  pb.close(a, nullptr, a.actor_p, a.actor_m, a.actor_v, a.adam_actor, a.adam_actor_dev, tau, omt, ws.terms, nullptr, 1, 2, a.sums + 1);
   p.alpha_step = 2;                         // slab_step_device.hpp: dsac_alpha_kernel's float32 step in the block that closes the sums
   p.log_alpha_f = a.log_alpha; p.alpha_m_f = a.alpha_m; p.alpha_v_f = a.alpha_v; p.target_entropy_f = a.target_entropy;
   p.lr_alpha = a.lr_alpha; p.abeta1 = a.alpha_beta1; p.abeta2 = a.alpha_beta2; p.aeps = a.alpha_eps;

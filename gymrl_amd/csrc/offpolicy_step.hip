@@ -53,14 +53,16 @@ __device__ __forceinline__ void sample_row(const float* mean, const float* log_s
   logp = lp;
 }
 
-// The eight weight images of gymrl_sac_update_args.images (f32[8][H*H]); all null when the caller passed none or H % 16 != 0
-struct Images {
+struct Images {                        // gymrl_sac_update_args.images, f32[8][H*H]: five forward images, then three input-gradient images
   const float *af, *c1f, *c2f, *t1f, *t2f, *ab, *c1b, *c2b;
   __host__ __device__ Images(const float* base, int H) {
-    const bool on = base && (H & 15) == 0;
-    const size_t n = (size_t)H * H;
-    af = on ? base : nullptr; c1f = on ? base + n : nullptr; c2f = on ? base + 2 * n : nullptr; t1f = on ? base + 3 * n : nullptr;
-    t2f = on ? base + 4 * n : nullptr; ab = on ? base + 5 * n : nullptr; c1b = on ? base + 6 * n : nullptr; c2b = on ? base + 7 * n : nullptr;
+    const ImageSlots at(base, H);
+    af = at(0); c1f = at(1); c2f = at(2); t1f = at(3); t2f = at(4); ab = at(5); c1b = at(6); c2b = at(7);
+  }
+  // the same slots as the layers they are packed from
+  static constexpr int kCount = 8;
+  static PackTable sources(const gymrl_sac_update_args& a) {
+    return PackTable{{a.actor.w[1], a.critic.w[1], a.critic.w[4], a.target.w[1], a.target.w[4], a.actor.w[1], a.critic.w[1], a.critic.w[4]}, 5};
   }
 };
 
@@ -485,10 +487,6 @@ __global__ __launch_bounds__(kThreads) void sac_act_kernel(const gymrl_sac_act_a
   sac_act_body<HC>(a, lds, blockIdx.x);
 }
 
-inline bool sac_shape_ok(int B, int D, int A, int H) {
-  return B > 0 && B <= kMaxBatch && D > 0 && D <= kMaxD && A > 0 && A <= kMaxA && H >= 4 && H <= 256 && (H & 3) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -503,22 +501,12 @@ int gymrl_step_prof_read(long long* out_host) {      // probe build only: [4][32
 
 size_t gymrl_sac_args_bytes(int which) { return which == 0 ? sizeof(gymrl_sac_act_args) : which == 1 ? sizeof(gymrl_sac_update_args) : 0; }
 
-static bool sac_act_args_ok(const gymrl_sac_act_args& a) {
-  if (a.N <= 0 || !sac_shape_ok(1, a.D, a.A, a.H) || a.env_kind != GYMRL_ENV_PENDULUM || a.D != 3 || a.A != 1) return false;
-  if (!a.env_state || !a.obs || !a.obs_out || !a.r_state || !a.r_action || !a.r_reward || !a.r_next || !a.r_flag || a.cap < a.N) return false;
-  for (int k = 0; k < 4; ++k) if (!a.actor.w[k] || !a.actor.b[k]) return false;
-  return true;
-}
-
 int gymrl_sac_act_step(const gymrl_sac_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_sac_act_args& a = *args;
-  if (!sac_act_args_ok(a)) return -22;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)sac_act_kernel<0>, (const void*)sac_act_kernel<256>}, (int)lds_bytes(256, 4))) return rc;
-    attr_set = true;
-  }
+  if (!act_args_ok(a, GYMRL_ENV_PENDULUM, 3, 1, /*refuse_neg_cursor=*/false) || !net_ok(a.actor)) return -22;
+  static bool done = false;
+  if (const int rc = set_max_lds_once(done, {(const void*)sac_act_kernel<0>, (const void*)sac_act_kernel<256>}, (int)lds_bytes(256, 4))) return rc;
   hipLaunchKernelGGL(a.H == 256 ? sac_act_kernel<256> : sac_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 4), (hipStream_t)stream_, a);
   GYMRL_CHECK_LAUNCH();
   return 0;
@@ -527,65 +515,50 @@ int gymrl_sac_act_step(const gymrl_sac_act_args* args, void* stream_) {
 int gymrl_sac_pack_images(const gymrl_sac_update_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_sac_update_args& a = *args;
-  if (!a.images || a.H <= 0 || (a.H & 15) != 0 || a.H > 256) return -22;
-  if (!a.actor.w[1] || !a.critic.w[1] || !a.critic.w[4] || !a.target.w[1] || !a.target.w[4]) return -22;
-  const PackTable tb{{a.actor.w[1], a.critic.w[1], a.critic.w[4], a.target.w[1], a.target.w[4], a.actor.w[1], a.critic.w[1], a.critic.w[4]}, 5};
-  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, 8), dim3(256), 0, (hipStream_t)stream_, tb, a.images, a.H);
+  if (!pack_args_ok(a) || !all_set({a.actor.w[1], a.critic.w[1], a.critic.w[4], a.target.w[1], a.target.w[4]})) return -22;
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, Images::kCount), dim3(256), 0, (hipStream_t)stream_, Images::sources(a), a.images, a.H);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
 
 static bool sac_update_args_ok(const gymrl_sac_update_args& a) {
-  if (!sac_shape_ok(a.B, a.D, a.A, a.H)) return false;
-  if (!a.r_state || !a.r_action || !a.r_reward || !a.r_next || !a.r_flag || !a.workspace || !a.sums || !a.log_alpha || !a.alpha_m || !a.alpha_v ||
-      !a.actor_p || !a.actor_m || !a.actor_v || !a.critic_p || !a.critic_m || !a.critic_v || (!a.idx && a.idx_size < a.B))
+  if (!slab_shape_ok(a.B, kMaxBatch, a.D, a.A, a.H)) return false;
+  if (!ring_ok(a) || !all_set({a.workspace, a.sums, a.log_alpha, a.alpha_m, a.alpha_v, a.actor_p, a.actor_m, a.actor_v, a.critic_p, a.critic_m, a.critic_v}) ||
+      !draw_ok(a, /*idx_dev_counts=*/false))      // (this check has never counted the device's draw record)
     return false;
-  for (int k = 0; k < 4; ++k) if (!a.actor.w[k] || !a.actor.b[k]) return false;
-  for (int k = 0; k < 6; ++k) if (!a.critic.w[k] || !a.critic.b[k] || !a.target.w[k] || !a.target.b[k]) return false;
-  return true;
+  return net_ok(a.actor) && net_ok(a.critic) && net_ok(a.target);
 }
 
 static int sac_set_lds_attr() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)sac_p1_kernel<0>, (const void*)sac_p1_kernel<256>, (const void*)sac_p3_kernel<0>, (const void*)sac_p3_kernel<256>},
-                                   (int)lds_bytes(256, 8)))
-      return rc;
-    attr_set = true;
-  }
-  return 0;
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)sac_p1_kernel<0>, (const void*)sac_p1_kernel<256>, (const void*)sac_p3_kernel<0>, (const void*)sac_p3_kernel<256>},
+                          (int)lds_bytes(256, 8));
 }
 
 // The tile lists of P2 (critic: c) and P4 (actor + temperature: p)
 static void sac_build_dw(const gymrl_sac_update_args& a, const SacWs& ws, DwArgs& c, DwArgs& p) {
   const int B = a.B, D = a.D, A = a.A, H = a.H;
-  const bool use_img = a.images && (a.H & 15) == 0;
-  const size_t hh = (size_t)a.H * a.H;
-  auto img = [&](int k) { return use_img ? a.images + k * hh : nullptr; };
+  const Images im(a.images, H);
+  const float *cf[2] = {im.c1f, im.c2f}, *cbk[2] = {im.c1b, im.c2b}, *tf[2] = {im.t1f, im.t2f};      // network i's images
   // critic: launch order of the layer-by-layer backward is irrelevant here (tiles are independent); fc1/fc4, fc2/fc5, fc3/fc6
   c = DwArgs{};
   DwBuilder cb{c, B};
   for (int i = 0; i < 2; ++i) {
     cb.seg(ws.Z1[i], H, H, ws.s, D, ws.a, A, D + A, D, a.critic.w[3 * i], a.critic.b[3 * i], a.target.w[3 * i], a.target.b[3 * i]);
     cb.seg(ws.Z2[i], H, H, ws.H1[i], H, nullptr, 0, H, H, a.critic.w[3 * i + 1], a.critic.b[3 * i + 1], a.target.w[3 * i + 1], a.target.b[3 * i + 1],
-        img(1 + i), img(6 + i), img(3 + i));
+        cf[i], cbk[i], tf[i]);
     cb.seg(ws.dq[i], 1, 1, ws.H2[i], H, nullptr, 0, H, H, a.critic.w[3 * i + 2], a.critic.b[3 * i + 2], a.target.w[3 * i + 2], a.target.b[3 * i + 2]);
   }
-  cb.finish(ws.dw_parts);
-  cb.optimiser(a.critic_p, a.critic_m, a.critic_v, a.adam_critic, a.adam_critic_dev, a.beta1, a.beta2, a.eps_adam);
-  c.tau = (float)a.tau; c.omt = (float)(1.0 - a.tau);
-  c.terms = ws.terms; c.terms_b = ws.terms2; c.term0 = 0; c.nterms = 1; c.sums = a.sums; c.alpha_step = 0;
+  cb.close(a, ws.dw_parts, a.critic_p, a.critic_m, a.critic_v, a.adam_critic, a.adam_critic_dev, (float)a.tau, (float)(1.0 - a.tau), ws.terms, ws.terms2, 0, 1, a.sums);
 
   p = DwArgs{};
   DwBuilder pb{p, B};
   pb.seg(ws.aZ1, H, H, ws.s, D, nullptr, 0, D, D, a.actor.w[0], a.actor.b[0]);
-  pb.seg(ws.aZ2, H, H, ws.aH1, H, nullptr, 0, H, H, a.actor.w[1], a.actor.b[1], nullptr, nullptr, img(0), img(5));
+  pb.seg(ws.aZ2, H, H, ws.aH1, H, nullptr, 0, H, H, a.actor.w[1], a.actor.b[1], nullptr, nullptr, im.af, im.ab);
   pb.seg(ws.dmean, A, A, ws.aH2, H, nullptr, 0, H, H, a.actor.w[2], a.actor.b[2]);
   pb.seg(ws.dls, A, A, ws.aH2, H, nullptr, 0, H, H, a.actor.w[3], a.actor.b[3]);
-  pb.finish(ws.dw_parts);
-  pb.optimiser(a.actor_p, a.actor_m, a.actor_v, a.adam_actor, a.adam_actor_dev, a.beta1, a.beta2, a.eps_adam);
-  p.tau = 0.0f; p.omt = 0.0f;
-  p.terms = ws.terms; p.term0 = 1; p.nterms = 2; p.sums = a.sums; p.alpha_step = 1;
+  pb.close(a, ws.dw_parts, a.actor_p, a.actor_m, a.actor_v, a.adam_actor, a.adam_actor_dev, 0.0f, 0.0f, ws.terms, nullptr, 1, 2, a.sums);
+  p.alpha_step = 1;
   p.log_alpha = a.log_alpha; p.alpha_m = a.alpha_m; p.alpha_v = a.alpha_v; p.lr_alpha = a.lr_alpha;
   p.abeta1 = 0.9; p.abeta2 = 0.999; p.aeps = 1e-8;
   p.alpha_bias[0] = a.alpha_bias[0]; p.alpha_bias[1] = a.alpha_bias[1]; p.alpha_bias_dev = a.alpha_bias_dev; p.alpha_loss = a.alpha_loss;

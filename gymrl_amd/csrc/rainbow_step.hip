@@ -285,12 +285,9 @@ int gymrl_rainbow_act_step(const gymrl_rainbow_act_args* args, void* stream_) {
     return -22;
   if (a.fc2_img && (a.H & 15) != 0) return -22;
   auto act_lds = [](int H, int ns) { return sizeof(float) * (size_t)(16 * ns * (kMaxD + 4 + 2 * lin::slab_ld(H))); };
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)rainbow_act_kernel<1, 0>, (const void*)rainbow_act_kernel<1, 256>}, (int)act_lds(256, 1))) return rc;
-    if (const int rc = set_max_lds({(const void*)rainbow_act_kernel<2, 0>, (const void*)rainbow_act_kernel<2, 256>}, (int)act_lds(256, 2))) return rc;
-    attr_set = true;
-  }
+  static bool done1 = false, done2 = false;
+  if (const int rc = set_max_lds_once(done1, {(const void*)rainbow_act_kernel<1, 0>, (const void*)rainbow_act_kernel<1, 256>}, (int)act_lds(256, 1))) return rc;
+  if (const int rc = set_max_lds_once(done2, {(const void*)rainbow_act_kernel<2, 0>, (const void*)rainbow_act_kernel<2, 256>}, (int)act_lds(256, 2))) return rc;
   using ActK = void (*)(const gymrl_rainbow_act_args);
   const ActK k1 = rainbow_act_kernel<1, 0>, k2 = rainbow_act_kernel<2, 0>, k1w = rainbow_act_kernel<1, 256>, k2w = rainbow_act_kernel<2, 256>;
   const bool wide = a.H == 256;      // the instances built for the reference's hidden width
@@ -313,11 +310,8 @@ int gymrl_rainbow_update(const gymrl_rainbow_update_args* args, int phase, void*
     return -22;
   if ((a.p_fc2_img_f || a.p_fc2_img_b || a.t_fc2_img_f) && (a.H & 15) != 0) return -22;
   hipStream_t stream = (hipStream_t)stream_;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)rainbow_rows_kernel<0>, (const void*)rainbow_rows_kernel<256>}, (int)lds_bytes(256, 7))) return rc;
-    attr_set = true;
-  }
+  static bool done = false;
+  if (const int rc = set_max_lds_once(done, {(const void*)rainbow_rows_kernel<0>, (const void*)rainbow_rows_kernel<256>}, (int)lds_bytes(256, 7))) return rc;
   RbWs ws;
   RbWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
   const int B = a.B, D = a.D, A1 = a.A + 1, H = a.H;

@@ -5,8 +5,8 @@
 // bwd_stage over FwdItem / BwdItem), the LDS layout (Lds), the narrow layers' staging (Stager), the hand-off flags,
 // the grid shapes and their deadlock argument (slab_grid), SAC's and TD3's hand-off workspace (SacWs), the
 // weight-gradient tile kernel (DwArgs / sac_dw_body / sac_dw_kernel) with its host-side list builder (DwBuilder), and the
-// blocks that the algorithms had each carried a copy of: the replay index draw, the Pendulum / CartPole acting tails, the weight-image
-// packing and the small host helpers.  Everything is __forceinline__ device code or inline host code inside an anonymous
+// blocks that the algorithms had each carried a copy of: the replay index draw, the Pendulum / CartPole
+// acting tails, the weight-image slots and their packing, the entry points' argument checks and the small host helpers.  Everything is __forceinline__ device code or inline host code inside an anonymous
 // namespace: every translation unit that includes this header has its own file-local kernels and the library exports none of it.
 #pragma once
 #include <initializer_list>
@@ -41,12 +41,50 @@ inline size_t workspace_bytes(int B, int D, int A, int H) {
   if (B <= 0 || D <= 0 || A <= 0 || H <= 0) return 0;
   return Ws::carve(nullptr, nullptr, B, D, A, H) + 256;
 }
-// the dynamic-LDS ceiling of a unit's kernels (the caller keeps a once-only flag); 0 or the C ABI's -1000 - hipError
-inline int set_max_lds(std::initializer_list<const void*> kernels, int bytes) {
+// the dynamic-LDS ceiling of a unit's kernels, set by the first call that gets here (`done`: the call site's own static flag);
+// 0 or the C ABI's -1000 - hipError
+inline int set_max_lds_once(bool& done, std::initializer_list<const void*> kernels, int bytes) {
+  if (done) return 0;
   for (const void* f : kernels)
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1000 - (int)hipGetLastError();
+  done = true;
   return 0;
 }
+
+// ---- what an entry point refuses with -22 before anything touches HIP: where the algorithms' checks differ, the call site says so ----
+inline bool slab_shape_ok(int B, int max_batch, int D, int A, int H) {
+  return B > 0 && B <= max_batch && D > 0 && D <= kMaxD && A > 0 && A <= kMaxA && H >= 4 && H <= 256 && (H & 3) == 0;
+}
+inline bool all_set(std::initializer_list<const void*> ps) {
+  for (const void* p : ps) if (!p) return false;
+  return true;
+}
+// the first `layers` layers of a gymrl_*_params struct (all of them by default; DDPG's single critic fills three of six)
+template <class Net>
+inline bool net_ok(const Net& n, int layers = (int)(sizeof(Net::w) / sizeof(void*))) {
+  for (int k = 0; k < layers; ++k) if (!n.w[k] || !n.b[k]) return false;
+  return true;
+}
+template <class Args>
+inline bool ring_ok(const Args& a) { return all_set({a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag}); }
+// an act step's env, I/O and ring: the env kind with its fixed D and A; refuse_neg_cursor: SAC's act step has never looked at the cursor
+template <class Args>
+inline bool act_args_ok(const Args& a, int env_kind, int D, int A, bool refuse_neg_cursor) {
+  return a.N > 0 && slab_shape_ok(1, 1, a.D, a.A, a.H) && a.env_kind == env_kind && a.D == D && a.A == A &&
+         all_set({a.env_state, a.obs, a.obs_out}) && ring_ok(a) && a.cap >= a.N && !(refuse_neg_cursor && a.cursor < 0);
+}
+// an update's replay rows: the caller's list, (where idx_dev_counts) the device's draw record, or a keyed draw over idx_size >= B rows
+template <class Args>
+inline bool draw_ok(const Args& a, bool idx_dev_counts) { return a.idx || (idx_dev_counts && a.idx_dev) || a.idx_size >= a.B; }
+// a pack call's images buffer and width
+template <class Args>
+inline bool pack_args_ok(const Args& a) { return a.images && a.H > 0 && (a.H & 15) == 0 && a.H <= 256; }
+// the k-th H x H weight image of an update's or an act step's `images`; all null without a buffer or when H % 16 != 0
+struct ImageSlots {
+  const float* base; bool on; size_t n;
+  __host__ __device__ ImageSlots(const float* images, int H) : base(images), on(images && (H & 15) == 0), n((size_t)H * H) {}
+  __host__ __device__ const float* operator()(int k) const { return on ? base + k * n : nullptr; }
+};
 
 // ---- hand-off between the row phases and the tile phases (caller-owned workspace) -------------------------------------
 struct SacWs {
@@ -669,16 +707,17 @@ __global__ __launch_bounds__(256) void pack_images_kernel(const PackTable tb, fl
 }
 
 // The tile list of one sac_dw_kernel launch, segment by segment: seg() appends a layer's weight gradient (wave0 / tile0 run on
-// over the segments, slices by lin_device.hpp's cut of the batch), finish() closes the list, optimiser() sets Adam's fields.
-// What else a launch needs (tau, terms, the temperature step, Rainbow's split heads) the caller sets on `d` itself.
+// over the segments, slices by lin_device.hpp's cut of the batch; the images arrive as the kernels' read-only slots and are
+// written here), finish() closes the list, optimiser() sets Adam's fields, close() is both + the target twins' tau and the
+// loss terms.  What else a launch needs (the temperature step, Rainbow's split heads) the caller sets on `d` itself.
 struct DwBuilder {
   DwArgs& d; int B;
   int w0 = 0, ns = 0, t0 = 0;
   void seg(const float* dZ, int ldz, int N, const float* X, int ldx, const float* X2, int ldx2, int K, int K1, float* W, float* b,
-           float* Wt = nullptr, float* bt = nullptr, float* img_f = nullptr, float* img_b = nullptr, float* img_tf = nullptr) {
+           float* Wt = nullptr, float* bt = nullptr, const float* img_f = nullptr, const float* img_b = nullptr, const float* img_tf = nullptr) {
     DwSeg& s = d.seg[ns++];
     s.dZ = dZ; s.X = X; s.X2 = X2; s.W = W; s.b = b; s.Wt = Wt; s.bt = bt;
-    s.img_f = img_f; s.img_b = img_b; s.img_tf = img_tf;
+    s.img_f = const_cast<float*>(img_f); s.img_b = const_cast<float*>(img_b); s.img_tf = const_cast<float*>(img_tf);
     s.ldz = ldz; s.ldx = ldx; s.ldx2 = ldx2; s.N = N; s.K = K; s.K1 = K1; s.wave0 = w0;
     const int tl = ((N + 15) / 16) * ((K + 15) / 16);
     s.slices = lin::bwd_weight_slices(B, N, K); s.tile0 = t0;
@@ -690,6 +729,15 @@ struct DwBuilder {
     for (int k = 0; k < 4; ++k) d.adam[k] = adam[k];
     d.adam_dev = adam_dev;
     d.omb1 = (float)(1.0 - beta1); d.beta2 = (float)beta2; d.omb2 = (float)(1.0 - beta2); d.eps = (float)eps;
+  }
+  // Args: an update's argument struct (beta1, beta2, eps_adam); terms [term0, term0 + nterms) of `terms` (+ terms_b on term 0) -> sums
+  template <class Args>
+  void close(const Args& a, float* parts, float* p, float* m, float* v, const float (&adam)[4], const float* adam_dev, float tau, float omt,
+             const double* terms, const double* terms_b, int term0, int nterms, double* sums) {
+    finish(parts);
+    optimiser(p, m, v, adam, adam_dev, a.beta1, a.beta2, a.eps_adam);
+    d.tau = tau; d.omt = omt;
+    d.terms = terms; d.terms_b = terms_b; d.term0 = term0; d.nterms = nterms; d.sums = sums; d.alpha_step = 0;
   }
 };
 

@@ -21,13 +21,17 @@ using namespace gymrl;
 using namespace gymrl::slab;
 
 constexpr int kTd3MaxBatch = 256;      // (ops.TD3_FUSED_MAX_BATCH) one grid of at most 16 slabs per row phase
-struct Td3Images {                     // gymrl_td3_update_args.images, f32[9][H*H]; all null without images or H % 16 != 0
+struct Td3Images {                     // gymrl_td3_update_args.images, f32[9][H*H]: six forward images, then three input-gradient images
   const float *af, *cf[2], *tf[2], *atf, *ab, *cb[2];
   __host__ __device__ Td3Images(const float* base, int H) {
-    const bool on = base && (H & 15) == 0;
-    const size_t n = (size_t)H * H;
-    auto at = [&](int k) { return on ? base + k * n : nullptr; };
+    const ImageSlots at(base, H);
     af = at(0); cf[0] = at(1); cf[1] = at(2); tf[0] = at(3); tf[1] = at(4); atf = at(5); ab = at(6); cb[0] = at(7); cb[1] = at(8);
+  }
+  // the same slots as the layers they are packed from (DDPG: the second network's stay null and are left alone)
+  static constexpr int kCount = 9;
+  static PackTable sources(const gymrl_td3_update_args& a) {
+    return PackTable{{a.actor.w[1], a.critic.w[1], a.critic.w[4], a.critic_target.w[1], a.critic_target.w[4], a.actor_target.w[1],
+                      a.actor.w[1], a.critic.w[1], a.critic.w[4]}, 6};
   }
 };
 __device__ __forceinline__ int td3_delayed(const gymrl_td3_update_args& a) { return a.delayed_dev ? a.delayed_dev[0] : a.delayed; }
@@ -273,10 +277,6 @@ __global__ __launch_bounds__(kThreads) void td3_act_kernel(const gymrl_td3_act_a
   }
 }
 
-inline bool td3_shape_ok(int B, int D, int A, int H) {
-  return B > 0 && B <= kTd3MaxBatch && D > 0 && D <= kMaxD && A > 0 && A <= kMaxA && H >= 4 && H <= 256 && (H & 3) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -286,22 +286,15 @@ size_t gymrl_td3_update_workspace_bytes(int B, int D, int A, int H) { return wor
 size_t gymrl_td3_args_bytes(int which) { return which == 0 ? sizeof(gymrl_td3_act_args) : which == 1 ? sizeof(gymrl_td3_update_args) : 0; }
 
 static int td3_set_lds_attr() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (const int rc = set_max_lds({(const void*)td3_r1_kernel<0>, (const void*)td3_r1_kernel<256>, (const void*)td3_r3_kernel<0>, (const void*)td3_r3_kernel<256>,
-                                    (const void*)td3_act_kernel<0>, (const void*)td3_act_kernel<256>}, (int)lds_bytes(256, 8)))
-      return rc;
-    attr_set = true;
-  }
-  return 0;
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)td3_r1_kernel<0>, (const void*)td3_r1_kernel<256>, (const void*)td3_r3_kernel<0>, (const void*)td3_r3_kernel<256>,
+                                 (const void*)td3_act_kernel<0>, (const void*)td3_act_kernel<256>}, (int)lds_bytes(256, 8));
 }
 
 int gymrl_td3_act_step(const gymrl_td3_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_td3_act_args& a = *args;
-  if (a.N <= 0 || !td3_shape_ok(1, a.D, a.A, a.H) || a.env_kind != GYMRL_ENV_PENDULUM || a.D != 3 || a.A != 1) return -22;
-  if (!a.env_state || !a.obs || !a.obs_out || !a.r_state || !a.r_action || !a.r_reward || !a.r_next || !a.r_flag || a.cap < a.N || a.cursor < 0) return -22;
-  for (int k = 0; k < 3; ++k) if (!a.actor.w[k] || !a.actor.b[k]) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_PENDULUM, 3, 1, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
   if (const int rc = td3_set_lds_attr()) return rc;
   hipLaunchKernelGGL(a.H == 256 ? td3_act_kernel<256> : td3_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
   GYMRL_CHECK_LAUNCH();
@@ -309,23 +302,19 @@ int gymrl_td3_act_step(const gymrl_td3_act_args* args, void* stream_) {
 }
 
 static bool td3_update_args_ok(const gymrl_td3_update_args& a) {
-  if (!td3_shape_ok(a.B, a.D, a.A, a.H) || (a.n_critics != 1 && a.n_critics != 2)) return false;
-  if (!a.r_state || !a.r_action || !a.r_reward || !a.r_next || !a.r_flag || !a.workspace || !a.sums || !a.actor_p || !a.actor_m || !a.actor_v ||
-      !a.critic_p || !a.critic_m || !a.critic_v || (!a.idx && !a.idx_dev && a.idx_size < a.B))
+  if (!slab_shape_ok(a.B, kTd3MaxBatch, a.D, a.A, a.H) || (a.n_critics != 1 && a.n_critics != 2)) return false;
+  if (!ring_ok(a) || !all_set({a.workspace, a.sums, a.actor_p, a.actor_m, a.actor_v, a.critic_p, a.critic_m, a.critic_v}) ||
+      !draw_ok(a, /*idx_dev_counts=*/true))
     return false;
-  for (int k = 0; k < 3; ++k) if (!a.actor.w[k] || !a.actor.b[k] || !a.actor_target.w[k] || !a.actor_target.b[k]) return false;
-  for (int k = 0; k < 3 * a.n_critics; ++k) if (!a.critic.w[k] || !a.critic.b[k] || !a.critic_target.w[k] || !a.critic_target.b[k]) return false;
-  return true;
+  return net_ok(a.actor) && net_ok(a.actor_target) && net_ok(a.critic, 3 * a.n_critics) && net_ok(a.critic_target, 3 * a.n_critics);
 }
 
 int gymrl_td3_pack_images(const gymrl_td3_update_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_td3_update_args& a = *args;
-  if (!a.images || a.H <= 0 || (a.H & 15) != 0 || a.H > 256 || (a.n_critics != 1 && a.n_critics != 2)) return -22;
+  if (!pack_args_ok(a) || (a.n_critics != 1 && a.n_critics != 2)) return -22;
   if (!a.actor.w[1] || !a.actor_target.w[1] || !a.critic.w[1] || !a.critic_target.w[1] || (a.n_critics == 2 && (!a.critic.w[4] || !a.critic_target.w[4]))) return -22;
-  const PackTable tb{{a.actor.w[1], a.critic.w[1], a.critic.w[4], a.critic_target.w[1], a.critic_target.w[4], a.actor_target.w[1],
-                      a.actor.w[1], a.critic.w[1], a.critic.w[4]}, 6};
-  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, 9), dim3(256), 0, (hipStream_t)stream_, tb, a.images, a.H);
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, Td3Images::kCount), dim3(256), 0, (hipStream_t)stream_, Td3Images::sources(a), a.images, a.H);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
@@ -340,29 +329,21 @@ int gymrl_td3_update(const gymrl_td3_update_args* args, void* stream_) {
   SacWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
   const int B = a.B, D = a.D, A = a.A, H = a.H, slabs = (B + 15) / 16;
   // the tile lists of T2 (critic: c) and T4 (actor: p), as sac_build_dw's
-  const bool use_img = a.images && (H & 15) == 0;
-  const size_t hh = (size_t)H * H;
-  auto img = [&](int k) { return use_img ? a.images + k * hh : nullptr; };
-  auto finish = [&](DwBuilder& bd, float* p, float* m, float* v, const float (&adam)[4], const float* adam_dev, int term0, const double* terms_b) {
-    bd.finish(ws.dw_parts);
-    bd.optimiser(p, m, v, adam, adam_dev, a.beta1, a.beta2, a.eps_adam);
-    DwArgs& d = bd.d;
-    d.tau = (float)a.tau; d.omt = (float)(1.0 - a.tau);
-    d.terms = ws.terms; d.terms_b = terms_b; d.term0 = term0; d.nterms = 1; d.sums = a.sums; d.alpha_step = 0;
-  };
+  const Td3Images im(a.images, H);
+  const float tau = (float)a.tau, omt = (float)(1.0 - a.tau);
   DwArgs c{}, p{};
   DwBuilder cb{c, B}, pb{p, B};
   for (int i = 0; i < a.n_critics; ++i) {
     cb.seg(ws.Z1[i], H, H, ws.s, D, ws.a, A, D + A, D, a.critic.w[3 * i], a.critic.b[3 * i], a.critic_target.w[3 * i], a.critic_target.b[3 * i]);
     cb.seg(ws.Z2[i], H, H, ws.H1[i], H, nullptr, 0, H, H, a.critic.w[3 * i + 1], a.critic.b[3 * i + 1], a.critic_target.w[3 * i + 1], a.critic_target.b[3 * i + 1],
-        img(1 + i), img(7 + i), img(3 + i));
+        im.cf[i], im.cb[i], im.tf[i]);
     cb.seg(ws.dq[i], 1, 1, ws.H2[i], H, nullptr, 0, H, H, a.critic.w[3 * i + 2], a.critic.b[3 * i + 2], a.critic_target.w[3 * i + 2], a.critic_target.b[3 * i + 2]);
   }
-  finish(cb, a.critic_p, a.critic_m, a.critic_v, a.adam_critic, a.adam_critic_dev, 0, a.n_critics == 2 ? ws.terms2 : nullptr);
+  cb.close(a, ws.dw_parts, a.critic_p, a.critic_m, a.critic_v, a.adam_critic, a.adam_critic_dev, tau, omt, ws.terms, a.n_critics == 2 ? ws.terms2 : nullptr, 0, 1, a.sums);
   pb.seg(ws.aZ1, H, H, ws.s, D, nullptr, 0, D, D, a.actor.w[0], a.actor.b[0], a.actor_target.w[0], a.actor_target.b[0]);
-  pb.seg(ws.aZ2, H, H, ws.aH1, H, nullptr, 0, H, H, a.actor.w[1], a.actor.b[1], a.actor_target.w[1], a.actor_target.b[1], img(0), img(6), img(5));
+  pb.seg(ws.aZ2, H, H, ws.aH1, H, nullptr, 0, H, H, a.actor.w[1], a.actor.b[1], a.actor_target.w[1], a.actor_target.b[1], im.af, im.ab, im.atf);
   pb.seg(ws.dmean, A, A, ws.aH2, H, nullptr, 0, H, H, a.actor.w[2], a.actor.b[2], a.actor_target.w[2], a.actor_target.b[2]);
-  finish(pb, a.actor_p, a.actor_m, a.actor_v, a.adam_actor, a.adam_actor_dev, 1, nullptr);
+  pb.close(a, ws.dw_parts, a.actor_p, a.actor_m, a.actor_v, a.adam_actor, a.adam_actor_dev, tau, omt, ws.terms, nullptr, 1, 1, a.sums);
   const bool wide = H == 256;            // the instances built for the reference's hidden width
   hipLaunchKernelGGL(wide ? td3_r1_kernel<256> : td3_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, 8), stream, a, ws);
   hipLaunchKernelGGL(td3_dw_kernel, dim3((c.total_waves + 3) / 4 + 1), dim3(256), 0, stream, c, a.delayed_dev, a.delayed, 0);

@@ -75,7 +75,7 @@ class DDPGTrainer(_ActorCriticBase):
         """Everything after the index draw; biases = device views of the (critic, actor) Adams' step scalars when the
         body runs inside / ahead of a hipGraph."""
         cfg = self.cfg
-        self._img_versions = None             # this path writes the parameters without the fused step's weight images
+        self._images_stale()                  # this path writes the parameters without the fused step's weight images
         bc, ba = biases if biases is not None else (None, None)
         states, actions, rewards, next_states, dones = self.memory.gather(indices)
         B = states.shape[0]

@@ -39,6 +39,32 @@ def flatten_module(module, device, order=None):
     return flat, grad
 
 
+class WeightImages:
+    """Mixin of the trainers with a fused vector step: when the step's weight images (`_fused[4]`) are rebuilt.
+
+    The images follow the parameters as long as only the fused update writes them.  Anything that went through torch
+    (load_state_dict, a checkpoint, a hard target copy) moves a version counter — and flatten_module above binds every
+    parameter as a VIEW tensor of its own, so load_state_dict / a checkpoint bump the PARAMETERS' counters, not the flat
+    buffers': both are summed, per network.  Writers that go around torch altogether (a raw-pointer soft_update(), the
+    layer-by-layer update, load_checkpoint()) move no counter and call _images_stale() themselves."""
+    _fused = None            # (act args, update args, workspace, env, weight images) of the fused step, built on first use
+    _img_params = None       # per network: its flat buffer and its parameter views
+    _img_versions = None     # per network: the version sum the images were last rebuilt from; None: stale
+
+    def _images_stale(self):
+        self._img_versions = None
+
+    def _refresh_images(self, groups, pack, upd):
+        """groups: the (flat buffer, module) pairs the images are built from; pack(upd) rebuilds them (one launch) when a
+        version sum has moved since the last rebuild."""
+        if self._img_params is None:
+            self._img_params = tuple([f] + list(net.parameters()) for f, net in groups)
+        v = tuple(sum([t._version for t in group]) for group in self._img_params)
+        if v != self._img_versions:
+            pack(upd)
+            self._img_versions = v
+
+
 class GradSink:
     """Lets autograd hand back FRESH gradient tensors and lands them in the flat buffer with one multi-tensor
     copy.  With `p.grad` pre-set to a view of the flat buffer, autograd accumulates (`grad += new`, one launch

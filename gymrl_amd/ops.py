@@ -1467,15 +1467,64 @@ def _addr(t):
 FUSED_MAX_BATCH = 8192     # row-slab kernels: B <= 256 as resident 2-D grids, above that slab-adjacent 1-D grids (slab_step_device.hpp slab_grid)
 
 
+# What the four row-slab steps' bindings below share (slab_step_device.hpp slab_shape_ok is the library's side of the first)
+def _fused_shape_ok(B, D, A, H, max_batch, max_A):
+    return 0 < B <= max_batch and 0 < D <= 8 and 0 < A <= max_A and 4 <= H <= 256 and H % 4 == 0
+
+
+def _zeroed_workspace(nbytes, device):
+    return torch.zeros(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def _set_ring(a, ring):
+    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+
+
+def _set_optimisers(a, betas_from, **opts):
+    """a.<name>_p / _m / _v: each FusedAdam's flat parameter buffer and its moments; betas and eps as `betas_from` has them."""
+    for name, opt in opts.items():
+        for f in "pmv":
+            setattr(a, f"{name}_{f}", _addr(getattr(opt, f)))
+    g = betas_from.param_groups[0]
+    a.beta1, a.beta2, a.eps_adam = g["betas"][0], g["betas"][1], g["eps"]
+
+
+def _set_adam_bias(a, **blocks):
+    """adam_bias() blocks (16 bytes each) into a's float[4] fields of those names; None leaves a field as it is."""
+    for name, blk in blocks.items():
+        if blk is not None:
+            getattr(a, name)[:] = (C.c_float * 4).from_buffer_copy(blk)[:]
+
+
+def _set_draw(a, idx, idx_seed, idx_counter, idx_size, idx_dev):
+    a.idx, a.idx_seed, a.idx_counter, a.idx_size, a.idx_dev = _addr(idx), idx_seed, idx_counter, idx_size, _addr(idx_dev)
+
+
+def _set_act_env(a, env, actor, ring, cap, images):
+    """An act step's fixed fields: the env, the shapes, the replay ring and the actor's fc2 image."""
+    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, actor.fc1.weight.shape[0]
+    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    _set_ring(a, ring)
+    a.cap, a.images = cap, _addr(images)
+
+
+def _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, outs):
+    """An act step's per-call fields; outs = (action_out, rew_out, done_out, ep_ret_out, ep_stats), each a tensor or None."""
+    a.env_seed = env.seed                              # reset(seed=...) may have moved it
+    a.obs, a.obs_out = _ptr(obs, torch.float32).value, _ptr(obs_out, torch.float32).value
+    a.cursor, a.cursor_dev = cursor, _addr(cursor_dev)
+    a.action_out, a.rew_out, a.done_out, a.ep_ret_out, a.ep_stats = (_addr(t) for t in outs)
+
+
 def sac_fused_shape_ok(B, D, A, H):
     """Shapes gymrl_sac_act_step / gymrl_sac_update take (include/gymrl.h): everything else runs layer by layer."""
-    return 0 < B <= FUSED_MAX_BATCH and 0 < D <= 8 and 0 < A <= 4 and 4 <= H <= 256 and H % 4 == 0
+    return _fused_shape_ok(B, D, A, H, FUSED_MAX_BATCH, 4)
 
 
 def sac_update_workspace(B, D, A, H, device):
     # zeroed: the hand-off flags between the row phases' workgroups and the large-batch grids' tickets live in it (zero before
     # the first launch, left zero)
-    return torch.zeros(int(lib().gymrl_sac_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
+    return _zeroed_workspace(lib().gymrl_sac_update_workspace_bytes(B, D, A, H), device)
 
 
 def _sac_actor_params(dst, actor):
@@ -1492,13 +1541,9 @@ def sac_act_args(env, actor, ring, cap, bound, log_std_min, log_std_max, images=
     """A gymrl_sac_act_args with everything that does not change from step to step filled in (env, actor parameters —
     views of a flat buffer the optimiser updates in place — and the replay ring)."""
     a = SacActArgs()
-    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, actor.fc1.weight.shape[0]
-    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    _set_act_env(a, env, actor, ring, cap, images)
     a.bound, a.log_std_min, a.log_std_max = float(bound), float(log_std_min), float(log_std_max)
     _sac_actor_params(a.actor, actor)
-    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
-    a.cap = cap
-    a.images = _addr(images)
     return a
 
 
@@ -1506,11 +1551,9 @@ def sac_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, eps=None, nois
                  action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None):
     """gymrl_sac_act_step: Actor forward on obs [N, D], reparameterised draw, env step with auto-reset, replay rows at
     (cursor + env) % cap — ONE launch (sac_pendulum.py:278-283)."""
-    a.env_seed = env.seed                              # reset(seed=...) may have moved it
-    a.obs, a.obs_out, a.eps = _ptr(obs, torch.float32).value, _ptr(obs_out, torch.float32).value, _addr(eps)
+    _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, (action_out, rew_out, done_out, ep_ret_out, ep_stats))
+    a.eps = _addr(eps)
     a.noise_seed, a.noise_counter, a.noise_counter_dev = noise_seed, noise_counter, _addr(noise_counter_dev)
-    a.cursor, a.cursor_dev = cursor, _addr(cursor_dev)
-    a.action_out, a.rew_out, a.done_out, a.ep_ret_out, a.ep_stats = (_addr(t) for t in (action_out, rew_out, done_out, ep_ret_out, ep_stats))
     check(lib().gymrl_sac_act_step(C.byref(a), _stream()), "gymrl_sac_act_step")
 
 
@@ -1532,14 +1575,11 @@ def sac_update_args(B, D, A, actor, critic, target, actor_opt, critic_opt, ring,
     a.B, a.D, a.A, a.H = B, D, A, actor.fc1.weight.shape[0]
     gamma, tau, bound, lo, hi, tent, lr_alpha = cfg_scalars
     a.gamma, a.tau, a.bound, a.log_std_min, a.log_std_max, a.target_entropy = float(gamma), float(tau), float(bound), float(lo), float(hi), float(tent)
-    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    _set_ring(a, ring)
     _sac_actor_params(a.actor, actor)
     _sac_critic_params(a.critic, critic)
     _sac_critic_params(a.target, target)
-    a.actor_p, a.actor_m, a.actor_v = _addr(actor_opt.p), _addr(actor_opt.m), _addr(actor_opt.v)
-    a.critic_p, a.critic_m, a.critic_v = _addr(critic_opt.p), _addr(critic_opt.m), _addr(critic_opt.v)
-    g = critic_opt.param_groups[0]
-    a.beta1, a.beta2, a.eps_adam = g["betas"][0], g["betas"][1], g["eps"]
+    _set_optimisers(a, critic_opt, actor=actor_opt, critic=critic_opt)
     a.log_alpha, a.alpha_m, a.alpha_v, a.lr_alpha = _addr(log_alpha), _addr(alpha_m), _addr(alpha_v), float(lr_alpha)
     a.sums, a.alpha_loss, a.workspace = _addr(sums), _addr(alpha_loss), _addr(workspace)
     a.images = _addr(images)
@@ -1551,14 +1591,10 @@ def sac_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None,
                alpha_bias=(1.0, 1.0), alpha_bias_dev=None):
     """gymrl_sac_update: SACTrainer.update() (sac_pendulum.py:213-267) as four launches.  adam_critic / adam_actor: the
     16-byte blocks of adam_bias() (host) or device views of them; alpha_bias = (1 - 0.9^t, 1 - 0.999^t)."""
-    a.idx, a.idx_seed, a.idx_counter, a.idx_size, a.idx_dev = _addr(idx), idx_seed, idx_counter, idx_size, _addr(idx_dev)
+    _set_draw(a, idx, idx_seed, idx_counter, idx_size, idx_dev)
     a.eps_next, a.eps_cur = _addr(eps_next), _addr(eps_cur)
     a.noise_seed, a.noise_counter, a.noise_counter_dev = noise_seed, noise_counter, _addr(noise_counter_dev)
-    for dst, blk in ((a.adam_critic, adam_critic), (a.adam_actor, adam_actor)):
-        if blk is not None:
-            vals = (C.c_float * 4).from_buffer_copy(blk)
-            for k in range(4):
-                dst[k] = vals[k]
+    _set_adam_bias(a, adam_critic=adam_critic, adam_actor=adam_actor)
     a.adam_critic_dev, a.adam_actor_dev = _addr(adam_critic_dev), _addr(adam_actor_dev)
     a.alpha_bias[0], a.alpha_bias[1], a.alpha_bias_dev = alpha_bias[0], alpha_bias[1], _addr(alpha_bias_dev)
     check(lib().gymrl_sac_update(C.byref(a), _stream()), "gymrl_sac_update")
@@ -1570,11 +1606,11 @@ TD3_FUSED_MAX_BATCH = 256      # one grid of at most 16 slabs per row phase (td3
 
 def td3_fused_shape_ok(B, D, A, H):
     """Shapes gymrl_td3_act_step / gymrl_td3_update take (include/gymrl.h): everything else runs layer by layer."""
-    return 0 < B <= TD3_FUSED_MAX_BATCH and 0 < D <= 8 and 0 < A <= 4 and 4 <= H <= 256 and H % 4 == 0
+    return _fused_shape_ok(B, D, A, H, TD3_FUSED_MAX_BATCH, 4)
 
 
 def td3_update_workspace(B, D, A, H, device):
-    return torch.zeros(int(lib().gymrl_td3_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
+    return _zeroed_workspace(lib().gymrl_td3_update_workspace_bytes(B, D, A, H), device)
 
 
 def _td3_actor_params(dst, actor):
@@ -1606,13 +1642,9 @@ def td3_act_args(env, actor, ring, cap, bound, noise_std, images=None):
     if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (env.act_dim,):
         raise ValueError(f"td3_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
     a = Td3ActArgs()
-    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, actor.fc1.weight.shape[0]
-    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    _set_act_env(a, env, actor, ring, cap, images)
     a.bound, a.noise_std = float(bound), float(noise_std)
     _td3_actor_params(a.actor, actor)
-    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
-    a.cap = cap
-    a.images = _addr(images)
     return a
 
 
@@ -1624,12 +1656,9 @@ def td3_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, eps=None, nois
         raise ValueError(f"td3_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
     if eps is not None and (eps.dtype != torch.float64 or eps.numel() != a.N * a.A):
         raise ValueError("td3_act_step: eps must be float64 [N, A]")
-    a.env_seed = env.seed                              # reset(seed=...) may have moved it
-    a.obs, a.obs_out = _ptr(obs, torch.float32).value, _ptr(obs_out, torch.float32).value
+    _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, (action_out, rew_out, done_out, ep_ret_out, ep_stats))
     a.eps = None if eps is None else _ptr(eps, torch.float64).value
     a.noise_seed, a.noise_counter, a.noise_counter_dev = noise_seed, noise_counter, _addr(noise_counter_dev)
-    a.cursor, a.cursor_dev = cursor, _addr(cursor_dev)
-    a.action_out, a.rew_out, a.done_out, a.ep_ret_out, a.ep_stats = (_addr(t) for t in (action_out, rew_out, done_out, ep_ret_out, ep_stats))
     check(lib().gymrl_td3_act_step(C.byref(a), _stream()), "gymrl_td3_act_step")
 
 
@@ -1645,15 +1674,12 @@ def td3_update_args(B, D, A, n_critics, actor, actor_target, critic, critic_targ
     a.B, a.D, a.A, a.H, a.n_critics = B, D, A, actor.fc1.weight.shape[0], n_critics
     gamma, tau, bound, policy_noise, noise_clip = cfg_scalars
     a.gamma, a.tau, a.bound, a.policy_noise, a.noise_clip = float(gamma), float(tau), float(bound), float(policy_noise), float(noise_clip)
-    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    _set_ring(a, ring)
     _td3_actor_params(a.actor, actor)
     _td3_actor_params(a.actor_target, actor_target)
     _td3_critic_params(a.critic, critic)
     _td3_critic_params(a.critic_target, critic_target)
-    a.actor_p, a.actor_m, a.actor_v = _addr(actor_opt.p), _addr(actor_opt.m), _addr(actor_opt.v)
-    a.critic_p, a.critic_m, a.critic_v = _addr(critic_opt.p), _addr(critic_opt.m), _addr(critic_opt.v)
-    g = critic_opt.param_groups[0]
-    a.beta1, a.beta2, a.eps_adam = g["betas"][0], g["betas"][1], g["eps"]
+    _set_optimisers(a, critic_opt, actor=actor_opt, critic=critic_opt)
     a.sums, a.workspace, a.images = _addr(sums), _addr(workspace), _addr(images)
     return a
 
@@ -1668,15 +1694,11 @@ def td3_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None,
         raise ValueError(f"td3_update: idx must be int32 [{a.B}]")
     if eps is not None and (eps.dtype != torch.float64 or eps.numel() != a.B * a.A):
         raise ValueError(f"td3_update: eps must be float64 [{a.B}, {a.A}]")
-    a.idx, a.idx_seed, a.idx_counter, a.idx_size, a.idx_dev = _addr(idx), idx_seed, idx_counter, idx_size, _addr(idx_dev)
+    _set_draw(a, idx, idx_seed, idx_counter, idx_size, idx_dev)
     a.eps = _addr(eps)
     a.noise_seed, a.noise_counter, a.noise_counter_dev = noise_seed, noise_counter, _addr(noise_counter_dev)
     a.delayed, a.delayed_dev = int(bool(delayed)), _addr(delayed_dev)
-    for dst, blk in ((a.adam_critic, adam_critic), (a.adam_actor, adam_actor)):
-        if blk is not None:
-            vals = (C.c_float * 4).from_buffer_copy(blk)
-            for k in range(4):
-                dst[k] = vals[k]
+    _set_adam_bias(a, adam_critic=adam_critic, adam_actor=adam_actor)
     a.adam_critic_dev, a.adam_actor_dev = _addr(adam_critic_dev), _addr(adam_actor_dev)
     check(lib().gymrl_td3_update(C.byref(a), _stream()), "gymrl_td3_update")
 
@@ -1687,7 +1709,7 @@ DSAC_FUSED_MAX_BATCH = 256     # one grid of at most 16 slabs per row phase (dsa
 
 def dsac_fused_shape_ok(B, D, A, H):
     """Shapes gymrl_dsac_act_step / gymrl_dsac_update take (include/gymrl.h): everything else runs layer by layer."""
-    return 0 < B <= DSAC_FUSED_MAX_BATCH and 0 < D <= 8 and 0 < A <= 4 and 4 <= H <= 256 and H % 4 == 0
+    return _fused_shape_ok(B, D, A, H, DSAC_FUSED_MAX_BATCH, 4)
 
 
 class _SoftmaxRows(torch.autograd.Function):
@@ -1719,7 +1741,7 @@ def softmax_rows(z):
 
 
 def dsac_update_workspace(B, D, A, H, device):
-    return torch.zeros(int(lib().gymrl_dsac_update_workspace_bytes(B, D, A, H)), dtype=torch.uint8, device=device)
+    return _zeroed_workspace(lib().gymrl_dsac_update_workspace_bytes(B, D, A, H), device)
 
 
 def dsac_images(H, device):
@@ -1737,12 +1759,8 @@ def dsac_act_args(env, actor, ring, cap, images=None):
     if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
         raise ValueError(f"dsac_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
     a = DsacActArgs()
-    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, actor.fc1.weight.shape[0]
-    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    _set_act_env(a, env, actor, ring, cap, images)
     _td3_actor_params(a.actor, actor)
-    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
-    a.cap = cap
-    a.images = _addr(images)
     return a
 
 
@@ -1757,12 +1775,9 @@ def dsac_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, noise_exp=Non
         raise ValueError("dsac_act_step: noise_exp must be float32 [N, A]")
     if action_out is not None and (action_out.dtype != torch.int32 or action_out.numel() != a.N):
         raise ValueError("dsac_act_step: action_out must be int32 [N]")
-    a.env_seed = env.seed                              # reset(seed=...) may have moved it
-    a.obs, a.obs_out = _ptr(obs, torch.float32).value, _ptr(obs_out, torch.float32).value
+    _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, (action_out, rew_out, done_out, ep_ret_out, ep_stats))
     a.noise_exp = _addr(noise_exp)
     a.seed, a.counter, a.counter_dev = seed, counter, _addr(counter_dev)
-    a.cursor, a.cursor_dev = cursor, _addr(cursor_dev)
-    a.action_out, a.rew_out, a.done_out, a.ep_ret_out, a.ep_stats = (_addr(t) for t in (action_out, rew_out, done_out, ep_ret_out, ep_stats))
     check(lib().gymrl_dsac_act_step(C.byref(a), _stream()), "gymrl_dsac_act_step")
 
 
@@ -1778,15 +1793,11 @@ def dsac_update_args(B, D, A, actor, critic1, critic2, critic1_target, critic2_t
     a.B, a.D, a.A, a.H = B, D, A, actor.fc1.weight.shape[0]
     gamma, tau, tent, lr_alpha = cfg_scalars
     a.gamma, a.tau, a.target_entropy = float(gamma), float(tau), float(tent)
-    a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag = (_addr(t) for t in ring)
+    _set_ring(a, ring)
     for dst, net in ((a.actor, actor), (a.critic1, critic1), (a.critic2, critic2), (a.critic1_target, critic1_target),
                      (a.critic2_target, critic2_target)):
         _td3_actor_params(dst, net)
-    a.actor_p, a.actor_m, a.actor_v = _addr(actor_opt.p), _addr(actor_opt.m), _addr(actor_opt.v)
-    a.critic1_p, a.critic1_m, a.critic1_v = _addr(critic1_opt.p), _addr(critic1_opt.m), _addr(critic1_opt.v)
-    a.critic2_p, a.critic2_m, a.critic2_v = _addr(critic2_opt.p), _addr(critic2_opt.m), _addr(critic2_opt.v)
-    g = critic1_opt.param_groups[0]
-    a.beta1, a.beta2, a.eps_adam = g["betas"][0], g["betas"][1], g["eps"]
+    _set_optimisers(a, critic1_opt, actor=actor_opt, critic1=critic1_opt, critic2=critic2_opt)
     a.log_alpha, a.alpha_m, a.alpha_v = (_ptr(t, torch.float32).value for t in (log_alpha, alpha_m, alpha_v))
     a.lr_alpha, a.alpha_beta1, a.alpha_beta2, a.alpha_eps = float(lr_alpha), 0.9, 0.999, 1e-8      # dsac_alpha_step's defaults
     a.sums, a.alpha_loss, a.workspace, a.images = _addr(sums), _addr(alpha_loss), _addr(workspace), _addr(images)
@@ -1800,12 +1811,8 @@ def dsac_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None
     alpha_bias_dev = f64[2] {1 - b1^t, 1 - b2^t} on the device."""
     if idx is not None and (idx.dtype != torch.int32 or idx.numel() != a.B):
         raise ValueError(f"dsac_update: idx must be int32 [{a.B}]")
-    a.idx, a.idx_seed, a.idx_counter, a.idx_size, a.idx_dev = _addr(idx), idx_seed, idx_counter, idx_size, _addr(idx_dev)
-    for dst, blk in ((a.adam_critic1, adam_critic1), (a.adam_critic2, adam_critic2), (a.adam_actor, adam_actor)):
-        if blk is not None:
-            vals = (C.c_float * 4).from_buffer_copy(blk)
-            for k in range(4):
-                dst[k] = vals[k]
+    _set_draw(a, idx, idx_seed, idx_counter, idx_size, idx_dev)
+    _set_adam_bias(a, adam_critic1=adam_critic1, adam_critic2=adam_critic2, adam_actor=adam_actor)
     a.adam_critic1_dev, a.adam_critic2_dev, a.adam_actor_dev = _addr(adam_critic1_dev), _addr(adam_critic2_dev), _addr(adam_actor_dev)
     a.alpha_t, a.alpha_bias_dev = int(alpha_t), _addr(alpha_bias_dev)
     check(lib().gymrl_dsac_update(C.byref(a), _stream()), "gymrl_dsac_update")
@@ -1813,7 +1820,7 @@ def dsac_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None
 
 # --------------------------------------------- fused Rainbow vector step ---
 def rainbow_fused_shape_ok(B, D, A, H):
-    return 0 < B <= FUSED_MAX_BATCH and 0 < D <= 8 and 0 < A <= 3 and 4 <= H <= 256 and H % 4 == 0
+    return _fused_shape_ok(B, D, A, H, FUSED_MAX_BATCH, 3)
 
 
 def rainbow_update_workspace(B, D, A, H, device):

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from . import ops
 from .dqn_cartpole import ReplayBuffer
 from .envs import EpisodeTracker, VecEnv
-from .flat import FusedAdam, GradSink, flatten_module
+from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear
 from .utils import scalar
 
@@ -80,7 +80,7 @@ class Critic(nn.Module):
         return self.fc3(self.fc2(self.fc1(x)))
 
 
-class SACTrainer:
+class SACTrainer(WeightImages):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -121,8 +121,6 @@ class SACTrainer:
         self._parity_noise = None      # tests: iterator of f32[N, A] Exp(1) draws for select_action
         self._parity_indices = None    # tests: iterator of i32[B] replay indices for update()
         self._graph = None             # hipGraph of the update, captured on first use (update_async)
-        self._fused = None             # (act args, update args, workspace, env, weight images) of the fused step, built on first use
-        self._img_versions = None      # versions of the flat buffers the weight images were last rebuilt from
 
     @torch.no_grad()
     def select_action(self, state, deterministic=False, noise_exp=None):
@@ -138,7 +136,7 @@ class SACTrainer:
     def soft_update(self, target_flat, source_flat):
         """:140-145 on the flat parameter buffers."""
         ops.soft_update(target_flat, source_flat, self.cfg.tau)
-        self._img_versions = None      # a raw-pointer write: the fused step's weight images of the target are stale
+        self._images_stale()           # a raw-pointer write: the fused step's weight images of the target are stale
 
     # ------------------------------------------------------------ fused vector step (csrc/dsac_step.hip) -------
     CHUNK = 16                         # vector steps per StepChunk replay (= the episode tracker's flush period)
@@ -169,20 +167,11 @@ class SACTrainer:
                                        (cfg.gamma, cfg.tau, cfg.target_entropy, cfg.lr_alpha), self.log_alpha, self._alpha_m,
                                        self._alpha_v, self._sums, self._alpha_loss, ws, img)
             self._fused = (act, upd, ws, env, img)
-            self._img_versions = None
-        # the weight images follow the parameters as long as only the fused update writes them; anything that went through
-        # torch (load_state_dict, a checkpoint: the parameters' version counters move) or around it (soft_update(), the
-        # layer-by-layer update, load_checkpoint(): they reset _img_versions) makes them stale: rebuild (one launch)
-        if self._fused[4] is not None:
-            ps = getattr(self, "_img_params", None)
-            if ps is None:
-                ps = self._img_params = tuple([f] + list(net.parameters()) for f, net in (
-                    (self.actor_flat, self.actor), (self.c1_flat, self.critic1), (self.c2_flat, self.critic2),
-                    (self.c1_target_flat, self.critic1_target), (self.c2_target_flat, self.critic2_target)))
-            v = tuple(sum([t._version for t in group]) for group in ps)
-            if v != self._img_versions:
-                ops.dsac_pack_images(self._fused[1])
-                self._img_versions = v
+            self._images_stale()
+        if self._fused[4] is not None:         # (flat.WeightImages: rebuilt when a parameter moved outside the fused update)
+            self._refresh_images(((self.actor_flat, self.actor), (self.c1_flat, self.critic1), (self.c2_flat, self.critic2),
+                                  (self.c1_target_flat, self.critic1_target), (self.c2_target_flat, self.critic2_target)),
+                                 ops.dsac_pack_images, self._fused[1])
         return self._fused
 
     def _update_fused(self, indices=None, dev=None):
@@ -321,7 +310,7 @@ class SACTrainer:
         """Everything after the index draw; biases = device views of the three Adams' step scalars (critic1, critic2,
         actor) and alpha_bias the temperature's, when the body runs inside / ahead of a hipGraph."""
         cfg = self.cfg
-        self._img_versions = None             # this path writes the parameters without the fused step's weight images
+        self._images_stale()                  # this path writes the parameters without the fused step's weight images
         bc1, bc2, ba = biases if biases is not None else (None, None, None)
         states, actions, rewards, next_states, dones = self.memory.gather(indices)
         B = states.shape[0]
@@ -366,7 +355,7 @@ class SACTrainer:
             self._graph = GraphedUpdate(self.device, cfg.batch_size, [self.critic1_optim, self.critic2_optim, self.actor_optim],
                                         lambda idx, biases, ab: self._update_body(idx, biases, ab),
                                         alpha=(self, "_alpha_steps", b1, b2))
-        self._img_versions = None             # (a replay runs no Python: _update_body's own reset is not enough)
+        self._images_stale()                  # (a replay runs no Python: _update_body's own reset is not enough)
         self._graph(self.memory, cfg.batch_size)
 
     def save_checkpoint(self, path, include_memory=True):
@@ -387,7 +376,7 @@ class SACTrainer:
         rest = checkpoint.load_agent(path, {k: getattr(self, k) for k in ("actor", "critic1", "critic2", "critic1_target", "critic2_target")},
                                      {"actor_optim": (self.actor, self.actor_optim), "critic1_optim": (self.critic1, self.critic1_optim),
                                       "critic2_optim": (self.critic2, self.critic2_optim)})
-        self._img_versions = None             # the fused step's weight images are rebuilt from the loaded parameters
+        self._images_stale()                  # the fused step's weight images are rebuilt from the loaded parameters
         self.log_alpha.copy_(rest["log_alpha"].to(self.device))
         self._alpha_m.copy_(rest["alpha_m"].to(self.device))
         self._alpha_v.copy_(rest["alpha_v"].to(self.device))

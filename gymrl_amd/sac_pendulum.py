@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import ops
 from .dqn_cartpole import ReplayBuffer as _Ring
 from .envs import EpisodeTracker, VecEnv
-from .flat import FusedAdam, GradSink, flatten_module
+from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear, frozen_parameters, fused_linears
 from .utils import scalar
 
@@ -135,7 +135,7 @@ class ReplayBuffer(_Ring):
         super().push(state, action, reward, next_state, done, cursor_dev=cursor_dev)     # the ring stores the f32 bits as words
 
 
-class SACTrainer:
+class SACTrainer(WeightImages):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -170,8 +170,6 @@ class SACTrainer:
         self._parity_eps = None        # tests: iterator of f32[N, A] N(0,1) draws for select_action
         self._graph = None             # hipGraph of the update, captured on first use (update_async)
         self._parity_updates = None    # tests: iterator of (indices i32[B], eps_next [B, A], eps_cur [B, A]) for update()
-        self._fused = None             # (act args, update args, workspace, env, weight images) of the fused step, built on first use
-        self._img_versions = None      # versions of the flat buffers the weight images were last rebuilt from
         self._act_noise = self._upd_noise = 0      # Philox counters of the fused step's own N(0,1) draws
 
     @property
@@ -182,7 +180,7 @@ class SACTrainer:
         """:194-199 on the flat parameter buffers."""
         ops.soft_update(self.critic_target_flat if target_flat is None else target_flat,
                         self.critic_flat if source_flat is None else source_flat, self.cfg.tau)
-        self._img_versions = None             # a raw-pointer write: the fused step's weight images of the target are stale
+        self._images_stale()                  # a raw-pointer write: the fused step's weight images of the target are stale
 
     # ------------------------------------------------------------ fused vector step (csrc/offpolicy_step.hip) --
     def _fused_update_ok(self):
@@ -210,22 +208,10 @@ class SACTrainer:
                                       (cfg.gamma, cfg.tau, self.action_bound, cfg.log_std_min, cfg.log_std_max, self.target_entropy,
                                        cfg.lr_alpha), self.log_alpha, self._alpha_m, self._alpha_v, self._sums, self._alpha_loss, ws, img)
             self._fused = (act, upd, ws, env, img)
-            self._img_versions = None
-        # the weight images follow the parameters as long as only the fused update writes them; anything that went through
-        # torch (load_state_dict, a checkpoint, a hard target copy: the flat buffers' version counters move) or through the
-        # layer-by-layer update (which resets _img_versions) makes them stale: rebuild (one launch)
-        if self._fused[4] is not None:
-            # (flatten_module binds every parameter as a VIEW tensor of its own: load_state_dict / a checkpoint bump the
-            # parameters' version counters, not the flat buffers' — so both are summed; writers that go around torch
-            # altogether, soft_update() and load_checkpoint(), reset _img_versions themselves)
-            ps = getattr(self, "_img_params", None)
-            if ps is None:
-                ps = self._img_params = tuple([f] + list(net.parameters()) for f, net in (
-                    (self.actor_flat, self.actor), (self.critic_flat, self.critic), (self.critic_target_flat, self.critic_target)))
-            v = tuple(sum([t._version for t in group]) for group in ps)
-            if v != self._img_versions:
-                ops.sac_pack_images(self._fused[1])
-                self._img_versions = v
+            self._images_stale()
+        if self._fused[4] is not None:         # (flat.WeightImages: rebuilt when a parameter moved outside the fused update)
+            self._refresh_images(((self.actor_flat, self.actor), (self.critic_flat, self.critic),
+                                  (self.critic_target_flat, self.critic_target)), ops.sac_pack_images, self._fused[1])
         return self._fused
 
     def _update_fused(self, indices=None, eps_next=None, eps_cur=None, dev=None):
@@ -277,7 +263,7 @@ class SACTrainer:
         """Everything after the index draw.  bias = (critic f32[4], actor f32[4], alpha f64[2]) device views when
         the body runs inside / ahead of a hipGraph; None on the eager path."""
         cfg = self.cfg
-        self._img_versions = None             # this path writes the parameters without the fused step's weight images
+        self._images_stale()                  # this path writes the parameters without the fused step's weight images
         states, actions, rewards, next_states, dones = self.memory.gather(indices)
         B = states.shape[0]
         self._sums.zero_()
@@ -355,7 +341,7 @@ class SACTrainer:
         rest = checkpoint.load_agent(path, {"actor": self.actor, "critic": self.critic, "critic_target": self.critic_target},
                                      {"actor_optimizer": (self.actor, self.actor_optimizer),
                                       "critic_optimizer": (self.critic, self.critic_optimizer)})
-        self._img_versions = None             # the fused step's weight images are rebuilt from the loaded parameters
+        self._images_stale()                  # the fused step's weight images are rebuilt from the loaded parameters
         self.log_alpha.copy_(rest["log_alpha"].to(self.device))
         self._alpha_m.copy_(rest["alpha_m"].to(self.device))
         self._alpha_v.copy_(rest["alpha_v"].to(self.device))

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import ops
 from .envs import EpisodeTracker, VecEnv
-from .flat import FusedAdam, GradSink, flatten_module
+from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear, frozen_parameters, fused_linears
 from .sac_pendulum import ReplayBuffer
 from .utils import scalar
@@ -83,7 +83,7 @@ class Critic(nn.Module):
         return self.fc3(self.fc2(self.fc1(state, action)))
 
 
-class _ActorCriticBase:
+class _ActorCriticBase(WeightImages):
     """What TD3 and DDPG share: env, replay ring, exploration, vectorised train / eval loops."""
 
     def _setup(self, config, critic_cls):
@@ -120,13 +120,11 @@ class _ActorCriticBase:
         self._parity_eps = None        # tests: iterator of f64[N, A] N(0,1) draws for select_action
         self._parity_updates = None    # tests: iterator of per-update tuples (see update())
         self._graph = None             # hipGraph of the update (trainers that define update_async)
-        self._fused = None             # (act args, update args, workspace, env, weight images) of the fused step, built on first use
-        self._img_versions = None      # versions of the flat buffers the weight images were last rebuilt from
 
     def soft_update(self, target_flat, source_flat):
         """:149-154 on the flat parameter buffers."""
         ops.soft_update(target_flat, source_flat, self.cfg.tau)
-        self._img_versions = None      # a raw-pointer write: the fused step's weight images of the target are stale
+        self._images_stale()           # a raw-pointer write: the fused step's weight images of the target are stale
 
     # ------------------------------------------------------------ fused vector step (csrc/td3_step.hip) --------
     N_CRITICS = 2                      # TD3's twin module; DDPGTrainer: 1
@@ -164,20 +162,11 @@ class _ActorCriticBase:
                                       self.actor_optimizer, self.critic_optimizer, m.ring,
                                       (cfg.gamma, cfg.tau, self.action_bound) + tuple(self._smoothing()), self._sums, ws, img)
             self._fused = (act, upd, ws, env, img)
-            self._img_versions = None
-        # the weight images follow the parameters as long as only the fused update writes them; anything that went through
-        # torch (load_state_dict: the parameters' version counters move) or around it (soft_update(), the layer-by-layer
-        # update: they reset _img_versions) makes them stale: rebuild (one launch) before the next fused call
-        if self._fused[4] is not None:
-            ps = getattr(self, "_img_params", None)
-            if ps is None:
-                ps = self._img_params = tuple([f] + list(net.parameters()) for f, net in (
-                    (self.actor_flat, self.actor), (self.critic_flat, self.critic),
-                    (self.actor_target_flat, self.actor_target), (self.critic_target_flat, self.critic_target)))
-            v = tuple(sum([t._version for t in group]) for group in ps)
-            if v != self._img_versions:
-                ops.td3_pack_images(self._fused[1])
-                self._img_versions = v
+            self._images_stale()
+        if self._fused[4] is not None:         # (flat.WeightImages: rebuilt when a parameter moved outside the fused update)
+            self._refresh_images(((self.actor_flat, self.actor), (self.critic_flat, self.critic),
+                                  (self.actor_target_flat, self.actor_target), (self.critic_target_flat, self.critic_target)),
+                                 ops.td3_pack_images, self._fused[1])
         return self._fused
 
     def _update_fused(self, indices=None, eps=None, dev=None):
@@ -401,7 +390,7 @@ class TD3Trainer(_ActorCriticBase):
             s = self._sums.tolist()
             return (-s[1] / cfg.batch_size if delayed else 0.0), s[0] / cfg.batch_size
         self.total_updates += 1
-        self._img_versions = None             # this path writes the parameters without the fused step's weight images
+        self._images_stale()                  # this path writes the parameters without the fused step's weight images
         states, actions, rewards, next_states, dones = self.memory.sample(cfg.batch_size, indices)
         B = states.shape[0]
         with torch.no_grad():                                          # :191-199
