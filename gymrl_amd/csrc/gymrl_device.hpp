@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 #define GYMRL_WAVE 64
 
@@ -21,6 +22,16 @@
   } while (0)
 
 namespace gymrl {
+
+// the dynamic-LDS ceiling of a unit's kernels, set by the first call that gets here (`done`: the call site's own static flag);
+// 0 or the C ABI's -1000 - hipError
+static inline int set_max_lds_once(bool& done, std::initializer_list<const void*> kernels, int bytes) {
+  if (done) return 0;
+  for (const void* f : kernels)
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1000 - (int)hipGetLastError();
+  done = true;
+  return 0;
+}
 
 // ---------------------------------------------------------------- Philox ---
 struct u32x4 { uint32_t x, y, z, w; };

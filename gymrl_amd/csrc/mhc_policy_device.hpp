@@ -1,38 +1,11 @@
 // mhc_policy_device.hpp — PPO-full's ActorCritic.forward (:377-407) for 16 rows on one 256-thread workgroup, shared by
-// mhc_policy_kernel (csrc/mhc.hip: the step-by-step rollout forward) and the persistent rollout (csrc/rollout_lunar.hip), plus the
-// transcendental helpers every mHC kernel uses.
+// mhc_policy_kernel (csrc/mhc.hip: the step-by-step rollout forward) and the persistent rollout (csrc/rollout_lunar.hip).
 #pragma once
-#include "train_device.hpp"
+#include "mhc_device.hpp"
 #include "../../include/gymrl.h"
 
 namespace gymrl {
 namespace mhc {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// exp and 1/x on the hardware units (v_exp_f32, v_rcp_f32: 1 ulp each).  The gate arithmetic and the SiLUs are what these kernels
-// issue most — a correctly rounded division is ~12 instructions, libm's expf ~15 — and every result is held to 1e-5 of the
-// float64 modules, not to torch's bits.  exp_: x log2(e) in two pieces, so that the product's rounding (up to |x| 2^-24 relative
-// in the result) is folded back in.
-__device__ __forceinline__ float rcp_(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float exp_(float x) {
-  const float t = x * 1.44269504088896341f;
-  const float lo = fmaf(x, 1.44269504088896341f, -t) + x * 1.92596299112661746e-8f;
-  return __builtin_amdgcn_exp2f(t) * (1.0f + lo * 0.693147180559945309f);
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return rcp_(1.0f + exp_(-x)); }
-__device__ __forceinline__ float silu_(float z) { return z * sigmoidf_(z); }
-__device__ __forceinline__ float silu_grad_(float z) { const float s = sigmoidf_(z); return s * (1.0f + z * (1.0f - s)); }
-
-// sum over the 16 lanes of a DPP row, every lane ending with the same bits: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
-// row_mirror — four v_add_f32_dpp, no LDS traffic (a 64-lane __shfl_xor tree is six ds_bpermute round trips)
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));
-  return v;
-}
 
 // ---- the whole rollout forward of PPO-full's network in ONE launch ------------------------------------------------------
 // ActorCritic.forward (:377-407) for n = 2 branches of D = 128 and 256-wide heads: input projection, every hyper-connection
@@ -209,28 +182,9 @@ __device__ __forceinline__ void policy_tile(const PolicyArgs& a, PolicyLds& L, c
 #pragma unroll
     for (int k = 0; k <= G; ++k) Hs[k] = row16_sum(Hs[k]);
     POL_MARK(8);
-    const float r_inv = 1.0f / (sqrtf(Hs[G]) / sqrtf((float)NC) + 1e-6f);
-    const float a0 = a.alpha[s][0], a1 = a.alpha[s][1], a2 = a.alpha[s][2];
-    const float* __restrict__ be = a.beta[s];
-    float pre[2], post[2], A[2][2], u[2] = {1.0f, 1.0f}, v[2] = {1.0f, 1.0f};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      pre[i] = sigmoidf_(r_inv * Hs[i] * a0 + be[i]);
-      post[i] = 2.0f * sigmoidf_(r_inv * Hs[2 + i] * a1 + be[2 + i]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) A[i][j] = exp_(r_inv * Hs[4 + 2 * i + j] * a2 + be[4 + 2 * i + j]);
-    }
-    for (int it = 0; it < a.sk_it; ++it) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) u[i] = rcp_(A[i][0] * v[0] + A[i][1] * v[1] + 1e-8f);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) v[j] = rcp_(A[0][j] * u[0] + A[1][j] * u[1] + 1e-8f);
-    }
-    float mix[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) mix[i][j] = u[i] * A[i][j] * v[j];
+    const float al[3] = {a.alpha[s][0], a.alpha[s][1], a.alpha[s][2]};
+    float pre[2], post[2], mix[2][2];
+    row_gates<2>(Hs, NC, al, a.beta[s], a.sk_it, pre, post, mix);
     POL_MARK(9);
     // read = pre_0 h_0 + pre_1 h_1 -> the Linear's input rows
 #pragma unroll

@@ -88,11 +88,7 @@ int gymrl_mlp_forward(const float* x, int n_rows, int in_dim, const gymrl_mlp_de
   if (n_rows == 0) return 0;
   const int blocks = (n_rows + kRows - 1) / kRows;
   static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)mlp_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess)
-      return -1000 - (int)hipGetLastError();
-    attr_set = true;
-  }
+  if (const int rc = set_max_lds_once(attr_set, {(const void*)mlp_forward_kernel}, kLdsBytes)) return rc;
   hipLaunchKernelGGL(mlp_forward_kernel, dim3(blocks), dim3(kWaves * 64), kLdsBytes, (hipStream_t)stream, x, n_rows,
                      in_dim, *desc);
   GYMRL_CHECK_LAUNCH();

@@ -729,15 +729,9 @@ int gymrl_per_update(double* tree, int64_t cap, const int32_t* idx, int64_t idx_
   hipStream_t stream = (hipStream_t)stream_;
   Ws ws(workspace, B);
   const int use_lds = B <= kLdsB ? 1 : 0;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)per_leaf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsB * 8) != hipSuccess ||
-        hipFuncSetAttribute((const void*)per_ancestor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsB * 16) != hipSuccess ||
-        hipFuncSetAttribute((const void*)per_leaf_sorted_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsB * 8) != hipSuccess ||
-        hipFuncSetAttribute((const void*)per_ancestor_sorted_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsB * 16) != hipSuccess)
-      return -1000 - (int)hipGetLastError();
-    attr_set = true;
-  }
+  static bool leaf_set = false, ancestor_set = false;
+  if (const int rc = set_max_lds_once(leaf_set, {(const void*)per_leaf_kernel, (const void*)per_leaf_sorted_kernel}, kLdsB * 8)) return rc;
+  if (const int rc = set_max_lds_once(ancestor_set, {(const void*)per_ancestor_kernel, (const void*)per_ancestor_sorted_kernel}, kLdsB * 16)) return rc;
   // deepest leaf depth = depth of the last tree slot; ancestors live at depths 0 .. that-1
   int depth = 0;
   { int64_t t = 2 * cap - 2; while (t > 0) { t = (t - 1) / 2; ++depth; } }

@@ -118,11 +118,7 @@ int gymrl_rollout_cartpole(const gymrl_rollout_lunar_args* a, const gymrl_mlp_de
   if (outs != 2 || cols > M::kHeadStride) return -22;
   if (a->nsteps == 0 && a->t0 != a->T) return 0;
   static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)rollout_cartpole_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynBytes) != hipSuccess)
-      return -1000 - (int)hipGetLastError();
-    attr_set = true;
-  }
+  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_cartpole_kernel}, kDynBytes)) return rc;
   const int blocks = (a->n_envs + M::kRows - 1) / M::kRows;
   hipLaunchKernelGGL(rollout_cartpole_kernel, dim3(blocks), dim3(kThreads), kDynBytes, (hipStream_t)stream, *a, *policy);
   GYMRL_CHECK_LAUNCH();

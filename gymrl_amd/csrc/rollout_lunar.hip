@@ -297,12 +297,7 @@ int gymrl_rollout_lunar(const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc*
   if (outs != 2 || cols > M::kHeadStride) return -22;
   if (a->nsteps == 0 && a->t0 != a->T) return 0;
   static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)rollout_lunar_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynBytes) !=
-        hipSuccess)
-      return -1000 - (int)hipGetLastError();
-    attr_set = true;
-  }
+  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_lunar_kernel}, kDynBytes)) return rc;
   const int blocks = (a->n_envs + M::kRows - 1) / M::kRows;
   hipLaunchKernelGGL(rollout_lunar_kernel, dim3(blocks), dim3(kThreads), kDynBytes, (hipStream_t)stream, *a, *policy);
   GYMRL_CHECK_LAUNCH();
@@ -336,11 +331,7 @@ int gymrl_rollout_lunar_mhc(const gymrl_rollout_lunar_args* a, const gymrl_mhc_p
   if (p.obs_dim != kObs || p.n_act != kActions) return -22;       // LunarLander: 8 observations, 4 actions
   if (a->nsteps == 0 && a->t0 != a->T) return 0;
   static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)rollout_lunar_mhc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kDynBytesMhc) != hipSuccess)
-      return -1000 - (int)hipGetLastError();
-    attr_set = true;
-  }
+  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_lunar_mhc_kernel}, kDynBytesMhc)) return rc;
   const int blocks = (a->n_envs + M::kRows - 1) / M::kRows;
   hipLaunchKernelGGL(rollout_lunar_mhc_kernel, dim3(blocks), dim3(kThreads), kDynBytesMhc, (hipStream_t)stream, *a, p);
   GYMRL_CHECK_LAUNCH();

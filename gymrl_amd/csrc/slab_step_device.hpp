@@ -41,15 +41,6 @@ inline size_t workspace_bytes(int B, int D, int A, int H) {
   if (B <= 0 || D <= 0 || A <= 0 || H <= 0) return 0;
   return Ws::carve(nullptr, nullptr, B, D, A, H) + 256;
 }
-// the dynamic-LDS ceiling of a unit's kernels, set by the first call that gets here (`done`: the call site's own static flag);
-// 0 or the C ABI's -1000 - hipError
-inline int set_max_lds_once(bool& done, std::initializer_list<const void*> kernels, int bytes) {
-  if (done) return 0;
-  for (const void* f : kernels)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1000 - (int)hipGetLastError();
-  done = true;
-  return 0;
-}
 
 // ---- what an entry point refuses with -22 before anything touches HIP: where the algorithms' checks differ, the call site says so ----
 inline bool slab_shape_ok(int B, int max_batch, int D, int A, int H) {

@@ -293,7 +293,7 @@ class _MhcSub(torch.autograd.Function):
 
 
 class _MhcRead(torch.autograd.Function):
-    """read = sum_i pre_i h_i (:161) with its backward, one launch each way (csrc/mhc.hip)."""
+    """read = sum_i pre_i h_i (:161) with its backward, one launch each way (csrc/mhc_layers.hip)."""
 
     @staticmethod
     def forward(ctx, pre, h):
@@ -436,7 +436,7 @@ class MLP(nn.Module):
                     and isinstance(mods[i + 2], SmallLinear) and getattr(mods[i + 2], "act", None) in (None, "none")
                     and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] > 0
                     and ops.norm_proj_ok(x.shape[1], mods[i + 2].out_features)):
-                # SiLU -> RMSNorm -> the output Linear in one launch each way (csrc/mhc.hip norm_proj_*_kernel)
+                # SiLU -> RMSNorm -> the output Linear in one launch each way (csrc/mhc_norm.hip norm_proj_*_kernel)
                 return _NormProj.apply(x, mods[i + 1].weight, mods[i + 1].eps, mods[i + 2].weight, mods[i + 2].bias)
             if i + 1 < len(mods) and isinstance(mods[i], nn.SiLU) and isinstance(mods[i + 1], RMSNorm):
                 x = mods[i + 1](x, silu=True)        # SiLU rides in the norm's launches on the GPU
@@ -499,7 +499,7 @@ class ActorCritic(nn.Module):
 
     @torch.no_grad()
     def forward_fused(self, x):
-        """forward(x) without gradients on the inference kernels (csrc/mhc.hip, csrc/lin.hip): ~20 launches instead of
+        """forward(x) without gradients on the inference kernels (csrc/mhc.hip, mhc_layers.hip, mhc_norm.hip, csrc/lin.hip): ~20 launches instead of
         ~400 — one per Linear (+ SiLU), three per hyper-connection (gates + read, Linear + SiLU, combine), the RMSNorms.
         Same values as the modules to 1e-5 (tests/test_mhc_fused_gpu.py).  None when the network is not the mHC one."""
         bb = self.shared

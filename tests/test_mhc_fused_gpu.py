@@ -1,4 +1,4 @@
-"""PPO-full's rollout forward on the inference kernels (csrc/mhc.hip + csrc/lin.hip) against the torch modules in float64."""
+"""PPO-full's rollout forward on the inference kernels (csrc/mhc.hip, mhc_layers.hip, mhc_norm.hip + csrc/lin.hip) against the torch modules in float64."""
 import pytest
 
 torch = pytest.importorskip("torch")
@@ -249,7 +249,7 @@ def test_one_launch_policy_forward_matches_actor_critic(B, layers, obs):
     assert torch.equal(plain[0], packed[0]) and torch.equal(plain[1], packed[1])
 
 
-@pytest.mark.parametrize("B", [1, 16, 100, 5000, 40000])
+@pytest.mark.parametrize("B", [1, 15, 16, 17, 100, 5000, 40000])
 def test_one_launch_sub_block_forward_matches_its_three_launches(B):
     """gymrl_mhc_sub_forward against gymrl_mhc_gates + gymrl_lin_fwd + gymrl_mhc_combine(SiLU): gates, read-out sums and branch
     sum bit for bit (same arithmetic), z and h' to the Linear's summation order."""
@@ -267,6 +267,23 @@ def test_one_launch_sub_block_forward_matches_its_three_launches(B):
     z64 = read.double() @ W.double().t() + b.double()
     _close(z, z64, 2e-6)
     _close(h_out, ops.mhc_combine(post, mix, z, h, act=ops.LIN_ACT["silu"]).double(), 1e-6)
+
+
+@pytest.mark.parametrize("B", [1, 257])
+@pytest.mark.parametrize("n,dim", [(2, 128), (2, 64), (4, 32)])    # the 16-lanes-per-row gates kernel, the wave-per-row one at n = 2 and 4
+def test_gates_and_sinkhorn_share_their_sweeps(n, dim, B):
+    """The Sinkhorn-Knopp sweeps are stated once (csrc/mhc_device.hpp): mix = u A v from gymrl_sinkhorn's u, v equals gymrl_mhc_gates'
+    mix bit for bit.  A, the gates' exp(...) matrix of each row, is read off exactly: with no sweeps u = v = 1 and mix = 1 A 1 = A."""
+    from gymrl_amd import ops
+    torch.manual_seed(100 * n + B)
+    d = "cuda"
+    h = torch.randn(B, n, dim, device=d) * 2
+    nw, w = torch.rand(n * dim, device=d) + 0.5, torch.randn(n * dim, n * n + 2 * n, device=d) * 0.3
+    alpha, beta = torch.tensor([0.7, -0.4, 0.9], device=d), torch.randn(n * n + 2 * n, device=d) * 0.1
+    A = ops.mhc_gates(h, nw, w, alpha, beta, 0)[2]
+    assert bool((A > 0).all())
+    u, v = ops.sinkhorn(A, 10)
+    assert torch.equal((u[:, :, None] * A) * v[:, None, :], ops.mhc_gates(h, nw, w, alpha, beta, 10)[2])
 
 
 @pytest.mark.parametrize("B,g_b,h_b,sum_b", [(1000, False, False, False), (1000, True, False, False), (1000, False, True, True),

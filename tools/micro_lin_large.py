@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """PPO-full's wide layers and hyper-connection kernels at a 262144-row micro-batch, microseconds per launch with the GB/s of
 the operands each launch has to move: csrc/lin.hip (forward, input gradient — both kernels —, weight gradient) against the
-library GEMMs, and csrc/mhc.hip (gates forward / backward, combine, read, RMSNorm)."""
+library GEMMs, and csrc/mhc_layers.hip (gates forward / backward, combine, read) with csrc/mhc_norm.hip (RMSNorm)."""
 import json
 import os
 import sys
