@@ -432,6 +432,9 @@ SIGNATURES = {
     "gymrl_dsac_update": (_i, [_P(DsacUpdateArgs), _vp]),
     "gymrl_softmax_rows_fwd": (_i, [_vp, _i, _i, _vp, _vp]),
     "gymrl_softmax_rows_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "gymrl_qlearn_state_bytes": (_sz, [_i]),
+    "gymrl_qlearn_train": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _u64, _i64, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_qlearn_eval": (_i, [_i, _i, _vp, _i, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -513,6 +513,48 @@ def env_step(kind, state, n, seed, env_id0, action, obs_out, rew_out, terminated
                                _ptr(ep_len_out, torch.int32, True), _ptr(ep_stats, torch.float64, True), _stream()), "gymrl_env_step")
 
 
+# ------------------------------------------------------ tabular Q-learning ---
+FROZENLAKE, CLIFFWALKING = 0, 1              # GYMRL_TABULAR_*
+TABULAR_STATES = {FROZENLAKE: 16, CLIFFWALKING: 48}
+TABULAR_ACTIONS = 4
+
+
+def qlearn_state_bytes(n_runs):
+    return int(lib().gymrl_qlearn_state_bytes(n_runs))
+
+
+def qlearn_train(kind, Q, state, eps_table, seed, run_id0, max_episodes, max_steps, max_iters, lr, gamma, episode_rewards,
+                 episode_lengths, k_out, episodes_out, is_slippery=False, shaped=False, restart=False):
+    """Advance every run of Q f64[R, S, 4] by at most max_iters Q-learning steps (qlearning_frozenlake.py:96-117 /
+    qlearning_cliffwalking.py:71-91, one lane per run, ONE launch); `state` (qlearn_state_bytes(R) bytes) carries the loops
+    between calls, restart begins them at episode 0."""
+    R = Q.shape[0]
+    if tuple(Q.shape) != (R, TABULAR_STATES.get(kind, -1), TABULAR_ACTIONS):
+        raise ValueError(f"Q is {tuple(Q.shape)}, env kind {kind} needs [R, {TABULAR_STATES.get(kind)}, {TABULAR_ACTIONS}]")
+    if eps_table.numel() != max_episodes * max_steps or tuple(episode_rewards.shape) != (R, max_episodes) or \
+            tuple(episode_lengths.shape) != (R, max_episodes) or k_out.numel() != R or episodes_out.numel() != R or \
+            state.numel() < qlearn_state_bytes(R):
+        raise ValueError("qlearn_train: a buffer does not have the size its run count and episode budget ask for")
+    check(lib().gymrl_qlearn_train(kind, int(bool(is_slippery)), int(bool(shaped)), _ptr(Q, torch.float64), _ptr(state, torch.uint8), R,
+                                   int(bool(restart)), seed, run_id0, _ptr(eps_table, torch.float64), max_episodes, max_steps, max_iters,
+                                   lr, gamma, _ptr(episode_rewards, torch.float64), _ptr(episode_lengths, torch.int32),
+                                   _ptr(k_out, torch.int32), _ptr(episodes_out, torch.int32), _stream()), "gymrl_qlearn_train")
+
+
+def qlearn_eval(kind, Q, n_episodes, seed, stream_id0, cap, is_slippery=False):
+    """n_episodes greedy episodes per run on Q f64[R, S, 4], one lane each -> (returns f64, lengths i32, reached-the-goal u8),
+    each [R, n_episodes]; an episode that is not over after `cap` steps stops there with its flag 0."""
+    R = Q.shape[0]
+    if tuple(Q.shape) != (R, TABULAR_STATES.get(kind, -1), TABULAR_ACTIONS):
+        raise ValueError(f"Q is {tuple(Q.shape)}, env kind {kind} needs [R, {TABULAR_STATES.get(kind)}, {TABULAR_ACTIONS}]")
+    returns = torch.empty(R, n_episodes, dtype=torch.float64, device=Q.device)
+    lengths = torch.empty(R, n_episodes, dtype=torch.int32, device=Q.device)
+    flags = torch.empty(R, n_episodes, dtype=torch.uint8, device=Q.device)
+    check(lib().gymrl_qlearn_eval(kind, int(bool(is_slippery)), _ptr(Q, torch.float64), R, n_episodes, seed, stream_id0, cap,
+                                  _ptr(returns), _ptr(lengths), _ptr(flags), _stream()), "gymrl_qlearn_eval")
+    return returns, lengths, flags
+
+
 # ============================================================== off-policy ===
 def env_abandon(kind, state, n, seed, env_id0, cap, obs_inout, flag_inout=None, ep_ret_out=None, ep_len_out=None,
                 ep_stats=None):

@@ -1465,6 +1465,42 @@ int gymrl_dsac_update(const gymrl_dsac_update_args* args, void* stream);
 int gymrl_softmax_rows_fwd(const float* z, int B, int A, float* p_out, void* stream);
 int gymrl_softmax_rows_bwd(const float* p, const float* g, int B, int A, float* dz_out, void* stream);
 
+/* ---- tabular Q-learning: a population of independent runs in one launch (csrc/tabular.hip) --------------------------------
+ * Replaces QLearningTrainer.train() / select_action() / update() / _shape_reward() / eval() of qlearning_frozenlake.py:56-153
+ * and qlearning_cliffwalking.py:49-124 together with the gym.make(...).reset() / .step() calls inside them (:100,105 / :75,80),
+ * for n_runs runs that share one Config and differ by their random stream.  One lane = one run; its table stays in LDS for the
+ * launch.  The env rules (gymnasium toy_text, third-party):
+ *   FrozenLake-v1 4x4  SFFF / FHFH / FFFH / HFFG, state row * 4 + col, start 0; 0 LEFT 1 DOWN 2 RIGHT 3 UP, clipped at the border;
+ *                      slippery: the executed direction is (a - 1) % 4, a, (a + 1) % 4 with probability 1/3 each; reward 1 on
+ *                      entering the goal 15; terminated on a hole {5, 7, 11, 12} or the goal; truncated at the env's 100th step
+ *   CliffWalking-v0    4 x 12, state row * 12 + col, start 36, goal 47; 0 UP 1 RIGHT 2 DOWN 3 LEFT, clipped; the cliff 37..46
+ *                      costs -100 and returns the agent to 36 without terminating, any other step costs -1; terminated at the
+ *                      goal only; no time limit
+ * One run's loop, float64 in the reference's operation order: k counts its training actions from 1 (sample_count);
+ * eps_table[k - 1] = end + (start - end) * exp(-k / decay) comes from the host (max_episodes * max_steps entries, shared by
+ * all runs); explore iff u < eps_k with a uniform action, else the FIRST maximum of Q[s, :]; done = terminated or truncated;
+ * `shaped` (FrozenLake) replaces the reward by -10 hole / 100 goal / -5 next == state / -1; target = r if done else
+ * r + gamma * max Q[s', :]; Q[s, a] = Q[s, a] + lr * (target - Q[s, a]); an episode also ends after max_steps steps without
+ * done.  Draws: Philox4x32-10 keyed (seed; stream lo, stream hi, k, 0x70000000), stream = run_id0 + r: words 0, 1 -> u, word 2
+ * -> the exploring action (w * 4) >> 32, word 3 -> the slip choice (w * 3) >> 32 (csrc/tabular_device.hpp).
+ * gymrl_qlearn_train advances every run by at most max_iters steps from the record in `state` (gymrl_qlearn_state_bytes(n_runs)
+ * bytes, 256-byte aligned; restart != 0: from the start of episode 0 instead) and leaves the record for the next call, which
+ * continues bit for bit.  Q f64[n_runs, S, 4] in / out (S = 16 / 48); episode_rewards f64 / episode_lengths i32
+ * [n_runs, max_episodes]: entry e is written when episode e ends; k_out / episodes_out i32[n_runs]: actions taken / episodes
+ * finished.  -22 for a NULL or misaligned pointer, n_runs <= 0, an unknown env kind or max_episodes * max_steps >= 2^31.
+ * gymrl_qlearn_eval runs n_episodes greedy episodes per run on Q (read only), one lane each, with the env's draws from stream
+ * stream_id0 + run * n_episodes + episode at k = the episode's step; an episode stops at terminated / truncated or after `cap`
+ * steps.  returns f64 / lengths i32 / flags u8 [n_runs, n_episodes]: the env's own reward summed, the steps taken, and whether
+ * the goal was reached (FrozenLake: the reference's success; CliffWalking: finished — its `while not done` has no cap). */
+enum { GYMRL_TABULAR_FROZENLAKE = 0, GYMRL_TABULAR_CLIFFWALKING = 1 };
+size_t gymrl_qlearn_state_bytes(int n_runs);
+int gymrl_qlearn_train(int env_kind, int is_slippery, int shaped, double* Q, void* state, int n_runs, int restart, uint64_t seed,
+                       int64_t run_id0, const double* eps_table, int max_episodes, int max_steps, int max_iters, double lr,
+                       double gamma, double* episode_rewards, int32_t* episode_lengths, int32_t* k_out, int32_t* episodes_out,
+                       void* stream);
+int gymrl_qlearn_eval(int env_kind, int is_slippery, const double* Q, int n_runs, int n_episodes, uint64_t seed,
+                      int64_t stream_id0, int cap, double* returns, int32_t* lengths, uint8_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
