@@ -252,6 +252,34 @@ class DsacUpdateArgs(C.Structure):
                 ("sums", C.c_void_p), ("alpha_loss", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
 
 
+class DqnActArgs(C.Structure):
+    _c_name_ = "gymrl_dqn_act_args"
+    _fields_ = [("N", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("env_kind", C.c_int),
+                ("env_state", C.c_void_p), ("env_seed", C.c_uint64), ("env_id0", C.c_int64),
+                ("obs", C.c_void_p), ("obs_out", C.c_void_p), ("u", C.c_void_p),
+                ("seed", C.c_uint64), ("counter", C.c_uint64), ("counter_dev", C.c_void_p),
+                ("epsilon", C.c_float), ("epsilon_dev", C.c_void_p),
+                ("policy", Td3ActorParams),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p), ("cap", C.c_int64), ("cursor", C.c_int64), ("cursor_dev", C.c_void_p),
+                ("action_out", C.c_void_p), ("rew_out", C.c_void_p), ("done_out", C.c_void_p), ("ep_ret_out", C.c_void_p),
+                ("ep_stats", C.c_void_p), ("images", C.c_void_p)]
+
+
+class DqnUpdateArgs(C.Structure):
+    _c_name_ = "gymrl_dqn_update_args"
+    _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("gamma", C.c_float),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p),
+                ("idx", C.c_void_p), ("idx_seed", C.c_uint64), ("idx_counter", C.c_uint64), ("idx_size", C.c_int64),
+                ("idx_dev", C.c_void_p),
+                ("policy", Td3ActorParams), ("target", Td3ActorParams),
+                ("policy_p", C.c_void_p), ("policy_m", C.c_void_p), ("policy_v", C.c_void_p),
+                ("adam_policy", C.c_float * 4), ("adam_policy_dev", C.c_void_p),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps_adam", C.c_double),
+                ("clamp_abs", C.c_float), ("loss_sum", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
+
+
 class WeightImage(C.Structure):
     _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
@@ -435,6 +463,11 @@ SIGNATURES = {
     "gymrl_qlearn_state_bytes": (_sz, [_i]),
     "gymrl_qlearn_train": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _u64, _i64, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_qlearn_eval": (_i, [_i, _i, _vp, _i, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_dqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_dqn_pack_images": (_i, [_P(DqnUpdateArgs), _vp]),
+    "gymrl_dqn_args_bytes": (_sz, [_i]),
+    "gymrl_dqn_act_step": (_i, [_P(DqnActArgs), _vp]),
+    "gymrl_dqn_update": (_i, [_P(DqnUpdateArgs), _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

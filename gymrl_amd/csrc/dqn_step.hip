@@ -1,0 +1,220 @@
+// dqn_step.hip — DQN's CartPole vector step (dqn_cartpole.py:124-133, :135-168) on the row-slab stages of
+// slab_step_device.hpp, in dsac_step.hip's scheme:
+//
+//   dqn_act_kernel  N/16 workgroups: policy net Q values, epsilon-greedy, CartPole step, replay row               (acting)
+//   dqn_r1_kernel   B/16 workgroups: draw + gather, policy(s) | target(s'), TD target, loss gradient, dX chain    (rows)
+//   sac_dw_kernel   the policy net's tiles + the +-1 gradient clamp + Adam, the loss sum                         (tiles)
+//
+// Discrete SAC's step with ONE online network and a hard-copied target: two chains in the row phase where dSAC runs five, no
+// second row phase, no Polyak twins in the tile phase (the segments carry none: the hard copy is the trainer's), and the
+// reference's clamp of every gradient element to +-1 (:163-165) as DwArgs.clamp_abs.  ONE workgroup carries a slab through the
+// whole row phase — policy(s) and target(s') ride along as items of the same stages — so nothing here waits for another
+// workgroup: no flag, no counter; launch order on one stream is the only ordering.
+#include "policy_device.hpp"
+#include "slab_step_device.hpp"
+
+namespace {
+
+using namespace gymrl;
+using namespace gymrl::slab;
+
+constexpr int kDqnMaxBatch = 256;      // (ops.DQN_FUSED_MAX_BATCH) one grid of at most 16 slabs in the row phase: the loss sum is one block's
+struct DqnImages {                     // gymrl_dqn_update_args.images, f32[3][H*H]: two forward images, then the input-gradient image
+  const float *pf, *tf, *pb;
+  __host__ __device__ DqnImages(const float* base, int H) {
+    const ImageSlots at(base, H);
+    pf = at(0); tf = at(1); pb = at(2);
+  }
+  static constexpr int kCount = 3;
+  static PackTable sources(const gymrl_dqn_update_args& a) {
+    return PackTable{{a.policy.w[1], a.target.w[1], a.policy.w[1], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 2};
+  }
+};
+
+// hand-off between the row phase and the tile phase (caller-owned workspace)
+struct DqnWs {
+  float* s;                            // [B][D]: the gathered states
+  float *H1, *Z1, *H2, *Z2, *dq;       // the policy net's activations and dL/dz per layer ([B][H]; dq [B][A])
+  double* terms;                       // [B][3]: the row's td^2 in column 0 (sac_dw_body's row pitch)
+  __host__ __device__ static size_t carve(DqnWs* w, void* base, int B, int D, int A, int H) {
+    carve_taker take{base};
+    float* s = take((size_t)B * D);
+    float* h[4];
+    for (int i = 0; i < 4; ++i) h[i] = take((size_t)B * H);
+    float* dq = take((size_t)B * A);
+    double* terms = reinterpret_cast<double*>(take((size_t)B * 6));
+    if (w) { w->s = s; w->H1 = h[0]; w->Z1 = h[1]; w->H2 = h[2]; w->Z2 = h[3]; w->dq = dq; w->terms = terms; }
+    return take.off;
+  }
+};
+
+// ---- R1: draw + gather, policy(s) next to target(s'), the TD target and the loss gradient, the policy net's dX chain ----
+template <int HC>
+__global__ __launch_bounds__(kThreads) void dqn_r1_kernel(const gymrl_dqn_update_args a, const DqnWs ws) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Lds L;
+  const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
+  // four activation slabs: the target's first (T1) is dead once its second layer is out and carries dL/dz2 then
+  const int P1 = L.big, T1 = P1 + 16 * ld, P2 = T1 + 16 * ld, T2 = P2 + 16 * ld;
+  const int Z0 = T1;
+  const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
+  const int t = threadIdx.x;
+  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
+  const DqnImages im(a.images, H);
+  const gymrl_td3_actor_params &p = a.policy, &tg = a.target;
+  // ---- index draw + ring gather: one thread per row, rows beyond the batch are zero ----
+  if (t < 16) {
+    const int b = row0 + t;
+    const bool ok = t < nrows;
+    const int64_t row = ok ? replay_draw_row(a, b) : 0;
+    for (int k = 0; k < kMaxD; ++k) {
+      const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
+      lds[L.S + t * kMaxD + k] = sv;
+      lds[L.S2 + t * kMaxD + k] = (ok && k < D) ? a.r_next[row * D + k] : 0.0f;
+      if (ok && k < D) ws.s[(size_t)b * D + k] = sv;
+    }
+    lds[L.Misc + t * 4 + 0] = ok ? a.r_reward[row] : 0.0f;
+    lds[L.Misc + t * 4 + 1] = ok ? (float)a.r_flag[row] : 0.0f;            // dones become float32
+    lds[L.Misc + t * 4 + 2] = ok ? __int_as_float((int)a.r_action[row]) : 0.0f;
+  }
+  __syncthreads();
+  // ---- policy_net(s) (:150) and target_net(s') (:154): two independent chains, layer by layer ----
+  {
+    const FwdItem st[2] = {fwd_item(L.S, kD, -1, 0, D, D, H, p.w[0], p.b[0], P1, ld, ws.H1, H, R),
+                           fwd_item(L.S2, kD, -1, 0, D, D, H, tg.w[0], tg.b[0], T1, ld, nullptr, 0, R)};
+    fwd_stage<2>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  {
+    const FwdItem st[2] = {fwd_item(P1, ld, -1, 0, H, H, H, p.w[1], p.b[1], P2, ld, ws.H2, H, R, 0.0f, 0.0f, im.pf),
+                           fwd_item(T1, ld, -1, 0, H, H, H, tg.w[1], tg.b[1], T2, ld, nullptr, 0, R, 0.0f, 0.0f, im.tf)};
+    fwd_stage<2>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  {
+    const FwdItem st[2] = {fwd_item(P2, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Cq0, 4, nullptr, 0, NA),
+                           fwd_item(T2, ld, -1, 0, H, H, A, tg.w[2], tg.b[2], L.Q0, 4, nullptr, 0, NA)};
+    fwd_stage<2>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  if (t < 16) {                           // offpolicy.hip dqn_td_kernel (:155-161) with qn_online == nullptr, w == nullptr, gamma_n = gamma
+    const float* sel = lds + L.Q0 + t * 4;
+    int astar = 0;
+    float best = sel[0];
+    for (int k = 1; k < A; ++k) if (sel[k] > best) { best = sel[k]; astar = k; }
+    const float nq = sel[astar];
+    const float y = lds[L.Misc + t * 4 + 0] + a.gamma * nq * (1.0f - lds[L.Misc + t * 4 + 1]);
+    const int act = __float_as_int(lds[L.Misc + t * 4 + 2]);
+    const float td = lds[L.Cq0 + t * 4 + act] - y;
+    const float wb = 1.0f, invB = 1.0f / (float)a.B;
+    for (int k = 0; k < 4; ++k) {
+      const float d = k == act ? (2.0f * td) * wb * invB : 0.0f;
+      lds[L.Dq0 + t * 4 + k] = d;
+      if (t < nrows && k < A) ws.dq[(size_t)(row0 + t) * A + k] = d;
+    }
+    if (t < nrows) ws.terms[(size_t)(row0 + t) * 3] = (double)((td * td) * wb);
+  }
+  __syncthreads();
+  // ---- the policy net's input-gradient chain (what backward() computes before the weight gradients) ----
+  bwd_one(lds, {BwdItem{L.Dq0, 4, A, p.w[2], H, -1, nullptr, P2, ld, R, Z0, ld, ws.Z2, H, nullptr}}, row0, nrows);
+  bwd_stage(lds, {BwdItem{Z0, ld, H, p.w[1], H, -1, nullptr, P1, ld, R, -1, 0, ws.Z1, H, im.pb}}, row0, nrows);      // (the last stage: no barrier behind it)
+}
+
+// ---- acting: the policy net's Q values, the epsilon-greedy choice (gymrl_epsilon_greedy's keys), CartPole step, replay row ----
+template <int HC>
+__global__ __launch_bounds__(kThreads) void dqn_act_kernel(const gymrl_dqn_act_args a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Lds L;
+  const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
+  const int X0 = L.big, X1 = X0 + 16 * ld;
+  const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.N - row0);
+  const int t = threadIdx.x;
+  if (t < 16) {
+    const int i = row0 + t;
+    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = (t < nrows && k < D) ? a.obs[(size_t)i * D + k] : 0.0f;
+  }
+  __syncthreads();
+  const int R = GYMRL_ACT_RELU, kD = kMaxD, kA = kMaxA;
+  const float* pf = (a.images && (H & 15) == 0) ? a.images : nullptr;
+  fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.policy.w[0], a.policy.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);
+  fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, a.policy.w[1], a.policy.b[1], X1, ld, nullptr, 0, R, 0.0f, 0.0f, pf)}, row0, nrows);
+  fwd_one(lds, {fwd_item(X1, ld, -1, 0, H, H, A, a.policy.w[2], a.policy.b[2], L.Mean, kA, nullptr, 0, GYMRL_ACT_NONE)}, row0, nrows);
+  // one lane per env: the choice, CartPole step with auto-reset, replay row (the first wave: 16 lanes busy)
+  if (t < 64) {
+    int act = 0;
+    if (t < nrows) {
+      const uint64_t counter = a.counter_dev ? a.counter_dev[0] : a.counter;
+      const float eps = a.epsilon_dev ? a.epsilon_dev[0] : a.epsilon;
+      act = epsilon_greedy_pick(lds + L.Mean + t * kMaxA, A, a.u ? a.u + (size_t)(row0 + t) * 2 : nullptr, a.seed,
+                                (uint64_t)(a.env_id0 + row0 + t), counter, eps);
+    }
+    cartpole_act_tail(a, lds, L, t, row0, nrows, act);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gymrl_dqn_update_workspace_bytes(int B, int D, int A, int H) { return workspace_bytes<DqnWs>(B, D, A, H); }
+size_t gymrl_dqn_args_bytes(int which) { return which == 0 ? sizeof(gymrl_dqn_act_args) : which == 1 ? sizeof(gymrl_dqn_update_args) : 0; }
+
+static int dqn_set_lds_attr() {
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)dqn_r1_kernel<0>, (const void*)dqn_r1_kernel<256>, (const void*)dqn_act_kernel<0>,
+                                 (const void*)dqn_act_kernel<256>}, (int)lds_bytes(256, 4));
+}
+
+int gymrl_dqn_act_step(const gymrl_dqn_act_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_dqn_act_args& a = *args;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
+  if (const int rc = dqn_set_lds_attr()) return rc;
+  hipLaunchKernelGGL(a.H == 256 ? dqn_act_kernel<256> : dqn_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+static bool dqn_update_args_ok(const gymrl_dqn_update_args& a) {
+  if (!slab_shape_ok(a.B, kDqnMaxBatch, a.D, a.A, a.H)) return false;
+  if (!ring_ok(a) || !all_set({a.workspace, a.loss_sum, a.policy_p, a.policy_m, a.policy_v}) || !draw_ok(a, /*idx_dev_counts=*/true) ||
+      !(a.clamp_abs >= 0.0f))
+    return false;
+  return net_ok(a.policy) && net_ok(a.target);
+}
+
+int gymrl_dqn_pack_images(const gymrl_dqn_update_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_dqn_update_args& a = *args;
+  if (!pack_args_ok(a) || !all_set({a.policy.w[1], a.target.w[1]})) return -22;
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, DqnImages::kCount), dim3(256), 0, (hipStream_t)stream_, DqnImages::sources(a), a.images, a.H);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+int gymrl_dqn_update(const gymrl_dqn_update_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_dqn_update_args& a = *args;
+  if (!dqn_update_args_ok(a)) return -22;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = dqn_set_lds_attr()) return rc;
+  DqnWs ws;
+  DqnWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
+  const int B = a.B, D = a.D, A = a.A, H = a.H, slabs = (B + 15) / 16;
+  const DqnImages im(a.images, H);
+  // the policy net's tile list: no target twins (the hard copy is the caller's), the clamp in front of Adam's moments
+  DwArgs p{};
+  DwBuilder pb{p, B};
+  pb.seg(ws.Z1, H, H, ws.s, D, nullptr, 0, D, D, a.policy.w[0], a.policy.b[0]);
+  pb.seg(ws.Z2, H, H, ws.H1, H, nullptr, 0, H, H, a.policy.w[1], a.policy.b[1], nullptr, nullptr, im.pf, im.pb);
+  pb.seg(ws.dq, A, A, ws.H2, H, nullptr, 0, H, H, a.policy.w[2], a.policy.b[2]);
+  // (at most 256 rows: no slice partials, and the loss sum closes in this launch's last block — dqn_td_kernel's one block)
+  pb.close(a, nullptr, a.policy_p, a.policy_m, a.policy_v, a.adam_policy, a.adam_policy_dev, 0.0f, 0.0f, ws.terms, nullptr, 0, 1, a.loss_sum);
+  p.clamp_abs = a.clamp_abs;
+  hipLaunchKernelGGL(H == 256 ? dqn_r1_kernel<256> : dqn_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, 4), stream, a, ws);
+  launch_dw(p, stream);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

@@ -459,9 +459,11 @@ __host__ __device__ __forceinline__ int bwd_weight_rows_per_slice(int B, int sli
 // torch.optim.Adam's step on ONE element (optim.hip adam_one with grad_scale = scale = 1 and no clamp: the off-policy
 // optimisers that clip by norm keep their own launch).  step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t).
 struct AdamScalars { float step_size, bc2_sqrt, omb1, beta2, omb2, eps; };
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& a) {
+// clamp_abs > 0: the gradient element is clamped to +-clamp_abs before the moments, where optim.hip adam_one does it
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& a, float clamp_abs = 0.0f) {
   float gg = g * 1.0f;
   gg = gg * 1.0f;
+  if (clamp_abs > 0.0f) gg = fminf(fmaxf(gg, -clamp_abs), clamp_abs);
   m = m + (gg - m) * a.omb1;
   v = v * a.beta2 + a.omb2 * gg * gg;
   const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;

@@ -12,8 +12,7 @@
 // All of these are per-sample elementwise maps over B <= a few thousand rows of <= 8
 // words: launch-latency bound at the reference batch sizes, HBM-streaming at large B.
 // Loss sums are reduced block-partials -> fixed-order final sum (no float atomics).
-#include "gymrl_device.hpp"
-#include "../../include/gymrl.h"
+#include "policy_device.hpp"
 
 using namespace gymrl;
 
@@ -101,24 +100,7 @@ __global__ __launch_bounds__(kBlock) void epsilon_greedy_kernel(const float* __r
                                                                 int32_t* __restrict__ act) {
   const int i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
-  float u0, u1;
-  if (u) { u0 = u[2 * i]; u1 = u[2 * i + 1]; }
-  else {
-    const uint64_t env = (uint64_t)(env_id0 + i);
-    const u32x4 r = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), (uint32_t)counter,
-                               RNG_POLICY | 0x08000000u | (uint32_t)((counter >> 32) & 0x07FFFFFFu));
-    u0 = u01f(r.x); u1 = u01f(r.y);
-  }
-  int a;
-  if (u0 < epsilon) {                                                // random.random() < eps -> action_space.sample()
-    a = (int)(u1 * (float)A);
-    a = a >= A ? A - 1 : a;
-  } else {
-    a = 0;
-    float best = q[(size_t)i * A];
-    for (int k = 1; k < A; ++k) { const float v = q[(size_t)i * A + k]; if (v > best) { best = v; a = k; } }
-  }
-  act[i] = a;
+  act[i] = epsilon_greedy_pick(q + (size_t)i * A, A, u ? u + 2 * (size_t)i : nullptr, seed, (uint64_t)(env_id0 + i), counter, epsilon);
 }
 
 // --------------------------------------------------------------- D4 / R4 -----

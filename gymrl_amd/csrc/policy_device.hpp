@@ -1,5 +1,5 @@
 // policy_device.hpp — row helpers, log-softmax and the categorical draw shared by ppo.hip and the
-// persistent rollout kernel.
+// persistent rollout kernel; the epsilon-greedy choice shared by offpolicy.hip and dqn_step.hip.
 #pragma once
 #include "gymrl_device.hpp"
 #include "../../include/gymrl.h"
@@ -137,6 +137,30 @@ __device__ __forceinline__ int categorical_pick(const float (&z)[A], const float
   lp = ln[0];
 #pragma unroll
   for (int k = 1; k < A; ++k) if (a == k) lp = ln[k];
+  return a;
+}
+
+// D3 (dqn_cartpole.py:117-133) for ONE env: explore iff u0 < epsilon with the action (int)(u1 * A) clamped to A - 1, else the
+// FIRST maximum of the env's Q row.  u_row: the explicit pair {u0, u1} (parity mode) or nullptr: Philox keyed by (seed, global
+// env id, counter).  Shared by epsilon_greedy_kernel and the fused DQN acting kernel, so both produce the same action.
+__device__ __forceinline__ int epsilon_greedy_pick(const float* q_row, int A, const float* u_row, uint64_t seed, uint64_t env,
+                                                   uint64_t counter, float epsilon) {
+  float u0, u1;
+  if (u_row) { u0 = u_row[0]; u1 = u_row[1]; }
+  else {
+    const u32x4 r = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), (uint32_t)counter,
+                               RNG_POLICY | 0x08000000u | (uint32_t)((counter >> 32) & 0x07FFFFFFu));
+    u0 = u01f(r.x); u1 = u01f(r.y);
+  }
+  int a;
+  if (u0 < epsilon) {                                                // random.random() < eps -> action_space.sample()
+    a = (int)(u1 * (float)A);
+    a = a >= A ? A - 1 : a;
+  } else {
+    a = 0;
+    float best = q_row[0];
+    for (int k = 1; k < A; ++k) { const float v = q_row[k]; if (v > best) { best = v; a = k; } }
+  }
   return a;
 }
 

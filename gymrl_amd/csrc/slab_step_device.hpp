@@ -1,6 +1,6 @@
 // slab_step_device.hpp — what the row-slab step kernels of every off-policy algorithm share.
 //
-// offpolicy_step.hip (SAC), rainbow_step.hip (Rainbow), td3_step.hip (TD3 / DDPG) and dsac_step.hip (discrete SAC) carry a 16-row slab of the batch through
+// offpolicy_step.hip (SAC), rainbow_step.hip (Rainbow), td3_step.hip (TD3 / DDPG), dsac_step.hip (discrete SAC) and dqn_step.hip (DQN) carry a 16-row slab of the batch through
 // a chain of layers in ONE workgroup of 16 waves (offpolicy_step.hip's header has the argument).  Here: the stages (fwd_stage /
 // bwd_stage over FwdItem / BwdItem), the LDS layout (Lds), the narrow layers' staging (Stager), the hand-off flags,
 // the grid shapes and their deadlock argument (slab_grid), SAC's and TD3's hand-off workspace (SacWs), the
@@ -367,6 +367,7 @@ struct DwArgs {
   float adam[4]; const float* adam_dev;
   float omb1, beta2, omb2, eps;
   float tau, omt;
+  float clamp_abs;                                // > 0: every gradient element is clamped to +-clamp_abs before Adam's moments (optim.hip adam_one; DQN's +-1); 0: off
   int store_grads;                                // != 0: seg.W / seg.b are gradient DESTINATIONS (overwritten), no optimiser step
   // store_grads: segment 0 is Rainbow's stacked noisy head and its gradient is split here (lin.hip noisy_split_kernel)
   int split_heads, split_A;
@@ -573,7 +574,7 @@ __device__ __forceinline__ void sac_dw_body(const DwArgs& a, const int block, co
       const size_t o = (size_t)no * s.K + kc;
       const size_t po = (size_t)(s.W - a.p) + o;
       float P = Pv[g], M = Mv[g], V = Vv[g];
-      lin::adam_elem(P, acc[g], M, V, ad);
+      lin::adam_elem(P, acc[g], M, V, ad, a.clamp_abs);
       s.W[o] = P; a.m[po] = M; a.v[po] = V;
       float T = 0.0f;
       if (s.Wt && polyak) { T = a.tau * P + a.omt * Tv[g]; s.Wt[o] = T; }
@@ -587,7 +588,7 @@ __device__ __forceinline__ void sac_dw_body(const DwArgs& a, const int block, co
   if (cg == 0 && q == 0 && n < s.N && s.b) {
     const size_t po = (size_t)(s.b - a.p) + n;
     float P = s.b[n], M = a.m[po], V = a.v[po];
-    lin::adam_elem(P, colsum, M, V, ad);
+    lin::adam_elem(P, colsum, M, V, ad, a.clamp_abs);
     s.b[n] = P; a.m[po] = M; a.v[po] = V;
     if (s.bt && polyak) s.bt[n] = a.tau * P + a.omt * s.bt[n];
   }

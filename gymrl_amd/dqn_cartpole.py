@@ -6,6 +6,9 @@ Underneath: `num_envs` CartPole instances step on the GPU, the replay buffer is 
 device-resident SoA ring (append / uniform-index / gather kernels), epsilon-greedy,
 the TD target + MSE loss forward/backward and the grad-clamp(+-1) + Adam step are HIP
 kernels behind the C-ABI; the three Linear layers run through PyTorch-ROCm.
+
+With Config.fused_step the vector step is gymrl_dqn_act_step + gymrl_dqn_update (csrc/dqn_step.hip: one launch to act,
+two to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described above.
 """
 import copy
 from collections import deque
@@ -16,7 +19,7 @@ import torch.nn as nn
 
 from . import ops
 from .envs import EpisodeTracker, VecEnv
-from .flat import FusedAdam, GradSink, flatten_module
+from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear
 from .utils import scalar
 
@@ -41,6 +44,8 @@ class Config:
         self.num_envs = 1
         self.updates_per_step = 1            # reference: one update() per env step (:184)
         self.use_graphs = True               # replay the update as one captured hipGraph (train(); update() stays eager)
+        self.fused_step = False              # the vector step as gymrl_dqn_act_step + gymrl_dqn_update (csrc/dqn_step.hip): opt-in
+        self.fused_images = True             # ... with weight images of the H x H layer (H % 16 == 0)
 
 
 def layer_init(layer, std=np.sqrt(2)):
@@ -132,7 +137,7 @@ class ReplayBuffer:
         self.cursor, self.size, self.draws = int(sd["cursor"]), int(sd["size"]), int(sd["draws"])
 
 
-class DQNTrainer:
+class DQNTrainer(WeightImages):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -184,6 +189,154 @@ class DQNTrainer:
 
     def load_target(self):
         self.target_flat.copy_(self.flat_params)        # target_net.load_state_dict(policy_net.state_dict())
+        self._images_stale()                            # the fused step's image of the target is rebuilt before its next launch
+
+    # ------------------------------------------------------------ fused vector step (csrc/dqn_step.hip) -------
+    CHUNK = 16                         # vector steps per StepChunk replay (= the episode tracker's flush period)
+
+    def _fused_update_ok(self):
+        """update() as gymrl_dqn_update: opt-in (cfg.fused_step) and a matter of shapes."""
+        cfg, m = self.cfg, self.memory
+        return (bool(getattr(cfg, "fused_step", False))
+                and ops.dqn_fused_shape_ok(cfg.batch_size, m.ring[0].shape[1], self.action_dim, cfg.hidden_dim))
+
+    def _fused_ok(self):
+        """The whole vector step fused: the update AND acting + env step + replay row (gymrl_dqn_act_step steps CartPole
+        itself and has no `abandon`: the trainer's own step cap must not cut an episode short; one update per step)."""
+        cfg, env = self.cfg, self.env
+        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind == ops.CARTPOLE
+                and cfg.max_steps >= env.max_steps and cfg.updates_per_step == 1 and self.memory.capacity >= env.n)
+
+    def _fused_args(self):
+        if self._fused is None or self._fused[3] is not self.env:
+            cfg, env, m = self.cfg, self.env, self.memory
+            D, A = m.ring[0].shape[1], self.action_dim
+            img = ops.dqn_images(cfg.hidden_dim, self.device) if getattr(cfg, "fused_images", True) else None
+            act = (ops.dqn_act_args(env, self.policy_net, m.ring, m.capacity, img)
+                   if isinstance(env, VecEnv) and env.kind == ops.CARTPOLE else None)
+            ws = ops.dqn_update_workspace(cfg.batch_size, D, A, cfg.hidden_dim, self.device)
+            upd = ops.dqn_update_args(cfg.batch_size, D, A, self.policy_net, self.target_net, self.optimizer, m.ring, cfg.gamma,
+                                      self._loss, ws, img)
+            self._fused = (act, upd, ws, env, img)
+            self._images_stale()
+        if self._fused[4] is not None:         # (flat.WeightImages: rebuilt when a parameter moved outside the fused update)
+            self._refresh_images(((self.flat_params, self.policy_net), (self.target_flat, self.target_net)),
+                                 ops.dqn_pack_images, self._fused[1])
+        return self._fused
+
+    def _update_fused(self, indices=None, dev=None):
+        """update() as gymrl_dqn_update's two launches.  dev = (draw, adam) device records of a StepChunk replay; None: this
+        call's scalars travel as arguments and the host counters advance here."""
+        m = self.memory
+        upd = self._fused_args()[1]
+        if dev is not None:
+            ops.dqn_update(upd, idx_seed=m.seed, idx_dev=dev[0], idx_size=m.capacity, adam_policy_dev=dev[1])
+            return
+        if indices is None:
+            counter, size = m.draws, m.size
+            m.draws += 1
+        else:
+            counter, size = 0, 0
+            if indices.dtype != torch.int32:
+                indices = indices.to(torch.int32)
+        ops.dqn_update(upd, idx=indices, idx_seed=m.seed, idx_counter=counter, idx_size=size, adam_policy=self.optimizer.next_bias())
+
+    def _act_fused(self, lb, obs, nxt, ep_ret, done, dev=None):
+        """Acting + env step + replay row of one vector step: one launch (select_action + env.step + memory.push).
+        dev = (push cursor, act counter, epsilon) device records of a StepChunk replay; None: get_epsilon() and the host
+        counters advance here."""
+        env, m = self.env, self.memory
+        u = None if self._parity_u is None else next(self._parity_u)
+        eps, cursor_dev, counter_dev, eps_dev = 0.0, None, None, None
+        if dev is None:
+            eps = self.get_epsilon()
+            self._act_counter += 1
+        else:
+            cursor_dev, counter_dev, eps_dev = dev
+        ops.dqn_act_step(self._fused_args()[0], env, obs, nxt, epsilon=eps, epsilon_dev=eps_dev, cursor=m.cursor, cursor_dev=cursor_dev,
+                         u=u, seed=self.base_seed, counter=self._act_counter, counter_dev=counter_dev,
+                         rew_out=lb["rew"], done_out=done, ep_ret_out=ep_ret, ep_stats=env.ep_stats)
+        if dev is None:
+            m.advance(env.n)
+
+    def _loop_buffers(self, N, D):
+        """Step buffers that outlive one train() call: the captured StepChunk graph holds their addresses."""
+        lb = getattr(self, "_loop", None)
+        if lb is None or lb["N"] != N:
+            d = self.device
+            lb = self._loop = dict(N=N, obs=torch.empty(N, D, device=d), nxt=torch.empty(N, D, device=d), rew=torch.empty(N, device=d),
+                                   tracker=EpisodeTracker(N, d, flush_every=1 if N == 1 else self.CHUNK))
+        lb["tracker"].k, lb["tracker"].episodes = 0, 0
+        return lb
+
+    def _chunk_body(self, lb, j):
+        """Vector step j of a StepChunk capture: the act launch and the update's, every per-step scalar read from record j."""
+        ch, tr = self._chunk, lb["tracker"]
+        obs, nxt = (lb["obs"], lb["nxt"]) if j % 2 == 0 else (lb["nxt"], lb["obs"])
+        self._act_fused(lb, obs, nxt, tr.ret[j], tr.done[j],
+                        dev=(ch.view(j, "push"), ch.view(j, "act"), ch.view(j, "eps", torch.float32)))
+        self._update_fused(dev=(ch.view(j, "draw"), ch.view(j, "adam", torch.float32)))
+
+    def _stage_chunk(self):
+        """The host's bookkeeping of the next CHUNK vector steps, in the eager loop's order, written into the records."""
+        ch, m, N = self._chunk, self.memory, self.env.n
+        for j in range(ch.K):
+            ch.set(j, "push", m.cursor)
+            m.advance(N)
+            ch.set(j, "eps", self.get_epsilon())       # rounded to the float32 the eager call passes
+            self._act_counter += 1
+            ch.set(j, "act", self._act_counter)
+            ch.set(j, "draw", m.draws, m.size)
+            m.draws += 1
+            ch.set_bytes(j, "adam", self.optimizer.next_bias())
+        ch.flush()
+
+    def _train_fused(self, max_vector_steps=None):
+        """_train on the fused step.  With hipGraphs on, CHUNK whole vector steps replay as one graph (graphs.StepChunk);
+        while the ring holds fewer rows than a batch — and for what a chunk cannot take — the loop is eager: the act launch,
+        then the update's, no host round trip (the loss sum stays on the device).  A chunk ends where the eager loop's
+        tracker flushes, and its episodes are collected THERE, before the next chunk is staged: the hard target copy and the
+        stop rule see `tracker.episodes` and `episode_rewards` at the same steps as in the eager loop."""
+        cfg, env, m = self.cfg, self.env, self.memory
+        N, D = env.n, env.obs_dim
+        lb = self._loop_buffers(N, D)
+        obs, nxt, tracker = lb["obs"], lb["nxt"], lb["tracker"]
+        env.reset(obs)
+        step, last_target = 0, 0
+        graphed = bool(getattr(cfg, "use_graphs", True)) and self._parity_indices is None
+        chunked = graphed and N > 1 and self._parity_u is None
+        limit = max_vector_steps or (cfg.max_episodes * cfg.max_steps // N + 1)
+        solved = lambda: len(self.episode_rewards) >= 100 and np.mean(self.episode_rewards) >= 495.0   # noqa: E731
+        while tracker.episodes < cfg.max_episodes and step < limit:
+            # (a chunk runs to the next flush without looking at the stop rule: not where the rule already holds — the eager
+            #  loop stops after ONE step then, e.g. a train() call on a solved trainer)
+            if (chunked and tracker.k == 0 and limit - step >= self.CHUNK and obs is lb["obs"] and len(m) >= cfg.batch_size
+                    and not solved()):
+                if getattr(self, "_chunk", None) is None:
+                    from .graphs import StepChunk
+                    self._chunk = StepChunk(self.device, self.CHUNK, [("push", "q"), ("act", "Q"), ("eps", "f"), ("draw", "Qq"),
+                                                                      ("adam", "4f")])
+                self._fused_args()             # weight images rebuilt (if stale) BEFORE the capture, not inside it
+                self._stage_chunk()
+                self._chunk.run(lambda j: self._chunk_body(lb, j), key=(id(env), env.state.data_ptr()))
+                step += self.CHUNK
+                tracker.k = self.CHUNK
+                tracker.flush(self.episode_rewards)    # the eager loop's flush at this step: no lag (it could move a target copy)
+            else:
+                ep_ret, done = tracker.slot()
+                self._act_fused(lb, obs, nxt, ep_ret, done)
+                if len(m) >= cfg.batch_size:
+                    self._update_fused(None if self._parity_indices is None else next(self._parity_indices))
+                obs, nxt = nxt, obs
+                step += 1
+                tracker.advance(self.episode_rewards)
+            if tracker.episodes - last_target >= cfg.target_update_freq:    # :193-194
+                self.load_target()
+                last_target = tracker.episodes
+            if solved():
+                break
+        tracker.flush(self.episode_rewards)
+        self.env.close()
 
     def update(self, indices=None):
         """:135-168.  Returns the loss as a python float (one host sync, like loss.item())."""
@@ -191,6 +344,9 @@ class DQNTrainer:
             return 0.0
         if indices is None and self._parity_indices is not None:
             indices = next(self._parity_indices)
+        if self._fused_update_ok() and (indices is None or indices.numel() == self.cfg.batch_size):
+            self._update_fused(indices)
+            return float(self._loss.item()) / self.cfg.batch_size
         if indices is None:
             indices = self.memory.draw_indices(self.cfg.batch_size)
         B = self._update_body(indices)
@@ -198,6 +354,7 @@ class DQNTrainer:
 
     def _update_body(self, indices, bias=None):
         """Everything after the index draw; bias = f32[4] device view of Adam's step scalars under a hipGraph."""
+        self._images_stale()                  # this path writes the parameters without the fused step's weight images
         states, actions, rewards, next_states, dones = self.memory.gather(indices)
         q = self.policy_net(states)
         with torch.no_grad():
@@ -216,6 +373,9 @@ class DQNTrainer:
         cfg, m = self.cfg, self.memory
         if len(m) < cfg.batch_size:
             return
+        if self._fused_update_ok():        # two launches: nothing left for a graph to save
+            return self._update_fused()
+        self._images_stale()                  # (a replay runs no Python: _update_body's own reset is not enough)
         if self._graph is None:
             from .graphs import GraphedStep, StepScalars
             self._scalars = StepScalars(self.device)
@@ -241,6 +401,7 @@ class DQNTrainer:
         from .utils import checkpoint
         rest = checkpoint.load_agent(path, {"policy_net": self.policy_net, "target_net": self.target_net},
                                      {"optimizer": (self.policy_net, self.optimizer)})
+        self._images_stale()                  # the fused step's weight images are rebuilt from the loaded parameters
         self.epsilon, self.sample_count = float(rest["epsilon"]), int(rest["sample_count"])
         self._act_counter = int(rest["_act_counter"])
         self.episode_rewards.clear()
@@ -256,6 +417,8 @@ class DQNTrainer:
     def _train(self, max_vector_steps=None):
         """:170-212 with N lock-stepped envs; "episodes" counts finished episodes over all envs."""
         cfg, env = self.cfg, self.env
+        if self._fused_ok():
+            return self._train_fused(max_vector_steps)
         N, D = env.n, env.obs_dim
         obs, nxt, tobs = (torch.empty(N, D, device=self.device) for _ in range(3))
         rew = torch.empty(N, device=self.device)

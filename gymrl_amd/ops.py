@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DqnActArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -1509,7 +1509,7 @@ def _addr(t):
 FUSED_MAX_BATCH = 8192     # row-slab kernels: B <= 256 as resident 2-D grids, above that slab-adjacent 1-D grids (slab_step_device.hpp slab_grid)
 
 
-# What the four row-slab steps' bindings below share (slab_step_device.hpp slab_shape_ok is the library's side of the first)
+# What the five row-slab steps' bindings below share (slab_step_device.hpp slab_shape_ok is the library's side of the first)
 def _fused_shape_ok(B, D, A, H, max_batch, max_A):
     return 0 < B <= max_batch and 0 < D <= 8 and 0 < A <= max_A and 4 <= H <= 256 and H % 4 == 0
 
@@ -1858,6 +1858,96 @@ def dsac_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None
     a.adam_critic1_dev, a.adam_critic2_dev, a.adam_actor_dev = _addr(adam_critic1_dev), _addr(adam_critic2_dev), _addr(adam_actor_dev)
     a.alpha_t, a.alpha_bias_dev = int(alpha_t), _addr(alpha_bias_dev)
     check(lib().gymrl_dsac_update(C.byref(a), _stream()), "gymrl_dsac_update")
+
+
+# ------------------------------------------------- fused DQN vector step ---
+DQN_FUSED_MAX_BATCH = 256      # one grid of at most 16 slabs in the row phase (dqn_step.hip kDqnMaxBatch)
+
+
+def dqn_fused_shape_ok(B, D, A, H):
+    """Shapes gymrl_dqn_act_step / gymrl_dqn_update take (include/gymrl.h): everything else runs layer by layer."""
+    return _fused_shape_ok(B, D, A, H, DQN_FUSED_MAX_BATCH, 4)
+
+
+class _QLayers:
+    """dqn_cartpole.QNetwork's three Linear layers (net.0, net.2, net.4) under the names the shared helpers read."""
+
+    def __init__(self, qnet):
+        self.fc1, self.fc2, self.fc3 = qnet.net[0], qnet.net[2], qnet.net[4]
+
+
+def dqn_update_workspace(B, D, A, H, device):
+    return _zeroed_workspace(lib().gymrl_dqn_update_workspace_bytes(B, D, A, H), device)
+
+
+def dqn_images(H, device):
+    """The three weight images of the H x H layer (gymrl_dqn_update_args.images), or None when H % 16 != 0."""
+    return torch.zeros(3 * H * H, device=device) if H % 16 == 0 else None
+
+
+def dqn_pack_images(a):
+    """gymrl_dqn_pack_images: rebuild every image from the parameters as they are now."""
+    check(lib().gymrl_dqn_pack_images(C.byref(a), _stream()), "gymrl_dqn_pack_images")
+
+
+def dqn_act_args(env, policy, ring, cap, images=None):
+    """A gymrl_dqn_act_args with everything that does not change from step to step filled in."""
+    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"dqn_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
+    a = DqnActArgs()
+    layers = _QLayers(policy)
+    _set_act_env(a, env, layers, ring, cap, images)
+    _td3_actor_params(a.policy, layers)
+    return a
+
+
+def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, cursor_dev=None, u=None, seed=0, counter=0,
+                 counter_dev=None, action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None):
+    """gymrl_dqn_act_step: policy net on obs [N, D], the epsilon-greedy choice (u = f32[N, 2] uniforms or None:
+    gymrl_epsilon_greedy's Philox keys under (seed, counter); epsilon rounded to float32 as epsilon_greedy() passes it, or
+    epsilon_dev = f32[1] on the device), CartPole step with auto-reset, replay rows at (cursor + env) % cap — ONE launch."""
+    if tuple(obs.shape) != (a.N, a.D) or tuple(obs_out.shape) != (a.N, a.D):
+        raise ValueError(f"dqn_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
+    if u is not None and (u.dtype != torch.float32 or u.numel() != a.N * 2 or not u.is_contiguous()):
+        raise ValueError("dqn_act_step: u must be a contiguous float32 [N, 2]")
+    if action_out is not None and (action_out.dtype != torch.int32 or action_out.numel() != a.N):
+        raise ValueError("dqn_act_step: action_out must be int32 [N]")
+    _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, (action_out, rew_out, done_out, ep_ret_out, ep_stats))
+    a.u = _addr(u)
+    a.seed, a.counter, a.counter_dev = seed, counter, _addr(counter_dev)
+    a.epsilon, a.epsilon_dev = float(epsilon), _addr(epsilon_dev)
+    check(lib().gymrl_dqn_act_step(C.byref(a), _stream()), "gymrl_dqn_act_step")
+
+
+def dqn_update_args(B, D, A, policy, target, opt, ring, gamma, loss_sum, workspace, images=None):
+    """A gymrl_dqn_update_args with the per-trainer constants filled in.  opt: the policy net's FusedAdam (its clamp_abs is the
+    update's); loss_sum: f64[1] (sum of td^2)."""
+    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise ValueError("dqn_update_args: loss_sum must be a float64[1]")
+    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"dqn_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
+    a = DqnUpdateArgs()
+    p, t = _QLayers(policy), _QLayers(target)
+    a.B, a.D, a.A, a.H = B, D, A, p.fc1.weight.shape[0]
+    a.gamma = float(gamma)
+    _set_ring(a, ring)
+    _td3_actor_params(a.policy, p)
+    _td3_actor_params(a.target, t)
+    _set_optimisers(a, opt, policy=opt)
+    a.clamp_abs = float(opt.clamp_abs)
+    a.loss_sum, a.workspace, a.images = _addr(loss_sum), _addr(workspace), _addr(images)
+    return a
+
+
+def dqn_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None, adam_policy=None, adam_policy_dev=None):
+    """gymrl_dqn_update: dqn_cartpole.DQNTrainer.update() as two launches.  idx: i32[B] rows or None (the keyed draw);
+    adam_policy: the 16-byte block of adam_bias() (host) or adam_policy_dev a device view of it."""
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != a.B):
+        raise ValueError(f"dqn_update: idx must be int32 [{a.B}]")
+    _set_draw(a, idx, idx_seed, idx_counter, idx_size, idx_dev)
+    _set_adam_bias(a, adam_policy=adam_policy)
+    a.adam_policy_dev = _addr(adam_policy_dev)
+    check(lib().gymrl_dqn_update(C.byref(a), _stream()), "gymrl_dqn_update")
 
 
 # --------------------------------------------- fused Rainbow vector step ---

@@ -1501,6 +1501,65 @@ int gymrl_qlearn_train(int env_kind, int is_slippery, int shaped, double* Q, voi
 int gymrl_qlearn_eval(int env_kind, int is_slippery, const double* Q, int n_runs, int n_episodes, uint64_t seed,
                       int64_t stream_id0, int cap, double* returns, int32_t* lengths, uint8_t* flags, void* stream);
 
+/*
+ * DQN's CartPole vector step on the same row-slab kernels (csrc/dqn_step.hip): dqn_cartpole.py's select_action :124-133 with
+ * the env step and memory.push of its train loop :178-184, and update :135-168.  Discrete SAC's scheme with ONE online network
+ * and its hard-copied target (two chains in the row phase where dSAC runs five), epsilon-greedy in place of the categorical
+ * draw, and the reference's +-1 gradient clamp (:163-165) inside the tile kernel's Adam:
+ *   gymrl_dqn_act_step   ONE launch (:124-133 + env.step + memory.push): policy_net on the N observations (net.0, net.2 ReLU,
+ *                        net.4), gymrl_epsilon_greedy's choice under its keys (seed, counter, env_id0 + env; or the explicit
+ *                        u rows) with epsilon / epsilon_dev[0], CartPole step with auto-reset, replay row (obs, int32 action
+ *                        word, reward, TERMINAL next obs, done) at (cursor + env) % cap, the episode bookkeeping outputs
+ *   gymrl_dqn_update     update() (:135-168), two launches:
+ *     R1 rows   index draw (gymrl_uniform_indices' permutation, or idx) + ring gather; policy_net(s) and target_net(s') as two
+ *               items of the same stages (:150-155); gymrl_dqn_td_loss's expressions for plain DQN (no online selector, no
+ *               weights, gamma_n = gamma): a* = first argmax of the target row, y = r + gamma q' (1 - d), td, dq = 2 td / B
+ *               on the taken action, the row's float64 td^2 (:157-161); the policy net's input-gradient chain
+ *     T2 tiles  weight / bias gradient tiles (gymrl_lin_bwd_weight's order), each element clamped to +-clamp_abs, Adam
+ *               (:162-166; gymrl_adam_step's arithmetic); the loss sum in gymrl_dqn_td_loss's order (B <= 256: one block's)
+ *   The target network is read only: the hard copy (:193-194) stays with the caller, as does rebuilding the images after it.
+ * Results are the layer-by-layer path's bits (tests/test_dqn_fused_step_gpu.py).  Limits: H % 4 == 0, H <= 256, D <= 8, A <= 4,
+ * B <= 256 (-22 otherwise, before any launch: the trainer stays on the layer path); CartPole-v1 (D = 4, A = 2) for the act step.
+ */
+typedef struct {
+  int N, D, A, H;
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE */
+  void* env_state; uint64_t env_seed; int64_t env_id0;
+  const float* obs; float* obs_out;        /* f32[N, D] in / next observations out (post-reset where an episode ended) */
+  const float* u;                          /* f32[N, 2] uniforms {explore?, which action}, or NULL: gymrl_epsilon_greedy's Philox keys */
+  uint64_t seed, counter; const uint64_t* counter_dev;     /* select_action's (base seed, _act_counter) */
+  float epsilon; const float* epsilon_dev; /* get_epsilon()'s value as float32, or the same from the device (hipGraph replay) */
+  gymrl_td3_actor_params policy;           /* net.0, net.2, net.4: the Q values */
+  float* r_state; uint32_t* r_action; float* r_reward; float* r_next; uint8_t* r_flag; int64_t cap, cursor;
+  const int64_t* cursor_dev;
+  int32_t* action_out; float* rew_out; uint8_t* done_out; float* ep_ret_out; double* ep_stats;     /* any may be NULL */
+  const float* images;                     /* gymrl_dqn_update_args.images of the same trainer, or NULL (reads net.2 in place) */
+} gymrl_dqn_act_args;
+typedef struct {
+  int B, D, A, H;
+  float gamma;
+  const float* r_state; const uint32_t* r_action; const float* r_reward; const float* r_next; const uint8_t* r_flag;
+  const int32_t* idx;                      /* i32[B] explicit rows, or NULL: the keyed permutation of gymrl_uniform_indices */
+  uint64_t idx_seed, idx_counter; int64_t idx_size; const void* idx_dev;     /* idx_dev: {uint64 counter; int64 size} */
+  gymrl_td3_actor_params policy, target;   /* net.0, net.2, net.4 each; the target is read only */
+  float* policy_p; float* policy_m; float* policy_v;       /* the policy net's flat parameter buffer and its Adam moments */
+  float adam_policy[4];                    /* gymrl_adam_bias' block */
+  const float* adam_policy_dev;
+  double beta1, beta2, eps_adam;
+  float clamp_abs;                         /* gymrl_adam_step's clamp_abs (the reference: 1; 0: no clamp) */
+  double* loss_sum;                        /* f64[1] out: sum of td^2 */
+  void* workspace;                         /* >= gymrl_dqn_update_workspace_bytes(B, D, A, H) */
+  /* Weight images of the H x H layer (H % 16 == 0), f32[3][H*H], or NULL: forward policy net.2, forward target net.2, input
+   * gradient policy net.2.  gymrl_dqn_update keeps the policy's two equal to the parameters it writes; gymrl_dqn_pack_images
+   * rebuilds all three after anything else wrote a parameter (the hard target copy, load_state_dict, a checkpoint, ...). */
+  float* images;
+} gymrl_dqn_update_args;
+size_t gymrl_dqn_update_workspace_bytes(int B, int D, int A, int H);
+int gymrl_dqn_pack_images(const gymrl_dqn_update_args* args, void* stream);
+size_t gymrl_dqn_args_bytes(int which);      /* sizeof(gymrl_dqn_act_args) (0) / sizeof(gymrl_dqn_update_args) (1) */
+int gymrl_dqn_act_step(const gymrl_dqn_act_args* args, void* stream);
+int gymrl_dqn_update(const gymrl_dqn_update_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
