@@ -280,6 +280,19 @@ class DqnUpdateArgs(C.Structure):
                 ("clamp_abs", C.c_float), ("loss_sum", C.c_void_p), ("workspace", C.c_void_p), ("images", C.c_void_p)]
 
 
+class DdqnUpdateArgs(C.Structure):
+    _c_name_ = "gymrl_ddqn_update_args"
+    _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("dueling", C.c_int), ("gamma", C.c_float),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p), ("cap", C.c_int64), ("idx", C.c_void_p), ("is_weight", C.c_void_p),
+                ("policy", Td3ActorParams), ("target", Td3ActorParams),
+                ("policy_p", C.c_void_p), ("policy_m", C.c_void_p), ("policy_v", C.c_void_p),
+                ("adam_policy", C.c_float * 4), ("adam_policy_dev", C.c_void_p),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps_adam", C.c_double),
+                ("clamp_abs", C.c_float), ("td_out", C.c_void_p), ("loss_sum", C.c_void_p), ("workspace", C.c_void_p),
+                ("images", C.c_void_p)]
+
+
 class WeightImage(C.Structure):
     _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
@@ -468,6 +481,11 @@ SIGNATURES = {
     "gymrl_dqn_args_bytes": (_sz, [_i]),
     "gymrl_dqn_act_step": (_i, [_P(DqnActArgs), _vp]),
     "gymrl_dqn_update": (_i, [_P(DqnUpdateArgs), _vp]),
+    "gymrl_ddqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_ddqn_pack_images": (_i, [_P(DdqnUpdateArgs), _vp]),
+    "gymrl_ddqn_args_bytes": (_sz, [_i]),
+    "gymrl_ddqn_update": (_i, [_P(DdqnUpdateArgs), _vp]),
+    "gymrl_ddqn_duel_act_step": (_i, [_P(DqnActArgs), _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -1,0 +1,376 @@
+// ddqn_step.hip — double DQN + PER's update (ddqn_per_cartpole.py:197-244) on the row-slab stages of slab_step_device.hpp, in
+// dqn_step.hip's scheme:
+//
+//   ddqn_r1_kernel  B/16 workgroups: gather by the SAMPLED rows, policy(s) | policy(s') | target(s'), the double-Q target,
+//                   the importance-weighted loss gradient, the TD errors for the sum tree, the policy net's dX chain     (rows)
+//   sac_dw_kernel   the policy net's tiles + the +-1 gradient clamp + Adam, the loss sum                                (tiles)
+//
+// DQN's row phase with a third forward chain (the online network on s' picks the action the target network evaluates, :225-228),
+// a weight per row (:232) and td_out leaving for gymrl_per_update_td.  Acting is gymrl_dqn_act_step itself: the network has
+// QNetwork's shape.  The stratified draw stays gymrl_per_sample's launch (the weights' batch-wide maximum is a reduction across
+// workgroups): idx and is_weight arrive as arrays.  ONE workgroup carries a slab through the whole row phase, so nothing here
+// waits for another workgroup: no flag, no counter; launch order on one stream is the only ordering.
+//
+// LDS per workgroup: the small per-row slabs (kSmallFloats floats = 4.0 KB) + six [16][slab_ld(H)] activation slabs — P1, N1,
+// T1 (first layers of policy(s), policy(s'), target(s')) and P2, N2, T2 (second layers); all six are live across the second
+// stage.  T1 is dead once that stage is out and carries dL/dz2 through the input-gradient chain, as in dqn_r1_kernel.  At
+// H = 256 (slab_ld = 260): 6 * 16 * 260 * 4 = 99,840 B + 4,096 B = 103,936 B of the compute unit's 160 KB: one workgroup per
+// compute unit, which a grid of at most 16 workgroups (B <= 256) never asks more of.  At H = 32 (slab_ld = 36): 17.9 KB.
+//
+// The dueling network (ddqn_per_duel_cartpole.py:58-78: fc1, then value_stream [1][H] and advantage_stream [A][H]) has a second
+// instance of the row kernel and an act kernel of its own, ddqn_duel_r1_kernel / ddqn_duel_act_kernel: one hidden layer, the two
+// heads as two items of one stage per chain, the combine q = v + (a - mean a) and its backward per row, ONE dX stage.  LDS: three
+// slabs (P1, N1, T1; N1 and T1 are dead after the heads and take the two heads' input gradients): 54,016 B at H = 256.  No
+// H x H layer, so no weight images.  duel_combine below states the arithmetic order.
+#include "policy_device.hpp"
+#include "slab_step_device.hpp"
+
+namespace {
+
+using namespace gymrl;
+using namespace gymrl::slab;
+
+constexpr int kDdqnMaxBatch = 256;     // (ops.DDQN_FUSED_MAX_BATCH) one grid of at most 16 slabs in the row phase: the loss sum is one block's
+constexpr int kDdqnSlabs = 6;
+struct DdqnImages {                    // gymrl_ddqn_update_args.images, f32[3][H*H]: gymrl_dqn_update_args.images' layout
+  const float *pf, *tf, *pb;
+  __host__ __device__ DdqnImages(const float* base, int H) {
+    const ImageSlots at(base, H);
+    pf = at(0); tf = at(1); pb = at(2);
+  }
+  static constexpr int kCount = 3;
+  static PackTable sources(const gymrl_ddqn_update_args& a) {
+    return PackTable{{a.policy.w[1], a.target.w[1], a.policy.w[1], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 2};
+  }
+};
+
+// hand-off between the row phase and the tile phase (caller-owned workspace)
+struct DdqnWs {
+  float* s;                            // [B][D]: the gathered states
+  float *H1, *Z1, *H2, *Z2, *dq;       // the policy net's activations on s and dL/dz per layer ([B][H]; dq [B][A])
+  double* terms;                       // [B][3]: the row's td^2 * w in column 0 (sac_dw_body's row pitch)
+  __host__ __device__ static size_t carve(DdqnWs* w, void* base, int B, int D, int A, int H) {
+    carve_taker take{base};
+    float* s = take((size_t)B * D);
+    float* h[4];
+    for (int i = 0; i < 4; ++i) h[i] = take((size_t)B * H);
+    float* dq = take((size_t)B * A);
+    double* terms = reinterpret_cast<double*>(take((size_t)B * 6));
+    if (w) { w->s = s; w->H1 = h[0]; w->Z1 = h[1]; w->H2 = h[2]; w->Z2 = h[3]; w->dq = dq; w->terms = terms; }
+    return take.off;
+  }
+};
+
+
+// The ring row of batch element b, or -1: beyond the batch, or an index outside [0, cap) — such a row is never read: it enters
+// the batch as zeros with weight 0 (td_out = -y of a zero row, no gradient), instead of a read outside the ring.
+__device__ __forceinline__ int64_t ddqn_row(const gymrl_ddqn_update_args& a, int b, bool in_batch) {
+  if (!in_batch) return -1;
+  const int64_t row = (int64_t)a.idx[b];
+  return (row >= 0 && row < a.cap) ? row : -1;
+}
+
+// q = value + (advantage - advantage.mean(dim=-1, keepdim=True)) as torch evaluates it on the device: the mean is the float32
+// sum of the row times the float32 reciprocal 1 / A (the reduction's `acc * factor`), then one subtraction and one addition
+// per element.  With A = 2 — the only width the entry points take — the sum has one addition and 1 / A is exact.
+__device__ __forceinline__ void duel_combine(const float* adv, float v, int A, float* q) {
+  float sum = adv[0];
+  for (int k = 1; k < A; ++k) sum += adv[k];
+  const float m = sum * (1.0f / (float)A);
+  for (int k = 0; k < A; ++k) q[k] = v + (adv[k] - m);
+}
+// Its backward in autograd's order, for the gradient dq of q: the broadcast value takes the row sum, dv = sum_k dq[k]; the
+// subtraction hands dq to the advantage and -dq to the broadcast mean, whose gradient is the row sum gm = sum_k (-dq[k]); the
+// mean spreads gm * (1 / A) over the row (a division by the host scalar A runs as a multiplication by its reciprocal); the two
+// gradients of the advantage are then added: da[k] = dq[k] + gm * (1 / A).
+__device__ __forceinline__ void duel_combine_bwd(const float* dq, int A, float* da, float& dv) {
+  float sv = dq[0], gm = -dq[0];
+  for (int k = 1; k < A; ++k) { sv += dq[k]; gm += -dq[k]; }
+  const float spread = gm * (1.0f / (float)A);
+  for (int k = 0; k < A; ++k) da[k] = dq[k] + spread;
+  dv = sv;
+}
+
+template <int HC>
+__global__ __launch_bounds__(kThreads) void ddqn_r1_kernel(const gymrl_ddqn_update_args a, const DdqnWs ws) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Lds L;
+  const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
+  const int P1 = L.big, N1 = P1 + 16 * ld, T1 = N1 + 16 * ld, P2 = T1 + 16 * ld, N2 = P2 + 16 * ld, T2 = N2 + 16 * ld;
+  const int Z0 = T1;
+  const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
+  const int t = threadIdx.x;
+  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
+  const DdqnImages im(a.images, H);
+  const gymrl_td3_actor_params &p = a.policy, &tg = a.target;
+  // ---- ring gather by the sampled rows: one thread per row, rows beyond the batch are zero (weight 0) ----
+  if (t < 16) {
+    const int b = row0 + t;
+    const int64_t row = ddqn_row(a, b, t < nrows);
+    const bool ok = row >= 0;
+    for (int k = 0; k < kMaxD; ++k) {
+      const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
+      lds[L.S + t * kMaxD + k] = sv;
+      lds[L.S2 + t * kMaxD + k] = (ok && k < D) ? a.r_next[row * D + k] : 0.0f;
+      if (t < nrows && k < D) ws.s[(size_t)b * D + k] = sv;
+    }
+    lds[L.Misc + t * 4 + 0] = ok ? a.r_reward[row] : 0.0f;
+    lds[L.Misc + t * 4 + 1] = ok ? (float)a.r_flag[row] : 0.0f;            // dones become float32
+    lds[L.Misc + t * 4 + 2] = ok ? __int_as_float((int)a.r_action[row]) : 0.0f;
+    lds[L.Misc + t * 4 + 3] = ok ? a.is_weight[b] : 0.0f;
+  }
+  __syncthreads();
+  // ---- policy_net(s) (:222), policy_net(s') (:225) and target_net(s') (:227): three independent chains, layer by layer ----
+  {
+    const FwdItem st[3] = {fwd_item(L.S, kD, -1, 0, D, D, H, p.w[0], p.b[0], P1, ld, ws.H1, H, R),
+                           fwd_item(L.S2, kD, -1, 0, D, D, H, p.w[0], p.b[0], N1, ld, nullptr, 0, R),
+                           fwd_item(L.S2, kD, -1, 0, D, D, H, tg.w[0], tg.b[0], T1, ld, nullptr, 0, R)};
+    fwd_stage<3>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  {
+    const FwdItem st[3] = {fwd_item(P1, ld, -1, 0, H, H, H, p.w[1], p.b[1], P2, ld, ws.H2, H, R, 0.0f, 0.0f, im.pf),
+                           fwd_item(N1, ld, -1, 0, H, H, H, p.w[1], p.b[1], N2, ld, nullptr, 0, R, 0.0f, 0.0f, im.pf),
+                           fwd_item(T1, ld, -1, 0, H, H, H, tg.w[1], tg.b[1], T2, ld, nullptr, 0, R, 0.0f, 0.0f, im.tf)};
+    fwd_stage<3>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  {
+    const FwdItem st[3] = {fwd_item(P2, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Cq0, 4, nullptr, 0, NA),
+                           fwd_item(N2, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Q1, 4, nullptr, 0, NA),
+                           fwd_item(T2, ld, -1, 0, H, H, A, tg.w[2], tg.b[2], L.Q0, 4, nullptr, 0, NA)};
+    fwd_stage<3>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  if (t < 16) {                           // offpolicy.hip dqn_td_kernel (:225-232) with qn_online and w set, gamma_n = gamma
+    const float* sel = lds + L.Q1 + t * 4;
+    int astar = 0;
+    float best = sel[0];
+    for (int k = 1; k < A; ++k) if (sel[k] > best) { best = sel[k]; astar = k; }
+    const float nq = lds[L.Q0 + t * 4 + astar];
+    const float y = lds[L.Misc + t * 4 + 0] + a.gamma * nq * (1.0f - lds[L.Misc + t * 4 + 1]);
+    const int act = __float_as_int(lds[L.Misc + t * 4 + 2]);
+    const float td = lds[L.Cq0 + t * 4 + act] - y;
+    const float wb = lds[L.Misc + t * 4 + 3], invB = 1.0f / (float)a.B;
+    for (int k = 0; k < 4; ++k) {
+      const float d = k == act ? (2.0f * td) * wb * invB : 0.0f;
+      lds[L.Dq0 + t * 4 + k] = d;
+      if (t < nrows && k < A) ws.dq[(size_t)(row0 + t) * A + k] = d;
+    }
+    if (t < nrows) {
+      a.td_out[row0 + t] = td;
+      ws.terms[(size_t)(row0 + t) * 3] = (double)((td * td) * wb);
+    }
+  }
+  __syncthreads();
+  // ---- the policy net's input-gradient chain (what backward() computes before the weight gradients) ----
+  bwd_one(lds, {BwdItem{L.Dq0, 4, A, p.w[2], H, -1, nullptr, P2, ld, R, Z0, ld, ws.Z2, H, nullptr}}, row0, nrows);
+  bwd_stage(lds, {BwdItem{Z0, ld, H, p.w[1], H, -1, nullptr, P1, ld, R, -1, 0, ws.Z1, H, im.pb}}, row0, nrows);      // (the last stage: no barrier behind it)
+}
+
+
+// ---- the dueling instance: policy.w / .b = {fc1, value_stream, advantage_stream}; ws.H2 holds dv [B], ws.dq holds da [B][A] ----
+template <int HC>
+__global__ __launch_bounds__(kThreads) void ddqn_duel_r1_kernel(const gymrl_ddqn_update_args a, const DdqnWs ws) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Lds L;
+  const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
+  const int P1 = L.big, N1 = P1 + 16 * ld, T1 = N1 + 16 * ld;
+  const int Xv = N1, Xa = T1;             // the heads' input gradients, once policy(s') and target(s') are through their heads
+  const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
+  const int t = threadIdx.x;
+  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
+  const gymrl_td3_actor_params &p = a.policy, &tg = a.target;
+  if (t < 16) {
+    const int b = row0 + t;
+    const int64_t row = ddqn_row(a, b, t < nrows);
+    const bool ok = row >= 0;
+    for (int k = 0; k < kMaxD; ++k) {
+      const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
+      lds[L.S + t * kMaxD + k] = sv;
+      lds[L.S2 + t * kMaxD + k] = (ok && k < D) ? a.r_next[row * D + k] : 0.0f;
+      if (t < nrows && k < D) ws.s[(size_t)b * D + k] = sv;
+    }
+    lds[L.Misc + t * 4 + 0] = ok ? a.r_reward[row] : 0.0f;
+    lds[L.Misc + t * 4 + 1] = ok ? (float)a.r_flag[row] : 0.0f;
+    lds[L.Misc + t * 4 + 2] = ok ? __int_as_float((int)a.r_action[row]) : 0.0f;
+    lds[L.Misc + t * 4 + 3] = ok ? a.is_weight[b] : 0.0f;
+  }
+  __syncthreads();
+  {
+    const FwdItem st[3] = {fwd_item(L.S, kD, -1, 0, D, D, H, p.w[0], p.b[0], P1, ld, ws.H1, H, R),
+                           fwd_item(L.S2, kD, -1, 0, D, D, H, p.w[0], p.b[0], N1, ld, nullptr, 0, R),
+                           fwd_item(L.S2, kD, -1, 0, D, D, H, tg.w[0], tg.b[0], T1, ld, nullptr, 0, R)};
+    fwd_stage<3>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  {                                       // value (1 column) and advantage (A columns) of every chain: six items of one stage
+    const FwdItem st[6] = {fwd_item(P1, ld, -1, 0, H, H, 1, p.w[1], p.b[1], L.Cq1, 4, nullptr, 0, NA),
+                           fwd_item(P1, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Cq0, 4, nullptr, 0, NA),
+                           fwd_item(N1, ld, -1, 0, H, H, 1, p.w[1], p.b[1], L.Dq1, 4, nullptr, 0, NA),
+                           fwd_item(N1, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Q1, 4, nullptr, 0, NA),
+                           fwd_item(T1, ld, -1, 0, H, H, 1, tg.w[1], tg.b[1], L.Mean, 4, nullptr, 0, NA),
+                           fwd_item(T1, ld, -1, 0, H, H, A, tg.w[2], tg.b[2], L.Q0, 4, nullptr, 0, NA)};
+    fwd_stage<6>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  if (t < 16) {                           // the three combines, then dqn_td_kernel with qn_online and w set, then the combine's backward
+    float q[4], qo[4], qt[4];
+    duel_combine(lds + L.Cq0 + t * 4, lds[L.Cq1 + t * 4], A, q);
+    duel_combine(lds + L.Q1 + t * 4, lds[L.Dq1 + t * 4], A, qo);
+    duel_combine(lds + L.Q0 + t * 4, lds[L.Mean + t * 4], A, qt);
+    int astar = 0;
+    float best = qo[0];
+    for (int k = 1; k < A; ++k) if (qo[k] > best) { best = qo[k]; astar = k; }
+    float nq = qt[0], qa = q[0];
+    const int act = __float_as_int(lds[L.Misc + t * 4 + 2]);
+    for (int k = 1; k < A; ++k) { if (k == astar) nq = qt[k]; if (k == act) qa = q[k]; }
+    const float y = lds[L.Misc + t * 4 + 0] + a.gamma * nq * (1.0f - lds[L.Misc + t * 4 + 1]);
+    const float td = qa - y;
+    const float wb = lds[L.Misc + t * 4 + 3], invB = 1.0f / (float)a.B;
+    float dq[4], da[4], dv;
+    for (int k = 0; k < 4; ++k) dq[k] = k == act ? (2.0f * td) * wb * invB : 0.0f;
+    duel_combine_bwd(dq, A, da, dv);
+    for (int k = 0; k < 4; ++k) {
+      lds[L.Dq0 + t * 4 + k] = k < A ? da[k] : 0.0f;
+      lds[L.Dq1 + t * 4 + k] = k == 0 ? dv : 0.0f;
+      if (t < nrows && k < A) ws.dq[(size_t)(row0 + t) * A + k] = da[k];
+    }
+    if (t < nrows) {
+      ws.H2[row0 + t] = dv;
+      a.td_out[row0 + t] = td;
+      ws.terms[(size_t)(row0 + t) * 3] = (double)((td * td) * wb);
+    }
+  }
+  __syncthreads();
+  // ---- ONE dX stage: each head's input gradient on its own (two backward launches on the layer path), autograd's sum of the two,
+  // then fc1's ReLU derivative from its saved output ----
+  {
+    const BwdItem st[2] = {BwdItem{L.Dq1, 4, 1, p.w[1], H, -1, nullptr, -1, 0, NA, Xv, ld, nullptr, 0, nullptr},
+                           BwdItem{L.Dq0, 4, A, p.w[2], H, -1, nullptr, -1, 0, NA, Xa, ld, nullptr, 0, nullptr}};
+    bwd_stage<2>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  for (int e = t; e < 16 * H; e += kThreads) {
+    const int row = e / H, k = e - row * H;
+    const float g = (lds[Xv + row * ld + k] + lds[Xa + row * ld + k]) * act_bwd(lds[P1 + row * ld + k], R, 0.0f, 0.0f);
+    if (row < nrows) ws.Z1[(size_t)(row0 + row) * H + k] = g;
+  }
+}
+
+// ---- acting with the dueling network: gymrl_dqn_act_step's kernel with the two heads and the combine in front of the choice ----
+template <int HC>
+__global__ __launch_bounds__(kThreads) void ddqn_duel_act_kernel(const gymrl_dqn_act_args a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const Lds L;
+  const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
+  const int X0 = L.big;
+  const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.N - row0);
+  const int t = threadIdx.x;
+  if (t < 16) {
+    const int i = row0 + t;
+    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = (t < nrows && k < D) ? a.obs[(size_t)i * D + k] : 0.0f;
+  }
+  __syncthreads();
+  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
+  fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.policy.w[0], a.policy.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);
+  {
+    const FwdItem st[2] = {fwd_item(X0, ld, -1, 0, H, H, 1, a.policy.w[1], a.policy.b[1], L.Cq1, 4, nullptr, 0, NA),
+                           fwd_item(X0, ld, -1, 0, H, H, A, a.policy.w[2], a.policy.b[2], L.Cq0, 4, nullptr, 0, NA)};
+    fwd_stage<2>(lds, st, row0, nrows);
+  }
+  __syncthreads();
+  if (t < 64) {
+    int act = 0;
+    if (t < nrows) {
+      float* q = lds + L.Mean + t * kMaxA;
+      duel_combine(lds + L.Cq0 + t * 4, lds[L.Cq1 + t * 4], A, q);
+      const uint64_t counter = a.counter_dev ? a.counter_dev[0] : a.counter;
+      const float eps = a.epsilon_dev ? a.epsilon_dev[0] : a.epsilon;
+      act = epsilon_greedy_pick(q, A, a.u ? a.u + (size_t)(row0 + t) * 2 : nullptr, a.seed, (uint64_t)(a.env_id0 + row0 + t), counter, eps);
+    }
+    cartpole_act_tail(a, lds, L, t, row0, nrows, act);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t gymrl_ddqn_update_workspace_bytes(int B, int D, int A, int H) { return workspace_bytes<DdqnWs>(B, D, A, H); }
+size_t gymrl_ddqn_args_bytes(int which) { return which == 1 ? sizeof(gymrl_ddqn_update_args) : 0; }
+
+static int ddqn_set_lds_attr() {
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)ddqn_r1_kernel<0>, (const void*)ddqn_r1_kernel<256>, (const void*)ddqn_duel_r1_kernel<0>,
+                                 (const void*)ddqn_duel_r1_kernel<256>, (const void*)ddqn_duel_act_kernel<0>,
+                                 (const void*)ddqn_duel_act_kernel<256>}, (int)lds_bytes(256, kDdqnSlabs));
+}
+
+static bool ddqn_update_args_ok(const gymrl_ddqn_update_args& a) {
+  if (!slab_shape_ok(a.B, kDdqnMaxBatch, a.D, a.A, a.H)) return false;
+  if (!ring_ok(a) || !all_set({a.idx, a.is_weight, a.td_out, a.workspace, a.loss_sum, a.policy_p, a.policy_m, a.policy_v}) ||
+      !(a.clamp_abs >= 0.0f) || a.cap < 1 || (a.dueling != 0 && a.dueling != 1))
+    return false;
+  if (a.dueling && a.A != 2) return false;            // duel_combine's order is pinned for two actions
+  return net_ok(a.policy) && net_ok(a.target);
+}
+
+int gymrl_ddqn_pack_images(const gymrl_ddqn_update_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_ddqn_update_args& a = *args;
+  if (!pack_args_ok(a) || a.dueling || !all_set({a.policy.w[1], a.target.w[1]})) return -22;      // (the dueling net has no H x H layer)
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, DdqnImages::kCount), dim3(256), 0, (hipStream_t)stream_, DdqnImages::sources(a), a.images, a.H);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+int gymrl_ddqn_update(const gymrl_ddqn_update_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_ddqn_update_args& a = *args;
+  if (!ddqn_update_args_ok(a)) return -22;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = ddqn_set_lds_attr()) return rc;
+  DdqnWs ws;
+  DdqnWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
+  const int B = a.B, D = a.D, A = a.A, H = a.H, slabs = (B + 15) / 16;
+  if (a.dueling) {
+    DwArgs p{};
+    DwBuilder pb{p, B};
+    pb.seg(ws.Z1, H, H, ws.s, D, nullptr, 0, D, D, a.policy.w[0], a.policy.b[0]);
+    pb.seg(ws.H2, 1, 1, ws.H1, H, nullptr, 0, H, H, a.policy.w[1], a.policy.b[1]);              // the value head: dv [B][1]
+    pb.seg(ws.dq, A, A, ws.H1, H, nullptr, 0, H, H, a.policy.w[2], a.policy.b[2]);              // the advantage head: da [B][A]
+    pb.close(a, nullptr, a.policy_p, a.policy_m, a.policy_v, a.adam_policy, a.adam_policy_dev, 0.0f, 0.0f, ws.terms, nullptr, 0, 1, a.loss_sum);
+    p.clamp_abs = a.clamp_abs;
+    hipLaunchKernelGGL(H == 256 ? ddqn_duel_r1_kernel<256> : ddqn_duel_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, 3), stream, a, ws);
+    launch_dw(p, stream);
+    GYMRL_CHECK_LAUNCH();
+    return 0;
+  }
+  const DdqnImages im(a.images, H);
+  // the policy net's tile list, as gymrl_dqn_update's: no target twins, the clamp in front of Adam's moments
+  DwArgs p{};
+  DwBuilder pb{p, B};
+  pb.seg(ws.Z1, H, H, ws.s, D, nullptr, 0, D, D, a.policy.w[0], a.policy.b[0]);
+  pb.seg(ws.Z2, H, H, ws.H1, H, nullptr, 0, H, H, a.policy.w[1], a.policy.b[1], nullptr, nullptr, im.pf, im.pb);
+  pb.seg(ws.dq, A, A, ws.H2, H, nullptr, 0, H, H, a.policy.w[2], a.policy.b[2]);
+  // (at most 256 rows: no slice partials, and the loss sum closes in this launch's last block — dqn_td_kernel's one block)
+  pb.close(a, nullptr, a.policy_p, a.policy_m, a.policy_v, a.adam_policy, a.adam_policy_dev, 0.0f, 0.0f, ws.terms, nullptr, 0, 1, a.loss_sum);
+  p.clamp_abs = a.clamp_abs;
+  hipLaunchKernelGGL(H == 256 ? ddqn_r1_kernel<256> : ddqn_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, kDdqnSlabs), stream, a, ws);
+  launch_dw(p, stream);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+int gymrl_ddqn_duel_act_step(const gymrl_dqn_act_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_dqn_act_args& a = *args;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
+  if (const int rc = ddqn_set_lds_attr()) return rc;
+  hipLaunchKernelGGL(a.H == 256 ? ddqn_duel_act_kernel<256> : ddqn_duel_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 1), (hipStream_t)stream_, a);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

@@ -149,7 +149,7 @@ class DQNTrainer(WeightImages):
         self.action_dim = action_dim
         g = torch.random.get_rng_state()
         torch.manual_seed(self.base_seed)
-        self.policy_net = QNetwork(state_dim, action_dim, config.hidden_dim)
+        self.policy_net = self._make_network(state_dim, action_dim, config.hidden_dim)
         torch.random.set_rng_state(g)
         self.target_net = copy.deepcopy(self.policy_net)
         self.flat_params, self.flat_grads = flatten_module(self.policy_net, self.device)
@@ -157,7 +157,7 @@ class DQNTrainer(WeightImages):
         self.target_net.eval()
         self._sink = GradSink(self.policy_net)
         self.optimizer = FusedAdam(self.flat_params, self.flat_grads, lr=config.lr, eps=1e-8, clamp_abs=1.0)
-        self.memory = ReplayBuffer(config.memory_capacity, state_dim, self.device, seed=self.base_seed)
+        self.memory = self._make_memory(state_dim)
         self.epsilon = config.epsilon_start
         self.sample_count = 0
         self.episode_rewards = deque(maxlen=100)
@@ -166,6 +166,13 @@ class DQNTrainer(WeightImages):
         self._parity_u = None          # tests: iterator of f32[N, 2] uniforms for select_action (explore?, which action)
         self._parity_indices = None    # tests: iterator of i32[B] replay indices for update()
         self._graph = None             # hipGraph of the update, captured on first use (update_async)
+
+    # (what a trainer that shares this loop replaces: ddqn_per_cartpole.py's networks and its prioritised buffer)
+    def _make_network(self, state_dim, action_dim, hidden_dim):
+        return QNetwork(state_dim, action_dim, hidden_dim)
+
+    def _make_memory(self, state_dim):
+        return ReplayBuffer(self.cfg.memory_capacity, state_dim, self.device, seed=self.base_seed)
 
     def get_epsilon(self):
         """:117-122 — advanced once per (vector) action selection."""
@@ -193,6 +200,8 @@ class DQNTrainer(WeightImages):
 
     # ------------------------------------------------------------ fused vector step (csrc/dqn_step.hip) -------
     CHUNK = 16                         # vector steps per StepChunk replay (= the episode tracker's flush period)
+    _act_step = staticmethod(ops.dqn_act_step)     # the act launch's binding
+    CHUNK_FIELDS = [("push", "q"), ("act", "Q"), ("eps", "f"), ("draw", "Qq"), ("adam", "4f")]     # one step's device record
 
     def _fused_update_ok(self):
         """update() as gymrl_dqn_update: opt-in (cfg.fused_step) and a matter of shapes."""
@@ -253,7 +262,7 @@ class DQNTrainer(WeightImages):
             self._act_counter += 1
         else:
             cursor_dev, counter_dev, eps_dev = dev
-        ops.dqn_act_step(self._fused_args()[0], env, obs, nxt, epsilon=eps, epsilon_dev=eps_dev, cursor=m.cursor, cursor_dev=cursor_dev,
+        self._act_step(self._fused_args()[0], env, obs, nxt, epsilon=eps, epsilon_dev=eps_dev, cursor=m.cursor, cursor_dev=cursor_dev,
                          u=u, seed=self.base_seed, counter=self._act_counter, counter_dev=counter_dev,
                          rew_out=lb["rew"], done_out=done, ep_ret_out=ep_ret, ep_stats=env.ep_stats)
         if dev is None:
@@ -286,10 +295,19 @@ class DQNTrainer(WeightImages):
             ch.set(j, "eps", self.get_epsilon())       # rounded to the float32 the eager call passes
             self._act_counter += 1
             ch.set(j, "act", self._act_counter)
-            ch.set(j, "draw", m.draws, m.size)
-            m.draws += 1
+            self._stage_draw(j)
             ch.set_bytes(j, "adam", self.optimizer.next_bias())
         ch.flush()
+
+    def _explicit_draws(self):
+        """Whether a test feeds random draws of its own: a StepChunk replay reads only the kernels' Philox keys."""
+        return self._parity_u is not None
+
+    def _stage_draw(self, j):
+        """Record j's share of update()'s index draw."""
+        m = self.memory
+        self._chunk.set(j, "draw", m.draws, m.size)
+        m.draws += 1
 
     def _train_fused(self, max_vector_steps=None):
         """_train on the fused step.  With hipGraphs on, CHUNK whole vector steps replay as one graph (graphs.StepChunk);
@@ -304,7 +322,7 @@ class DQNTrainer(WeightImages):
         env.reset(obs)
         step, last_target = 0, 0
         graphed = bool(getattr(cfg, "use_graphs", True)) and self._parity_indices is None
-        chunked = graphed and N > 1 and self._parity_u is None
+        chunked = graphed and N > 1 and not self._explicit_draws()
         limit = max_vector_steps or (cfg.max_episodes * cfg.max_steps // N + 1)
         solved = lambda: len(self.episode_rewards) >= 100 and np.mean(self.episode_rewards) >= 495.0   # noqa: E731
         while tracker.episodes < cfg.max_episodes and step < limit:
@@ -314,8 +332,7 @@ class DQNTrainer(WeightImages):
                     and not solved()):
                 if getattr(self, "_chunk", None) is None:
                     from .graphs import StepChunk
-                    self._chunk = StepChunk(self.device, self.CHUNK, [("push", "q"), ("act", "Q"), ("eps", "f"), ("draw", "Qq"),
-                                                                      ("adam", "4f")])
+                    self._chunk = StepChunk(self.device, self.CHUNK, self.CHUNK_FIELDS)
                 self._fused_args()             # weight images rebuilt (if stale) BEFORE the capture, not inside it
                 self._stage_chunk()
                 self._chunk.run(lambda j: self._chunk_body(lb, j), key=(id(env), env.state.data_ptr()))

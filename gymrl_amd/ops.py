@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DqnActArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DdqnUpdateArgs, DqnActArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -1902,7 +1902,8 @@ def dqn_act_args(env, policy, ring, cap, images=None):
 
 
 def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, cursor_dev=None, u=None, seed=0, counter=0,
-                 counter_dev=None, action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None):
+                 counter_dev=None, action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None,
+                 entry="gymrl_dqn_act_step"):
     """gymrl_dqn_act_step: policy net on obs [N, D], the epsilon-greedy choice (u = f32[N, 2] uniforms or None:
     gymrl_epsilon_greedy's Philox keys under (seed, counter); epsilon rounded to float32 as epsilon_greedy() passes it, or
     epsilon_dev = f32[1] on the device), CartPole step with auto-reset, replay rows at (cursor + env) % cap — ONE launch."""
@@ -1916,7 +1917,7 @@ def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, 
     a.u = _addr(u)
     a.seed, a.counter, a.counter_dev = seed, counter, _addr(counter_dev)
     a.epsilon, a.epsilon_dev = float(epsilon), _addr(epsilon_dev)
-    check(lib().gymrl_dqn_act_step(C.byref(a), _stream()), "gymrl_dqn_act_step")
+    check(getattr(lib(), entry)(C.byref(a), _stream()), entry)
 
 
 def dqn_update_args(B, D, A, policy, target, opt, ring, gamma, loss_sum, workspace, images=None):
@@ -1948,6 +1949,84 @@ def dqn_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None,
     _set_adam_bias(a, adam_policy=adam_policy)
     a.adam_policy_dev = _addr(adam_policy_dev)
     check(lib().gymrl_dqn_update(C.byref(a), _stream()), "gymrl_dqn_update")
+
+
+# ------------------------------------------ fused DDQN + PER update step ---
+DDQN_FUSED_MAX_BATCH = 256     # one grid of at most 16 slabs in the row phase (ddqn_step.hip kDdqnMaxBatch)
+
+
+def ddqn_fused_shape_ok(B, D, A, H, dueling=False):
+    """Shapes gymrl_ddqn_update takes (include/gymrl.h; the dueling instance: two actions): everything else runs layer by layer."""
+    return _fused_shape_ok(B, D, A, H, DDQN_FUSED_MAX_BATCH, 4) and (A == 2 or not dueling)
+
+
+def ddqn_update_workspace(B, D, A, H, device):
+    return _zeroed_workspace(lib().gymrl_ddqn_update_workspace_bytes(B, D, A, H), device)
+
+
+def ddqn_pack_images(a):
+    """gymrl_ddqn_pack_images: rebuild every image (dqn_images' buffer) from the parameters as they are now."""
+    check(lib().gymrl_ddqn_pack_images(C.byref(a), _stream()), "gymrl_ddqn_pack_images")
+
+
+class _Layers3:
+    """Three Linear layers under the names the shared helpers read: (fc1, fc2, fc3), or the dueling net's (fc1, value_stream,
+    advantage_stream) in gymrl_ddqn_update_args' slots."""
+
+    def __init__(self, layers):
+        self.fc1, self.fc2, self.fc3 = layers
+
+
+def ddqn_act_args(env, layers, ring, cap, images=None):
+    """A gymrl_dqn_act_args for gymrl_dqn_act_step (layers = fc1, fc2, fc3) or gymrl_ddqn_duel_act_step (fc1, value_stream,
+    advantage_stream; no images)."""
+    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"ddqn_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
+    a = DqnActArgs()
+    layers = _Layers3(layers)
+    _set_act_env(a, env, layers, ring, cap, images)
+    _td3_actor_params(a.policy, layers)
+    return a
+
+
+def ddqn_duel_act_step(a, env, obs, obs_out, **kw):
+    """gymrl_ddqn_duel_act_step: dqn_act_step's arguments, the dueling network's kernel."""
+    dqn_act_step(a, env, obs, obs_out, entry="gymrl_ddqn_duel_act_step", **kw)
+
+
+def ddqn_update_args(B, D, A, policy_layers, target_layers, opt, ring, gamma, td_out, loss_sum, workspace, images=None, dueling=False):
+    """A gymrl_ddqn_update_args with the per-trainer constants filled in.  policy_layers / target_layers: (fc1, fc2, fc3), or
+    with dueling (fc1, value_stream, advantage_stream); opt: the policy net's FusedAdam (its clamp_abs is the update's);
+    td_out: f32[B]; loss_sum: f64[1] (sum of td^2 * w)."""
+    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise ValueError("ddqn_update_args: loss_sum must be a float64[1]")
+    if td_out.dtype != torch.float32 or td_out.numel() != B:
+        raise ValueError(f"ddqn_update_args: td_out must be a float32 [{B}]")
+    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"ddqn_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
+    a = DdqnUpdateArgs()
+    p, t = _Layers3(policy_layers), _Layers3(target_layers)
+    a.B, a.D, a.A, a.H, a.dueling = B, D, A, p.fc1.weight.shape[0], int(dueling)
+    a.gamma, a.cap = float(gamma), ring[0].shape[0]
+    _set_ring(a, ring)
+    _td3_actor_params(a.policy, p)
+    _td3_actor_params(a.target, t)
+    _set_optimisers(a, opt, policy=opt)
+    a.clamp_abs = float(opt.clamp_abs)
+    a.td_out, a.loss_sum, a.workspace, a.images = _addr(td_out), _addr(loss_sum), _addr(workspace), _addr(None if dueling else images)
+    return a
+
+
+def ddqn_update(a, idx, is_weight, adam_policy=None, adam_policy_dev=None):
+    """gymrl_ddqn_update: ddqn_per_cartpole.DDQNPERTrainer.update() between the draw and the tree update, two launches.
+    idx: i32[B] ring rows, is_weight: f32[B]; adam_policy: the 16-byte block of adam_bias() (host) or adam_policy_dev a device
+    view of it.  A row outside the ring is not read: it counts as a zero row of weight 0."""
+    if idx.dtype != torch.int32 or idx.numel() != a.B or is_weight.dtype != torch.float32 or is_weight.numel() != a.B:
+        raise ValueError(f"ddqn_update: idx must be int32 [{a.B}] and is_weight float32 [{a.B}]")
+    a.idx, a.is_weight = _addr(idx), _addr(is_weight)
+    _set_adam_bias(a, adam_policy=adam_policy)
+    a.adam_policy_dev = _addr(adam_policy_dev)
+    check(lib().gymrl_ddqn_update(C.byref(a), _stream()), "gymrl_ddqn_update")
 
 
 # --------------------------------------------- fused Rainbow vector step ---

@@ -1560,6 +1560,51 @@ size_t gymrl_dqn_args_bytes(int which);      /* sizeof(gymrl_dqn_act_args) (0) /
 int gymrl_dqn_act_step(const gymrl_dqn_act_args* args, void* stream);
 int gymrl_dqn_update(const gymrl_dqn_update_args* args, void* stream);
 
+/*
+ * Double DQN + prioritised replay's update on the same row-slab kernels (csrc/ddqn_step.hip): ddqn_per_cartpole.py's update
+ * :197-244 between its sample() and its update_priorities().  gymrl_dqn_update with a third forward chain, a weight per row and
+ * the TD errors as an output; acting is gymrl_dqn_act_step (the network is fc1, fc2 ReLU, fc3, the shape of DQN's), and the
+ * stratified draw stays gymrl_per_sample(variant_b = 1): its weights' maximum is a reduction over the whole batch.
+ *   gymrl_ddqn_update    two launches:
+ *     R1 rows   ring gather by idx; policy_net(s), policy_net(s') and target_net(s') as three items of the same stages
+ *               (:222-228); gymrl_dqn_td_loss's expressions with q_next_online and w: a* = first argmax of the online row,
+ *               y = r + gamma q_target'[a*] (1 - d), td = q[a] - y -> td_out, dq = 2 td w / B on the taken action, the row's
+ *               float64 td^2 w (:229-232); the policy net's input-gradient chain
+ *     T2 tiles  as gymrl_dqn_update's: weight / bias gradient tiles, each element clamped to +-clamp_abs, Adam (:237-242); the
+ *               loss sum in gymrl_dqn_td_loss's order
+ *   The caller runs gymrl_per_update_td(idx, td_out, alpha, eps, clip = error_max) behind it (:234-235) and owns the hard
+ *   target copy and the images' rebuild after it.
+ * Results are the layer-by-layer path's bits (tests/test_ddqn_fused_step_gpu.py).  Limits: H % 4 == 0, H <= 256, D <= 8, A <= 4,
+ * B <= 256 (-22 otherwise, before any launch: the trainer stays on the layer path).
+ */
+typedef struct {
+  int B, D, A, H;
+  int dueling;                             /* 0: fc1, fc2, fc3.  1: ddqn_per_duel_cartpole.py's net, policy / target = {fc1, value_stream
+                                            * [1][H], advantage_stream [A][H]}, q = v + (a - mean a); A == 2; no images */
+  float gamma;
+  const float* r_state; const uint32_t* r_action; const float* r_reward; const float* r_next; const uint8_t* r_flag;
+  int64_t cap;                             /* rows of the ring: an idx outside [0, cap) is not read (a zero row of weight 0) */
+  const int32_t* idx;                      /* i32[B] ring rows of the sampled batch (gymrl_per_sample's tree index - cap + 1) */
+  const float* is_weight;                  /* f32[B] importance weights (gymrl_per_sample's w_out) */
+  gymrl_td3_actor_params policy, target;   /* fc1, fc2, fc3 each; the target is read only */
+  float* policy_p; float* policy_m; float* policy_v;       /* the policy net's flat parameter buffer and its Adam moments */
+  float adam_policy[4];                    /* gymrl_adam_bias' block */
+  const float* adam_policy_dev;
+  double beta1, beta2, eps_adam;
+  float clamp_abs;                         /* gymrl_adam_step's clamp_abs (the reference: 1; 0: no clamp) */
+  float* td_out;                           /* f32[B] out: the TD errors, for gymrl_per_update_td */
+  double* loss_sum;                        /* f64[1] out: sum of td^2 * w */
+  void* workspace;                         /* >= gymrl_ddqn_update_workspace_bytes(B, D, A, H) */
+  float* images;                           /* f32[3][H*H] or NULL: gymrl_dqn_update_args.images' layout and rules (gymrl_ddqn_pack_images) */
+} gymrl_ddqn_update_args;
+size_t gymrl_ddqn_update_workspace_bytes(int B, int D, int A, int H);
+int gymrl_ddqn_pack_images(const gymrl_ddqn_update_args* args, void* stream);
+size_t gymrl_ddqn_args_bytes(int which);     /* sizeof(gymrl_ddqn_update_args) (1), 0 otherwise: there is no act struct of its own */
+int gymrl_ddqn_update(const gymrl_ddqn_update_args* args, void* stream);
+/* gymrl_dqn_act_step for the dueling network: args->policy = {fc1, value_stream, advantage_stream}, the combine in front of the
+ * epsilon-greedy choice (gymrl_epsilon_greedy's keys); args->images is not read. */
+int gymrl_ddqn_duel_act_step(const gymrl_dqn_act_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
