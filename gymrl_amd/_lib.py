@@ -293,6 +293,42 @@ class DdqnUpdateArgs(C.Structure):
                 ("images", C.c_void_p)]
 
 
+class NdqnParams(C.Structure):
+    _c_name_ = "gymrl_ndqn_params"   # fc1, fc2, value_stream, advantage_stream
+    _fields_ = [("w_mu", C.c_void_p * 4), ("w_sigma", C.c_void_p * 4), ("b_mu", C.c_void_p * 4), ("b_sigma", C.c_void_p * 4)]
+
+
+class NdqnCombineArgs(C.Structure):
+    _c_name_ = "gymrl_ndqn_combine_args"
+    _fields_ = [("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("policy", NdqnParams), ("seed", C.c_uint64 * 4),
+                ("counter", C.c_uint64 * 3), ("counter_dev", C.c_void_p), ("raw", C.c_void_p * 3), ("workspace", C.c_void_p)]
+
+
+class NdqnActArgs(C.Structure):
+    _c_name_ = "gymrl_ndqn_act_args"
+    _fields_ = [("N", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("env_kind", C.c_int),
+                ("env_state", C.c_void_p), ("env_seed", C.c_uint64), ("env_id0", C.c_int64),
+                ("obs", C.c_void_p), ("obs_out", C.c_void_p),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p), ("cap", C.c_int64), ("cursor", C.c_int64), ("cursor_dev", C.c_void_p),
+                ("action_out", C.c_void_p), ("rew_out", C.c_void_p), ("done_out", C.c_void_p), ("ep_ret_out", C.c_void_p),
+                ("ep_stats", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+class NdqnUpdateArgs(C.Structure):
+    _c_name_ = "gymrl_ndqn_update_args"
+    _fields_ = [("B", C.c_int), ("D", C.c_int), ("A", C.c_int), ("H", C.c_int), ("gamma", C.c_float),
+                ("r_state", C.c_void_p), ("r_action", C.c_void_p), ("r_reward", C.c_void_p), ("r_next", C.c_void_p),
+                ("r_flag", C.c_void_p), ("cap", C.c_int64),
+                ("idx", C.c_void_p), ("idx_seed", C.c_uint64), ("idx_counter", C.c_uint64), ("idx_size", C.c_int64),
+                ("idx_dev", C.c_void_p),
+                ("policy", NdqnParams), ("target", NdqnParams),
+                ("policy_p", C.c_void_p), ("policy_m", C.c_void_p), ("policy_v", C.c_void_p),
+                ("adam_policy", C.c_float * 4), ("adam_policy_dev", C.c_void_p),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps_adam", C.c_double),
+                ("loss_sum", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class WeightImage(C.Structure):
     _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
@@ -486,6 +522,11 @@ SIGNATURES = {
     "gymrl_ddqn_args_bytes": (_sz, [_i]),
     "gymrl_ddqn_update": (_i, [_P(DdqnUpdateArgs), _vp]),
     "gymrl_ddqn_duel_act_step": (_i, [_P(DqnActArgs), _vp]),
+    "gymrl_ndqn_args_bytes": (_sz, [_i]),
+    "gymrl_ndqn_combine": (_i, [_P(NdqnCombineArgs), _vp]),
+    "gymrl_ndqn_act_step": (_i, [_P(NdqnActArgs), _vp]),
+    "gymrl_ndqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gymrl_ndqn_update": (_i, [_P(NdqnUpdateArgs), _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

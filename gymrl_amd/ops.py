@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DdqnUpdateArgs, DqnActArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -2097,3 +2097,106 @@ def rainbow_update(a, idx, is_weight, head_w, head_b, td_out, split=None, phase=
             a.w_eps[l], a.b_eps[l] = _addr(we), _addr(be)
     check(lib().gymrl_rainbow_update(C.byref(a), phase, _stream()), "gymrl_rainbow_update")
 
+
+
+# ---------------------------------- fused NoisyNet dueling DQN vector step ---
+NDQN_FUSED_MAX_BATCH = 256     # one grid of at most 16 slabs in the row phase (noisy_dqn_step.hip kNdqnMaxBatch)
+NDQN_LAYERS = ("fc1", "fc2", "value_stream", "advantage_stream")
+
+
+def ndqn_fused_shape_ok(B, D, A, H):
+    """Shapes gymrl_ndqn_combine / _act_step / _update take (include/gymrl.h; two actions: the dueling combine's order is
+    pinned for them): everything else runs layer by layer."""
+    return _fused_shape_ok(B, D, A, H, NDQN_FUSED_MAX_BATCH, 4) and A == 2
+
+
+def ndqn_raw_len(D, A, H):
+    """Floats of one forward's raw-draw row: per layer the input-side draws, then the output-side ones."""
+    return (D + H) + (H + H) + (H + 1) + (H + A)
+
+
+def ndqn_update_workspace(B, D, A, H, device):
+    return _zeroed_workspace(lib().gymrl_ndqn_update_workspace_bytes(B, D, A, H), device)
+
+
+def _ndqn_params(dst, net):
+    for k, name in enumerate(NDQN_LAYERS):
+        layer = getattr(net, name)
+        dst.w_mu[k], dst.w_sigma[k], dst.b_mu[k], dst.b_sigma[k] = (_addr(t) for t in (layer.weight_mu, layer.weight_sigma, layer.bias_mu,
+                                                                                      layer.bias_sigma))
+
+
+def ndqn_combine_args(D, A, policy, workspace):
+    """A gymrl_ndqn_combine_args for `policy` (a NoisyDuelingQNetwork: the layers' own seeds key the draws)."""
+    a = NdqnCombineArgs()
+    a.D, a.A, a.H = D, A, policy.fc1.out_features
+    _ndqn_params(a.policy, policy)
+    for k, name in enumerate(NDQN_LAYERS):
+        a.seed[k] = getattr(policy, name).seed
+    a.workspace = _addr(workspace)
+    return a
+
+
+def ndqn_combine(a, counters=(0, 0, 0), counter_dev=None, raw=(None, None, None)):
+    """gymrl_ndqn_combine: the effective parameters of sets C, A, B in one launch.  counters: the three draws' Philox counters
+    (or counter_dev = u64[3] on the device); raw: per set a float32 raw row (ndqn_raw_len floats) in place of the draw."""
+    n = ndqn_raw_len(a.D, a.A, a.H)
+    for k in range(3):
+        a.counter[k] = int(counters[k])
+        if raw[k] is not None and (raw[k].dtype != torch.float32 or raw[k].numel() != n or not raw[k].is_contiguous()):
+            raise ValueError(f"ndqn_combine: raw[{k}] must be a contiguous float32 [{n}]")
+        a.raw[k] = _addr(raw[k])
+    a.counter_dev = _addr(counter_dev)
+    check(lib().gymrl_ndqn_combine(C.byref(a), _stream()), "gymrl_ndqn_combine")
+
+
+def ndqn_act_args(env, policy, ring, cap, workspace):
+    """A gymrl_ndqn_act_args with everything that does not change from step to step filled in."""
+    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"ndqn_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
+    a = NdqnActArgs()
+    a.N, a.D, a.A, a.H = env.n, env.obs_dim, env.act_dim, policy.fc1.out_features
+    a.env_kind, a.env_state, a.env_seed, a.env_id0 = env.kind, _addr(env.state), env.seed, env.env_id0
+    _set_ring(a, ring)
+    a.cap, a.workspace = cap, _addr(workspace)
+    return a
+
+
+def ndqn_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, action_out=None, rew_out=None, done_out=None, ep_ret_out=None,
+                  ep_stats=None):
+    """gymrl_ndqn_act_step: the noisy Q on set C of the last gymrl_ndqn_combine, argmax, CartPole step with auto-reset, replay
+    rows at (cursor + env) % cap — ONE launch."""
+    if tuple(obs.shape) != (a.N, a.D) or tuple(obs_out.shape) != (a.N, a.D):
+        raise ValueError(f"ndqn_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
+    if action_out is not None and (action_out.dtype != torch.int32 or action_out.numel() != a.N):
+        raise ValueError("ndqn_act_step: action_out must be int32 [N]")
+    _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, (action_out, rew_out, done_out, ep_ret_out, ep_stats))
+    check(lib().gymrl_ndqn_act_step(C.byref(a), _stream()), "gymrl_ndqn_act_step")
+
+
+def ndqn_update_args(B, D, A, policy, target, opt, ring, gamma, loss_sum, workspace):
+    """A gymrl_ndqn_update_args with the per-trainer constants filled in.  opt: the policy net's FusedAdam; loss_sum: f64[1]."""
+    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise ValueError("ndqn_update_args: loss_sum must be a float64[1]")
+    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"ndqn_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
+    a = NdqnUpdateArgs()
+    a.B, a.D, a.A, a.H = B, D, A, policy.fc1.out_features
+    a.gamma, a.cap = float(gamma), ring[0].shape[0]
+    _set_ring(a, ring)
+    _ndqn_params(a.policy, policy)
+    _ndqn_params(a.target, target)
+    _set_optimisers(a, opt, policy=opt)
+    a.loss_sum, a.workspace = _addr(loss_sum), _addr(workspace)
+    return a
+
+
+def ndqn_update(a, idx=None, idx_seed=0, idx_counter=0, idx_size=0, idx_dev=None, adam_policy=None, adam_policy_dev=None):
+    """gymrl_ndqn_update: noisy_dqn_cartpole.NoisyDQNTrainer.update() behind a gymrl_ndqn_combine, three launches.  idx: i32[B]
+    rows or None (the keyed draw); adam_policy: the 16-byte block of adam_bias() (host) or adam_policy_dev a device view of it."""
+    if idx is not None and (idx.dtype != torch.int32 or idx.numel() != a.B):
+        raise ValueError(f"ndqn_update: idx must be int32 [{a.B}]")
+    _set_draw(a, idx, idx_seed, idx_counter, idx_size, idx_dev)
+    _set_adam_bias(a, adam_policy=adam_policy)
+    a.adam_policy_dev = _addr(adam_policy_dev)
+    check(lib().gymrl_ndqn_update(C.byref(a), _stream()), "gymrl_ndqn_update")

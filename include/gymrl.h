@@ -1605,6 +1605,70 @@ int gymrl_ddqn_update(const gymrl_ddqn_update_args* args, void* stream);
  * epsilon-greedy choice (gymrl_epsilon_greedy's keys); args->images is not read. */
 int gymrl_ddqn_duel_act_step(const gymrl_dqn_act_args* args, void* stream);
 
+/*
+ * NoisyNet dueling DQN's CartPole vector step on the same row-slab kernels (csrc/noisy_dqn_step.hip): noisy_dqn_cartpole.py's
+ * select_action :198-212 with the env step and memory.push of its train loop, and update :214-257.  All four layers are
+ * NoisyLinear (fc1 D -> H, fc2 H -> H, value_stream H -> 1, advantage_stream H -> A), so a step first forms the EFFECTIVE
+ * parameters W = mu + sigma * (eps_out (x) eps_in), b = mu + sigma * eps_out of its three draws, and the other launches read them:
+ *   gymrl_ndqn_combine   ONE launch: set 0 = C (acting), set 1 = A (policy_net(states): the gradient flows through it), set 2 = B
+ *                        (policy_net(next_states): the double-Q choice) into `workspace`; eps = f(Box-Muller on Philox(seed[layer],
+ *                        counter[set]; stream 0 input side / 1 output side; element)), f(x) = sign(x) sqrt|x| — gymrl_noisy_noise's
+ *                        bits for the same (seed, counter) — or f of the raw N(0,1) rows raw[set]; set A's eps vectors are kept
+ *   gymrl_ndqn_act_step  ONE launch: the Q values on set C, q = v + (a - mean a), argmax (the first maximum), CartPole step with
+ *                        auto-reset, replay row (obs, int32 action word, reward, TERMINAL next obs, done) at (cursor + env) % cap
+ *   gymrl_ndqn_update    update(), three launches behind a gymrl_ndqn_combine:
+ *     R1 rows   index draw (gymrl_uniform_indices' permutation, or idx) + ring gather; policy(s) on set A, policy(s') on set B,
+ *               target(s') on the target's mu; a* = first argmax of the online row, y = r + gamma q_target'[a*] (1 - d),
+ *               td = q[a] - y, dq = 2 td / B on the taken action (F.mse_loss: no weights, no clamp), the row's float64 td^2;
+ *               the combine's backward and set A's input-gradient chain.  A row outside [0, cap) is a zero row without gradient
+ *     T2 tiles  dW / db of set A's effective parameters (gymrl_lin_bwd_weight's order); the loss sum (gymrl_dqn_td_loss's order)
+ *     A3        d mu = dW, d sigma = dW * eps_A (biases: db * eps_out), Adam on mu and sigma (gymrl_adam_step's arithmetic)
+ *   The target network is read only (its mu): the hard copy stays with the caller.
+ * Results are the layer-by-layer path's bits (tests/test_ndqn_fused_step_gpu.py).  Limits: A == 2, H % 4 == 0, H <= 256, D <= 8,
+ * B <= 256 (-22 otherwise, before any launch: the trainer stays on the layer path); CartPole-v1 (D = 4) for the act step.
+ * A raw row holds, per layer in the forward's order, the K input-side draws and then the N output-side draws:
+ * (D + H) + (H + H) + (H + 1) + (H + A) floats.
+ */
+typedef struct { float* w_mu[4]; float* w_sigma[4]; float* b_mu[4]; float* b_sigma[4]; } gymrl_ndqn_params;     /* fc1, fc2, value_stream, advantage_stream */
+typedef struct {
+  int D, A, H;
+  gymrl_ndqn_params policy;                /* read only here */
+  uint64_t seed[4];                        /* per layer */
+  uint64_t counter[3]; const uint64_t* counter_dev;     /* per set (C, A, B); counter_dev: u64[3] on the device (hipGraph replay) */
+  const float* raw[3];                     /* per set: f32 raw row (parity mode), or NULL: the Philox draw */
+  void* workspace;                         /* >= gymrl_ndqn_update_workspace_bytes(B, D, A, H) of the trainer's B */
+} gymrl_ndqn_combine_args;
+typedef struct {
+  int N, D, A, H;
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE */
+  void* env_state; uint64_t env_seed; int64_t env_id0;
+  const float* obs; float* obs_out;        /* f32[N, D] in / next observations out (post-reset where an episode ended) */
+  float* r_state; uint32_t* r_action; float* r_reward; float* r_next; uint8_t* r_flag; int64_t cap, cursor;
+  const int64_t* cursor_dev;
+  int32_t* action_out; float* rew_out; uint8_t* done_out; float* ep_ret_out; double* ep_stats;     /* any may be NULL */
+  const void* workspace;                   /* the gymrl_ndqn_combine workspace: set C is read */
+} gymrl_ndqn_act_args;
+typedef struct {
+  int B, D, A, H;
+  float gamma;
+  const float* r_state; const uint32_t* r_action; const float* r_reward; const float* r_next; const uint8_t* r_flag;
+  int64_t cap;                             /* rows of the ring: an idx outside [0, cap) is not read */
+  const int32_t* idx;                      /* i32[B] explicit rows, or NULL: the keyed permutation of gymrl_uniform_indices */
+  uint64_t idx_seed, idx_counter; int64_t idx_size; const void* idx_dev;     /* idx_dev: {uint64 counter; int64 size} */
+  gymrl_ndqn_params policy, target;        /* the target: its w_mu / b_mu are read, nothing is written */
+  float* policy_p; float* policy_m; float* policy_v;       /* the policy net's flat parameter buffer and its Adam moments */
+  float adam_policy[4];                    /* gymrl_adam_bias' block */
+  const float* adam_policy_dev;
+  double beta1, beta2, eps_adam;
+  double* loss_sum;                        /* f64[1] out: sum of td^2 */
+  void* workspace;                         /* the gymrl_ndqn_combine workspace: sets A and B are read, the hand-off lives behind them */
+} gymrl_ndqn_update_args;
+size_t gymrl_ndqn_args_bytes(int which);     /* sizeof(gymrl_ndqn_act_args) (0) / _update_args (1) / _combine_args (2) */
+int gymrl_ndqn_combine(const gymrl_ndqn_combine_args* args, void* stream);
+int gymrl_ndqn_act_step(const gymrl_ndqn_act_args* args, void* stream);
+size_t gymrl_ndqn_update_workspace_bytes(int B, int D, int A, int H);
+int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
