@@ -329,6 +329,13 @@ class NdqnUpdateArgs(C.Structure):
                 ("loss_sum", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class MountainCarEvalArgs(C.Structure):
+    _c_name_ = "gymrl_mountaincar_eval_args"
+    _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("stream_id0", C.c_int64),
+                ("coefs", C.c_void_p), ("start", C.c_void_p), ("returns", C.c_void_p), ("lengths", C.c_void_p),
+                ("reached", C.c_void_p), ("final_state", C.c_void_p)]
+
+
 class WeightImage(C.Structure):
     _c_name_ = "gymrl_weight_image"
     _fields_ = [("W", C.c_void_p), ("H", C.c_int), ("img_fwd", C.c_void_p), ("img_bwd", C.c_void_p)]
@@ -527,6 +534,7 @@ SIGNATURES = {
     "gymrl_ndqn_act_step": (_i, [_P(NdqnActArgs), _vp]),
     "gymrl_ndqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_ndqn_update": (_i, [_P(NdqnUpdateArgs), _vp]),
+    "gymrl_mountaincar_rule_eval": (_i, [_P(MountainCarEvalArgs), _vp]),
 }
 SYMBOLS = list(SIGNATURES)
 

@@ -1,4 +1,4 @@
-// env_classic.hip — CartPole-v1 and Pendulum-v1 batched steppers + the
+// env_classic.hip — CartPole-v1, Pendulum-v1 and MountainCar-v0 batched steppers + the
 // gymrl_env_* C-ABI dispatch (LunarLander lives in env_lunar.hip).
 //
 // Replaces gym.make(...).reset()/.step() as called from dqn_cartpole.py:176,181,
@@ -106,10 +106,57 @@ __global__ __launch_bounds__(kEnvBlock) void pendulum_step_kernel(
   accumulate_ep_stats(ep_stats, r.done, r.ret, r.len);
 }
 
+// ---------------------------------------------------------- MountainCar ----
+// (mountaincar_baseline.py:29,53,60: gym.make / reset / step; two floats per env, one float2 store)
+__global__ __launch_bounds__(kEnvBlock) void mountaincar_reset_kernel(void* buf, int n, uint64_t seed,
+                                                                      int64_t env_id0,
+                                                                      float* __restrict__ obs_out) {
+  MountainCarState st(buf, n);
+  const int i = blockIdx.x * kEnvBlock + threadIdx.x;
+  if (i >= n) return;
+  double pos, vel;
+  mountaincar_draw(seed, (uint64_t)(env_id0 + i), 0u, pos, vel);
+  st.pos[i] = pos; st.vel[i] = vel;
+  st.ep.ep_ret[i] = 0.0; st.ep.ep_len[i] = 0; st.ep.episode[i] = 0u;
+  reinterpret_cast<float2*>(obs_out)[i] = make_float2((float)pos, (float)vel);
+}
+
+__global__ __launch_bounds__(kEnvBlock) void mountaincar_step_kernel(
+    void* buf, int n, uint64_t seed, int64_t env_id0, const int32_t* __restrict__ action,
+    float* __restrict__ obs_out, float* __restrict__ term_obs_out, float* __restrict__ rew_out,
+    uint8_t* __restrict__ terminated_out, uint8_t* __restrict__ truncated_out,
+    uint8_t* __restrict__ done_out, float* __restrict__ ep_ret_out,
+    int32_t* __restrict__ ep_len_out, double* __restrict__ ep_stats) {
+  MountainCarState st(buf, n);
+  const int i = blockIdx.x * kEnvBlock + threadIdx.x;
+  const bool valid = i < n;
+  ClassicStep<2> r;
+  r.done = false; r.ret = 0.0; r.len = 0;
+  if (valid) {
+    mountaincar_step_one(st, i, seed, env_id0, action[i], r);
+    rew_out[i] = r.reward;
+    terminated_out[i] = r.terminated; truncated_out[i] = r.truncated;
+    if (done_out) done_out[i] = r.done;
+    if (term_obs_out) reinterpret_cast<float2*>(term_obs_out)[i] = make_float2(r.o_term[0], r.o_term[1]);
+    if (r.done) {
+      if (ep_ret_out) ep_ret_out[i] = (float)r.ret;
+      if (ep_len_out) ep_len_out[i] = r.len;
+    }
+    reinterpret_cast<float2*>(obs_out)[i] = make_float2(r.o_next[0], r.o_next[1]);
+  }
+  accumulate_ep_stats(ep_stats, r.done, r.ret, r.len);
+}
+
 // Episodes a trainer abandons at its own step cap (dqn_cartpole.py:178 `for step in range(cfg.max_steps)` below the
 // env's TimeLimit): an env whose running episode has reached `cap` steps starts its next episode — no done flag, the
 // transition just stored keeps the real next observation — and reports the abandoned episode's return / length.
-__global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(int kind, void* buf, int n, uint64_t seed, int64_t env_id0,
+template <int KIND> struct StateOf;
+template <> struct StateOf<GYMRL_ENV_CARTPOLE> { using type = CartPoleState; };
+template <> struct StateOf<GYMRL_ENV_PENDULUM> { using type = PendulumState; };
+template <> struct StateOf<GYMRL_ENV_MOUNTAINCAR> { using type = MountainCarState; };
+
+template <int KIND>
+__global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(void* buf, int n, uint64_t seed, int64_t env_id0,
                                                                     int cap, float* __restrict__ obs, uint8_t* __restrict__ flag_out,
                                                                     float* __restrict__ ep_ret_out, int32_t* __restrict__ ep_len_out,
                                                                     double* __restrict__ ep_stats) {
@@ -117,26 +164,30 @@ __global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(int kind, vo
   bool hit = false;
   double ret = 0.0; int len = 0;
   if (i < n) {
-    EpisodeFields ep = kind == GYMRL_ENV_CARTPOLE ? CartPoleState(buf, n).ep : PendulumState(buf, n).ep;
+    const typename StateOf<KIND>::type st(buf, n);
+    const EpisodeFields ep = st.ep;
     len = ep.ep_len[i];
     hit = len >= cap;
     if (hit) {
       ret = ep.ep_ret[i];
       const uint32_t e = ep.episode[i] + 1u;
-      if (kind == GYMRL_ENV_CARTPOLE) {
-        CartPoleState st(buf, n);
+      if constexpr (KIND == GYMRL_ENV_CARTPOLE) {
         double r[4];
         cartpole_draw(seed, (uint64_t)(env_id0 + i), e, r);
         st.x[i] = r[0]; st.xd[i] = r[1]; st.th[i] = r[2]; st.thd[i] = r[3];
         reinterpret_cast<float4*>(obs)[i] = make_float4((float)r[0], (float)r[1], (float)r[2], (float)r[3]);
-      } else {
-        PendulumState st(buf, n);
+      } else if constexpr (KIND == GYMRL_ENV_PENDULUM) {
         double th, thd;
         pendulum_draw(seed, (uint64_t)(env_id0 + i), e, th, thd);
         st.th[i] = th; st.thd[i] = thd;
         float o[3];
         pendulum_obs(th, thd, o);
         obs[3 * (size_t)i] = o[0]; obs[3 * (size_t)i + 1] = o[1]; obs[3 * (size_t)i + 2] = o[2];
+      } else {
+        double pos, vel;
+        mountaincar_draw(seed, (uint64_t)(env_id0 + i), e, pos, vel);
+        st.pos[i] = pos; st.vel[i] = vel;
+        reinterpret_cast<float2*>(obs)[i] = make_float2((float)pos, (float)vel);
       }
       ep.ep_ret[i] = 0.0; ep.ep_len[i] = 0; ep.episode[i] = e;
       if (ep_ret_out) ep_ret_out[i] = (float)ret;
@@ -147,6 +198,7 @@ __global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(int kind, vo
   accumulate_ep_stats(ep_stats, hit, ret, len);
 }
 
+inline bool classic_kind(int kind) { return kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_PENDULUM || kind == GYMRL_ENV_MOUNTAINCAR; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
@@ -167,16 +219,16 @@ int gymrl_device_ok(void) {
 }
 
 int gymrl_env_obs_dim(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 4 : kind == GYMRL_ENV_PENDULUM ? 3 : kind == GYMRL_ENV_LUNARLANDER ? 8 : -22;
+  return kind == GYMRL_ENV_CARTPOLE ? 4 : kind == GYMRL_ENV_PENDULUM ? 3 : kind == GYMRL_ENV_LUNARLANDER ? 8 : kind == GYMRL_ENV_MOUNTAINCAR ? 2 : -22;
 }
 int gymrl_env_act_dim(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 2 : kind == GYMRL_ENV_PENDULUM ? 1 : kind == GYMRL_ENV_LUNARLANDER ? 4 : -22;
+  return kind == GYMRL_ENV_CARTPOLE ? 2 : kind == GYMRL_ENV_PENDULUM ? 1 : kind == GYMRL_ENV_LUNARLANDER ? 4 : kind == GYMRL_ENV_MOUNTAINCAR ? 3 : -22;
 }
 int gymrl_env_is_discrete(int kind) {
-  return kind == GYMRL_ENV_PENDULUM ? 0 : (kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_LUNARLANDER) ? 1 : -22;
+  return kind == GYMRL_ENV_PENDULUM ? 0 : (kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_LUNARLANDER || kind == GYMRL_ENV_MOUNTAINCAR) ? 1 : -22;
 }
 int gymrl_env_max_steps(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 500 : kind == GYMRL_ENV_PENDULUM ? 200 : kind == GYMRL_ENV_LUNARLANDER ? 1000 : -22;
+  return kind == GYMRL_ENV_CARTPOLE ? 500 : kind == GYMRL_ENV_PENDULUM ? 200 : kind == GYMRL_ENV_LUNARLANDER ? 1000 : kind == GYMRL_ENV_MOUNTAINCAR ? 200 : -22;
 }
 
 size_t gymrl_env_state_bytes(int kind, int n_envs) {
@@ -185,6 +237,7 @@ size_t gymrl_env_state_bytes(int kind, int n_envs) {
     case GYMRL_ENV_CARTPOLE: return CartPoleState(nullptr, n_envs).bytes;
     case GYMRL_ENV_PENDULUM: return PendulumState(nullptr, n_envs).bytes;
     case GYMRL_ENV_LUNARLANDER: return lunar_state_bytes(n_envs);
+    case GYMRL_ENV_MOUNTAINCAR: return MountainCarState(nullptr, n_envs).bytes;
     default: return 0;
   }
 }
@@ -205,6 +258,10 @@ int gymrl_env_reset(int kind, void* state, int n, uint64_t seed, int64_t env_id0
       break;
     case GYMRL_ENV_LUNARLANDER:
       return lunar_reset(state, n, seed, env_id0, obs_out, s);
+    case GYMRL_ENV_MOUNTAINCAR:
+      hipLaunchKernelGGL(mountaincar_reset_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, s,
+                         state, n, seed, env_id0, obs_out);
+      break;
     default: return -22;
   }
   GYMRL_CHECK_LAUNCH();
@@ -214,9 +271,11 @@ int gymrl_env_reset(int kind, void* state, int n, uint64_t seed, int64_t env_id0
 int gymrl_env_abandon(int kind, void* state, int n, uint64_t seed, int64_t env_id0, int cap, float* obs_inout,
                       uint8_t* flag_inout, float* ep_ret_out, int32_t* ep_len_out, double* ep_stats, void* stream_) {
   if (!state || !obs_inout || n < 0 || cap <= 0 || !aligned(state, 256) || !aligned(obs_inout, 16)) return -22;
-  if (kind != GYMRL_ENV_CARTPOLE && kind != GYMRL_ENV_PENDULUM) return -22;    // no reference off-policy script runs LunarLander
+  if (!classic_kind(kind)) return -22;    // no reference off-policy script runs LunarLander
   if (n == 0) return 0;
-  hipLaunchKernelGGL(classic_abandon_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, (hipStream_t)stream_, kind, state,
+  const auto kernel = kind == GYMRL_ENV_CARTPOLE ? classic_abandon_kernel<GYMRL_ENV_CARTPOLE>
+                      : kind == GYMRL_ENV_PENDULUM ? classic_abandon_kernel<GYMRL_ENV_PENDULUM> : classic_abandon_kernel<GYMRL_ENV_MOUNTAINCAR>;
+  hipLaunchKernelGGL(kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, (hipStream_t)stream_, state,
                      n, seed, env_id0, cap, obs_inout, flag_inout, ep_ret_out, ep_len_out, ep_stats);
   GYMRL_CHECK_LAUNCH();
   return 0;
@@ -226,7 +285,7 @@ int gymrl_env_refill(int kind, void* state, int n, uint64_t seed, int64_t env_id
   if (!state || n < 0 || !aligned(state, 256)) return -22;
   if (n == 0) return 0;
   if (kind == GYMRL_ENV_LUNARLANDER) return lunar_refill(state, n, seed, env_id0, (hipStream_t)stream_);
-  return (kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_PENDULUM) ? 0 : -22;   // cheap resets: nothing to prepare
+  return classic_kind(kind) ? 0 : -22;   // cheap resets: nothing to prepare
 }
 
 int gymrl_env_step(int kind, void* state, int n, uint64_t seed, int64_t env_id0, const void* action,
@@ -256,6 +315,12 @@ int gymrl_env_step(int kind, void* state, int n, uint64_t seed, int64_t env_id0,
       return lunar_step(state, n, seed, env_id0, (const int32_t*)action, obs_out, term_obs_out,
                         rew_out, terminated_out, truncated_out, done_out, ep_ret_out, ep_len_out,
                         ep_stats, s);
+    case GYMRL_ENV_MOUNTAINCAR:
+      hipLaunchKernelGGL(mountaincar_step_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, s,
+                         state, n, seed, env_id0, (const int32_t*)action, obs_out, term_obs_out,
+                         rew_out, terminated_out, truncated_out, done_out, ep_ret_out, ep_len_out,
+                         ep_stats);
+      break;
     default: return -22;
   }
   GYMRL_CHECK_LAUNCH();

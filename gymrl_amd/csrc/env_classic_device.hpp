@@ -1,9 +1,9 @@
-// env_classic_device.hpp — CartPole-v1 / Pendulum-v1: state layout, reset draws and ONE env's step as device functions.
+// env_classic_device.hpp — CartPole-v1 / Pendulum-v1 / MountainCar-v0: state layout, reset draws and ONE env's step as device functions.
 //
-// The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1").step()/reset() (gymnasium classic_control, third-party:
+// The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1" | "MountainCar-v0").step()/reset() (gymnasium classic_control, third-party:
 // SURVEY.md 8c.2) for one env = one lane.  Shared by the stand-alone steppers (env_classic.hip: gymrl_env_step) and the
 // fused acting kernels (offpolicy_step.hip, rainbow_step.hip, td3_step.hip: forward + draw + env step + ring append in one launch), so both produce the
-// same bits.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
+// same bits; MountainCar's core is shared with the one-launch episode kernel (mountaincar.hip) in the same way.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
 #pragma once
 #include "env_common.hpp"
 
@@ -33,6 +33,18 @@ struct PendulumState {
   }
 };
 
+struct MountainCarState {
+  double *pos, *vel;
+  EpisodeFields ep;
+  size_t bytes;
+  __host__ __device__ MountainCarState(void* buf, int n) {
+    Carver c(buf, n);
+    pos = c.take<double>(); vel = c.take<double>();
+    ep.ep_ret = c.take<double>(); ep.ep_len = c.take<int32_t>(); ep.episode = c.take<uint32_t>();
+    bytes = c.off;
+  }
+};
+
 __device__ __forceinline__ void cartpole_draw(uint64_t seed, uint64_t env, uint32_t episode,
                                               double (&s)[4]) {
   // reset: U(-0.05, 0.05)^4 in float64 (gymnasium CartPoleEnv.reset)
@@ -50,6 +62,14 @@ __device__ __forceinline__ void pendulum_draw(uint64_t seed, uint64_t env, uint3
   const double pi = 3.14159265358979323846;
   th = -pi + (2.0 * pi) * u01d(a.x, a.y);
   thd = -1.0 + 2.0 * u01d(a.z, a.w);
+}
+
+__device__ __forceinline__ void mountaincar_draw(uint64_t seed, uint64_t env, uint32_t episode,
+                                                 double& pos, double& vel) {
+  // reset: position U(-0.6, -0.4), velocity 0 (gymnasium MountainCarEnv.reset)
+  const u32x4 a = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), episode, RNG_ENV_RESET | 0u);
+  pos = -0.6 + 0.2 * u01d(a.x, a.y);
+  vel = 0.0;
 }
 
 __device__ __forceinline__ void pendulum_obs(double th, double thd, float (&o)[3]) {
@@ -141,6 +161,45 @@ __device__ __forceinline__ void pendulum_step_one(const PendulumState& st, int i
     st.th[i] = nth; st.thd[i] = nthd;
     st.ep.ep_ret[i] = r.ret; st.ep.ep_len[i] = r.len;
     r.o_next[0] = r.o_term[0]; r.o_next[1] = r.o_term[1]; r.o_next[2] = r.o_term[2];
+  }
+}
+
+// MountainCar-v0, registers only: force 0.001 per action step against gravity 0.0025 * cos(3 pos), speed clipped to +-0.07,
+// position to [-1.2, 0.6], the left wall is inelastic; -> terminated (at or past 0.5 and not moving left).  The stepper below
+// and the episode kernel (mountaincar.hip) both call it.
+__device__ __forceinline__ bool mountaincar_advance(double& pos, double& vel, int action) {
+  double s, c;
+  det_sincos(3.0 * pos, &s, &c);
+  vel = vel + (((double)(action - 1)) * 0.001 + c * (-0.0025));
+  vel = vel < -0.07 ? -0.07 : (vel > 0.07 ? 0.07 : vel);
+  pos = pos + vel;
+  pos = pos < -1.2 ? -1.2 : (pos > 0.6 ? 0.6 : pos);
+  if (pos == -1.2 && vel < 0.0) vel = 0.0;
+  return pos >= 0.5 && vel >= 0.0;
+}
+
+// MountainCar-v0: reward -1 on every step including the terminating one, TimeLimit 200; auto-reset into episode + 1's draw.
+__device__ __forceinline__ void mountaincar_step_one(const MountainCarState& st, int i, uint64_t seed, int64_t env_id0, int action,
+                                                     ClassicStep<2>& r) {
+  double pos = st.pos[i], vel = st.vel[i];
+  r.terminated = mountaincar_advance(pos, vel, action);
+  r.len = st.ep.ep_len[i] + 1;
+  r.truncated = r.len >= 200;
+  r.done = r.terminated || r.truncated;
+  r.ret = st.ep.ep_ret[i] + (-1.0);
+  r.reward = -1.0f;
+  r.o_term[0] = (float)pos; r.o_term[1] = (float)vel;
+  if (r.done) {
+    const uint32_t e = st.ep.episode[i] + 1u;
+    double rp, rv;
+    mountaincar_draw(seed, (uint64_t)(env_id0 + i), e, rp, rv);
+    st.pos[i] = rp; st.vel[i] = rv;
+    st.ep.ep_ret[i] = 0.0; st.ep.ep_len[i] = 0; st.ep.episode[i] = e;
+    r.o_next[0] = (float)rp; r.o_next[1] = (float)rv;
+  } else {
+    st.pos[i] = pos; st.vel[i] = vel;
+    st.ep.ep_ret[i] = r.ret; st.ep.ep_len[i] = r.len;
+    r.o_next[0] = r.o_term[0]; r.o_next[1] = r.o_term[1];
   }
 }
 

@@ -1,8 +1,8 @@
-"""Device-resident batched environments (CartPole-v1 / Pendulum-v1 / LunarLander-v3).
+"""Device-resident batched environments (CartPole-v1 / Pendulum-v1 / LunarLander-v3 / MountainCar-v0).
 
 Stands where `gym.make(name)` stands in the reference trainers
 (ppo_lunarlander.py:160, dqn_cartpole.py:94, rainbow_dqn_cartpole.py:270,
-sac_pendulum.py:154, utils/runner.py:53).  N env instances live in one SoA state
+sac_pendulum.py:154, utils/runner.py:53, mountaincar_baseline.py:29).  N env instances live in one SoA state
 buffer in HBM and are stepped by one HIP kernel launch (one env per lane) with
 auto-reset; observations, rewards and flags never leave the device.
 """

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   MlpDesc, MlprnnParams, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   MlpDesc, MlprnnParams, MountainCarEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -479,8 +479,8 @@ def soft_update(target, source, tau):
 
 
 # -------------------------------------------------------------------- env ---
-CARTPOLE, PENDULUM, LUNARLANDER = 0, 1, 2
-ENV_KINDS = {"CartPole-v1": CARTPOLE, "Pendulum-v1": PENDULUM, "LunarLander-v3": LUNARLANDER}
+CARTPOLE, PENDULUM, LUNARLANDER, MOUNTAINCAR = 0, 1, 2, 3
+ENV_KINDS = {"CartPole-v1": CARTPOLE, "Pendulum-v1": PENDULUM, "LunarLander-v3": LUNARLANDER, "MountainCar-v0": MOUNTAINCAR}
 
 
 def env_dims(kind):
@@ -553,6 +553,33 @@ def qlearn_eval(kind, Q, n_episodes, seed, stream_id0, cap, is_slippery=False):
     check(lib().gymrl_qlearn_eval(kind, int(bool(is_slippery)), _ptr(Q, torch.float64), R, n_episodes, seed, stream_id0, cap,
                                   _ptr(returns), _ptr(lengths), _ptr(flags), _stream()), "gymrl_qlearn_eval")
     return returns, lengths, flags
+
+
+# ------------------------------------------- MountainCar-v0 rule baseline ---
+MOUNTAINCAR_RULE_COEFS = (-0.09, 0.25, 0.03, 0.3, 0.9, 0.008, -0.07, 0.38, 0.07)     # mountaincar_baseline.py:37-40
+MOUNTAINCAR_MAX_STEPS = 200
+
+
+def mountaincar_rule_eval(n_episodes, seed, stream_id0, cap, device, coefs=None, start=None, want_final_state=False):
+    """n_episodes episodes of MountainCar-v0 per rule policy, one lane each and ONE launch (include/gymrl.h) ->
+    (returns f64, lengths i32, reached u8), each [P, n_episodes], and final_state f64[P, n_episodes, 2] when asked for.
+    coefs f64[P, 9] on the device, or None: the reference's constants, P = 1.  start f64[P, n_episodes, 2] replaces the reset draws."""
+    P = 1 if coefs is None else coefs.shape[0]
+    if coefs is not None and tuple(coefs.shape) != (P, len(MOUNTAINCAR_RULE_COEFS)):
+        raise ValueError(f"coefs is {tuple(coefs.shape)}, a population of rule policies is [P, {len(MOUNTAINCAR_RULE_COEFS)}]")
+    if start is not None and tuple(start.shape) != (P, n_episodes, 2):
+        raise ValueError(f"start is {tuple(start.shape)}, {P} policies x {n_episodes} episodes need [{P}, {n_episodes}, 2]")
+    returns = torch.empty(P, n_episodes, dtype=torch.float64, device=device)
+    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=device)
+    reached = torch.empty(P, n_episodes, dtype=torch.uint8, device=device)
+    final = torch.empty(P, n_episodes, 2, dtype=torch.float64, device=device) if want_final_state else None
+    a = MountainCarEvalArgs()
+    a.P, a.E, a.cap, a.seed, a.stream_id0 = P, n_episodes, cap, seed, stream_id0
+    a.coefs, a.start = _ptr(coefs, torch.float64, True), _ptr(start, torch.float64, True)
+    a.returns, a.lengths, a.reached = _ptr(returns), _ptr(lengths), _ptr(reached)
+    a.final_state = _ptr(final, torch.float64, True)
+    check(lib().gymrl_mountaincar_rule_eval(C.byref(a), _stream()), "gymrl_mountaincar_rule_eval")
+    return (returns, lengths, reached, final) if want_final_state else (returns, lengths, reached)
 
 
 # ============================================================== off-policy ===

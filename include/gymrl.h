@@ -41,26 +41,29 @@ int gymrl_device_ok(void);
 enum {
   GYMRL_ENV_CARTPOLE    = 0, /* CartPole-v1   obs 4, 2 discrete actions   */
   GYMRL_ENV_PENDULUM    = 1, /* Pendulum-v1   obs 3, 1 continuous in [-2,2] */
-  GYMRL_ENV_LUNARLANDER = 2  /* LunarLander-v3 obs 8, 4 discrete actions  */
+  GYMRL_ENV_LUNARLANDER = 2, /* LunarLander-v3 obs 8, 4 discrete actions  */
+  GYMRL_ENV_MOUNTAINCAR = 3  /* MountainCar-v0 obs 2, 3 discrete actions (the steppers and gymrl_mountaincar_rule_eval only:
+                              * the fused acting, ring and rollout kernels refuse it with -EINVAL) */
 };
 
 /*
  * Batched env stepper.  Replaces gym.make / env.reset / env.step as used by
  * ppo_lunarlander.py:160,200,211,222  dqn_cartpole.py:94,176,181
  * rainbow_dqn_cartpole.py:270,369,373  sac_pendulum.py:154,275,281
- * utils/runner.py:53,111,123.
+ * utils/runner.py:53,111,123  mountaincar_baseline.py:29,53,60.
  * One env instance per lane; state is a caller-owned SoA byte buffer of
  * gymrl_env_state_bytes(kind, n_envs) bytes (256-B aligned base required).
  * Classic envs: consecutive fields [n_envs], each field's byte size rounded up to a multiple of 256 —
  *   CartPole-v1  f64 x, f64 x_dot, f64 theta, f64 theta_dot, f64 ep_ret, i32 ep_len, u32 episode
  *   Pendulum-v1  f64 theta, f64 theta_dot, f64 ep_ret, i32 ep_len, u32 episode
+ *   MountainCar-v0  f64 position, f64 velocity, f64 ep_ret, i32 ep_len, u32 episode
  * (float64 like gymnasium's own state; tests/test_classic_micro_gpu.py writes states through this layout, and a
  * checkpoint of a running vector is a copy of the buffer).  LunarLander: 144 dwords per env, word-major.
  */
 int    gymrl_env_obs_dim(int kind);
 int    gymrl_env_act_dim(int kind);     /* #discrete actions, or continuous dim */
 int    gymrl_env_is_discrete(int kind);
-int    gymrl_env_max_steps(int kind);   /* TimeLimit: 500 / 200 / 1000 */
+int    gymrl_env_max_steps(int kind);   /* TimeLimit: 500 / 200 / 1000 / 200 */
 size_t gymrl_env_state_bytes(int kind, int n_envs);
 
 /* (Re)initialise every env: episode counter := 0, draws from the counter-based
@@ -92,7 +95,7 @@ int gymrl_env_step(int kind, void* state, int n_envs, uint64_t seed, int64_t env
  * Call after gymrl_env_step: every env whose running episode has reached `cap` steps starts its next episode;
  * obs_inout [N, obs] rows of those envs become the reset observation, flag_inout u8[N] (or NULL) is OR-ed with 1
  * for them, ep_ret_out / ep_len_out / ep_stats receive the abandoned episode as gymrl_env_step would for a
- * finished one.  CartPole-v1 and Pendulum-v1 (no reference off-policy script runs LunarLander: -EINVAL). */
+ * finished one.  CartPole-v1, Pendulum-v1 and MountainCar-v0 (no reference off-policy script runs LunarLander: -EINVAL). */
 int gymrl_env_abandon(int kind, void* state, int n_envs, uint64_t seed, int64_t env_id0, int cap,
                       float* obs_inout, uint8_t* flag_inout, float* ep_ret_out, int32_t* ep_len_out,
                       double* ep_stats, void* stream);
@@ -102,7 +105,7 @@ int gymrl_env_abandon(int kind, void* state, int n_envs, uint64_t seed, int64_t 
  * episode in a spare slot of `state`; gymrl_env_step then swaps it in when the episode ends
  * instead of running the reset inside the step.  Results are bit-identical with or without
  * it.  Intended for a side stream (it may overlap later gymrl_env_step calls on the same
- * state); a no-op for CartPole / Pendulum. */
+ * state); a no-op for CartPole / Pendulum / MountainCar. */
 int gymrl_env_refill(int kind, void* state, int n_envs, uint64_t seed, int64_t env_id0,
                      void* stream);
 
@@ -1668,6 +1671,38 @@ int gymrl_ndqn_combine(const gymrl_ndqn_combine_args* args, void* stream);
 int gymrl_ndqn_act_step(const gymrl_ndqn_act_args* args, void* stream);
 size_t gymrl_ndqn_update_workspace_bytes(int B, int D, int A, int H);
 int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
+
+/* ------------------------------------------- MountainCar-v0 rule baseline ---- */
+/*
+ * Replaces RuleBasedAgent.select_action() / run_episode() / eval() of mountaincar_baseline.py:35-84 together with the
+ * gym.make(...).reset() / .step() calls inside them, P policies x E episodes at a time.  An episode is a strictly serial chain of
+ * at most 200 steps of six float64 operations and one cos; P * E of them are independent, so one LANE is one (policy p,
+ * episode e) pair, i = p * E + e, and they all run to their end in one launch: position, velocity, step count and the nine
+ * coefficients stay in registers, no LDS, no atomics, a wave leaves the loop when its last episode is over.
+ *
+ * The env is GYMRL_ENV_MOUNTAINCAR's (csrc/env_classic_device.hpp: the same device function steps both); episode i starts from
+ * the reset draw of (seed, stream_id0 + i, episode 0), i.e. the first episode of env i of a gymrl_env_reset with
+ * env_id0 = stream_id0, or from start[i] = (position, velocity) where `start` is given.
+ *
+ * The policy is select_action with its nine constants as k[0..8] (the reference's: -0.09, 0.25, 0.03, 0.3, 0.9, 0.008, -0.07,
+ * 0.38, 0.07), in float64 on the float32 observation, powers as products:
+ *   p = (double)(float)pos, v = (double)(float)vel
+ *   lb = min(k0 * (p + k1)^2 + k2, k3 * (p + k4)^4 - k5), ub = k6 * (p + k7)^2 + k8, action = lb < v && v < ub ? 2 : 0
+ *
+ * Outputs, each [P * E]: returns (-1 per step), lengths, reached (1: the env terminated; 0: the episode was cut at `cap`
+ * steps, the env's TimeLimit 200 included), final_state [P * E][2] (optional) the float64 state after the last step.
+ * -EINVAL before any launch: NULL args or a NULL required output, P < 1, E < 1, cap outside 1..200, coefs == NULL with P != 1,
+ * P * E above INT32_MAX, stream_id0 < 0, a pointer that is not aligned to its element.
+ */
+typedef struct {
+  int P, E, cap;
+  uint64_t seed; int64_t stream_id0;
+  const double* coefs;                     /* f64[P][9], or NULL: the reference's constants (P == 1) */
+  const double* start;                     /* f64[P * E][2] (position, velocity), or NULL: the reset draw */
+  double* returns; int32_t* lengths; uint8_t* reached;
+  double* final_state;                     /* f64[P * E][2] or NULL */
+} gymrl_mountaincar_eval_args;
+int gymrl_mountaincar_rule_eval(const gymrl_mountaincar_eval_args* args, void* stream);
 
 #ifdef __cplusplus
 }
