@@ -396,6 +396,10 @@ SIGNATURES = {
     "gymrl_rnd_reward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "gymrl_gru_seq_fwd": (_i, [_vp, _vp, _vp, _vp, _P(C.c_int32), _i, _i, _i, _vp, _vp, _vp]),
     "gymrl_gru_seq_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_int32), _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_lstm_cell_fwd": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "gymrl_lstm_cell_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "gymrl_lstm_seq_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _P(C.c_int32), _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_lstm_seq_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(C.c_int32), _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gymrl_episode_gae": (_i, [_vp, _vp, _vp, _vp, _vp, _P(_i64), _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_ppg_policy_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _P(_i64), _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_ppg_aux_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _P(_i64), _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),

@@ -279,6 +279,83 @@ def gru_seq_bwd(gi, W_hh, b_hh, h_seq, lengths, d_hseq=None, d_hlast=None, h0=No
     return dgi, dgh, dh0
 
 
+def lstm_cell_fwd(gi, gh, c):
+    """The pointwise half of nn.LSTM's cell (gymrl_lstm_cell_fwd).  gi, gh f32[B,4H], c f32[B,H] -> (h', c')."""
+    B, H = c.shape
+    _need_shape(gi, (B, 4 * H), "gi")
+    _need_shape(gh, (B, 4 * H), "gh")
+    h_out, c_out = torch.empty_like(c), torch.empty_like(c)
+    check(lib().gymrl_lstm_cell_fwd(_ptr(gi, torch.float32), _ptr(gh, torch.float32), _ptr(c, torch.float32), B, H,
+                                    _ptr(h_out, torch.float32), _ptr(c_out, torch.float32), _stream()), "gymrl_lstm_cell_fwd")
+    return h_out, c_out
+
+
+def lstm_cell_bwd(gi, gh, c, dh_out, dc_out=None):
+    """Backward of lstm_cell_fwd (gymrl_lstm_cell_bwd).  Returns (dgates f32[B,4H] = dgi = dgh, dc f32[B,H])."""
+    B, H = c.shape
+    _need_shape(gi, (B, 4 * H), "gi")
+    _need_shape(gh, (B, 4 * H), "gh")
+    _need_shape(dh_out, (B, H), "dh_out")
+    _need_shape(dc_out, (B, H), "dc_out")
+    dgates, dc = torch.empty_like(gi), torch.empty_like(c)
+    check(lib().gymrl_lstm_cell_bwd(_ptr(gi, torch.float32), _ptr(gh, torch.float32), _ptr(c, torch.float32),
+                                    _ptr(dh_out, torch.float32), _ptr(dc_out, torch.float32, True), B, H, _ptr(dgates), _ptr(dc),
+                                    _stream()), "gymrl_lstm_cell_bwd")
+    return dgates, dc
+
+
+def _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, lens_len, T, B, H, **more):
+    if gi.dim() != 3 or gi.shape[2] % 4:
+        raise ValueError(f"gi: expected [T, B, 4H], got {tuple(gi.shape)}")
+    if lens_len != B:
+        raise ValueError(f"lengths has {lens_len} entries for {B} rows")
+    _need_shape(W_hh, (4 * H, H), "W_hh")
+    _need_shape(b_hh, (4 * H,), "b_hh")
+    _need_shape(h0, (B, H), "h0")
+    _need_shape(c0, (B, H), "c0")
+    for name, (t, shape) in more.items():
+        _need_shape(t, shape, name)
+
+
+def lstm_seq_fwd(gi, W_hh, b_hh, lengths, h0=None, c0=None):
+    """The LSTM recurrence in one launch (gymrl_lstm_seq_fwd).  gi f32[T,B,4H] time-major, lengths: host ints [B].
+    Returns (h_seq, c_seq f32[T,B,H], zero past each length; h_last, c_last f32[B,H])."""
+    if gi.dim() != 3:
+        raise ValueError(f"gi: expected [T, B, 4H], got {tuple(gi.shape)}")
+    T, B, H4 = gi.shape
+    H = H4 // 4
+    lens, nb = _host_i32(lengths)
+    _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, nb, T, B, H)
+    h_seq, c_seq = (torch.empty(T, B, H, dtype=torch.float32, device=gi.device) for _ in range(2))
+    h_last, c_last = (torch.empty(B, H, dtype=torch.float32, device=gi.device) for _ in range(2))
+    check(lib().gymrl_lstm_seq_fwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
+                                   _ptr(h0, torch.float32, True), _ptr(c0, torch.float32, True), lens, T, B, H, _ptr(h_seq),
+                                   _ptr(c_seq), _ptr(h_last), _ptr(c_last), _stream()), "gymrl_lstm_seq_fwd")
+    return h_seq, c_seq, h_last, c_last
+
+
+def lstm_seq_bwd(gi, W_hh, b_hh, h_seq, c_seq, lengths, d_hseq=None, d_hlast=None, d_clast=None, h0=None, c0=None,
+                 need_d0=True):
+    """Reverse recurrence of lstm_seq_fwd (gymrl_lstm_seq_bwd).  Returns (dgates f32[T,B,4H] = dgi = dgh, dh0, dc0
+    f32[B,H] or None)."""
+    if gi.dim() != 3:
+        raise ValueError(f"gi: expected [T, B, 4H], got {tuple(gi.shape)}")
+    T, B, H4 = gi.shape
+    H = H4 // 4
+    lens, nb = _host_i32(lengths)
+    _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, nb, T, B, H, h_seq=(h_seq, (T, B, H)), c_seq=(c_seq, (T, B, H)),
+                     d_hseq=(d_hseq, (T, B, H)), d_hlast=(d_hlast, (B, H)), d_clast=(d_clast, (B, H)))
+    dgates = torch.empty_like(gi)
+    dh0, dc0 = ((torch.empty(B, H, dtype=torch.float32, device=gi.device) for _ in range(2)) if need_d0 else (None, None))
+    check(lib().gymrl_lstm_seq_bwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
+                                   _ptr(h0, torch.float32, True), _ptr(c0, torch.float32, True), _ptr(h_seq, torch.float32),
+                                   _ptr(c_seq, torch.float32), _ptr(d_hseq, torch.float32, True),
+                                   _ptr(d_hlast, torch.float32, True), _ptr(d_clast, torch.float32, True), lens, T, B, H,
+                                   _ptr(dgates), _ptr(dh0, torch.float32, True), _ptr(dc0, torch.float32, True), _stream()),
+          "gymrl_lstm_seq_bwd")
+    return dgates, dh0, dc0
+
+
 def episode_gae(rew, val, next_val, done, dw, offsets, gamma, lam, want_raw=False, ep_moments=None):
     """EpisodeBuffer.compute_advantage per episode (ppg_rnn_lunarlander.py:198-215) over episodes stored back to back;
     offsets: host ints [E+1].  Returns (adv_norm, v_target, adv_raw or None)."""

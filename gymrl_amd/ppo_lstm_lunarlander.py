@@ -7,7 +7,9 @@ update_model :657-812).
 
 What runs where: env stepping, categorical sampling (+ behaviour entropy), the RND reward, decoupled-lambda
 GAE, the L4 loss forward/backward (`gymrl_ppo_rnn_loss_fwd_bwd`), the GRU cell's pointwise half
-(`gymrl_gru_cell_fwd/_bwd` behind a torch.autograd.Function), clip-norm + Adam and the gradient all-reduce are
+(`gymrl_gru_cell_fwd/_bwd` behind a torch.autograd.Function; with `rnn_layer = "lstm"` the LSTM cell
+`gymrl_lstm_cell_fwd/_bwd` and, for a window at rnn_hidden in {16, 32, 48, 64}, the whole recurrence as
+`gymrl_lstm_seq_fwd/_bwd`, one launch per direction), clip-norm + Adam and the gradient all-reduce are
 the HIP / RCCL path; the dense layers (backbone, gate GEMMs, heads, RND towers) are PyTorch-ROCm library work.
 Parameter names are the reference's (`rnn.rnn.weight_ih_l0`, ...), so its state_dicts load unchanged.
 
@@ -67,6 +69,8 @@ class Config:
         self.rnn_hidden = 512              # the reference hard-codes these three (:84-95)
         self.head_hidden = 512
         self.rnd_embed = 512
+        self.rnn_layer = "gru"             # "lstm": URNN on nn.LSTM (the reference's layer=nn.LSTM, state cat(h, c))
+        self.rnn_fused = True              # LSTM only: windows run as one launch per direction where the kernels cover rnn_hidden
 
 
 class _GRUCell(torch.autograd.Function):
@@ -84,28 +88,91 @@ class _GRUCell(torch.autograd.Function):
         return ops.gru_cell_bwd(gi, gh, h, dh_out.contiguous())
 
 
-class URNN(nn.Module):
-    """One-layer batch_first GRU with the hidden state carried as [B, H] (:449-491).  `self.rnn` is a
-    torch.nn.GRU used as the parameter container (reference key names and init); its own forward is never
-    called — the gate GEMMs are F.linear and the cell is `_GRUCell`."""
+class _LSTMCell(torch.autograd.Function):
+    """(h', c') = LSTM pointwise(gi, gh, c) on the HIP kernels; the gates are recomputed in backward."""
 
-    def __init__(self, input_size, hidden_size, layer=nn.GRU):
+    @staticmethod
+    def forward(ctx, gi, gh, c):
+        gi, gh, c = gi.contiguous(), gh.contiguous(), c.contiguous()
+        ctx.save_for_backward(gi, gh, c)
+        return ops.lstm_cell_fwd(gi, gh, c)
+
+    @staticmethod
+    def backward(ctx, dh_out, dc_out):
+        gi, gh, c = ctx.saved_tensors
+        dgates, dc = ops.lstm_cell_bwd(gi, gh, c, dh_out.contiguous(), dc_out.contiguous())
+        return dgates, dgates, dc
+
+
+class _LSTMSeq(torch.autograd.Function):
+    """The LSTM recurrence over a [L, B, 4H] window of gate pre-activations in one launch per direction
+    (gymrl_lstm_seq_fwd / _bwd, uniform lengths L); the weight gradients are GEMMs over the flattened rows."""
+
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, h0, c0):
+        gi, w_hh, b_hh, h0, c0 = (a.contiguous() for a in (gi, w_hh, b_hh, h0, c0))
+        lens = [gi.shape[0]] * gi.shape[1]
+        h_seq, c_seq, h_last, c_last = ops.lstm_seq_fwd(gi, w_hh, b_hh, lens, h0=h0, c0=c0)
+        ctx.save_for_backward(gi, w_hh, b_hh, h0, c0, h_seq, c_seq)
+        return h_seq, h_last, c_last
+
+    @staticmethod
+    def backward(ctx, d_hseq, d_hlast, d_clast):
+        gi, w_hh, b_hh, h0, c0, h_seq, c_seq = ctx.saved_tensors
+        L, B, H4 = gi.shape
+        dgates, dh0, dc0 = ops.lstm_seq_bwd(gi, w_hh, b_hh, h_seq, c_seq, [L] * B, d_hseq=d_hseq.contiguous(),
+                                            d_hlast=d_hlast.contiguous(), d_clast=d_clast.contiguous(), h0=h0, c0=c0)
+        h_prev = torch.cat([h0.unsqueeze(0), h_seq[:-1]], 0).view(L * B, -1)
+        flat = dgates.view(L * B, H4)
+        return dgates, flat.t() @ h_prev, flat.sum(0), dh0, dc0
+
+
+LSTM_SEQ_HIDDEN = (16, 32, 48, 64)       # the hidden sizes gymrl_lstm_seq_* cover
+
+
+class URNN(nn.Module):
+    """One-layer batch_first GRU or LSTM with the hidden state carried as [B, H * chunk_size] (:449-491; for the LSTM
+    cat(h, c), chunk_size 2).  `self.rnn` is a torch.nn.GRU / nn.LSTM used as the parameter container (reference key
+    names and init); its own forward is never called — the gate GEMMs are F.linear and the cell is `_GRUCell` /
+    `_LSTMCell`.  An LSTM window (L > 1) whose hidden size the one-launch kernels cover runs as `_LSTMSeq` unless
+    `fused` is False."""
+
+    def __init__(self, input_size, hidden_size, layer=nn.GRU, fused=True):
         super().__init__()
-        if layer is not nn.GRU:
-            raise NotImplementedError("only the GRU the reference's ActorCritic instantiates (:84-88) is built")
-        self.input_size, self.hidden_size, self.chunk_size = input_size, hidden_size, 1
-        self.rnn = nn.GRU(input_size=input_size, hidden_size=hidden_size, batch_first=True)
+        if layer is not nn.GRU and layer is not nn.LSTM:
+            raise NotImplementedError("only the GRU and the LSTM the reference's URNN accepts (:463-468) are built")
+        self.input_size, self.hidden_size, self.chunk_size = input_size, hidden_size, 2 if layer is nn.LSTM else 1
+        self.fused = bool(fused)
+        self.rnn = layer(input_size=input_size, hidden_size=hidden_size, batch_first=True)
 
     def forward(self, x, hidden_state):
         B, L = x.shape[0], x.shape[1]
         r = self.rnn
-        h = torch.zeros(B, self.hidden_size, device=x.device) if hidden_state is None else hidden_state
-        gi = F.linear(x.transpose(0, 1), r.weight_ih_l0, r.bias_ih_l0)       # [L, B, 3H]: one GEMM for the window
+        if hidden_state is None:
+            hidden_state = torch.zeros(B, self.hidden_size * self.chunk_size, device=x.device)
+        gi = F.linear(x.transpose(0, 1), r.weight_ih_l0, r.bias_ih_l0)       # [L, B, 3H or 4H]: one GEMM for the window
+        if self.chunk_size == 2:
+            return self._forward_lstm(gi, hidden_state)
+        h = hidden_state
         outs = []
         for step in range(L):
             h = _GRUCell.apply(gi[step], F.linear(h, r.weight_hh_l0, r.bias_hh_l0), h)
             outs.append(h)
         return torch.stack(outs, dim=1), h
+
+    def _forward_lstm(self, gi, hidden_state):
+        r, L = self.rnn, gi.shape[0]
+        h, c = hidden_state.chunk(2, dim=-1)                                 # :479-483
+        if L > 1 and self.fused and self.hidden_size in LSTM_SEQ_HIDDEN:
+            h_seq, h, c = _LSTMSeq.apply(gi, r.weight_hh_l0, r.bias_hh_l0, h, c)
+            out = h_seq.transpose(0, 1)
+        else:
+            outs = []
+            for step in range(L):
+                h, c = _LSTMCell.apply(gi[step], F.linear(h, r.weight_hh_l0, r.bias_hh_l0), c)
+                outs.append(h)
+            out = torch.stack(outs, dim=1)
+        return out, torch.cat([h, c], dim=-1)
 
 
 class RND(nn.Module):
@@ -136,7 +203,10 @@ class ActorCritic(nn.Module):
         else:
             shared_out = getattr(cfg, "pscn_dim", 512)
             self.shared = PSCN(state_dim, shared_out, 5)
-        self.rnn = URNN(shared_out, H)
+        layer = {"gru": nn.GRU, "lstm": nn.LSTM}.get(str(getattr(cfg, "rnn_layer", "gru")).lower())
+        if layer is None:
+            raise ValueError(f"rnn_layer must be 'gru' or 'lstm', got {cfg.rnn_layer!r}")
+        self.rnn = URNN(shared_out, H, layer=layer, fused=bool(getattr(cfg, "rnn_fused", True)))
         self.actor = MLP([H, Hh, action_dim], last_std=0.001)
         self.critic = MLP([H, Hh, 1], last_std=1.0)
         self.rnd = RND(state_dim, getattr(cfg, "rnd_embed", 512))
@@ -209,6 +279,16 @@ class PPOTrainer:
         gdist.broadcast(self.flat_params)
         self.optimizer = FusedAdam(self.flat_params, self.flat_grads, lr=config.lr, eps=1e-5,
                                    max_grad_norm=config.max_grad_norm)
+        # Adam ranges of the flat buffer: the RND predictor [a, b) is stepped every minibatch (optimizer.step_count); the
+        # network [0, a) only when the minibatch's entropy-ratio mask is not empty (_adam_step); the RND target (frozen)
+        # lies behind b and is never stepped
+        offs = {n: (q.data_ptr() - self.flat_params.data_ptr()) // 4 for n, q in self.model.named_parameters()}
+        pred = [o for n, o in offs.items() if n.startswith("rnd.predictor.")]
+        behind = [o for n, o in offs.items() if n.startswith("rnd.target.")]
+        self._rnd_range = (min(pred), min(behind))
+        assert all((o < self._rnd_range[0]) != n.startswith("rnd.") for n, o in offs.items()) and max(pred) < min(behind)
+        self._net_live = torch.zeros(1, dtype=torch.float64, device=self.device)    # Adam step count of the network range
+        self._net_bias = torch.zeros(4, dtype=torch.float32, device=self.device)    # its gymrl_adam_bias scalars
         self.hidden_size = self.model.rnn.hidden_size * self.model.rnn.chunk_size
         self.step_count = 0
         self.rollout_count = 0
@@ -306,7 +386,7 @@ class PPOTrainer:
             self._sink.collect()
             if self.collective:
                 gdist.all_reduce_sum(self.flat_grads)
-            self.optimizer.step(grad_scale=1.0 / self.world_size, bias_dev=bias)
+            self._adam_step(metrics_row[9:10], bias)
             rnd_out.copy_(rnd_loss.detach())
 
         # Same scheme as PPO-full: the minibatch body is captured once per update_model() call and replayed.
@@ -370,6 +450,43 @@ class PPOTrainer:
                 "approx_kl": float((m[:, 4] / Bs).mean()), "erc_clip_frac": float((m[:, 5] / Bs).mean()),
                 "cov": float(cov.mean()), "rnd_loss": float(rnd_all.mean().item())}
 
+    @torch.no_grad()
+    def _adam_step(self, mask_count, bias=None):
+        """clip_grad_norm_ + optimizer.step() of :779-784 as torch.optim.Adam runs them.  A minibatch whose entropy-ratio
+        mask is empty has the constant masked_mean of :653-654 for its policy, value and entropy terms: the loss reaches only
+        the RND predictor, every other parameter keeps grad None, and torch.optim.Adam neither moves it nor counts a step
+        for it.  So the clip norm is taken over the whole gradient buffer, the RND predictor's range is stepped every time,
+        and the network's range is stepped under its own step count, kept on the device, and put back as it was when
+        `mask_count` (f64[1] on the device: metric 9 of the loss kernel) is zero — without a host synchronisation, so the
+        same body is captured as a hipGraph.  bias: the predictor range's step scalars on the device (graph replay)."""
+        opt, (a, b) = self.optimizer, self._rnd_range
+        g = opt.param_groups[0]
+        b1, b2 = g["betas"]
+        if self.collective:
+            mask_count = gdist.all_reduce_sum(mask_count.clone())
+        live = mask_count > 0
+        self._net_live.add_(live.to(torch.float64))
+        t = self._net_live.clamp(min=1.0)
+        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+        self._net_bias.copy_(torch.cat([g["lr"] / bc1, 1.0 / bc1, bc2.sqrt(), torch.zeros_like(t)]))   # gymrl_adam_bias
+        scale = 1.0 / self.world_size
+        ops.sqnorm(opt.g, opt._sq, opt._ws, grad_scale=scale)
+        if bias is None:
+            opt.step_count += 1
+        kw = dict(grad_scale=scale, max_grad_norm=opt.max_grad_norm, sqnorm_buf=opt._sq, zero_grad=True)
+        ops.adam_step(opt.p[a:b], opt.g[a:b], opt.m[a:b], opt.v[a:b], g["lr"], b1, b2, g["eps"], max(opt.step_count, 1),
+                      bias_dev=bias, **kw)
+        before = [x[:a].clone() for x in (opt.p, opt.m, opt.v)]
+        ops.adam_step(opt.p[:a], opt.g[:a], opt.m[:a], opt.v[:a], g["lr"], b1, b2, g["eps"], 1, bias_dev=self._net_bias, **kw)
+        for x, x0 in zip((opt.p, opt.m, opt.v), before):
+            x[:a].copy_(torch.where(live, x[:a], x0))
+
+    def _param_steps(self):
+        """Adam step count of every parameter, in model.parameters() order (the RND target is never stepped)."""
+        live = int(self._net_live.item())
+        return [0 if n.startswith("rnd.target.") else self.optimizer.step_count if n.startswith("rnd.") else live
+                for n, _ in self.model.named_parameters()]
+
     def train(self):
         update_count = 0
         while self.step_count * self.world_size < self.cfg.max_train_steps:
@@ -386,13 +503,20 @@ class PPOTrainer:
         """Reference layout for recurrent agents (ppo_rnn_lunarlander.py:372-392 keys `net_state_dict`,
         `optimizer_state_dict`, `learn_step`) through the ModelLoader-style writer."""
         from .utils import checkpoint
-        return checkpoint.save_agent(path, {"net": self.model}, {"optimizer": (self.model, self.optimizer)},
-                                     learn_step=self.rollout_count, step_count=self.step_count,
-                                     episode_rewards=list(self.episode_rewards), lr=self.lr, ent_coef=self.ent_coef)
+        state = {"net_state_dict": {n: v.detach().cpu() for n, v in self.model.state_dict().items()},
+                 "optimizer_state_dict": checkpoint.adam_state_dict(self.model, self.optimizer, steps=self._param_steps()),
+                 "learn_step": self.rollout_count, "step_count": self.step_count,
+                 "episode_rewards": list(self.episode_rewards), "lr": self.lr, "ent_coef": self.ent_coef}
+        torch.save(state, path)
+        return state
 
     def load_checkpoint(self, path):
         from .utils import checkpoint
-        rest = checkpoint.load_agent(path, {"net": self.model}, {"optimizer": (self.model, self.optimizer)})
+        rest = checkpoint.load_agent(path, {"net": self.model}, {})
+        steps = dict(zip((n for n, _ in self.model.named_parameters()),
+                         checkpoint.load_adam_state_dict(self.model, self.optimizer, rest.pop("optimizer_state_dict"), per_param=True)))
+        self.optimizer.step_count = max(v for n, v in steps.items() if n.startswith("rnd.predictor."))
+        self._net_live.fill_(float(max(v for n, v in steps.items() if not n.startswith("rnd."))))
         self.rollout_count = int(rest.get("learn_step", 0))
         self.step_count = int(rest.get("step_count", 0))
         self.lr, self.ent_coef = float(rest.get("lr", self.lr)), float(rest.get("ent_coef", self.ent_coef))

@@ -322,6 +322,35 @@ int gymrl_gru_seq_bwd(const float* gi, const float* W_hh, const float* b_hh, con
                       const float* d_hseq, const float* d_hlast, const int32_t* len, int T, int B, int H, float* dgi,
                       float* dgh, float* dh0, void* stream);
 
+/* torch.nn.LSTM's cell — ppo_lstm_lunarlander.py:449-491 (URNN with layer=nn.LSTM, hidden state cat(h, c)).  The
+ * pointwise half on gi = x W_ih^T + b_ih and gh = h W_hh^T + b_hh, both f32[B,4H] in PyTorch's gate order (i, f, g, o);
+ * c f32[B,H]:  a = gi + gh, i = s(a_i), f = s(a_f), g = tanh(a_g), o = s(a_o), c_out = f*c + i*g, h_out = o*tanh(c_out).
+ * _bwd recomputes the gates from (gi, gh, c); dh_out, dc_out f32[B,H] are dL/dh_out and dL/dc_out (dc_out may be NULL =
+ * zeros).  It writes dgates f32[B,4H], which is both dgi and dgh, and dc f32[B,H] = dL/dc through the cell state (the
+ * path through h is the caller's dgates . W_hh).  H % 4 == 0, 16-byte aligned pointers; -22 otherwise, before any HIP
+ * call. */
+int gymrl_lstm_cell_fwd(const float* gi, const float* gh, const float* c, int B, int H, float* h_out, float* c_out,
+                        void* stream);
+int gymrl_lstm_cell_bwd(const float* gi, const float* gh, const float* c, const float* dh_out, const float* dc_out, int B,
+                        int H, float* dgates, float* dc, void* stream);
+
+/* The LSTM recurrence in one launch per direction; the contract is gymrl_gru_seq_*'s.  B rows in one time-major batch:
+ * gi f32[T,B,4H] = x W_ih^T + b_ih (one library GEMM), W_hh f32[4H,H], b_hh f32[4H], h0, c0 f32[B,H] or NULL (zeros),
+ * len i32[B] a HOST array with 0 <= len[b] <= T.  Gate order and cell arithmetic are gymrl_lstm_cell_fwd's.  _fwd writes
+ * h_seq, c_seq f32[T,B,H] (zero for t >= len[b]) and h_last, c_last f32[B,H] = (h, c)_{len[b]-1} ((h0, c0) when
+ * len[b] == 0; either may be NULL).  _bwd runs the reverse recurrence from the stored h_seq, c_seq: d_hseq f32[T,B,H],
+ * d_hlast and d_clast f32[B,H] are the incoming gradients (each may be NULL = zeros); it writes dgates f32[T,B,4H] (both
+ * dgi and dgh; zero for t >= len[b]) and dh0, dc0 f32[B,H] (each may be NULL).  dW_hh = sum_t dgates_t^T h_{t-1}, db_hh,
+ * dW_ih and dx are the caller's GEMMs over the flattened rows.  One launch per 768 rows, all T steps inside;
+ * H in {16, 32, 48, 64}; W_hh, h0, h_seq 16-byte aligned.  -22 on anything else, before any HIP call. */
+int gymrl_lstm_seq_fwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const float* c0,
+                       const int32_t* len, int T, int B, int H, float* h_seq, float* c_seq, float* h_last, float* c_last,
+                       void* stream);
+int gymrl_lstm_seq_bwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const float* c0,
+                       const float* h_seq, const float* c_seq, const float* d_hseq, const float* d_hlast,
+                       const float* d_clast, const int32_t* len, int T, int B, int H, float* dgates, float* dh0, float* dc0,
+                       void* stream);
+
 /* EpisodeBuffer.compute_advantage — ppg_rnn_lunarlander.py:198-215 (== ppo_rnn_lunarlander.py), per episode, E
  * episodes stored back to back: episode e is rows [offsets[e], offsets[e+1]) of the flat f32 / u8 arrays; offsets
  * i64[E+1] a HOST array, offsets[0] == 0, no empty episode.  G2's arithmetic (gymrl_gae_dw): f32 td-error
