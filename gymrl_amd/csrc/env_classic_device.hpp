@@ -3,7 +3,7 @@
 // The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1" | "MountainCar-v0").step()/reset() (gymnasium classic_control, third-party:
 // SURVEY.md 8c.2) for one env = one lane.  Shared by the stand-alone steppers (env_classic.hip: gymrl_env_step) and the
 // fused acting kernels (offpolicy_step.hip, rainbow_step.hip, td3_step.hip: forward + draw + env step + ring append in one launch), so both produce the
-// same bits; MountainCar's core is shared with the one-launch episode kernel (mountaincar.hip) in the same way.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
+// same bits; each env's register-only core (*_advance) is shared with its one-launch episode kernel (mountaincar.hip, eval_classic.hip) in the same way.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
 #pragma once
 #include "env_common.hpp"
 
@@ -90,11 +90,9 @@ struct ClassicStep {
   int len;
 };
 
-// CartPole-v1: explicit Euler with the pre-step velocities, terminated beyond |x| > 2.4 or |theta| > 12 degrees, reward 1
-// on every step including the terminating one, TimeLimit 500; auto-reset into episode + 1's draw.
-__device__ __forceinline__ void cartpole_step_one(const CartPoleState& st, int i, uint64_t seed, int64_t env_id0, int action,
-                                                  ClassicStep<4>& r) {
-  double x = st.x[i], xd = st.xd[i], th = st.th[i], thd = st.thd[i];
+// CartPole-v1, registers only: explicit Euler with the pre-step velocities; -> terminated (beyond |x| > 2.4 or |theta| > 12 degrees).
+// The stepper below and the policy episode kernel (eval_classic.hip) both call it.
+__device__ __forceinline__ bool cartpole_advance(double& x, double& xd, double& th, double& thd, int action) {
   const double force = action == 1 ? 10.0 : -10.0;
   double s, c;
   det_sincos(th, &s, &c);                          // not ocml: reproducible on the host bit for bit
@@ -104,7 +102,14 @@ __device__ __forceinline__ void cartpole_step_one(const CartPoleState& st, int i
   x = x + 0.02 * xd; xd = xd + 0.02 * xacc;
   th = th + 0.02 * thd; thd = thd + 0.02 * thacc;
   const double th_lim = 12.0 * 2.0 * 3.14159265358979323846 / 360.0;
-  r.terminated = x < -2.4 || x > 2.4 || th < -th_lim || th > th_lim;
+  return x < -2.4 || x > 2.4 || th < -th_lim || th > th_lim;
+}
+
+// CartPole-v1: reward 1 on every step including the terminating one, TimeLimit 500; auto-reset into episode + 1's draw.
+__device__ __forceinline__ void cartpole_step_one(const CartPoleState& st, int i, uint64_t seed, int64_t env_id0, int action,
+                                                  ClassicStep<4>& r) {
+  double x = st.x[i], xd = st.xd[i], th = st.th[i], thd = st.thd[i];
+  r.terminated = cartpole_advance(x, xd, th, thd, action);
   r.len = st.ep.ep_len[i] + 1;
   r.truncated = r.len >= 500;
   r.done = r.terminated || r.truncated;
@@ -126,11 +131,10 @@ __device__ __forceinline__ void cartpole_step_one(const CartPoleState& st, int i
   }
 }
 
-// Pendulum-v1: torque clipped to +-2, cost from the PRE-step state, speed clipped to +-8, never terminates, TimeLimit 200.
-__device__ __forceinline__ void pendulum_step_one(const PendulumState& st, int i, uint64_t seed, int64_t env_id0, float action,
-                                                  ClassicStep<3>& r) {
+// Pendulum-v1, registers only: torque clipped to +-2, cost from the PRE-step state, speed clipped to +-8; -> cost (the reward is
+// its negative).  The stepper below and the policy episode kernel (eval_classic.hip) both call it.
+__device__ __forceinline__ double pendulum_advance(double& th, double& thd, float action) {
   const double pi = 3.14159265358979323846;
-  double th = st.th[i], thd = st.thd[i];
   double u = (double)action;
   u = u < -2.0 ? -2.0 : (u > 2.0 ? 2.0 : u);
   // angle_normalize(x) = ((x + pi) mod 2pi) - pi with python's floor-mod
@@ -142,7 +146,16 @@ __device__ __forceinline__ void pendulum_step_one(const PendulumState& st, int i
   det_sincos(th, &sin_th, &cos_th);
   double nthd = thd + (15.0 * sin_th + 3.0 * u) * 0.05;    // 3g/(2l) = 15, 3/(ml^2) = 3
   nthd = nthd < -8.0 ? -8.0 : (nthd > 8.0 ? 8.0 : nthd);
-  const double nth = th + nthd * 0.05;
+  th = th + nthd * 0.05;
+  thd = nthd;
+  return cost;
+}
+
+// Pendulum-v1: never terminates, TimeLimit 200; auto-reset into episode + 1's draw.
+__device__ __forceinline__ void pendulum_step_one(const PendulumState& st, int i, uint64_t seed, int64_t env_id0, float action,
+                                                  ClassicStep<3>& r) {
+  double nth = st.th[i], nthd = st.thd[i];
+  const double cost = pendulum_advance(nth, nthd, action);
   r.len = st.ep.ep_len[i] + 1;
   r.terminated = false;
   r.truncated = r.len >= 200;

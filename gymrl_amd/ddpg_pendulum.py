@@ -33,6 +33,7 @@ class Config:
         self.updates_per_step = 1
         self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/td3_step.hip): opt-in
         self.fused_images = True       # ... with weight images of the H x H layers (H % 16 == 0)
+        self.fused_eval = False        # eval() as ONE launch of whole episodes (csrc/eval_classic.hip): opt-in, the same list
 
 
 class Critic(nn.Module):

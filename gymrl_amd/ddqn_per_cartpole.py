@@ -50,6 +50,7 @@ class Config:
         self.use_graphs = True               # replay the update as one captured hipGraph (train(); update() stays eager)
         self.fused_step = False              # the vector step as gymrl_dqn_act_step + gymrl_ddqn_update (csrc/ddqn_step.hip): opt-in
         self.fused_images = True             # ... with weight images of the H x H layer (H % 16 == 0)
+        self.fused_eval = False              # eval() as ONE launch of whole episodes (csrc/eval_classic.hip): opt-in, the same list
 
 
 class QNetwork(nn.Module):

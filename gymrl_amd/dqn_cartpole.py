@@ -21,6 +21,7 @@ from . import ops
 from .envs import EpisodeTracker, VecEnv
 from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear
+from .policy_eval import PolicyEval
 from .utils import scalar
 
 
@@ -46,6 +47,7 @@ class Config:
         self.use_graphs = True               # replay the update as one captured hipGraph (train(); update() stays eager)
         self.fused_step = False              # the vector step as gymrl_dqn_act_step + gymrl_dqn_update (csrc/dqn_step.hip): opt-in
         self.fused_images = True             # ... with weight images of the H x H layer (H % 16 == 0)
+        self.fused_eval = False              # eval() as ONE launch of whole episodes (csrc/eval_classic.hip): opt-in, the same list
 
 
 def layer_init(layer, std=np.sqrt(2)):
@@ -137,7 +139,7 @@ class ReplayBuffer:
         self.cursor, self.size, self.draws = int(sd["cursor"]), int(sd["size"]), int(sd["draws"])
 
 
-class DQNTrainer(WeightImages):
+class DQNTrainer(WeightImages, PolicyEval):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -173,6 +175,16 @@ class DQNTrainer(WeightImages):
 
     def _make_memory(self, state_dim):
         return ReplayBuffer(self.cfg.memory_capacity, state_dim, self.device, seed=self.base_seed)
+
+    def _eval_policy(self):
+        """The three Linear layers eval() acts greedily on: QNetwork's net.0 / net.2 / net.4, or fc1 / fc2 / fc3 (DDQN + PER); a
+        network of another shape (the dueling one) has none."""
+        net = self.policy_net
+        layers = ((net.net[0], net.net[2], net.net[4]) if hasattr(net, "net") and len(net.net) == 5 else
+                  tuple(getattr(net, n, None) for n in ("fc1", "fc2", "fc3")))
+        if any(not isinstance(layer, SmallLinear) for layer in layers) or len(list(net.parameters())) != 6:
+            return None
+        return layers, self.flat_params, ops.CLASSIC_HEAD_ARGMAX, 0.0
 
     def get_epsilon(self):
         """:117-122 — advanced once per (vector) action selection."""
@@ -469,6 +481,9 @@ class DQNTrainer(WeightImages):
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
+        fused = self._eval_fused(num_episodes)
+        if fused is not None:
+            return fused
         env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 999, env_id0=1 << 40)
         obs = env.reset()
         nxt = torch.empty_like(obs)

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicEvalArgs, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    MlpDesc, MlprnnParams, MountainCarEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -657,6 +657,78 @@ def mountaincar_rule_eval(n_episodes, seed, stream_id0, cap, device, coefs=None,
     a.final_state = _ptr(final, torch.float64, True)
     check(lib().gymrl_mountaincar_rule_eval(C.byref(a), _stream()), "gymrl_mountaincar_rule_eval")
     return (returns, lengths, reached, final) if want_final_state else (returns, lengths, reached)
+
+
+# ----------------------- classic-control policies: whole episodes in one launch ---
+CLASSIC_HEAD_ARGMAX, CLASSIC_HEAD_TANH = 0, 1
+CLASSIC_EVAL_SHAPES = {0: (CLASSIC_HEAD_ARGMAX, 4, 2), 1: (CLASSIC_HEAD_TANH, 3, 1)}     # env kind -> (head, D, A)
+
+
+def classic_eval_shape_ok(kind, head, D, A, H):
+    """What gymrl_classic_policy_eval takes (include/gymrl.h): CartPole-v1 under an argmax head, Pendulum-v1 under a tanh head,
+    a hidden width the row-slab stages carry."""
+    return CLASSIC_EVAL_SHAPES.get(kind) == (head, D, A) and 4 <= H <= 256 and H % 4 == 0
+
+
+def lin_fwd_image(W):
+    """The forward image of a square layer's weight [H, H], H % 16 == 0 (csrc/lin_device.hpp img_fwd_index): a permutation of
+    its elements, as gymrl_*_pack_images lays it out."""
+    H = W.shape[0]
+    if W.dim() != 2 or W.shape[1] != H or H % 16:
+        raise ValueError(f"lin_fwd_image: a weight image is of a square layer with H % 16 == 0, got {tuple(W.shape)}")
+    n = torch.arange(H, device=W.device).view(H, 1)
+    k = torch.arange(H, device=W.device).view(1, H)
+    at = (((n >> 4) * (H >> 4) + (k >> 4)) * 64 + ((k & 15) >> 2) * 16 + (n & 15)) * 4 + (k & 3)
+    img = torch.empty(H * H, dtype=W.dtype, device=W.device)
+    img[at.reshape(-1)] = W.detach().reshape(-1)
+    return img
+
+
+def classic_policy_eval(kind, layers, n_episodes, seed, stream_id0, cap, head, bound=0.0, flat=None, params=None, images=None,
+                        start=None, want_final_obs=False):
+    """n_episodes whole episodes of CartPole-v1 / Pendulum-v1 per policy in ONE launch (include/gymrl.h
+    gymrl_classic_policy_eval) -> (returns f32, lengths i32, terminated u8), each [P, n_episodes], and final_obs
+    f32[P, n_episodes, D] when asked for.  layers = (fc1, fc2, fc3): Linear layers D -> H -> H -> A.  params = None: ONE policy,
+    the layers' own tensors.  params = f32[P, n]: P flat parameter buffers in the layout of `flat`, the buffer the layers'
+    tensors are views of (n >= flat.numel(); rows are padded here to a multiple of four floats).  Episode e of every policy starts
+    from the reset draw of (seed, stream_id0 + e), or from start f64[P, n_episodes, 4 | 2]."""
+    fc1, fc2, fc3 = layers
+    H, D, A = fc1.weight.shape[0], fc1.weight.shape[1], fc3.weight.shape[0]
+    if tuple(fc2.weight.shape) != (H, H) or fc3.weight.shape[1] != H:
+        raise ValueError("classic_policy_eval: the layers are not D -> H -> H -> A")
+    tensors = [fc1.weight, fc2.weight, fc3.weight, fc1.bias, fc2.bias, fc3.bias]
+    a = ClassicEvalArgs()
+    if params is None:
+        P, stride = 1, 0
+        addr = [_ptr(t.detach(), torch.float32).value for t in tensors]
+    else:
+        if flat is None or params.dim() != 2 or params.shape[1] < flat.numel():
+            raise ValueError("classic_policy_eval: params is a stack [P, n] of flat buffers in the layout of `flat`")
+        if params.shape[1] % 4:
+            params = torch.nn.functional.pad(params, (0, 4 - params.shape[1] % 4))
+        P, stride = params.shape[0], params.shape[1]
+        base = _ptr(params, torch.float32).value
+        offs = [(t.data_ptr() - flat.data_ptr()) // 4 for t in tensors]
+        if any(o < 0 or o + t.numel() > flat.numel() for o, t in zip(offs, tensors)):
+            raise ValueError("classic_policy_eval: the layers' tensors are not views of `flat`")
+        addr = [base + 4 * o for o in offs]
+    dev = tensors[0].device
+    nst = 4 if kind == CARTPOLE else 2
+    if start is not None and tuple(start.shape) != (P, n_episodes, nst):
+        raise ValueError(f"start is {tuple(start.shape)}, {P} policies x {n_episodes} episodes need [{P}, {n_episodes}, {nst}]")
+    returns = torch.empty(P, n_episodes, dtype=torch.float32, device=dev)
+    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
+    terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
+    final = torch.empty(P, n_episodes, D, dtype=torch.float32, device=dev) if want_final_obs else None
+    a.P, a.E, a.cap, a.env_kind, a.head, a.D, a.A, a.H, a.bound = P, n_episodes, cap, kind, head, D, A, H, float(bound)
+    for k in range(3):
+        a.w[k], a.b[k] = addr[k], addr[3 + k]
+    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
+    a.seed, a.stream_id0, a.start = seed, stream_id0, _ptr(start, torch.float64, True)
+    a.returns, a.lengths, a.terminated = _ptr(returns), _ptr(lengths), _ptr(terminated)
+    a.final_obs = _ptr(final, torch.float32, True)
+    check(lib().gymrl_classic_policy_eval(C.byref(a), _stream()), "gymrl_classic_policy_eval")
+    return (returns, lengths, terminated, final) if want_final_obs else (returns, lengths, terminated)
 
 
 # ============================================================== off-policy ===

@@ -23,6 +23,7 @@ from .dqn_cartpole import ReplayBuffer
 from .envs import EpisodeTracker, VecEnv
 from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear
+from .policy_eval import PolicyEval
 from .utils import scalar
 
 
@@ -48,6 +49,7 @@ class Config:
         self.use_graphs = True             # replay the update as one captured hipGraph (train(); update() stays eager)
         self.fused_step = False            # the vector step as gymrl_dsac_act_step + gymrl_dsac_update (csrc/dsac_step.hip): opt-in
         self.fused_images = True           # ... with weight images of the H x H layers (H % 16 == 0)
+        self.fused_eval = False            # eval() as ONE launch of whole episodes (csrc/eval_classic.hip): opt-in, the same list
         self.kernel_softmax = False        # Actor.forward through ops.softmax_rows (csrc/softmax_device.hpp) instead of F.softmax;
                                            # fused_step implies it (read when the trainer is built), so that the layer path and
                                            # the fused path of one run produce the same bits and the run can change paths
@@ -80,7 +82,7 @@ class Critic(nn.Module):
         return self.fc3(self.fc2(self.fc1(x)))
 
 
-class SACTrainer(WeightImages):
+class SACTrainer(WeightImages, PolicyEval):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -132,6 +134,10 @@ class SACTrainer(WeightImages):
         act, _, _, _ = ops.categorical_sample(logits, noise_exp=noise_exp, seed=self.base_seed, counter=self._act_counter,
                                               env_id0=self.env.env_id0, deterministic=deterministic)
         return scalar.discrete_out(act, kind)
+
+    def _eval_policy(self):
+        """eval() takes the argmax of the actor's logits (the softmax does not move it)."""
+        return (self.actor.fc1, self.actor.fc2, self.actor.fc3), self.actor_flat, ops.CLASSIC_HEAD_ARGMAX, 0.0
 
     def soft_update(self, target_flat, source_flat):
         """:140-145 on the flat parameter buffers."""
@@ -424,6 +430,9 @@ class SACTrainer(WeightImages):
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
+        fused = self._eval_fused(num_episodes)
+        if fused is not None:
+            return fused
         env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 999, env_id0=1 << 40)
         obs = env.reset()
         nxt = torch.empty_like(obs)

@@ -21,6 +21,7 @@ from . import ops
 from .envs import EpisodeTracker, VecEnv
 from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear, frozen_parameters, fused_linears
+from .policy_eval import PolicyEval
 from .sac_pendulum import ReplayBuffer
 from .utils import scalar
 
@@ -48,6 +49,7 @@ class Config:
         self.updates_per_step = 1
         self.fused_step = False        # the vector step as gymrl_td3_act_step + gymrl_td3_update (csrc/td3_step.hip): opt-in
         self.fused_images = True       # ... with weight images of the H x H layers (H % 16 == 0)
+        self.fused_eval = False        # eval() as ONE launch of whole episodes (csrc/eval_classic.hip): opt-in, the same list
 
 
 class Actor(nn.Module):
@@ -83,7 +85,7 @@ class Critic(nn.Module):
         return self.fc3(self.fc2(self.fc1(state, action)))
 
 
-class _ActorCriticBase(WeightImages):
+class _ActorCriticBase(WeightImages, PolicyEval):
     """What TD3 and DDPG share: env, replay ring, exploration, vectorised train / eval loops."""
 
     def _setup(self, config, critic_cls):
@@ -120,6 +122,10 @@ class _ActorCriticBase(WeightImages):
         self._parity_eps = None        # tests: iterator of f64[N, A] N(0,1) draws for select_action
         self._parity_updates = None    # tests: iterator of per-update tuples (see update())
         self._graph = None             # hipGraph of the update (trainers that define update_async)
+
+    def _eval_policy(self):
+        """eval() acts with the actor's own output: tanh(fc3) times the action bound."""
+        return (self.actor.fc1, self.actor.fc2, self.actor.fc3), self.actor_flat, ops.CLASSIC_HEAD_TANH, self.action_bound
 
     def soft_update(self, target_flat, source_flat):
         """:149-154 on the flat parameter buffers."""
@@ -342,6 +348,9 @@ class _ActorCriticBase(WeightImages):
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
+        fused = self._eval_fused(num_episodes)
+        if fused is not None:
+            return fused
         env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 999, env_id0=1 << 40)
         obs = env.reset()
         nxt = torch.empty_like(obs)

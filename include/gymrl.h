@@ -43,7 +43,7 @@ enum {
   GYMRL_ENV_PENDULUM    = 1, /* Pendulum-v1   obs 3, 1 continuous in [-2,2] */
   GYMRL_ENV_LUNARLANDER = 2, /* LunarLander-v3 obs 8, 4 discrete actions  */
   GYMRL_ENV_MOUNTAINCAR = 3  /* MountainCar-v0 obs 2, 3 discrete actions (the steppers and gymrl_mountaincar_rule_eval only:
-                              * the fused acting, ring and rollout kernels refuse it with -EINVAL) */
+                              * the fused acting, ring, rollout and policy-episode kernels refuse it with -EINVAL) */
 };
 
 /*
@@ -1700,6 +1700,51 @@ int gymrl_ndqn_combine(const gymrl_ndqn_combine_args* args, void* stream);
 int gymrl_ndqn_act_step(const gymrl_ndqn_act_args* args, void* stream);
 size_t gymrl_ndqn_update_workspace_bytes(int B, int D, int A, int H);
 int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
+
+/* ----------------------------- classic-control policies: whole episodes in one launch ---- */
+/*
+ * Replaces the eval() loops of dqn_cartpole.py:214-233, ddqn_per_cartpole.py, sac_cartpole.py, td3_pendulum.py and
+ * ddpg_pendulum.py (select_action without exploration -> env.step, up to the TimeLimit) for P policies x E episodes at a time
+ * (csrc/eval_classic.hip).  ONE workgroup of 1024 threads carries 16 episodes of one policy from reset to their end; the grid is
+ * P * ceil(E / 16) workgroups.  Per step: lanes 0..15 of the first wave put the float32 observation of their float64 register
+ * state into LDS, all sixteen waves run the D -> H -> H -> A forward (fc1, fc2 ReLU, fc3: the row-slab stages of the fused acting
+ * kernels, so the bits are gymrl_lin_fwd's), the lanes take the action and advance their env in registers (csrc/
+ * env_classic_device.hpp: the stepper's own cartpole_advance / pendulum_advance).  A finished lane idles with its state, return and
+ * length frozen; the workgroup leaves when all 16 are finished (at `cap` at the latest) on one LDS word behind a barrier every
+ * thread reaches.  No atomics, nothing waits for another workgroup, and inside the loop global memory is only read (the weights).
+ *
+ *   head 0  argmax: the FIRST maximum of fc3's row — gymrl_epsilon_greedy's greedy branch, gymrl_categorical_sample's
+ *           deterministic one.  CartPole-v1 only, (D, A) = (4, 2).
+ *   head 1  tanh: action = tanh(fc3) * bound, gymrl_td3_act_step's expression in front of its noise.  Pendulum-v1 only, (3, 1).
+ *
+ * Policy p reads w[k] + p * policy_stride and b[k] + p * policy_stride (floats; 0: P == 1).  Episode i = p * E + e starts from the
+ * reset draw of (seed, stream_id0 + e, episode 0) — the SAME starts for every policy, the first episode of env e of a
+ * gymrl_env_reset with env_id0 = stream_id0 — or from start[i] = the float64 state (x, x_dot, theta, theta_dot | theta, theta_dot).
+ *
+ * Outputs, each [P * E]: returns (the float32 cast of the float64 return: gymrl_env_step's ep_ret_out), lengths, terminated (1:
+ * the env terminated on the last step; 0: the episode was cut at `cap` steps, the TimeLimit included), final_obs [P * E][D]
+ * (optional) the observation after the last step (gymrl_env_step's term_obs_out).
+ * -EINVAL before any launch: NULL args, a NULL w[k] / b[k] / returns / lengths / terminated, P < 1, E < 1, cap outside 1..TimeLimit
+ * (500 / 200), an env kind other than CartPole-v1 / Pendulum-v1, a (head, D, A) that is not the kind's, H % 4 != 0 or H outside
+ * 4..256, a negative policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, P * E
+ * above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (w[k], images: 16 bytes; start: 8; the others: 4).
+ * Out of scope: dueling, NoisyNet, Rainbow and SAC-Pendulum heads, MountainCar-v0, LunarLander-v3.
+ */
+typedef struct {
+  int P, E, cap;
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE | GYMRL_ENV_PENDULUM */
+  int head, D, A, H;
+  float bound;                             /* head 1: the action bound */
+  const float* w[3]; const float* b[3];    /* fc1 [H][D], fc2 [H][H], fc3 [A][H] and their biases, of policy 0 */
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  const float* images;                     /* the forward image of fc2 (H % 16 == 0; P == 1), or NULL: fc2 is read in place */
+  uint64_t seed; int64_t stream_id0;
+  const double* start;                     /* f64[P * E][4 | 2], or NULL: the reset draw */
+  float* returns; int32_t* lengths; uint8_t* terminated;
+  float* final_obs;                        /* f32[P * E][D] or NULL */
+} gymrl_classic_eval_args;
+size_t gymrl_classic_eval_args_bytes(void);  /* sizeof(gymrl_classic_eval_args) */
+int gymrl_classic_policy_eval(const gymrl_classic_eval_args* args, void* stream);
 
 /* ------------------------------------------- MountainCar-v0 rule baseline ---- */
 /*
