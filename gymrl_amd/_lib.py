@@ -338,6 +338,15 @@ class ClassicEvalArgs(C.Structure):
                 ("final_obs", C.c_void_p)]
 
 
+class ClassicDuelEvalArgs(C.Structure):
+    _c_name_ = "gymrl_classic_duel_eval_args"
+    _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("env_kind", C.c_int), ("n_hidden", C.c_int), ("D", C.c_int),
+                ("A", C.c_int), ("H", C.c_int), ("w", C.c_void_p * 2), ("b", C.c_void_p * 2), ("value_w", C.c_void_p),
+                ("value_b", C.c_void_p), ("adv_w", C.c_void_p), ("adv_b", C.c_void_p), ("policy_stride", C.c_int64),
+                ("images", C.c_void_p), ("seed", C.c_uint64), ("stream_id0", C.c_int64), ("start", C.c_void_p),
+                ("returns", C.c_void_p), ("lengths", C.c_void_p), ("terminated", C.c_void_p), ("final_obs", C.c_void_p)]
+
+
 class MountainCarEvalArgs(C.Structure):
     _c_name_ = "gymrl_mountaincar_eval_args"
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("stream_id0", C.c_int64),
@@ -549,6 +558,8 @@ SIGNATURES = {
     "gymrl_ndqn_update": (_i, [_P(NdqnUpdateArgs), _vp]),
     "gymrl_classic_eval_args_bytes": (_sz, []),
     "gymrl_classic_policy_eval": (_i, [_P(ClassicEvalArgs), _vp]),
+    "gymrl_classic_duel_eval_args_bytes": (_sz, []),
+    "gymrl_classic_duel_eval": (_i, [_P(ClassicDuelEvalArgs), _vp]),
     "gymrl_mountaincar_rule_eval": (_i, [_P(MountainCarEvalArgs), _vp]),
 }
 SYMBOLS = list(SIGNATURES)

@@ -17,8 +17,7 @@
 // iteration.  No __syncthreads() sits behind a per-lane or per-wave condition, nothing waits for another workgroup, there are no
 // atomics, and inside the loop global memory is only READ (the weights, from L2 after the first step).  The loop runs at most
 // `cap` <= TimeLimit times.
-#include "policy_device.hpp"
-#include "slab_step_device.hpp"
+#include "eval_episode_device.hpp"
 
 namespace {
 
@@ -28,96 +27,44 @@ using namespace gymrl::slab;
 constexpr int kHeadArgmax = 0, kHeadTanh = 1;
 
 // KIND: GYMRL_ENV_CARTPOLE (head 0, D = 4, A = 2) or GYMRL_ENV_PENDULUM (head 1, D = 3, A = 1); HC: the hidden width the instance is built for (0: a.H)
+// The episode loop itself is eval_episode_device.hpp's run_episodes; what is stated here is one step's policy forward and its action.
 template <int HC, int KIND>
 __global__ __launch_bounds__(kThreads) void classic_eval_kernel(const gymrl_classic_eval_args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int running;                 // the loop's exit word: written by wave 0, read by everybody behind the barrier
   const Lds L;
   constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE;
-  constexpr int D = cart ? 4 : 3, A = cart ? 2 : 1, NS = cart ? 4 : 2;
+  constexpr int D = cart ? 4 : 3, A = cart ? 2 : 1;
   const int H = HC ? HC : a.H, ld = lin::slab_ld(H);
   const int X0 = L.big, X1 = X0 + 16 * ld;
   const int groups = (a.E + 15) / 16;
   const int p = (int)blockIdx.x / groups, e0 = ((int)blockIdx.x - p * groups) * 16, nrows = min(16, a.E - e0);
-  const int t = threadIdx.x;
   const size_t shift = (size_t)p * (size_t)a.policy_stride;
   const float *w0 = a.w[0] + shift, *w1 = a.w[1] + shift, *w2 = a.w[2] + shift;
   const float *b0 = a.b[0] + shift, *b1 = a.b[1] + shift, *b2 = a.b[2] + shift;
   const float* img = (a.images && (H & 15) == 0) ? a.images : nullptr;
-  const int64_t i = (int64_t)p * a.E + e0 + t;       // this lane's episode (t < nrows)
-  // ---- one lane per episode: the env state, the return and the length live in registers ----
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  double ret = 0.0;
-  int len = 0;
-  bool terminated = false, active = t < nrows;
-  if (t < 16)
-    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = 0.0f;     // rows beyond the episodes and columns beyond D stay zero
-  if (active) {
-    if (a.start) {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) s[k] = a.start[i * NS + k];
-    } else if constexpr (cart) {
-      cartpole_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
-    } else {
-      pendulum_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
-    }
-  }
   const int R = GYMRL_ACT_RELU, kD = kMaxD, kA = kMaxA;
-  for (int it = 0; it < a.cap; ++it) {
-    if (t < 64) {
-      if (active) {
-        float* o = lds + L.S + t * kMaxD;
+  run_episodes<KIND>(
+      a, lds, running, L, p, e0, nrows,
+      [=]() {
+        const float *v0 = w0, *v1 = w1, *v2 = w2, *c0 = b0, *c1 = b1, *c2 = b2, *im = img;
+        // (the pointers pass through an empty asm: the stages' per-lane operand addresses are formed again in every iteration — hoisted
+        // out of the loop they were 47 spilled registers, reloaded from scratch memory step by step)
+        asm volatile("" : "+s"(v0), "+s"(v1), "+s"(v2), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(im));
+        fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, v0, c0, X0, ld, nullptr, 0, R)}, 0, nrows);
+        fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, v1, c1, X1, ld, nullptr, 0, R, 0.0f, 0.0f, im)}, 0, nrows);
+        fwd_one(lds, {fwd_item(X1, ld, -1, 0, H, H, A, v2, c2, L.Mean, kA, nullptr, 0, cart ? GYMRL_ACT_NONE : GYMRL_ACT_TANH)}, 0, nrows);
+      },
+      [=](int t) {
         if constexpr (cart) {
-          o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
+          // the greedy branch of epsilon_greedy_pick (u0 = 1 is never below epsilon = 0): the first maximum, no draw
+          const float never[2] = {1.0f, 0.0f};
+          return epsilon_greedy_pick(lds + L.Mean + t * kMaxA, A, never, 0ull, 0ull, 0ull, 0.0f);
         } else {
-          float ob[3];
-          pendulum_obs(s[0], s[1], ob);
-          o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
+          return lds[L.Mean + t * kMaxA] * a.bound;
         }
-      }
-      const bool any = __ballot(active) != 0ull;
-      if (t == 0) running = any ? 1 : 0;
-    }
-    __syncthreads();
-    if (!running) break;                  // one word, the same for every thread of the workgroup
-    // (the pointers pass through an empty asm: the stages' per-lane operand addresses are formed again in every iteration — hoisted
-    // out of the loop they were 47 spilled registers, reloaded from scratch memory step by step)
-    asm volatile("" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(b0), "+s"(b1), "+s"(b2), "+s"(img));
-    fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, w0, b0, X0, ld, nullptr, 0, R)}, 0, nrows);
-    fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, w1, b1, X1, ld, nullptr, 0, R, 0.0f, 0.0f, img)}, 0, nrows);
-    fwd_one(lds, {fwd_item(X1, ld, -1, 0, H, H, A, w2, b2, L.Mean, kA, nullptr, 0, cart ? GYMRL_ACT_NONE : GYMRL_ACT_TANH)}, 0, nrows);
-    if (active) {
-      if constexpr (cart) {
-        // the greedy branch of epsilon_greedy_pick (u0 = 1 is never below epsilon = 0): the first maximum, no draw
-        const float never[2] = {1.0f, 0.0f};
-        const int act = epsilon_greedy_pick(lds + L.Mean + t * kMaxA, A, never, 0ull, 0ull, 0ull, 0.0f);
-        terminated = cartpole_advance(s[0], s[1], s[2], s[3], act);
-        ret = ret + 1.0;
-      } else {
-        const float mu = lds[L.Mean + t * kMaxA] * a.bound;
-        ret = ret + (-pendulum_advance(s[0], s[1], mu));
-      }
-      len += 1;
-      active = !terminated && len < a.cap;
-    }
-    // (the next iteration's stores to L.S and `running` follow fwd_one's closing barrier; their last readers sit in front of it)
-  }
-  if (t < nrows) {
-    a.returns[i] = (float)ret; a.lengths[i] = len; a.terminated[i] = terminated;
-    if (a.final_obs) {
-      float* o = a.final_obs + i * D;
-      if constexpr (cart) {
-        o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
-      } else {
-        float ob[3];
-        pendulum_obs(s[0], s[1], ob);
-        o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
-      }
-    }
-  }
+      });
 }
-
-inline bool aligned(const void* p, size_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) == 0; }
 
 }  // namespace
 
@@ -130,16 +77,12 @@ int gymrl_classic_policy_eval(const gymrl_classic_eval_args* args, void* stream)
   const gymrl_classic_eval_args& a = *args;
   const bool cart = a.env_kind == GYMRL_ENV_CARTPOLE;
   if (!cart && a.env_kind != GYMRL_ENV_PENDULUM) return -22;
-  if (a.P < 1 || a.E < 1 || a.cap < 1 || a.cap > (cart ? 500 : 200) || a.stream_id0 < 0) return -22;
+  if (!episode_args_ok(a, cart ? 500 : 200)) return -22;
   if (cart ? (a.head != kHeadArgmax || a.D != 4 || a.A != 2) : (a.head != kHeadTanh || a.D != 3 || a.A != 1)) return -22;
   if (!slab_shape_ok(1, 1, a.D, a.A, a.H)) return -22;
-  if ((int64_t)a.P * a.E > 0x7fffffffLL) return -22;
-  if (a.policy_stride < 0 || (a.policy_stride & 3) != 0 || (a.policy_stride == 0 && a.P != 1)) return -22;
-  if (a.images && a.P != 1) return -22;
-  if (!all_set({a.w[0], a.w[1], a.w[2], a.b[0], a.b[1], a.b[2], a.returns, a.lengths, a.terminated})) return -22;
+  if (!all_set({a.w[0], a.w[1], a.w[2], a.b[0], a.b[1], a.b[2]})) return -22;
   for (int k = 0; k < 3; ++k)
     if (!aligned(a.w[k], 16) || !aligned(a.b[k], 4)) return -22;
-  if (!aligned(a.images, 16) || !aligned(a.start, 8) || !aligned(a.returns, 4) || !aligned(a.lengths, 4) || !aligned(a.final_obs, 4)) return -22;
   static bool lds_set = false;
   if (const int rc = set_max_lds_once(lds_set, {(const void*)classic_eval_kernel<0, GYMRL_ENV_CARTPOLE>, (const void*)classic_eval_kernel<256, GYMRL_ENV_CARTPOLE>,
                                                 (const void*)classic_eval_kernel<0, GYMRL_ENV_PENDULUM>, (const void*)classic_eval_kernel<256, GYMRL_ENV_PENDULUM>},

@@ -63,6 +63,7 @@ class Config:
         self.use_graphs = True               # replay the update as one captured hipGraph (train(); update() stays eager)
         self.fused_step = False              # the vector step as csrc/noisy_dqn_step.hip's launches: opt-in
         self.chunk_steps = 16                # vector steps per captured hipGraph on the fused path
+        self.fused_eval = False              # eval() as ONE launch of whole episodes (csrc/eval_duel.hip): opt-in, the same list
 
 
 def _linear(x, weight, bias, act=None):
@@ -172,6 +173,13 @@ class NoisyDQNTrainer(DQNTrainer):
     def _next_draw(self):
         self.noise_draws += 1
         return self.noise_draws
+
+    def _eval_duel_policy(self):
+        """eval() acts on mu only (select_action(deterministic=True)): every layer's weight_mu / bias_mu, no draw, and neither
+        `noise_draws` nor policy_net.training moves (csrc/eval_duel.hip)."""
+        net = self.policy_net
+        pair = lambda m: (m.weight_mu, m.bias_mu)     # noqa: E731
+        return [pair(net.fc1), pair(net.fc2)], pair(net.value_stream), pair(net.advantage_stream), self.flat_params
 
     # ------------------------------------------------------------ acting (:198-212) ---------------------------
     @torch.no_grad()

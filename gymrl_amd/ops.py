@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicEvalArgs, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    MlpDesc, MlprnnParams, MountainCarEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -684,6 +684,37 @@ def lin_fwd_image(W):
     return img
 
 
+def _policy_addresses(who, tensors, flat, params):
+    """-> (P, policy_stride, params as passed on, the tensors' device addresses in policy 0).  params = None: ONE policy, the tensors
+    themselves.  params = f32[P, n]: the tensors' places in `flat`, the buffer they are views of, carried over to row 0 of the
+    stack (n >= flat.numel(); rows are padded here to a multiple of four floats, the entry points' stride rule)."""
+    if params is None:
+        return 1, 0, None, [_ptr(t.detach(), torch.float32).value for t in tensors]
+    if flat is None or params.dim() != 2 or params.shape[1] < flat.numel():
+        raise ValueError(f"{who}: params is a stack [P, n] of flat buffers in the layout of `flat`")
+    if params.shape[1] % 4:
+        params = torch.nn.functional.pad(params, (0, 4 - params.shape[1] % 4))
+    offs = [(t.data_ptr() - flat.data_ptr()) // 4 for t in tensors]
+    if any(o < 0 or o + t.numel() > flat.numel() for o, t in zip(offs, tensors)):
+        raise ValueError(f"{who}: the layers' tensors are not views of `flat`")
+    base = _ptr(params, torch.float32).value
+    return params.shape[0], params.shape[1], params, [base + 4 * o for o in offs]
+
+
+def _episode_io(a, P, n_episodes, nst, D, seed, stream_id0, start, want_final_obs, dev):
+    """The starts and the outputs of an episode launch's argument block -> (returns, lengths, terminated, final_obs | None)."""
+    if start is not None and tuple(start.shape) != (P, n_episodes, nst):
+        raise ValueError(f"start is {tuple(start.shape)}, {P} policies x {n_episodes} episodes need [{P}, {n_episodes}, {nst}]")
+    returns = torch.empty(P, n_episodes, dtype=torch.float32, device=dev)
+    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
+    terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
+    final = torch.empty(P, n_episodes, D, dtype=torch.float32, device=dev) if want_final_obs else None
+    a.seed, a.stream_id0, a.start = seed, stream_id0, _ptr(start, torch.float64, True)
+    a.returns, a.lengths, a.terminated = _ptr(returns), _ptr(lengths), _ptr(terminated)
+    a.final_obs = _ptr(final, torch.float32, True)
+    return returns, lengths, terminated, final
+
+
 def classic_policy_eval(kind, layers, n_episodes, seed, stream_id0, cap, head, bound=0.0, flat=None, params=None, images=None,
                         start=None, want_final_obs=False):
     """n_episodes whole episodes of CartPole-v1 / Pendulum-v1 per policy in ONE launch (include/gymrl.h
@@ -698,37 +729,51 @@ def classic_policy_eval(kind, layers, n_episodes, seed, stream_id0, cap, head, b
         raise ValueError("classic_policy_eval: the layers are not D -> H -> H -> A")
     tensors = [fc1.weight, fc2.weight, fc3.weight, fc1.bias, fc2.bias, fc3.bias]
     a = ClassicEvalArgs()
-    if params is None:
-        P, stride = 1, 0
-        addr = [_ptr(t.detach(), torch.float32).value for t in tensors]
-    else:
-        if flat is None or params.dim() != 2 or params.shape[1] < flat.numel():
-            raise ValueError("classic_policy_eval: params is a stack [P, n] of flat buffers in the layout of `flat`")
-        if params.shape[1] % 4:
-            params = torch.nn.functional.pad(params, (0, 4 - params.shape[1] % 4))
-        P, stride = params.shape[0], params.shape[1]
-        base = _ptr(params, torch.float32).value
-        offs = [(t.data_ptr() - flat.data_ptr()) // 4 for t in tensors]
-        if any(o < 0 or o + t.numel() > flat.numel() for o, t in zip(offs, tensors)):
-            raise ValueError("classic_policy_eval: the layers' tensors are not views of `flat`")
-        addr = [base + 4 * o for o in offs]
-    dev = tensors[0].device
-    nst = 4 if kind == CARTPOLE else 2
-    if start is not None and tuple(start.shape) != (P, n_episodes, nst):
-        raise ValueError(f"start is {tuple(start.shape)}, {P} policies x {n_episodes} episodes need [{P}, {n_episodes}, {nst}]")
-    returns = torch.empty(P, n_episodes, dtype=torch.float32, device=dev)
-    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
-    terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
-    final = torch.empty(P, n_episodes, D, dtype=torch.float32, device=dev) if want_final_obs else None
+    P, stride, params, addr = _policy_addresses("classic_policy_eval", tensors, flat, params)
+    out = _episode_io(a, P, n_episodes, 4 if kind == CARTPOLE else 2, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
     a.P, a.E, a.cap, a.env_kind, a.head, a.D, a.A, a.H, a.bound = P, n_episodes, cap, kind, head, D, A, H, float(bound)
     for k in range(3):
         a.w[k], a.b[k] = addr[k], addr[3 + k]
     a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
-    a.seed, a.stream_id0, a.start = seed, stream_id0, _ptr(start, torch.float64, True)
-    a.returns, a.lengths, a.terminated = _ptr(returns), _ptr(lengths), _ptr(terminated)
-    a.final_obs = _ptr(final, torch.float32, True)
     check(lib().gymrl_classic_policy_eval(C.byref(a), _stream()), "gymrl_classic_policy_eval")
-    return (returns, lengths, terminated, final) if want_final_obs else (returns, lengths, terminated)
+    return out if want_final_obs else out[:3]
+
+
+def classic_duel_eval_shape_ok(kind, n_hidden, D, A, H):
+    """What gymrl_classic_duel_eval takes (include/gymrl.h): CartPole-v1, a trunk of one or two hidden layers, two actions, a hidden
+    width the row-slab stages carry."""
+    return kind == CARTPOLE and n_hidden in (1, 2) and (D, A) == (4, 2) and 4 <= H <= 256 and H % 4 == 0
+
+
+def classic_duel_eval(kind, trunk, value, advantage, n_episodes, seed, stream_id0, cap, flat=None, params=None, images=None,
+                      start=None, want_final_obs=False):
+    """classic_policy_eval for a dueling network (include/gymrl.h gymrl_classic_duel_eval): the same episodes, the same outputs.
+    Every layer is a (weight, bias) tensor pair — a NoisyLinear passes its weight_mu / bias_mu as they are: trunk = one or two pairs
+    (D -> H, H -> H), value = the H -> 1 head, advantage = the H -> A head.  params / flat: classic_policy_eval's offset scheme; the
+    stride shifts every pointer, so whatever else lies in a row (a noisy layer's sigmas) travels unused."""
+    trunk = [tuple(pair) for pair in trunk]
+    if len(trunk) not in (1, 2):
+        raise ValueError("classic_duel_eval: the trunk is one or two (weight, bias) pairs")
+    pairs = trunk + [tuple(value), tuple(advantage)]
+    if any(len(pair) != 2 or pair[0].dim() != 2 or pair[1].dim() != 1 or pair[1].shape[0] != pair[0].shape[0] for pair in pairs):
+        raise ValueError("classic_duel_eval: a layer is a (weight [N, K], bias [N]) pair")
+    H, D, A = trunk[0][0].shape[0], trunk[0][0].shape[1], advantage[0].shape[0]
+    if len(trunk) == 2 and tuple(trunk[1][0].shape) != (H, H):
+        raise ValueError("classic_duel_eval: the trunk is not D -> H (-> H)")
+    if tuple(value[0].shape) != (1, H) or advantage[0].shape[1] != H:
+        raise ValueError("classic_duel_eval: the heads are not H -> 1 and H -> A")
+    tensors = [w for w, _ in pairs] + [b for _, b in pairs]
+    n = len(pairs)
+    a = ClassicDuelEvalArgs()
+    P, stride, params, addr = _policy_addresses("classic_duel_eval", tensors, flat, params)
+    out = _episode_io(a, P, n_episodes, 4, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
+    a.P, a.E, a.cap, a.env_kind, a.n_hidden, a.D, a.A, a.H = P, n_episodes, cap, kind, len(trunk), D, A, H
+    for k in range(len(trunk)):
+        a.w[k], a.b[k] = addr[k], addr[n + k]
+    a.value_w, a.value_b, a.adv_w, a.adv_b = addr[n - 2], addr[2 * n - 2], addr[n - 1], addr[2 * n - 1]
+    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
+    check(lib().gymrl_classic_duel_eval(C.byref(a), _stream()), "gymrl_classic_duel_eval")
+    return out if want_final_obs else out[:3]
 
 
 # ============================================================== off-policy ===

@@ -23,6 +23,7 @@ from . import ops
 from .envs import EpisodeTracker, VecEnv
 from .flat import FusedAdam, GradSink, flatten_module
 from .nn import SmallLinear, small_linear
+from .policy_eval import PolicyEval
 from .utils import scalar
 
 
@@ -56,6 +57,7 @@ class Config:
         self.chunk_steps = 16              # whole vector steps (acting, env, n-step store, sum tree, draw, update) as one
         #                                    hipGraph per 16 (graphs.StepChunk); 0: eager acting + a graph per update.  The
         #                                    eager launches of a step cost the host 0.46 ms at N = 8192 — more than the GPU needs
+        self.fused_eval = False            # eval() as ONE launch of whole episodes (csrc/eval_duel.hip): opt-in, the same list
 
 
 class NoisyLinear(nn.Module):
@@ -413,7 +415,7 @@ class PrioritizedNStepBuffer:
         self.draws, self.beta = int(sd["draws"]), float(sd["beta"])
 
 
-class RainbowDQNTrainer:
+class RainbowDQNTrainer(PolicyEval):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -478,6 +480,14 @@ class RainbowDQNTrainer:
         if not update:
             return [(self.policy_net.fc2.weight, img[0], None)]
         return [(self.policy_net.fc2.weight, img[0], img[1]), (self.target_net.fc2.weight, img[2], None)]
+
+    def _eval_duel_policy(self):
+        """eval() acts on fc1, fc2 and the heads' weight_mu / bias_mu (policy_net.eval(): no draw; `total_steps` and
+        NoisyLinear._counter do not move).  The layer path stacks the two heads [A + 1, H]; a column of a tile does not depend on
+        its neighbours, so they pass as separate heads (csrc/eval_duel.hip)."""
+        net = self.policy_net
+        return ([(net.fc1.weight, net.fc1.bias), (net.fc2.weight, net.fc2.bias)], (net.value.weight_mu, net.value.bias_mu),
+                (net.advantage.weight_mu, net.advantage.bias_mu), self.flat_params)
 
     @staticmethod
     def _noisy_fields(m, **kw):
@@ -913,6 +923,9 @@ class RainbowDQNTrainer:
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
+        fused = self._eval_fused(num_episodes)
+        if fused is not None:
+            return fused
         env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 999, env_id0=1 << 40)
         obs = env.reset()
         nxt = torch.empty_like(obs)

@@ -20,6 +20,7 @@ from .dqn_cartpole import ReplayBuffer as _Ring
 from .envs import EpisodeTracker, VecEnv
 from .flat import FusedAdam, GradSink, WeightImages, flatten_module
 from .nn import SmallLinear, frozen_parameters, fused_linears
+from .policy_eval import PolicyEval
 from .utils import scalar
 
 
@@ -49,6 +50,8 @@ class Config:
         self.fused_step = True             # a vector step = 5 launches (csrc/offpolicy_step.hip: acting + env + append in one, the
         #                                    update in four) instead of ~60; bit-identical to the layer-by-layer path, which remains
         #                                    for shapes beyond the kernels' limits (hidden_dim > 256, batch > 256) and custom envs
+        self.fused_eval = False            # accepted for the trainers' common surface; eval() keeps the step loop here (its tanh is
+        #                                    torch's, not the launch's: DESIGN §4q) — evaluate() is the one-launch form
         self.chunk_steps = 0               # 16: whole vector steps as one hipGraph per 16 (graphs.StepChunk).  Measured slower
         #                                    here (0.37 vs 0.29 ms per step at N = 4096, B = 128): SAC's step is GPU-bound, and
         #                                    the executor's cost per graph node grows with the graph (944 nodes per chunk)
@@ -135,7 +138,7 @@ class ReplayBuffer(_Ring):
         super().push(state, action, reward, next_state, done, cursor_dev=cursor_dev)     # the ring stores the f32 bits as words
 
 
-class SACTrainer(WeightImages):
+class SACTrainer(WeightImages, PolicyEval):
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():
@@ -171,6 +174,18 @@ class SACTrainer(WeightImages):
         self._graph = None             # hipGraph of the update, captured on first use (update_async)
         self._parity_updates = None    # tests: iterator of (indices i32[B], eps_next [B, A], eps_cur [B, A]) for update()
         self._act_noise = self._upd_noise = 0      # Philox counters of the fused step's own N(0,1) draws
+
+    def _eval_policy(self):
+        """evaluate() acts with tanh(mean(fc2(fc1 s))) times the action bound, the tanh being the layer kernels' epilogue
+        (GYMRL_ACT_TANH: 1 - 2 / (exp2(2 log2(e) z) + 1) on the hardware's exp2 and reciprocal); the log_std head is not read."""
+        return (self.actor.fc1, self.actor.fc2, self.actor.mean), self.actor_flat, ops.CLASSIC_HEAD_TANH, self.action_bound
+
+    def _eval_fused(self, num_episodes):
+        """None whatever Config.fused_eval says: eval() keeps the step loop.  Actor.get_action(deterministic=True) applies
+        torch.tanh — the device library's routine — to the mean, the launch the epilogue above; the means agree bit for bit, the
+        two tanh differ in the last place on some of them, and a Pendulum return sums 200 rewards of actions that differ so
+        (tests/test_duel_eval_gpu.py pins both facts).  evaluate() is the launch."""
+        return None
 
     @property
     def alpha(self):
@@ -486,6 +501,9 @@ class SACTrainer(WeightImages):
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
+        fused = self._eval_fused(num_episodes)
+        if fused is not None:
+            return fused
         env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 999, env_id0=1 << 40)
         obs = env.reset()
         nxt = torch.empty_like(obs)

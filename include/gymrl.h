@@ -1728,7 +1728,8 @@ int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
  * (500 / 200), an env kind other than CartPole-v1 / Pendulum-v1, a (head, D, A) that is not the kind's, H % 4 != 0 or H outside
  * 4..256, a negative policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, P * E
  * above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (w[k], images: 16 bytes; start: 8; the others: 4).
- * Out of scope: dueling, NoisyNet, Rainbow and SAC-Pendulum heads, MountainCar-v0, LunarLander-v3.
+ * SAC-Pendulum's greedy action tanh(mean(fc2(fc1 s))) * bound is head 1 on (fc1, fc2, mean).  Dueling networks: the entry point below.
+ * Out of scope: MountainCar-v0, LunarLander-v3.
  */
 typedef struct {
   int P, E, cap;
@@ -1745,6 +1746,37 @@ typedef struct {
 } gymrl_classic_eval_args;
 size_t gymrl_classic_eval_args_bytes(void);  /* sizeof(gymrl_classic_eval_args) */
 int gymrl_classic_policy_eval(const gymrl_classic_eval_args* args, void* stream);
+
+/*
+ * The same launch for a DUELING network on CartPole-v1 (csrc/eval_duel.hip; the episode loop is the one above, stated once in
+ * csrc/eval_episode_device.hpp): replaces the eval() loops of ddqn_per_duel_cartpole.py, noisy_dqn_cartpole.py and
+ * rainbow_dqn_cartpole.py.  In evaluation mode the three networks are one function: a ReLU trunk of n_hidden layers (1: fc1; 2:
+ * fc1, fc2), a value head [1][H] and an advantage head [A][H] on its output — both in ONE two-item row-slab stage, as
+ * gymrl_ndqn_act_step runs them — q = v + (a - mean a) with the mean as sum * (1 / A), and the FIRST maximum of q.  A NoisyLinear
+ * layer is passed as its weight_mu / bias_mu: no noise is drawn.  Grid, lanes, exit, starts, policy_stride (which shifts every
+ * pointer of the block) and the outputs are gymrl_classic_policy_eval's.
+ * -EINVAL before any launch: NULL args, a NULL w[0] / b[0] / value_w / value_b / adv_w / adv_b / returns / lengths / terminated,
+ * P < 1, E < 1, cap outside 1..500, an env kind other than CartPole-v1, (D, A) other than (4, 2), n_hidden outside {1, 2}, a NULL
+ * w[1] / b[1] with n_hidden == 2 or a non-NULL one with n_hidden == 1, H % 4 != 0 or H outside 4..256, a negative policy_stride or
+ * one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, with n_hidden == 1 or with H % 16 != 0,
+ * P * E above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (the weights, images: 16 bytes; start: 8; the others: 4).
+ */
+typedef struct {
+  int P, E, cap;
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE */
+  int n_hidden, D, A, H;                   /* hidden layers of the trunk (1 | 2); (D, A) = (4, 2) */
+  const float* w[2]; const float* b[2];    /* fc1 [H][D], fc2 [H][H] and their biases, of policy 0; entry 1 is NULL when n_hidden == 1 */
+  const float* value_w; const float* value_b;      /* the value head [1][H], [1] */
+  const float* adv_w; const float* adv_b;          /* the advantage head [A][H], [A] */
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  const float* images;                     /* the forward image of fc2 (n_hidden == 2, H % 16 == 0, P == 1), or NULL: fc2 is read in place */
+  uint64_t seed; int64_t stream_id0;
+  const double* start;                     /* f64[P * E][4], or NULL: the reset draw */
+  float* returns; int32_t* lengths; uint8_t* terminated;
+  float* final_obs;                        /* f32[P * E][4] or NULL */
+} gymrl_classic_duel_eval_args;
+size_t gymrl_classic_duel_eval_args_bytes(void);  /* sizeof(gymrl_classic_duel_eval_args) */
+int gymrl_classic_duel_eval(const gymrl_classic_duel_eval_args* args, void* stream);
 
 /* ------------------------------------------- MountainCar-v0 rule baseline ---- */
 /*
