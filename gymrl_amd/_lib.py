@@ -483,6 +483,7 @@ SIGNATURES = {
     "gymrl_linear_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "gymrl_linear_bwd_input": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "gymrl_linear_bwd_input_add": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "gymrl_linear_geometry": (_i, [_i, _i64, _i, _i, _P(_i), _P(_i)]),
     "gymrl_linear_bwd_weight_geometry": (_i, [_i64, _i, _P(_i), _P(_i64)]),
     "gymrl_linear_bwd_weight": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "gymrl_update_finalize": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

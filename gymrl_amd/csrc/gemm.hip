@@ -601,18 +601,26 @@ int g_ws_slices256 = kSlices256;   // column slices of the 256-wide forward / in
 constexpr int g_ws_slices256 = kSlices256;
 #endif
 
-// row groups of the weight-stationary kernels: at most one workgroup per CU (the weight slice fills LDS)
-inline int ws_row_groups(int64_t M, int rows_per_task, int slices) {
+// What a row-streaming launch does with the rows (gymrl_linear_geometry): row group g's wave w takes the row tiles
+// (g + j * row_groups) * 4 + w, j = 0, 1, ..: rows_per_round = 4 * ROWS rows per row group and loop iteration.
+// A launcher that is handed one fills it in INSTEAD of launching, so the query walks the entries' own dispatch.
+struct RowGeometry { int row_groups, rows_per_round; };
+
+// row groups of the row-streaming kernels: `per_cu` workgroups per CU (1 where the weight slice fills LDS), and no more
+// than there are rounds of 4 row tiles
+inline int ws_row_groups(int64_t M, int rows_per_task, int slices, int per_cu = 1) {
   const int waves = 4;
   const int64_t tasks = (M + rows_per_task - 1) / rows_per_task;
   const int64_t bts = (tasks + waves - 1) / waves;
-  int64_t rg = kCUs / slices;
+  int64_t rg = (int64_t)kCUs * per_cu / slices;
   if (bts < rg) rg = bts;
   return (int)(rg < 1 ? 1 : rg);
 }
 
 template <int RED, int NT, int RT, bool TRANS_W, int EPI, int LDO>
-void launch_ws(const WsArgs& a, int rg, hipStream_t s) {
+void launch_ws(const WsArgs& a, hipStream_t s, RowGeometry* geo) {
+  const int rg = ws_row_groups(a.M, 32 * RT, a.slices);
+  if (geo) { *geo = RowGeometry{rg, 4 * 32 * RT}; return; }
   const dim3 grid(rg * a.slices), block(256);
 #ifdef GYMRL_PROF_BUILD
   if constexpr (EPI == EPI_TANH && LDO == 256) {
@@ -631,15 +639,78 @@ void launch_ws(const WsArgs& a, int rg, hipStream_t s) {
 }
 
 template <int RED, int NT, bool TRANS_W, int EPI, int LDO>
-void launch_ns(const WsArgs& a, hipStream_t s) {
+void launch_ns(const WsArgs& a, hipStream_t s, RowGeometry* geo) {
   // 32-row tasks; up to two workgroups per CU where the LDS footprint allows (the kernel is as much HBM- as MFMA-bound)
   constexpr int lds_bytes = (RED * 32 * NT + 32 * NT + 4 * 32 * (RED + 4)) * 4;
   const int per_cu = lds_bytes <= 80 * 1024 ? 2 : 1;
-  const int64_t tasks = (a.M + 31) / 32, bts = (tasks + 3) / 4;
-  int64_t rg = (int64_t)kCUs * per_cu / a.slices;
-  if (bts < rg) rg = bts;
-  if (rg < 1) rg = 1;
+  const int rg = ws_row_groups(a.M, 32, a.slices, per_cu);
+  if (geo) { *geo = RowGeometry{rg, 4 * 32}; return; }
   hipLaunchKernelGGL((gemm_ns_kernel<RED, NT, TRANS_W, EPI, LDO>), dim3((unsigned)(rg * a.slices)), dim3(256), 0, s, a);
+}
+
+// The entries' dispatch: shape -> kernel instantiation and column slices.  false: a shape no kernel is written for.
+// geo != nullptr: the chosen launcher reports its geometry and nothing is launched (no HIP call is made).
+bool dispatch_fwd(WsArgs& a, int K, int N, int act, hipStream_t s, RowGeometry* geo) {
+  const bool wide = K == 256 && (N == 256 || N == 512);
+  const bool narrow = (K == 64 || K == 128) && (N == K || N == 2 * K);
+  if (!(wide || narrow) || (act != 0 && act != 1)) return false;
+  if (wide) {
+    a.slices = N / 128;
+    if (N == 256 && g_ws_slices256 == 4) {
+      a.slices = 4;
+      if (act == 1) launch_ws<256, 2, 2, false, EPI_TANH, 256>(a, s, geo);
+      else launch_ws<256, 2, 2, false, EPI_NONE, 256>(a, s, geo);
+    } else if (N == 256) {
+      if (act == 1) launch_ws<256, 4, 2, false, EPI_TANH, 256>(a, s, geo);
+      else launch_ws<256, 4, 2, false, EPI_NONE, 256>(a, s, geo);
+    } else {
+      if (act == 1) launch_ws<256, 4, 2, false, EPI_TANH, 512>(a, s, geo);
+      else launch_ws<256, 4, 2, false, EPI_NONE, 512>(a, s, geo);
+    }
+  } else if (K == 128) {                      // column slices of 128
+    a.slices = N / 128;
+    if (N == 128) { if (act == 1) launch_ns<128, 4, false, EPI_TANH, 128>(a, s, geo); else launch_ns<128, 4, false, EPI_NONE, 128>(a, s, geo); }
+    else { if (act == 1) launch_ns<128, 4, false, EPI_TANH, 256>(a, s, geo); else launch_ns<128, 4, false, EPI_NONE, 256>(a, s, geo); }
+  } else {                                    // K == 64: column slices of 64
+    a.slices = N / 64;
+    if (N == 64) { if (act == 1) launch_ns<64, 2, false, EPI_TANH, 64>(a, s, geo); else launch_ns<64, 2, false, EPI_NONE, 64>(a, s, geo); }
+    else { if (act == 1) launch_ns<64, 2, false, EPI_TANH, 128>(a, s, geo); else launch_ns<64, 2, false, EPI_NONE, 128>(a, s, geo); }
+  }
+  return true;
+}
+
+bool dispatch_bwd_input(WsArgs& a, int N, int K, hipStream_t s, RowGeometry* geo) {
+  const bool wide = K == 256 && (N == 256 || N == 512);
+  const bool narrow = (K == 64 || K == 128) && (N == K || N == 2 * K);
+  if (!(wide || narrow)) return false;
+  if (wide) {
+    if (N == 256 && g_ws_slices256 == 4) {
+      a.slices = 4;
+      launch_ws<256, 2, 2, true, EPI_TANHBWD, 256>(a, s, geo);
+    } else if (N == 256) {
+      a.slices = 2;
+      launch_ws<256, 4, 2, true, EPI_TANHBWD, 256>(a, s, geo);
+    } else {
+      a.slices = 4;
+      launch_ws<512, 2, 2, true, EPI_TANHBWD, 256>(a, s, geo);
+    }
+  } else if (K == 128) {
+    a.slices = 1;                             // one 128-column slice: the whole [N x 128] matrix is the workgroup's
+    if (N == 128) launch_ns<128, 4, true, EPI_TANHBWD, 128>(a, s, geo);
+    else launch_ws<256, 4, 2, true, EPI_TANHBWD, 128>(a, s, geo);     // reduction over 256: streamed rows
+  } else {
+    a.slices = 1;
+    if (N == 64) launch_ns<64, 2, true, EPI_TANHBWD, 64>(a, s, geo);
+    else launch_ns<128, 2, true, EPI_TANHBWD, 64>(a, s, geo);
+  }
+  return true;
+}
+
+bool dispatch_bwd_input_add(WsArgs& a, int N, int K, hipStream_t s, RowGeometry* geo) {
+  if (N != 256 || K != 128) return false;
+  a.slices = 1;
+  launch_ws<256, 4, 2, true, EPI_ADD, 128>(a, s, geo);
+  return true;
 }
 
 using fin::tn_geometry;
@@ -672,84 +743,52 @@ int gymrl_linear_bwd_weight_geometry(int64_t B, int N, int* slices, int64_t* row
   return 0;
 }
 
+int gymrl_linear_geometry(int kind, int64_t B, int K, int N, int* row_groups, int* rows_per_round) {
+  if (B <= 0 || !row_groups || !rows_per_round) return -22;
+  WsArgs a{};
+  a.M = B;
+  RowGeometry geo{};
+  bool ok = false;
+  if (kind == 0) ok = dispatch_fwd(a, K, N, 0, nullptr, &geo);
+  else if (kind == 1) ok = dispatch_bwd_input(a, N, K, nullptr, &geo);
+  else if (kind == 2) ok = dispatch_bwd_input_add(a, N, K, nullptr, &geo);
+  if (!ok) return -22;
+  *row_groups = geo.row_groups;
+  *rows_per_round = geo.rows_per_round;
+  return 0;
+}
+
 int gymrl_linear_fwd(const float* X, const float* W, const float* b, int64_t B, int K, int N, int act, float* Y,
                      void* stream) {
-  const bool wide = K == 256 && (N == 256 || N == 512);
-  const bool narrow = (K == 64 || K == 128) && (N == K || N == 2 * K);
-  if (!X || !W || !Y || B < 0 || !(wide || narrow) || (act != 0 && act != 1) || !al16(X) || !al16(W) || !al16(Y))
-    return -22;
-  if (B == 0) return 0;
+  if (!X || !W || !Y || B < 0 || !al16(X) || !al16(W) || !al16(Y)) return -22;
   WsArgs a{};
   a.A = X; a.M = B; a.lda = K; a.W = W; a.ldw = K; a.out = Y; a.ldo = N; a.bias = b;
-  hipStream_t s = (hipStream_t)stream;
-  if (wide) {
-    a.slices = N / 128;
-    const int rg = ws_row_groups(B, 64, a.slices);
-    if (N == 256 && g_ws_slices256 == 4) {
-      a.slices = 4;
-      if (act == 1) launch_ws<256, 2, 2, false, EPI_TANH, 256>(a, ws_row_groups(B, 64, 4), s);
-      else launch_ws<256, 2, 2, false, EPI_NONE, 256>(a, ws_row_groups(B, 64, 4), s);
-    } else if (N == 256) {
-      if (act == 1) launch_ws<256, 4, 2, false, EPI_TANH, 256>(a, rg, s);
-      else launch_ws<256, 4, 2, false, EPI_NONE, 256>(a, rg, s);
-    } else {
-      if (act == 1) launch_ws<256, 4, 2, false, EPI_TANH, 512>(a, rg, s);
-      else launch_ws<256, 4, 2, false, EPI_NONE, 512>(a, rg, s);
-    }
-  } else if (K == 128) {                      // column slices of 128
-    a.slices = N / 128;
-    if (N == 128) { if (act == 1) launch_ns<128, 4, false, EPI_TANH, 128>(a, s); else launch_ns<128, 4, false, EPI_NONE, 128>(a, s); }
-    else { if (act == 1) launch_ns<128, 4, false, EPI_TANH, 256>(a, s); else launch_ns<128, 4, false, EPI_NONE, 256>(a, s); }
-  } else {                                    // K == 64: column slices of 64
-    a.slices = N / 64;
-    if (N == 64) { if (act == 1) launch_ns<64, 2, false, EPI_TANH, 64>(a, s); else launch_ns<64, 2, false, EPI_NONE, 64>(a, s); }
-    else { if (act == 1) launch_ns<64, 2, false, EPI_TANH, 128>(a, s); else launch_ns<64, 2, false, EPI_NONE, 128>(a, s); }
-  }
+  RowGeometry probe{};                        // B == 0: the shape is still checked, nothing is launched
+  if (!dispatch_fwd(a, K, N, act, (hipStream_t)stream, B == 0 ? &probe : nullptr)) return -22;
+  if (B == 0) return 0;
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
 
 int gymrl_linear_bwd_input(const float* dY, const float* W, const float* H, int64_t B, int N, int K, float* dX,
                            void* stream) {
-  const bool wide = K == 256 && (N == 256 || N == 512);
-  const bool narrow = (K == 64 || K == 128) && (N == K || N == 2 * K);
-  if (!dY || !W || !dX || B < 0 || !(wide || narrow) || !al16(dY) || !al16(W) || !al16(dX) || (H && !al16(H)))
-    return -22;
-  if (B == 0) return 0;
+  if (!dY || !W || !dX || B < 0 || !al16(dY) || !al16(W) || !al16(dX) || (H && !al16(H))) return -22;
   WsArgs a{};
   a.A = dY; a.M = B; a.lda = N; a.W = W; a.ldw = K; a.out = dX; a.ldo = K; a.H = H; a.ldh = K;
-  hipStream_t s = (hipStream_t)stream;
-  if (wide) {
-    if (N == 256 && g_ws_slices256 == 4) {
-      a.slices = 4;
-      launch_ws<256, 2, 2, true, EPI_TANHBWD, 256>(a, ws_row_groups(B, 64, 4), s);
-    } else if (N == 256) {
-      a.slices = 2;
-      launch_ws<256, 4, 2, true, EPI_TANHBWD, 256>(a, ws_row_groups(B, 64, 2), s);
-    } else {
-      a.slices = 4;
-      launch_ws<512, 2, 2, true, EPI_TANHBWD, 256>(a, ws_row_groups(B, 64, 4), s);
-    }
-  } else if (K == 128) {
-    a.slices = 1;                             // one 128-column slice: the whole [N x 128] matrix is the workgroup's
-    if (N == 128) launch_ns<128, 4, true, EPI_TANHBWD, 128>(a, s);
-    else launch_ws<256, 4, 2, true, EPI_TANHBWD, 128>(a, ws_row_groups(B, 64, 1), s);     // reduction over 256: streamed rows
-  } else {
-    a.slices = 1;
-    if (N == 64) launch_ns<64, 2, true, EPI_TANHBWD, 64>(a, s);
-    else launch_ns<128, 2, true, EPI_TANHBWD, 64>(a, s);
-  }
+  RowGeometry probe{};
+  if (!dispatch_bwd_input(a, N, K, (hipStream_t)stream, B == 0 ? &probe : nullptr)) return -22;
+  if (B == 0) return 0;
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
 
 int gymrl_linear_bwd_input_add(const float* dY, const float* W, const float* G, int64_t B, int N, int K, float* dX, void* stream) {
-  if (!dY || !W || !G || !dX || B < 0 || N != 256 || K != 128 || !al16(dY) || !al16(W) || !al16(dX) || !al16(G)) return -22;
-  if (B == 0) return 0;
+  if (!dY || !W || !G || !dX || B < 0 || !al16(dY) || !al16(W) || !al16(dX) || !al16(G)) return -22;
   WsArgs a{};
   a.A = dY; a.M = B; a.lda = N; a.W = W; a.ldw = K; a.out = dX; a.ldo = K; a.H = G; a.ldh = K;
-  a.slices = 1;
-  launch_ws<256, 4, 2, true, EPI_ADD, 128>(a, ws_row_groups(B, 64, 1), (hipStream_t)stream);
+  RowGeometry probe{};
+  if (!dispatch_bwd_input_add(a, N, K, (hipStream_t)stream, B == 0 ? &probe : nullptr)) return -22;
+  if (B == 0) return 0;
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

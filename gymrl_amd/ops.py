@@ -1219,6 +1219,18 @@ def linear_bwd_input_add(dy, W, g, dx):
     return dx
 
 
+LINEAR_FWD, LINEAR_BWD_INPUT, LINEAR_BWD_INPUT_ADD = 0, 1, 2
+
+
+def linear_geometry(kind, B, K, N):
+    """(row_groups, rows_per_round) of the row-streaming kernel behind linear_fwd / linear_bwd_input / linear_bwd_input_add
+    (kind LINEAR_*) at x [B, K] -> [B, N] resp. dy [B, N] -> [B, K]: a wave of the launch runs
+    ceil(ceil(B / rows_per_round) / row_groups) loop iterations (include/gymrl.h gymrl_linear_geometry).  Host only."""
+    g, r = C.c_int(0), C.c_int(0)
+    check(lib().gymrl_linear_geometry(kind, B, K, N, C.byref(g), C.byref(r)), "gymrl_linear_geometry")
+    return g.value, r.value
+
+
 def linear_bwd_weight_geometry(B, N):
     s, r = C.c_int(0), C.c_int64(0)
     check(lib().gymrl_linear_bwd_weight_geometry(B, N, C.byref(s), C.byref(r)), "gymrl_linear_bwd_weight_geometry")

@@ -975,6 +975,12 @@ int gymrl_linear_bwd_input(const float* dY, const float* W, const float* H, int6
  * first one's in the GEMM's epilogue (PPO-full's actor and critic heads both read the backbone's output: the separate add was a
  * 0.8 GB pass per 524 288-row micro-batch).  Same sums as gymrl_linear_bwd_input followed by G + . ; G may not alias dX. */
 int gymrl_linear_bwd_input_add(const float* dY, const float* W, const float* G, int64_t B, int N, int K, float* dX, void* stream);
+/* How the row-streaming kernels behind linear_fwd (kind 0), linear_bwd_input (1) and linear_bwd_input_add (2) cut B rows, for
+ * the kernel the entry picks at (K, N) — host only, nothing is launched.  The launch has `row_groups` row groups of four waves;
+ * a wave owns rows_per_round / 4 rows at a time, and row group g's loop iteration j covers the rows from
+ * (g + j * row_groups) * rows_per_round on.  So one call runs ceil(ceil(B / rows_per_round) / row_groups) iterations per wave;
+ * tests use this to reach (or to stay out of) the iterations after the first.  -22: B <= 0 or a shape the entry refuses. */
+int gymrl_linear_geometry(int kind, int64_t B, int K, int N, int* row_groups, int* rows_per_round);
 int gymrl_linear_bwd_weight_geometry(int64_t B, int N, int* slices, int64_t* rows_per_slice);
 int gymrl_linear_bwd_weight(const float* dY, const float* X, int64_t B, int N, int K, float* dW,
                             float* db, void* workspace, void* stream);

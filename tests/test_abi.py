@@ -300,6 +300,29 @@ def test_mhc_entry_points_validate_arguments_without_gpu():
     assert small == 32 * (128 * 128 + 128) * 4 and big == 512 * (128 * 128 + 128) * 4
 
 
+def test_linear_geometry_is_host_only_and_refuses_what_the_entries_refuse():
+    """gymrl_linear_geometry walks the entries' dispatch without a launch: one round up to row_groups * rows_per_round rows,
+    a row-group count that stops growing there, and -EINVAL for the shapes gymrl_linear_fwd / _bwd_input / _bwd_input_add refuse."""
+    from gymrl_amd import _lib, ops
+    L = _lib.lib()
+    g, r = ctypes.c_int(0), ctypes.c_int(0)
+    for kind, shapes in ((0, [(256, 256), (256, 512), (128, 128), (128, 256), (64, 64), (64, 128)]),
+                         (1, [(256, 256), (256, 512), (128, 256), (128, 128), (64, 128), (64, 64)]), (2, [(128, 256)])):
+        for K, N in shapes:
+            rg_max, rpr = ops.linear_geometry(kind, 1 << 40, K, N)
+            assert rpr in (128, 256) and rg_max >= 8
+            assert ops.linear_geometry(kind, 1, K, N) == (1, rpr)
+            assert ops.linear_geometry(kind, 5 * rpr + 1, K, N) == (6, rpr)              # one row group per started round-of-one
+            assert ops.linear_geometry(kind, rg_max * rpr, K, N) == (rg_max, rpr)        # the largest single-round call
+            assert ops.linear_geometry(kind, rg_max * rpr + 1, K, N) == (rg_max, rpr)    # one row more: a second round
+    assert L.gymrl_linear_geometry(0, 100, 256, 128, g, r) == -22                        # no such forward
+    assert L.gymrl_linear_geometry(1, 100, 96, 96, g, r) == -22
+    assert L.gymrl_linear_geometry(2, 100, 256, 256, g, r) == -22                        # bwd_input_add: (N, K) = (256, 128) only
+    assert L.gymrl_linear_geometry(3, 100, 256, 256, g, r) == -22                        # unknown kind
+    assert L.gymrl_linear_geometry(0, 0, 256, 256, g, r) == -22 and L.gymrl_linear_geometry(0, -4, 256, 256, g, r) == -22
+    assert L.gymrl_linear_geometry(0, 100, 256, 256, None, r) == -22 and L.gymrl_linear_geometry(0, 100, 256, 256, g, None) == -22
+
+
 def test_ops_refuse_cpu_tensors():
     import pytest
     import torch
