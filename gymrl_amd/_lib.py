@@ -100,6 +100,13 @@ class RolloutLunarArgs(C.Structure):
                 ("refill", C.c_int), ("gae_carry", C.c_int)]
 
 
+class LunarEvalArgs(C.Structure):
+    _c_name_ = "gymrl_lunar_eval_args"
+    _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("stream_id0", C.c_int64),
+                ("policy_stride", C.c_int64), ("returns", C.c_void_p), ("lengths", C.c_void_p), ("terminated", C.c_void_p),
+                ("terminal_obs", C.c_void_p)]
+
+
 class SacActorParams(C.Structure):
     _c_name_ = "gymrl_sac_actor_params"   # fc1, fc2, mean, log_std
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
@@ -439,6 +446,9 @@ SIGNATURES = {
     "gymrl_rollout_lunar": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_cartpole": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_lunar_mhc": (_i, [_P(RolloutLunarArgs), _P(MhcPolicy), _vp]),
+    "gymrl_lunar_eval_args_bytes": (_sz, []),
+    "gymrl_lunar_policy_eval": (_i, [_P(LunarEvalArgs), _P(MlpDesc), _vp]),
+    "gymrl_lunar_mhc_eval": (_i, [_P(LunarEvalArgs), _P(MhcPolicy), _vp]),
     "gymrl_lin_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_lin_fwd": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gymrl_lin_bwd_input": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

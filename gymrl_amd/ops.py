@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   MlpDesc, MlprnnParams, MountainCarEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   LunarEvalArgs, MlpDesc, MlprnnParams, MountainCarEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -774,6 +774,88 @@ def classic_duel_eval(kind, trunk, value, advantage, n_episodes, seed, stream_id
     a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
     check(lib().gymrl_classic_duel_eval(C.byref(a), _stream()), "gymrl_classic_duel_eval")
     return out if want_final_obs else out[:3]
+
+
+# ---------------------- LunarLander-v3 PPO policies: whole episodes in one launch ---
+LUNAR_MAX_STEPS = 1000
+
+
+class LunarPolicyStack:
+    """P policies of one FusedMLP's shape for lunar_policy_eval, in ONE buffer f32[P, stride]: per row every stage's packed
+    weight (gymrl_mlp_pack's image) and then every stage's bias, each from a multiple of four floats on.  params f32[P, n]: flat
+    parameter vectors in the layout of `flat`, the buffer the network's own tensors are views of.  stride (floats, a multiple of
+    4): None = tight."""
+
+    def __init__(self, fused, flat, params, stride=None):
+        mods = [m for m, _, _, _ in fused.stages]
+        if params.dim() != 2 or params.shape[1] < flat.numel() or params.dtype != torch.float32 or not params.is_cuda:
+            raise ValueError("LunarPolicyStack: params is a stack f32[P, n] of flat buffers in the layout of `flat`, on the device")
+        if any(m.bias is None for m in mods):
+            raise ValueError("LunarPolicyStack: every layer carries a bias")
+        tensors = [m.weight for m in mods] + [m.bias for m in mods]
+        offs = [(t.data_ptr() - flat.data_ptr()) // 4 for t in tensors]
+        if any(o < 0 or o + t.numel() > flat.numel() for o, t in zip(offs, tensors)):
+            raise ValueError("LunarPolicyStack: the layers' tensors are not views of `flat`")
+        sizes = [int(lib().gymrl_mlp_packed_floats(*m.weight.shape)) for m in mods] + [(m.bias.numel() + 3) // 4 * 4 for m in mods]
+        at = [sum(sizes[:k]) for k in range(len(sizes))]
+        tight = sum(sizes)
+        self.stride = tight if stride is None else int(stride)
+        if self.stride < tight or self.stride % 4:
+            raise ValueError(f"LunarPolicyStack: the stride is a multiple of 4 floats and at least {tight}")
+        params = params.contiguous()
+        self.P, L = params.shape[0], len(mods)
+        self.buffer = torch.zeros(self.P, self.stride, dtype=torch.float32, device=params.device)
+        for p in range(self.P):
+            for k, m in enumerate(mods):
+                W = params[p, offs[k]:offs[k] + m.weight.numel()].view(m.weight.shape)
+                mlp_pack(W, self.buffer[p, at[k]:at[k] + sizes[k]])
+                self.buffer[p, at[L + k]:at[L + k] + m.bias.numel()] = params[p, offs[L + k]:offs[L + k] + m.bias.numel()]
+        d = MlpDesc()
+        d.n_stages = L
+        base = self.buffer.data_ptr()
+        for k, (m, act, src, dst) in enumerate(fused.stages):
+            e = d.stage[k]
+            e.W, e.b = base + 4 * at[k], base + 4 * at[L + k]
+            e.out_dim, e.in_dim = m.weight.shape
+            e.act, e.src, e.dst = fused._ACT[act], int(src), int(dst)
+        d._keepalive = self.buffer                   # the table holds raw pointers
+        self.desc = d
+
+
+def _lunar_eval_args(P, n_episodes, seed, stream_id0, cap, stride, want_terminal_obs, dev):
+    returns = torch.empty(P, n_episodes, dtype=torch.float64, device=dev)
+    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
+    terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
+    final = torch.empty(P, n_episodes, 8, dtype=torch.float32, device=dev) if want_terminal_obs else None
+    a = LunarEvalArgs()
+    a.P, a.E, a.cap, a.seed, a.stream_id0, a.policy_stride = P, n_episodes, cap, seed, stream_id0, stride
+    a.returns, a.lengths, a.terminated = _ptr(returns), _ptr(lengths), _ptr(terminated)
+    a.terminal_obs = _ptr(final, torch.float32, True)
+    return a, (returns, lengths, terminated, final)
+
+
+def lunar_policy_eval(policy, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS, want_terminal_obs=True, device=None):
+    """n_episodes whole LunarLander-v3 episodes per policy under the first maximum of the logits, in ONE launch (include/gymrl.h
+    gymrl_lunar_policy_eval) -> (returns f64, lengths i32, terminated u8, terminal_obs f32[..., 8] | None), each [P, n_episodes].
+    policy: a nn.FusedMLP (logits [4] then value [1]; P = 1, the weights as its last refresh() packed them) or a LunarPolicyStack.
+    Episode e of every policy is the first episode of env stream_id0 + e under `seed`."""
+    if isinstance(policy, LunarPolicyStack):
+        P, stride, desc, dev = policy.P, policy.stride, policy.desc, policy.buffer.device
+    else:
+        dev = device if device is not None else policy.stages[0][0].weight.device
+        P, stride, desc = 1, 0, policy.descriptor(16, dev)
+    a, out = _lunar_eval_args(P, n_episodes, seed, stream_id0, cap, stride, want_terminal_obs, dev)
+    check(lib().gymrl_lunar_policy_eval(C.byref(a), C.byref(desc), _stream()), "gymrl_lunar_policy_eval")
+    return out
+
+
+def lunar_mhc_eval(policy_desc, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS, want_terminal_obs=True, device=None):
+    """lunar_policy_eval for PPO-full's mHC network: policy_desc is a filled _lib.MhcPolicy (its `image` as the caller left it:
+    None reads the parameters in place), one policy."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    a, out = _lunar_eval_args(1, n_episodes, seed, stream_id0, cap, 0, want_terminal_obs, dev)
+    check(lib().gymrl_lunar_mhc_eval(C.byref(a), C.byref(policy_desc), _stream()), "gymrl_lunar_mhc_eval")
+    return out
 
 
 # ============================================================== off-policy ===

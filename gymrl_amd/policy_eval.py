@@ -12,7 +12,9 @@ launch.  Two entry points serve nine trainers:
                               first maximum (dueling DDQN+PER: one hidden layer; NoisyNet dueling DQN and Rainbow: two, the noisy
                               layers at their weight_mu / bias_mu — no noise is drawn and no draw counter moves)
 
-MountainCar-v0, LunarLander-v3 and every shape the entry points refuse (hidden 260, more than two actions) keep the loop."""
+MountainCar-v0 and every shape the entry points refuse (hidden 260, more than two actions) keep the loop.  LunarLander-v3 has a
+launch of its own on the two PPO trainers themselves (csrc/eval_lunar.hip, DESIGN §4r: other streams, a float64 return, a
+population packed per policy), not through this mixin."""
 import torch
 
 from . import ops

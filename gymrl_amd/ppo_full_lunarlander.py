@@ -67,6 +67,8 @@ class Config:
                                            # this is accumulated over equal micro-batches before ONE optimiser step — the
                                            # same gradient, bounded activation memory (4096 envs x F0's ratio = 4.2 M rows)
         self.gae_variant = 1               # 1 = time-blocked G3 with the chunk maps composed during the rollout, 0 = sequential
+        self.fused_eval = False            # LunarLander + the default network shape: eval() as ONE launch (gymrl_lunar_mhc_eval), the
+                                           # loop's own episodes bit for bit
 
 
 FUSED_GATES = True          # training pass: the gates as one forward + one backward launch (False: torch ops + gymrl_sinkhorn)
@@ -920,10 +922,47 @@ class PPOTrainer:
                       f"Avg Reward: {np.mean(self.episode_rewards):.1f} | KL: {metrics['approx_kl']:.4f}")
         self.env.close()
 
+    EVAL_SEED_OFFSET, EVAL_ENV_ID0 = 1_000_003, 1 << 40      # eval()'s env streams: seed base_seed + 1_000_003, env ids from 1 << 40
+
+    def _eval_desc(self):
+        """The descriptor gymrl_lunar_mhc_eval takes (the parameters read in place), or None: an env other than the built-in
+        LunarLander, or a network the one-launch forward is not written for — where eval()'s loop does not act on it either."""
+        if ops.ENV_KINDS.get(self.cfg.env_name) != ops.LUNARLANDER or not (FUSED_INFERENCE and FUSED_POLICY):
+            return None
+        desc = self.model._policy_desc() if hasattr(self.model, "_policy_desc") else None
+        if desc is None or desc.obs_dim != 8 or desc.n_act != 4:
+            return None
+        desc.image = None
+        return desc
+
+    @torch.no_grad()
+    def evaluate(self, num_episodes, params=None, stream_offset=0):
+        """-> (returns f64, lengths i32, terminated u8), numpy arrays [1, num_episodes]: whole deterministic episodes on eval()'s
+        streams (episode e: seed base_seed + 1_000_003, env id (1 << 40) + stream_offset + e) in ONE launch (csrc/eval_lunar.hip)
+        whatever Config.fused_eval says.  params: None only — the mHC entry point carries one policy.  Moves neither the rollout's
+        counters, nor self.env, the buffer or the optimiser.  Raises where the entry point takes no such policy."""
+        if params is not None:
+            raise ValueError("PPOTrainer.evaluate: gymrl_lunar_mhc_eval carries one policy, the trainer's own (params=None)")
+        desc = self._eval_desc()
+        if desc is None:
+            raise RuntimeError("PPOTrainer.evaluate: gymrl_lunar_mhc_eval takes LunarLander-v3 under the default mHC network shape "
+                               "(include/gymrl.h)")
+        out = ops.lunar_mhc_eval(desc, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET,
+                                 self.EVAL_ENV_ID0 + int(stream_offset), want_terminal_obs=False, device=self.device)
+        return tuple(t.cpu().numpy() for t in out[:3])
+
     @torch.no_grad()
     def eval(self, num_episodes=10):
-        env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 1_000_003,
-                     env_id0=1 << 40)
+        """Deterministic (argmax) episodes, run as `num_episodes` parallel envs, each contributing its first finished episode.  With
+        Config.fused_eval the same episodes are ONE launch (gymrl_lunar_mhc_eval): the loop acts on forward_inference, the
+        launch on the same tile, so the two lists are equal."""
+        desc = self._eval_desc() if getattr(self.cfg, "fused_eval", False) and num_episodes >= 1 else None
+        if desc is not None:
+            returns = ops.lunar_mhc_eval(desc, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0,
+                                         want_terminal_obs=False, device=self.device)[0]
+            return returns[0].to(torch.float32).tolist()       # the loop's ep_ret_out: the float32 cast of the float64 return
+        env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + self.EVAL_SEED_OFFSET,
+                     env_id0=self.EVAL_ENV_ID0)
         obs = env.reset()
         nxt = torch.empty_like(obs)
         rew = torch.empty(num_episodes, device=self.device)

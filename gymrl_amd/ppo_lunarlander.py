@@ -70,6 +70,9 @@ class Config:
                                           # Bit-identical to the eager loop, but measured SLOWER at bench shape (update 889 vs 881
                                           # ms, A/B in one call: the host already runs ~19 launches ahead of 2.8 ms of kernels,
                                           # and the graph executor's 4-7 us per kernel node exceed the eager queue's gaps)
+        self.fused_eval = False           # LunarLander: eval() as ONE launch (gymrl_lunar_policy_eval) on the loop's own streams, acting on
+                                          # act_forward's logits — the forward the persistent rollout trains under; eval()'s loop runs
+                                          # torch's layers, which can differ from it in a logit's last place
         self.solved_reward = 200.0
 
 
@@ -658,15 +661,71 @@ class PPOTrainer:
             print("Training completed!")
         self.env.close()
 
+    EVAL_SEED_OFFSET, EVAL_ENV_ID0 = 1_000_003, 1 << 40      # eval()'s env streams: seed base_seed + 1_000_003, env ids from 1 << 40
+
+    def _eval_net(self):
+        """The one-launch forward gymrl_lunar_policy_eval acts on (weights packed as they are now), or None: an env other than the
+        built-in LunarLander, or a network FusedMLP.supported refuses."""
+        if ops.ENV_KINDS.get(self.cfg.env_name) != ops.LUNARLANDER or self.action_dim != 4:
+            return None
+        net = self.model._act_net()
+        if not net:
+            return None
+        net.refresh()
+        return net
+
+    @torch.no_grad()
+    def evaluate(self, num_episodes, params=None, stream_offset=0):
+        """-> (returns f64, lengths i32, terminated u8), numpy arrays [P, num_episodes]: whole deterministic episodes on eval()'s
+        streams (episode e: seed base_seed + 1_000_003, env id (1 << 40) + stream_offset + e), every policy from the same starts,
+        in ONE launch (csrc/eval_lunar.hip) whatever Config.fused_eval says.  params = None: the trainer's own policy (P = 1);
+        params = f32[P, n]: a stack of flat parameter vectors in the layout of flat_params.  The actions are the first maxima of
+        act_forward's logits (gymrl_mlp_forward's bits).  Moves neither the rollout's counters, nor self.env, the buffer or the
+        optimiser.  Raises where the entry point takes no such policy."""
+        net = self._eval_net()
+        if net is None:
+            raise RuntimeError("PPOTrainer.evaluate: gymrl_lunar_policy_eval takes LunarLander-v3 under a network the one-launch "
+                               "forward supports (include/gymrl.h)")
+        policy = net
+        if params is not None:
+            params = torch.as_tensor(params, dtype=torch.float32).to(self.device)
+            policy = ops.LunarPolicyStack(net, self.flat_params, params.view(1, -1) if params.dim() == 1 else params)
+        out = ops.lunar_policy_eval(policy, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET,
+                                    self.EVAL_ENV_ID0 + int(stream_offset), want_terminal_obs=False, device=self.device)
+        return tuple(t.cpu().numpy() for t in out[:3])
+
+    def _eval_fused(self, num_episodes):
+        """eval(num_episodes) as one launch -> the list the loop returns, or None: fused_eval is off, the test hook supplies the env,
+        or _eval_net() has no such policy."""
+        if not getattr(self.cfg, "fused_eval", False) or self._eval_env_factory is not None or num_episodes < 1:
+            return None
+        net = self._eval_net()
+        if net is None:
+            return None
+        returns = ops.lunar_policy_eval(net, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0,
+                                        want_terminal_obs=False, device=self.device)[0]
+        return returns[0].to(torch.float32).tolist()           # the loop's ep_ret_out: the float32 cast of the float64 return
+
     @torch.no_grad()
     def eval(self, num_episodes=10):
         """:368-399: deterministic (argmax) episodes — run as `num_episodes` parallel envs,
-        each contributing its first finished episode."""
+        each contributing its first finished episode.  With Config.fused_eval the same episodes are ONE launch
+        (gymrl_lunar_policy_eval) that reproduces this loop run on act_forward (gymrl_mlp_forward) bit for bit; the loop below
+        runs torch's library layers, whose logits can differ from act_forward's in the last place — argmax makes a different
+        action rare, not impossible, so the two lists are not promised equal."""
+        rewards = self._eval_fused(num_episodes)
+        if rewards is None:
+            rewards = self._eval_loop(num_episodes)
+        if self.rank == 0:
+            print(f"Evaluation Results: Mean = {np.mean(rewards):.1f} +/- {np.std(rewards):.1f}")
+        return rewards
+
+    def _eval_loop(self, num_episodes):
         if self._eval_env_factory is not None:
             env = self._eval_env_factory(num_episodes)
         else:
-            env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + 1_000_003,
-                         env_id0=1 << 40)
+            env = VecEnv(self.cfg.env_name, num_episodes, device=self.device, seed=self.base_seed + self.EVAL_SEED_OFFSET,
+                         env_id0=self.EVAL_ENV_ID0)
         obs = env.reset()
         nxt = torch.empty_like(obs)
         rew = torch.empty(num_episodes, device=self.device)
@@ -683,10 +742,7 @@ class PPOTrainer:
             if not torch.isnan(result).any():
                 break
         self.model.train()
-        rewards = result.tolist()
-        if self.rank == 0:
-            print(f"Evaluation Results: Mean = {np.mean(rewards):.1f} +/- {np.std(rewards):.1f}")
-        return rewards
+        return result.tolist()
 
     def test(self):
         """:401-426 without the render window (the batched env has no renderer)."""

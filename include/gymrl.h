@@ -627,6 +627,47 @@ int gymrl_rollout_cartpole(const gymrl_rollout_lunar_args* args, const gymrl_mlp
 struct gymrl_mhc_policy_s;
 int gymrl_rollout_lunar_mhc(const gymrl_rollout_lunar_args* args, const struct gymrl_mhc_policy_s* policy, void* stream);
 
+/* ------------------------------ LunarLander-v3 PPO policies: whole episodes in one launch ---- */
+/*
+ * Replaces the eval() loops of ppo_lunarlander.py:368-399 and ppo_full_lunarlander.py (get_action(deterministic=True) -> env.step
+ * until the episode is over, up to the TimeLimit of 1000 steps) for P policies x E episodes at a time (csrc/eval_lunar.hip; the
+ * episode loop is stated once in csrc/eval_lunar_device.hpp).  ONE workgroup of 256 threads carries 16 episodes of one policy from
+ * reset to their end, laid out like gymrl_rollout_lunar's: all four waves run the policy forward of the 16 observations, wave 0
+ * takes the FIRST maximum of the four logits (gymrl_categorical_sample's deterministic branch) and steps the envs four lanes per
+ * env.  The grid is P * ceil(E / 16) workgroups.  The worlds are built in the kernel (gymrl_env_reset's arithmetic) and stay in
+ * LDS: there is no env_state buffer.  A finished episode's lanes idle; the workgroup leaves when all 16 are finished (at `cap` at
+ * the latest) on one LDS word behind a barrier every thread reaches.  No atomics, nothing waits for another workgroup, no random
+ * draw, and global memory is only written where an episode ends.
+ *
+ * Episode i = p * E + e is the first episode of env stream_id0 + e under `seed` — the SAME starts for every policy, env e of a
+ * gymrl_env_reset with env_id0 = stream_id0.  It ends with terminated = 1 when the env says so, with terminated = 0 when its length
+ * reaches `cap`.
+ *
+ * Outputs, each [P * E], written once when the episode ends: returns (float64: the sum of the float32 rewards in step order),
+ * lengths, terminated, terminal_obs [P * E][8] (optional) the observation after the last step.
+ *
+ * gymrl_lunar_policy_eval: the policy is gymrl_rollout_lunar's descriptor, logits [4] then value [1] as the two dst == -1 stages
+ * (their `out` pointers are ignored); stages that only feed the value are not run.  Policy p reads every stage's W and b
+ * p * policy_stride floats behind policy 0's (0: P == 1), the rule of gymrl_classic_policy_eval further down.  Bit-identical to the step-by-step
+ * sequence gymrl_mlp_forward -> gymrl_categorical_sample(deterministic) -> gymrl_env_step.
+ * gymrl_lunar_mhc_eval: the policy is the mHC network (gymrl_mhc_policy; obs_dim 8, n_act 4), P == 1.  Bit-identical to
+ * gymrl_mhc_policy_forward -> gymrl_categorical_sample(deterministic) -> gymrl_env_step.
+ * -EINVAL before any launch: NULL args / policy / returns / lengths / terminated, P < 1, E < 1, cap outside 1..1000, a negative
+ * policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, P > 1 on the mHC entry, P * E above INT32_MAX,
+ * stream_id0 < 0, a pointer that is not aligned (returns: 8 bytes; lengths: 4; terminal_obs: 16), and every descriptor
+ * gymrl_rollout_lunar / gymrl_rollout_lunar_mhc refuse.
+ */
+typedef struct {
+  int P, E, cap;
+  uint64_t seed; int64_t stream_id0;
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  double* returns; int32_t* lengths; uint8_t* terminated;
+  float* terminal_obs;                     /* f32[P * E][8] or NULL */
+} gymrl_lunar_eval_args;
+size_t gymrl_lunar_eval_args_bytes(void);  /* sizeof(gymrl_lunar_eval_args) */
+int gymrl_lunar_policy_eval(const gymrl_lunar_eval_args* args, const gymrl_mlp_desc* policy, void* stream);
+int gymrl_lunar_mhc_eval(const gymrl_lunar_eval_args* args, const struct gymrl_mhc_policy_s* policy, void* stream);
+
 /* ================================================ low-latency Linear layers == */
 /*
  * D2 / A2 / T1 update path and the vectorised acting forward of the off-policy trainers: every
@@ -1735,7 +1776,7 @@ int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
  * 4..256, a negative policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, P * E
  * above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (w[k], images: 16 bytes; start: 8; the others: 4).
  * SAC-Pendulum's greedy action tanh(mean(fc2(fc1 s))) * bound is head 1 on (fc1, fc2, mean).  Dueling networks: the entry point below.
- * Out of scope: MountainCar-v0, LunarLander-v3.
+ * Out of scope: MountainCar-v0 (LunarLander-v3 under a PPO policy: gymrl_lunar_policy_eval below).
  */
 typedef struct {
   int P, E, cap;
