@@ -449,6 +449,7 @@ SIGNATURES = {
     "gymrl_lunar_eval_args_bytes": (_sz, []),
     "gymrl_lunar_policy_eval": (_i, [_P(LunarEvalArgs), _P(MlpDesc), _vp]),
     "gymrl_lunar_mhc_eval": (_i, [_P(LunarEvalArgs), _P(MhcPolicy), _vp]),
+    "gymrl_lunar_mlprnn_eval": (_i, [_P(LunarEvalArgs), _P(MlprnnParams), _vp, _i64, _vp, _vp]),
     "gymrl_lin_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_lin_fwd": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gymrl_lin_bwd_input": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -32,16 +32,6 @@ constexpr int kDynBytesMhc = 40 * 1024;    // (its static LDS — policy tile, s
 static_assert(kDynFloats * 4 <= kDynBytes, "LDS carve-up");
 static_assert((M::kRows * kXStride + M::kRows * M::kHeadStride) * 4 <= kDynBytesMhc, "LDS carve-up");
 
-// which 16 episodes of which policy this workgroup carries: the grid is P * ceil(E / 16)
-struct EpisodeSlot {
-  int p, e0;
-  __device__ explicit EpisodeSlot(int E) {
-    const int groups = (E + 15) / 16;
-    p = (int)blockIdx.x / groups;
-    e0 = ((int)blockIdx.x - p * groups) * 16;
-  }
-};
-
 __global__ __launch_bounds__(kEvalThreads) void lunar_eval_kernel(const gymrl_lunar_eval_args a, const gymrl_mlp_desc d) {
   extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
   __shared__ uint32_t lds_words[kLdsWords * kEnvBlock];            // the solver's per-lane columns (wave 0)
@@ -62,8 +52,8 @@ __global__ __launch_bounds__(kEvalThreads) void lunar_eval_kernel(const gymrl_lu
   }
   if (tid == 0) pd.n_stages = d.n_stages;
   const uint32_t vdefer = M::deferrable_stages(d, kEvalActions);   // the critic's stages (0: the network has no such split)
-  run_lunar_episodes(a, lds_words, lds_park, running, xin, M::kInStride, head, slot.p, slot.e0,
-                     [&]() { M::forward_tile(pd, lds, xin, head, 0, M::kRows, tid, vdefer); });
+  run_lunar_episodes<kEvalThreads>(a, lds_words, lds_park, running, xin, M::kInStride, slot.p, slot.e0,
+                                   logits_policy(head, [&]() { M::forward_tile(pd, lds, xin, head, 0, M::kRows, tid, vdefer); }));
 }
 
 // its own function: the tile's ~170 registers and the solver's are allocated separately (as in rollout_lunar.hip)
@@ -82,10 +72,10 @@ __global__ __launch_bounds__(kEvalThreads) void lunar_eval_mhc_kernel(const gymr
   const int tid = threadIdx.x;
   const int prow = 4 * (tid >> 6) + ((tid & 63) >> 4);             // the policy tile's view: this lane's row
   const EpisodeSlot slot(a.E);
-  run_lunar_episodes(a, lds_words, lds_park, running, xin, kXStride, head, slot.p, slot.e0, [&]() {
+  run_lunar_episodes<kEvalThreads>(a, lds_words, lds_park, running, xin, kXStride, slot.p, slot.e0, logits_policy(head, [&]() {
     eval_policy_tile_call(p, L, xin + prow * kXStride, head);
     __syncthreads();                                               // logits -> head[row][0..3]
-  });
+  }));
 }
 
 // the policy must be a 2-output network on the LunarLander observation, logits [4] then value [1]: gymrl_rollout_lunar's rule

@@ -1,15 +1,17 @@
 // eval_lunar_device.hpp — the episode loop of the one-launch LunarLander evaluation, stated once: eval_lunar.hip's two kernels
-// (PPO's Linear + Tanh network, PPO-full's mHC network) instantiate it with their own policy forward.
+// (PPO's Linear + Tanh network, PPO-full's mHC network) and eval_lunar_rnn.hip's (the PPG / PPO-RNN recurrent network)
+// instantiate it with their own policy: its forward, its greedy pick, what it reads of an observation, and what it keeps of an
+// episode at its end.
 //
-// ONE workgroup of mlp::kWaves * 64 threads carries 16 episodes of one policy from their reset to their end, laid out like
+// ONE workgroup of THREADS threads (mlp::kWaves * 64 in eval_lunar.hip) carries 16 episodes of one policy from their reset to their end, laid out like
 // rollout_lunar_kernel: every wave runs the policy forward on the 16 observations, wave 0 then steps the 16 envs four lanes
 // per env (env_lunar_device.hpp).  What the rollout has and this loop has not: no slab, no draw, no GAE state, no next episode
 // (so no spare world, no refill wave and no env_state buffer) — the worlds are built in the kernel and never touch HBM.
 //
 //   iteration 0   wave 0 builds episode 0 of its envs: init_episode + env_step_once(action 0), VecEnv.reset()'s arithmetic
 //                 (lunar_reset_kernel), parks the worlds in LDS and puts the observations into the forward's input tile
-//   iteration t   everybody: the forward of the 16 observations, closed by a barrier; wave 0: the FIRST maximum of the four
-//                 logits (categorical_pick's deterministic scan), un-park, env_step_once with step_idx = len,
+//   iteration t   everybody: the forward of the 16 observations, closed by a barrier; wave 0: the policy's pick (LogitsPolicy:
+//                 the FIRST maximum of the four logits, categorical_pick's deterministic scan), un-park, env_step_once with step_idx = len,
 //                 ret = ret + (double)reward, park, next observation -> input tile; an episode that ended writes its
 //                 results, once, and its quad idles from then on (its input row keeps its last observation and is computed
 //                 along, unread)
@@ -29,6 +31,16 @@ namespace {
 
 constexpr int kEvalThreads = mlp::kWaves * 64;
 constexpr int kEvalActions = 4, kEvalObs = 8;
+
+// which 16 episodes of which policy this workgroup carries: the grid is P * ceil(E / 16)
+struct EpisodeSlot {
+  int p, e0;
+  __device__ explicit EpisodeSlot(int E) {
+    const int groups = (E + 15) / 16;
+    p = (int)blockIdx.x / groups;
+    e0 = ((int)blockIdx.x - p * groups) * 16;
+  }
+};
 
 // One pass of the solver for the episode of this quad — the ONE call site of env_step_once in an evaluation kernel.
 //   start   (wave-uniform) reset(): the world is built here and stepped with action 0 under the reset draw's force; the reward
@@ -61,13 +73,34 @@ __device__ __forceinline__ bool eval_step_quad(const Lds& lds, int role, bool ac
   return done;
 }
 
-// xin: the forward's input tile [16][xstride] (columns 0..7 are written here, the rest is zeroed once); head: its output tile
-// [16][mlp::kHeadStride], logits in columns 0..3.  forward(): every thread, closed by a workgroup barrier.  `running`: the
-// caller's __shared__ word.
+// The policy of the two feed-forward kernels: the first maximum of the four logits in head [16][mlp::kHeadStride] (columns 0..3),
+// the raw observation as the input, nothing kept at an episode's end.
 template <class Forward>
+struct LogitsPolicy {
+  const float* head;
+  Forward fwd;
+  __device__ __forceinline__ void forward() { fwd(); }
+  __device__ __forceinline__ int pick(int row) const {
+    float z[kEvalActions], lp, H;
+#pragma unroll
+    for (int k = 0; k < kEvalActions; ++k) z[k] = head[row * mlp::kHeadStride + k];
+    return categorical_pick<kEvalActions>(z, nullptr, 0ull, 0ull, 0ull, 1, lp, H);
+  }
+  __device__ __forceinline__ float input(int, float x) const { return x; }
+  __device__ __forceinline__ void episode_end(int64_t, int, int) const {}
+};
+template <class Forward>
+__device__ __forceinline__ LogitsPolicy<Forward> logits_policy(const float* head, Forward fwd) { return LogitsPolicy<Forward>{head, fwd}; }
+
+// THREADS: the workgroup's size (wave 0 steps the envs whatever it is).  xin: the forward's input tile [16][xstride] (columns 0..7
+// are written here, the rest is zeroed once).  `running`: the caller's __shared__ word.  The policy supplies
+//   forward()                  every thread: the forward of the input tile, closed by a workgroup barrier
+//   pick(row) -> action        wave 0: the greedy action of the tile's row `row`, read from the forward's output
+//   input(k, x) -> float       wave 0: what the input tile takes for component k of an observation, x itself or x normalised
+//   episode_end(i, row, role)  wave 0, the four lanes of the quad: episode i = p * E + e has just ended
+template <int THREADS, class Policy>
 __device__ __forceinline__ void run_lunar_episodes(const gymrl_lunar_eval_args& a, uint32_t* lds_words, uint32_t* lds_park, int& running,
-                                                   float* xin, const int xstride, const float* head, const int p, const int e0,
-                                                   Forward&& forward) {
+                                                   float* xin, const int xstride, const int p, const int e0, Policy&& policy) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int role = lane & 3, row = lane >> 2, e = e0 + row;        // wave 0's view: four lanes per env
 #ifdef GYMRL_LUNAR_PROF
@@ -77,7 +110,7 @@ __device__ __forceinline__ void run_lunar_episodes(const gymrl_lunar_eval_args& 
 #endif
   const uint64_t env = (uint64_t)(a.stream_id0 + e);
   bool active = wave == 0 && e < a.E;                               // quad-uniform; rows beyond the episodes never start
-  for (int i = tid; i < mlp::kRows * xstride; i += kEvalThreads) xin[i] = 0.0f;
+  for (int i = tid; i < mlp::kRows * xstride; i += THREADS) xin[i] = 0.0f;
   for (int it = 0; it <= a.cap; ++it) {
     if (wave == 0) {
       const bool any = __ballot(active) != 0ull;
@@ -85,16 +118,11 @@ __device__ __forceinline__ void run_lunar_episodes(const gymrl_lunar_eval_args& 
     }
     __syncthreads();                      // the word, the input tile of this step (at it == 0: its zeroes)
     if (!running) break;                  // one word, the same for every thread of the workgroup
-    if (it > 0) forward();                // (uniform: `it` is the loop counter)
+    if (it > 0) policy.forward();         // (uniform: `it` is the loop counter)
     else __syncthreads();                 // everybody has read the word before wave 0 comes round to write it again
     if (wave == 0) {
       int act = 0;
-      if (it > 0) {
-        float z[kEvalActions], lp, H;
-#pragma unroll
-        for (int k = 0; k < kEvalActions; ++k) z[k] = head[row * mlp::kHeadStride + k];
-        act = categorical_pick<kEvalActions>(z, nullptr, 0ull, 0ull, 0ull, 1, lp, H);
-      }
+      if (it > 0) act = policy.pick(row);
       float o[8];
       int len = 0;
       double ret = 0.0;
@@ -103,8 +131,9 @@ __device__ __forceinline__ void run_lunar_episodes(const gymrl_lunar_eval_args& 
       if (active) {
         if (role < 2) {                   // next policy input: straight into the forward's LDS tile
 #pragma unroll
-          for (int k = 0; k < 4; ++k) xin[row * xstride + 4 * role + k] = o[4 * role + k];
+          for (int k = 0; k < 4; ++k) xin[row * xstride + 4 * role + k] = policy.input(4 * role + k, o[4 * role + k]);
         }
+        if (done) policy.episode_end((int64_t)p * a.E + e, row, role);
         if (done && role == 0) {
           const int64_t i = (int64_t)p * a.E + e;
           a.returns[i] = ret; a.lengths[i] = len; a.terminated[i] = terminated ? 1 : 0;

@@ -13,6 +13,7 @@
 // words: launch-latency bound at the reference batch sizes, HBM-streaming at large B.
 // Loss sums are reduced block-partials -> fixed-order final sum (no float atomics).
 #include "policy_device.hpp"
+#include "running_norm_device.hpp"
 
 using namespace gymrl;
 
@@ -255,9 +256,9 @@ __global__ void running_norm_kernel(const float* __restrict__ x, const uint8_t* 
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   const bool valid = k < D;
   double n = stats[0];
-  float mean = valid ? (float)stats[2 + k] : 0.0f;
+  float mean = valid ? running_norm_mean(stats, k) : 0.0f;
   double S = valid ? stats[2 + D + k] : 0.0;
-  double std = valid ? stats[2 + 2 * D + k] : 0.0;
+  double std = valid ? running_norm_std(stats, D, k) : 0.0;
   for (int i = 0; valid && i < N; ++i) {
     if (live && !live[i]) continue;
     const float xv = x[(size_t)i * D + k];
@@ -271,7 +272,7 @@ __global__ void running_norm_kernel(const float* __restrict__ x, const uint8_t* 
         std = sqrt(S / n);                                                    // :21
       }
     }
-    y[(size_t)i * D + k] = (float)((double)(xv - mean) / (std + 1e-8));      // :33
+    y[(size_t)i * D + k] = running_norm_point(xv, mean, std);                // :33
   }
   __syncthreads();          // every lane has read stats[0] before lane 0 rewrites it
   if (valid) { stats[2 + k] = (double)mean; stats[2 + D + k] = S; stats[2 + 2 * D + k] = std; }

@@ -431,6 +431,7 @@ def mlprnn_params(net):
     for t in [p for p in net.parameters()]:
         if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("mlprnn_params: every parameter must be a contiguous f32 device tensor")
+    P._device = net.fc_head.layers[0].mlp[0].weight.device       # (where lunar_mlprnn_eval allocates its outputs)
     return P
 
 
@@ -856,6 +857,87 @@ def lunar_mhc_eval(policy_desc, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEP
     a, out = _lunar_eval_args(1, n_episodes, seed, stream_id0, cap, 0, want_terminal_obs, dev)
     check(lib().gymrl_lunar_mhc_eval(C.byref(a), C.byref(policy_desc), _stream()), "gymrl_lunar_mhc_eval")
     return out
+
+
+LUNAR_NORM_STATS = 2 + 3 * 8       # RunningMeanStd.stats of the 8 observations: n, -, mean[8], S[8], std[8]
+
+
+def _mlprnn_fields(P):
+    """(struct, index or None, field name) of every pointer of a gymrl_mlprnn_params."""
+    for name, ctype in P._fields_:
+        if issubclass(ctype, C.Array):
+            for i in range(ctype._length_):
+                yield getattr(P, name), i, name
+        else:
+            yield P, None, name
+
+
+class MlprnnPolicyStack:
+    """P policies of one PSCN -> MLPRNN -> heads network for lunar_mlprnn_eval, in ONE buffer f32[P, stride]: row p is policy p's
+    flat parameter vector.  params f32[P, n]: flat parameter vectors in the layout of `flat`, the buffer `net`'s own tensors are
+    views of (the trainers' flat_params order).  stride (floats, a multiple of 4): None = n rounded up.  norm_stats f64[P, 26]
+    (RunningMeanStd.stats per policy), f64[26] (one set shared by all) or None.  `desc` points at row 0."""
+
+    def __init__(self, net, flat, params, norm_stats=None, stride=None):
+        if params.dim() != 2 or params.shape[1] != flat.numel() or params.dtype != torch.float32 or not params.is_cuda:
+            raise ValueError("MlprnnPolicyStack: params is a stack f32[P, n] of flat buffers in the layout of `flat`, on the device")
+        n = flat.numel()
+        tight = (n + 3) // 4 * 4
+        self.stride = tight if stride is None else int(stride)
+        if self.stride < tight or self.stride % 4:
+            raise ValueError(f"MlprnnPolicyStack: the stride is a multiple of 4 floats and at least {tight}")
+        self.P = params.shape[0]
+        self.buffer = torch.zeros(self.P, self.stride, dtype=torch.float32, device=params.device)
+        self.buffer[:, :n] = params
+        own = mlprnn_params(net)
+        d = MlprnnParams()
+        lo, base = flat.data_ptr(), self.buffer.data_ptr()
+        for (src, i, name), (dst, _, _) in zip(_mlprnn_fields(own), _mlprnn_fields(d)):
+            addr = getattr(src, name) if i is None else src[i]
+            if addr is None or not lo <= addr < lo + 4 * n:
+                raise ValueError("MlprnnPolicyStack: the network's tensors are not views of `flat`")
+            if i is None:
+                setattr(dst, name, base + (addr - lo))
+            else:
+                dst[i] = base + (addr - lo)
+        d._keepalive, d._device = self.buffer, params.device     # the table holds raw pointers
+        self.desc = d
+        self.norm_stats = None
+        if norm_stats is not None:
+            s = torch.as_tensor(norm_stats, dtype=torch.float64).to(params.device).contiguous()
+            if tuple(s.shape) not in ((LUNAR_NORM_STATS,), (self.P, LUNAR_NORM_STATS)):
+                raise ValueError(f"MlprnnPolicyStack: norm_stats is f64[{LUNAR_NORM_STATS}] or f64[P, {LUNAR_NORM_STATS}]")
+            self.norm_stats = s
+
+
+def lunar_mlprnn_eval(policy, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS, norm_stats=None, want_terminal_obs=True,
+                      want_h_final=False):
+    """lunar_policy_eval for the recurrent PPG / PPO-RNN network (include/gymrl.h gymrl_lunar_mlprnn_eval): every episode from the
+    hidden state 0, the action the first maximum of the probabilities (mlprnn_act's deterministic branch) ->
+    (returns f64, lengths i32, terminated u8, terminal_obs f32[..., 8] | None[, h_final f32[..., 64]]), each [P, n_episodes].
+    policy: mlprnn_params(net) (P = 1) or a MlprnnPolicyStack.  norm_stats: RunningMeanStd.stats f64[26] the network's input is
+    normalised with (gymrl_running_norm_masked without update; one set for every policy), f64[P, >= 26] one per policy, or None
+    — then a stack's own, and without any the network reads raw observations."""
+    if isinstance(policy, MlprnnPolicyStack):
+        P, stride, desc, dev = policy.P, policy.stride, policy.desc, policy.buffer.device
+        if norm_stats is None:
+            norm_stats = policy.norm_stats
+    else:
+        P, stride, desc, dev = 1, 0, policy, getattr(policy, "_device", None)
+    norm_stride = 0
+    if norm_stats is not None:
+        _ptr(norm_stats, torch.float64)
+        if norm_stats.dim() == 2 and norm_stats.shape[0] == P and norm_stats.shape[1] >= LUNAR_NORM_STATS:
+            norm_stride = norm_stats.shape[1] if P > 1 else 0
+        elif norm_stats.dim() != 1 or norm_stats.numel() < LUNAR_NORM_STATS:
+            raise ValueError(f"norm_stats: expected f64[{LUNAR_NORM_STATS}] or f64[{P}, >= {LUNAR_NORM_STATS}], got {tuple(norm_stats.shape)}")
+    if dev is None:
+        dev = norm_stats.device if norm_stats is not None else torch.device("cuda", torch.cuda.current_device())
+    a, out = _lunar_eval_args(P, n_episodes, seed, stream_id0, cap, stride, want_terminal_obs, dev)
+    h_final = torch.empty(P, n_episodes, 64, dtype=torch.float32, device=dev) if want_h_final else None
+    check(lib().gymrl_lunar_mlprnn_eval(C.byref(a), C.byref(desc), _ptr(norm_stats, torch.float64, True), norm_stride,
+                                        _ptr(h_final, torch.float32, True), _stream()), "gymrl_lunar_mlprnn_eval")
+    return out + (h_final,) if want_h_final else out
 
 
 # ============================================================== off-policy ===

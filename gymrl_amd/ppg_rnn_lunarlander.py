@@ -59,6 +59,7 @@ class Config:
         # --- vectorised-engine additions ---
         self.num_envs = 1                  # envs stepped together; one round = one episode of each
         self.episodes_per_minibatch = 1    # G episodes per optimiser step (loss = mean over episodes); 1 = the reference
+        self.fused_eval = False            # LunarLander: eval() as ONE launch (gymrl_lunar_mlprnn_eval) on the loop's own streams
 
 
 def initialize_weights(layer):
@@ -552,12 +553,59 @@ class PPGTrainer:
         self.save_model()
         self.env.close()
 
+    EVAL_SEED_OFFSET, EVAL_ENV_ID0 = 1_000_003, 1 << 40      # eval()'s env streams: seed base_seed + 1_000_003, env ids from 1 << 40
+
+    def _eval_fusable(self):
+        """Whether gymrl_lunar_mlprnn_eval plays this trainer's env: the built-in LunarLander-v3 (8 observations, 4 actions)."""
+        return ops.ENV_KINDS.get(self._env_name()) == ops.LUNARLANDER and self.state_dim == 8 and self.action_dim == 4
+
+    @torch.no_grad()
+    def evaluate(self, num_episodes, params=None, norm_stats=None, stream_offset=0):
+        """-> (returns f64, lengths i32, terminated u8), numpy arrays [P, num_episodes]: whole greedy episodes on eval()'s streams
+        (episode e: seed base_seed + 1_000_003, env id (1 << 40) + stream_offset + e), every policy from the same starts and from
+        the hidden state 0, in ONE launch (csrc/eval_lunar_rnn.hip) whatever Config.fused_eval says.  params = None: the trainer's
+        own policy (P = 1); params = f32[P, n]: a stack of flat parameter vectors in the layout of flat_params.  norm_stats = None:
+        the trainer's state_norm statistics as they are now, for every policy; f64[26] or f64[P, 26]: RunningMeanStd.stats to
+        normalise the observations with instead.  Actions, lengths and terminal observations are eval()'s loop's, bit for bit.
+        Moves neither round_count, net.rnn_h, state_norm, reward_scaler, self.env, the batch nor the optimiser."""
+        if not self._eval_fusable():
+            raise RuntimeError("PPGTrainer.evaluate: gymrl_lunar_mlprnn_eval takes LunarLander-v3 (include/gymrl.h)")
+        stats = self.state_norm.running_ms.stats if norm_stats is None else \
+            torch.as_tensor(norm_stats, dtype=torch.float64).to(self.device).contiguous()
+        policy = self._act_params
+        if params is not None:
+            params = torch.as_tensor(params, dtype=torch.float32).to(self.device)
+            policy = ops.MlprnnPolicyStack(self.net, self.flat_params, params.view(1, -1) if params.dim() == 1 else params)
+        out = ops.lunar_mlprnn_eval(policy, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET,
+                                    self.EVAL_ENV_ID0 + int(stream_offset), norm_stats=stats, want_terminal_obs=False)
+        return tuple(t.cpu().numpy() for t in out[:3])
+
+    def _eval_fused(self, n):
+        """eval(n)'s returns as one launch, or None: fused_eval is off, or the env is not the built-in LunarLander-v3."""
+        if not getattr(self.cfg, "fused_eval", False) or n < 1 or not self._eval_fusable():
+            return None
+        returns = ops.lunar_mlprnn_eval(self._act_params, n, self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0,
+                                        norm_stats=self.state_norm.running_ms.stats, want_terminal_obs=False)[0]
+        return returns[0].to(torch.float32).tolist()           # the float32 cast of the float64 return
+
     @torch.no_grad()
     def eval(self, num_episodes=10):
-        """:501-524 as `num_episodes` parallel greedy episodes (state_norm without update), each with its own GRU state."""
+        """:501-524 as `num_episodes` parallel greedy episodes (state_norm without update), each with its own GRU state.  With
+        Config.fused_eval the same episodes are ONE launch (gymrl_lunar_mlprnn_eval): the same actions, lengths and terminal
+        observations bit for bit; the loop below sums an episode's rewards in float32, the launch in float64, so a printed
+        return may differ from the loop's in the last place."""
         print(f"\nEvaluating for {num_episodes} episodes...")
-        n, dev = int(num_episodes), self.device
-        env = VecEnv(self._env_name(), n, device=dev, seed=self.base_seed + 1_000_003, env_id0=1 << 40)
+        rewards = self._eval_fused(int(num_episodes))
+        if rewards is None:
+            rewards = self._eval_loop(int(num_episodes))
+        for ep, r in enumerate(rewards):
+            print(f"  Episode {ep + 1}: Reward = {r:.0f}")
+        print(f"Evaluation: Mean = {np.mean(rewards):.1f} +/- {np.std(rewards):.1f}")
+        return rewards
+
+    def _eval_loop(self, n):
+        dev = self.device
+        env = VecEnv(self._env_name(), n, device=dev, seed=self.base_seed + self.EVAL_SEED_OFFSET, env_id0=self.EVAL_ENV_ID0)
         raw, term = env.reset(), torch.empty(n, self.state_dim, device=dev)
         rew = torch.empty(n, device=dev)
         terminated, truncated = (torch.zeros(n, dtype=torch.uint8, device=dev) for _ in range(2))
@@ -578,11 +626,7 @@ class PPGTrainer:
             if (t + 1) % 16 == 0 and not bool(live.any()):
                 break
         env.close()
-        rewards = ret.cpu().tolist()
-        for ep, r in enumerate(rewards):
-            print(f"  Episode {ep + 1}: Reward = {r:.0f}")
-        print(f"Evaluation: Mean = {np.mean(rewards):.1f} +/- {np.std(rewards):.1f}")
-        return rewards
+        return ret.cpu().tolist()
 
     def test(self):
         """:526-547 — load + eval(5); there is no renderer, so the human-render episode is not played."""

@@ -32,6 +32,7 @@ class Config:
         # --- vectorised-engine additions ---
         self.num_envs = 1
         self.episodes_per_minibatch = 1
+        self.fused_eval = False            # eval() as ONE launch (gymrl_lunar_mlprnn_eval), as in gymrl_amd.ppg_rnn_lunarlander
 
 
 class ActorCritic(_ppg.ActorCriticPPG):

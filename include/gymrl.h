@@ -667,6 +667,23 @@ typedef struct {
 size_t gymrl_lunar_eval_args_bytes(void);  /* sizeof(gymrl_lunar_eval_args) */
 int gymrl_lunar_policy_eval(const gymrl_lunar_eval_args* args, const gymrl_mlp_desc* policy, void* stream);
 int gymrl_lunar_mhc_eval(const gymrl_lunar_eval_args* args, const struct gymrl_mhc_policy_s* policy, void* stream);
+/*
+ * gymrl_lunar_mlprnn_eval: the same episodes under the recurrent PPG / PPO-RNN network (gymrl_mlprnn_params, D = 8, A = 4) —
+ * the eval() loop of ppg_rnn_lunarlander.py:501-524 (csrc/eval_lunar_rnn.hip).  Every episode starts from the hidden state 0,
+ * which stays on chip for the whole episode; the action is gymrl_mlprnn_act's deterministic branch, the FIRST maximum of the
+ * probabilities (not of the logits).  Policy p reads every pointer of `policy` p * policy_stride floats behind policy 0's.
+ *   norm_stats f64 [2 + 3 * 8] per policy in RunningMeanStd.stats layout (may be NULL: the network reads raw observations):
+ *     the network reads gymrl_running_norm_masked(update = 0) of every observation; policy p's stats start
+ *     p * norm_stride doubles behind policy 0's (0: one set shared by all, otherwise >= 26).  terminal_obs stays raw.
+ *   h_final f32 [P * E][64] (may be NULL): the hidden state after the last forward of each episode.
+ * Bit-identical in actions, lengths, flags, terminal observations and h_final to the step-by-step sequence gymrl_mlprnn_act
+ * (deterministic, live) -> gymrl_env_step -> gymrl_running_norm_masked(update = 0); returns are the float64 sum of the float32
+ * rewards in step order.  -EINVAL before any launch: everything above that concerns `args`, a NULL policy or member, a weight
+ * gymrl_mlprnn_act reads 16 bytes at a time that is not 16-byte aligned, a negative norm_stride or one in 1..25, norm_stats not
+ * 8-byte or h_final not 16-byte aligned.
+ */
+int gymrl_lunar_mlprnn_eval(const gymrl_lunar_eval_args* args, const gymrl_mlprnn_params* policy,
+                            const double* norm_stats, int64_t norm_stride, float* h_final, void* stream);
 
 /* ================================================ low-latency Linear layers == */
 /*
