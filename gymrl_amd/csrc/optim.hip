@@ -89,7 +89,7 @@ __device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v,
                                          float scale, float step_size) {
   float gg = g * a.grad_scale;
   gg = gg * scale;
-  if (a.clamp_abs > 0.0f) gg = fminf(fmaxf(gg, -a.clamp_abs), a.clamp_abs);
+  if (a.clamp_abs > 0.0f && gg == gg) gg = fminf(fmaxf(gg, -a.clamp_abs), a.clamp_abs);   // clamp_ keeps NaN; fmaxf would return -clamp_abs
   m = m + (gg - m) * a.omb1;                // exp_avg.lerp_(grad, 1 - beta1)
   v = v * a.beta2 + a.omb2 * gg * gg;        // mul_(beta2).addcmul_(g, g, 1 - beta2)
   const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, flo
   if (a.max_grad_norm > 0.0f && sqnorm) {
     const float total = (float)sqrt(sqnorm[0]);
     const float coef = a.max_grad_norm / (total + 1e-6f);
-    scale = coef < 1.0f ? coef : 1.0f;
+    scale = !(coef >= 1.0f) ? coef : 1.0f;   // torch.clamp(coef, max=1): a NaN norm gives a NaN coefficient, and every parameter goes NaN with it
   }
   const float step_size = lr_dev ? lr_dev[0] * a.inv_bc1 : a.step_size_host;
   const int64_t n4 = n >> 2;

@@ -465,7 +465,10 @@ int gymrl_gather_rows(const float* src, const int32_t* idx, int B, int row_float
  *                    threads 0..2 of workgroup 0; waves fold by halves (32, 16, .. 1), the 4 wave sums add in
  *                    order; the final pass gives thread t partials t, t+256, ... and folds 256 sums by halves.
  *   gymrl_adam_step: scale = max_grad_norm>0 ? min(1, max_norm/(sqrt(sqnorm)+1e-6)) : 1
- *                    g' = clamp_abs>0 ? clamp(g*grad_scale, +-clamp_abs) : g*grad_scale*scale
+ *                    g' = g*grad_scale*scale, then clamped to +-clamp_abs when clamp_abs>0
+ *                    A gradient that is not finite does what torch does: a NaN norm gives scale = NaN (every
+ *                    parameter goes NaN), an infinite one scale = 0 (NaN at the infinite element only), and the
+ *                    clamp keeps a NaN element NaN.
  *                    m,v,p updated as torch.optim.Adam (no amsgrad, no decay);
  *                    g is zeroed (zero_grad fused) when zero_grad != 0.
  *   lr_dev f32[1] or NULL (then lr_host is used): device-resident lr lets LR

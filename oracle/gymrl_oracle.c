@@ -696,7 +696,7 @@ void orc_adam_step(float* p, float* g, float* m, float* v, int64_t n, double lr,
   if (max_grad_norm > 0.0f && sqnorm) {
     float total = (float)sqrt(sqnorm[0]);
     float coef = max_grad_norm / (total + 1e-6f);
-    scale = coef < 1.0f ? coef : 1.0f;
+    scale = !(coef >= 1.0f) ? coef : 1.0f;          /* torch.clamp(coef, max=1) keeps a NaN coefficient */
   }
   double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
@@ -704,7 +704,7 @@ void orc_adam_step(float* p, float* g, float* m, float* v, int64_t n, double lr,
   for (int64_t i = 0; i < n; ++i) {
     float gg = g[i] * grad_scale;
     gg = gg * scale;
-    if (clamp_abs > 0.0f) gg = fminf(fmaxf(gg, -clamp_abs), clamp_abs);   /* dqn_cartpole.py:163-165 */
+    if (clamp_abs > 0.0f && gg == gg) gg = fminf(fmaxf(gg, -clamp_abs), clamp_abs);   /* dqn_cartpole.py:163-165 */
     m[i] = m[i] + (gg - m[i]) * omb1;
     v[i] = v[i] * b2 + omb2 * gg * gg;
     float denom = sqrtf(v[i]) / bc2_sqrt + e;
