@@ -336,6 +336,15 @@ class NdqnUpdateArgs(C.Structure):
                 ("loss_sum", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class MountainCarNetEvalArgs(C.Structure):
+    _c_name_ = "gymrl_mountaincar_net_eval_args"
+    _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("net", C.c_int), ("n_hidden", C.c_int), ("H", C.c_int),
+                ("w", C.c_void_p * 2), ("b", C.c_void_p * 2), ("head_w", C.c_void_p), ("head_b", C.c_void_p),
+                ("value_w", C.c_void_p), ("value_b", C.c_void_p), ("policy_stride", C.c_int64), ("images", C.c_void_p),
+                ("seed", C.c_uint64), ("stream_id0", C.c_int64), ("start", C.c_void_p), ("returns", C.c_void_p),
+                ("lengths", C.c_void_p), ("terminated", C.c_void_p), ("final_obs", C.c_void_p)]
+
+
 class ClassicEvalArgs(C.Structure):
     _c_name_ = "gymrl_classic_eval_args"
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("env_kind", C.c_int), ("head", C.c_int), ("D", C.c_int),
@@ -568,6 +577,8 @@ SIGNATURES = {
     "gymrl_ndqn_act_step": (_i, [_P(NdqnActArgs), _vp]),
     "gymrl_ndqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_ndqn_update": (_i, [_P(NdqnUpdateArgs), _vp]),
+    "gymrl_mountaincar_net_eval_args_bytes": (_sz, []),
+    "gymrl_mountaincar_net_eval": (_i, [_P(MountainCarNetEvalArgs), _vp]),
     "gymrl_classic_eval_args_bytes": (_sz, []),
     "gymrl_classic_policy_eval": (_i, [_P(ClassicEvalArgs), _vp]),
     "gymrl_classic_duel_eval_args_bytes": (_sz, []),

@@ -17,54 +17,17 @@
 // iteration.  No __syncthreads() sits behind a per-lane or per-wave condition, nothing waits for another workgroup, there are no
 // atomics, and inside the loop global memory is only READ (the weights, from L2 after the first step).  The loop runs at most
 // `cap` <= TimeLimit times.
-#include "eval_episode_device.hpp"
+#include "eval_kernels_device.hpp"
 
 namespace {
 
 using namespace gymrl;
 using namespace gymrl::slab;
 
-constexpr int kHeadArgmax = 0, kHeadTanh = 1;
-
 // KIND: GYMRL_ENV_CARTPOLE (head 0, D = 4, A = 2) or GYMRL_ENV_PENDULUM (head 1, D = 3, A = 1); HC: the hidden width the instance is built for (0: a.H)
-// The episode loop itself is eval_episode_device.hpp's run_episodes; what is stated here is one step's policy forward and its action.
+// One step's policy forward and its action: eval_kernels_device.hpp's classic_eval_kernel, on this entry point's argument block.
 template <int HC, int KIND>
-__global__ __launch_bounds__(kThreads) void classic_eval_kernel(const gymrl_classic_eval_args a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  __shared__ int running;                 // the loop's exit word: written by wave 0, read by everybody behind the barrier
-  const Lds L;
-  constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE;
-  constexpr int D = cart ? 4 : 3, A = cart ? 2 : 1;
-  const int H = HC ? HC : a.H, ld = lin::slab_ld(H);
-  const int X0 = L.big, X1 = X0 + 16 * ld;
-  const int groups = (a.E + 15) / 16;
-  const int p = (int)blockIdx.x / groups, e0 = ((int)blockIdx.x - p * groups) * 16, nrows = min(16, a.E - e0);
-  const size_t shift = (size_t)p * (size_t)a.policy_stride;
-  const float *w0 = a.w[0] + shift, *w1 = a.w[1] + shift, *w2 = a.w[2] + shift;
-  const float *b0 = a.b[0] + shift, *b1 = a.b[1] + shift, *b2 = a.b[2] + shift;
-  const float* img = (a.images && (H & 15) == 0) ? a.images : nullptr;
-  const int R = GYMRL_ACT_RELU, kD = kMaxD, kA = kMaxA;
-  run_episodes<KIND>(
-      a, lds, running, L, p, e0, nrows,
-      [=]() {
-        const float *v0 = w0, *v1 = w1, *v2 = w2, *c0 = b0, *c1 = b1, *c2 = b2, *im = img;
-        // (the pointers pass through an empty asm: the stages' per-lane operand addresses are formed again in every iteration — hoisted
-        // out of the loop they were 47 spilled registers, reloaded from scratch memory step by step)
-        asm volatile("" : "+s"(v0), "+s"(v1), "+s"(v2), "+s"(c0), "+s"(c1), "+s"(c2), "+s"(im));
-        fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, v0, c0, X0, ld, nullptr, 0, R)}, 0, nrows);
-        fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, v1, c1, X1, ld, nullptr, 0, R, 0.0f, 0.0f, im)}, 0, nrows);
-        fwd_one(lds, {fwd_item(X1, ld, -1, 0, H, H, A, v2, c2, L.Mean, kA, nullptr, 0, cart ? GYMRL_ACT_NONE : GYMRL_ACT_TANH)}, 0, nrows);
-      },
-      [=](int t) {
-        if constexpr (cart) {
-          // the greedy branch of epsilon_greedy_pick (u0 = 1 is never below epsilon = 0): the first maximum, no draw
-          const float never[2] = {1.0f, 0.0f};
-          return epsilon_greedy_pick(lds + L.Mean + t * kMaxA, A, never, 0ull, 0ull, 0ull, 0.0f);
-        } else {
-          return lds[L.Mean + t * kMaxA] * a.bound;
-        }
-      });
-}
+constexpr auto kernel = classic_eval_kernel<HC, KIND, gymrl_classic_eval_args>;
 
 }  // namespace
 
@@ -84,16 +47,16 @@ int gymrl_classic_policy_eval(const gymrl_classic_eval_args* args, void* stream)
   for (int k = 0; k < 3; ++k)
     if (!aligned(a.w[k], 16) || !aligned(a.b[k], 4)) return -22;
   static bool lds_set = false;
-  if (const int rc = set_max_lds_once(lds_set, {(const void*)classic_eval_kernel<0, GYMRL_ENV_CARTPOLE>, (const void*)classic_eval_kernel<256, GYMRL_ENV_CARTPOLE>,
-                                                (const void*)classic_eval_kernel<0, GYMRL_ENV_PENDULUM>, (const void*)classic_eval_kernel<256, GYMRL_ENV_PENDULUM>},
+  if (const int rc = set_max_lds_once(lds_set, {(const void*)kernel<0, GYMRL_ENV_CARTPOLE>, (const void*)kernel<256, GYMRL_ENV_CARTPOLE>,
+                                                (const void*)kernel<0, GYMRL_ENV_PENDULUM>, (const void*)kernel<256, GYMRL_ENV_PENDULUM>},
                                       (int)lds_bytes(256, 2)))
     return rc;
   const dim3 grid((unsigned)(a.P * ((a.E + 15) / 16))), block(kThreads);
   const size_t smem = lds_bytes(a.H, 2);
   hipStream_t st = (hipStream_t)stream;
   const bool wide = a.H == 256;           // the instances built for the reference's hidden width
-  if (cart) hipLaunchKernelGGL((wide ? classic_eval_kernel<256, GYMRL_ENV_CARTPOLE> : classic_eval_kernel<0, GYMRL_ENV_CARTPOLE>), grid, block, smem, st, a);
-  else hipLaunchKernelGGL((wide ? classic_eval_kernel<256, GYMRL_ENV_PENDULUM> : classic_eval_kernel<0, GYMRL_ENV_PENDULUM>), grid, block, smem, st, a);
+  if (cart) hipLaunchKernelGGL((wide ? kernel<256, GYMRL_ENV_CARTPOLE> : kernel<0, GYMRL_ENV_CARTPOLE>), grid, block, smem, st, a);
+  else hipLaunchKernelGGL((wide ? kernel<256, GYMRL_ENV_PENDULUM> : kernel<0, GYMRL_ENV_PENDULUM>), grid, block, smem, st, a);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

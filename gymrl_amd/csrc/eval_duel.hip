@@ -16,53 +16,17 @@
 // — and its action: duel_combine on the lane's row, then the first maximum (torch.argmax's rule).  Rainbow's layer path computes
 // a stacked [A + 1]-column head and combines with sum / A; a tile's output column does not depend on its neighbours and at A = 2,
 // the only width taken here, sum / 2 and sum * 0.5 are the same float, so its two weight_mu tensors pass as separate heads.
-#include "duel_device.hpp"
-#include "eval_episode_device.hpp"
+#include "eval_kernels_device.hpp"
 
 namespace {
 
 using namespace gymrl;
 using namespace gymrl::slab;
 
-// NH: hidden layers of the trunk (1 | 2); HC: the hidden width the instance is built for (0: a.H)
+// NH: hidden layers of the trunk (1 | 2); HC: the hidden width the instance is built for (0: a.H).  One step's policy forward and
+// its action: eval_kernels_device.hpp's duel_eval_kernel on this entry point's argument block, CartPole-v1, duel_combine.
 template <int HC, int NH>
-__global__ __launch_bounds__(kThreads) void duel_eval_kernel(const gymrl_classic_duel_eval_args a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  __shared__ int running;                 // the loop's exit word: written by wave 0, read by everybody behind the barrier
-  const Lds L;
-  constexpr int D = 4, A = 2;
-  const int H = HC ? HC : a.H, ld = lin::slab_ld(H);
-  const int X0 = L.big, X1 = X0 + 16 * ld, Xh = NH == 2 ? X1 : X0;       // Xh: the slab the heads read
-  const int groups = (a.E + 15) / 16;
-  const int p = (int)blockIdx.x / groups, e0 = ((int)blockIdx.x - p * groups) * 16, nrows = min(16, a.E - e0);
-  const size_t shift = (size_t)p * (size_t)a.policy_stride;
-  const float *w0 = a.w[0] + shift, *b0 = a.b[0] + shift;
-  const float *w1 = NH == 2 ? a.w[1] + shift : nullptr, *b1 = NH == 2 ? a.b[1] + shift : nullptr;
-  const float *wv = a.value_w + shift, *bv = a.value_b + shift, *wa = a.adv_w + shift, *ba = a.adv_b + shift;
-  const float* img = (NH == 2 && a.images && (H & 15) == 0) ? a.images : nullptr;
-  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
-  run_episodes<GYMRL_ENV_CARTPOLE>(
-      a, lds, running, L, p, e0, nrows,
-      [=]() {
-        const float *v0 = w0, *c0 = b0, *v1 = w1, *c1 = b1, *vv = wv, *cv = bv, *va = wa, *ca = ba, *im = img;
-        // (eval_classic.hip's laundering: the stages' per-lane operand addresses are formed again in every iteration, not spilled)
-        asm volatile("" : "+s"(v0), "+s"(c0), "+s"(v1), "+s"(c1), "+s"(vv), "+s"(cv), "+s"(va), "+s"(ca), "+s"(im));
-        fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, v0, c0, X0, ld, nullptr, 0, R)}, 0, nrows);
-        if constexpr (NH == 2) fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, v1, c1, X1, ld, nullptr, 0, R, 0.0f, 0.0f, im)}, 0, nrows);
-        const FwdItem st[2] = {fwd_item(Xh, ld, -1, 0, H, H, 1, vv, cv, L.Cq1, 4, nullptr, 0, NA),
-                               fwd_item(Xh, ld, -1, 0, H, H, A, va, ca, L.Cq0, 4, nullptr, 0, NA)};
-        fwd_stage<2>(lds, st, 0, nrows);
-        __syncthreads();
-      },
-      [=](int t) {
-        float q[kMaxA];
-        duel_combine(lds + L.Cq0 + t * 4, lds[L.Cq1 + t * 4], A, q);
-        int act = 0;
-        float best = q[0];
-        for (int k = 1; k < A; ++k) if (q[k] > best) { best = q[k]; act = k; }
-        return act;
-      });
-}
+constexpr auto kernel = duel_eval_kernel<HC, NH, GYMRL_ENV_CARTPOLE, kCombineMean, gymrl_classic_duel_eval_args>;
 
 }  // namespace
 
@@ -86,16 +50,16 @@ int gymrl_classic_duel_eval(const gymrl_classic_duel_eval_args* args, void* stre
   for (const float* b : {a.b[0], a.b[1], a.value_b, a.adv_b})
     if (!aligned(b, 4)) return -22;
   static bool lds_set = false;
-  if (const int rc = set_max_lds_once(lds_set, {(const void*)duel_eval_kernel<0, 1>, (const void*)duel_eval_kernel<256, 1>,
-                                                (const void*)duel_eval_kernel<0, 2>, (const void*)duel_eval_kernel<256, 2>},
+  if (const int rc = set_max_lds_once(lds_set, {(const void*)kernel<0, 1>, (const void*)kernel<256, 1>,
+                                                (const void*)kernel<0, 2>, (const void*)kernel<256, 2>},
                                       (int)lds_bytes(256, 2)))
     return rc;
   const dim3 grid((unsigned)(a.P * ((a.E + 15) / 16))), block(kThreads);
   const size_t smem = lds_bytes(a.H, a.n_hidden);
   hipStream_t st = (hipStream_t)stream;
   const bool wide = a.H == 256;           // the instances built for the reference's hidden width
-  if (two) hipLaunchKernelGGL((wide ? duel_eval_kernel<256, 2> : duel_eval_kernel<0, 2>), grid, block, smem, st, a);
-  else hipLaunchKernelGGL((wide ? duel_eval_kernel<256, 1> : duel_eval_kernel<0, 1>), grid, block, smem, st, a);
+  if (two) hipLaunchKernelGGL((wide ? kernel<256, 2> : kernel<0, 2>), grid, block, smem, st, a);
+  else hipLaunchKernelGGL((wide ? kernel<256, 1> : kernel<0, 1>), grid, block, smem, st, a);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

@@ -1,6 +1,6 @@
 // eval_episode_device.hpp — the episode loop of the one-launch policy evaluation, stated once: eval_classic.hip (a three-layer MLP
-// on CartPole-v1 / Pendulum-v1) and eval_duel.hip (a dueling network on CartPole-v1) instantiate it with their own "policy forward"
-// and "action" steps.
+// on CartPole-v1 / Pendulum-v1), eval_duel.hip (a dueling network on CartPole-v1) and eval_mountaincar.hip (either network on
+// MountainCar-v0) instantiate it, through eval_kernels_device.hpp, with their own "policy forward" and "action" steps.
 //
 // ONE workgroup of slab::kThreads threads carries 16 episodes of one policy from their reset to their end.  Lane t < 16 of wave 0
 // owns episode e0 + t: its float64 env state, its float64 return, its length and its flags live in registers.  Per iteration
@@ -9,7 +9,8 @@
 //                running", beside them
 //   everybody    meets at the barrier that publishes both and leaves on that word — the same for every thread of the workgroup
 //   forward()    every thread: the policy's stages over the slab, each closed by a workgroup barrier, the last one included
-//   action(t)    the running lanes: the greedy action of row t, then cartpole_advance / pendulum_advance in registers
+//   action(t)    the running lanes: the greedy action of row t, then cartpole_advance / pendulum_advance / mountaincar_advance in
+//                registers
 //
 // A finished lane idles with its registers frozen (its slab row keeps its last observation and is computed along, unread).  No
 // __syncthreads() sits behind a per-lane or per-wave condition, nothing waits for another workgroup, there are no atomics, inside
@@ -33,14 +34,28 @@ struct EpisodeSlot {
   }
 };
 
-// KIND: GYMRL_ENV_CARTPOLE (action(t) -> int) or GYMRL_ENV_PENDULUM (action(t) -> the torque, float).  Args: an argument block
-// with E, cap, seed, stream_id0, start, returns, lengths, terminated, final_obs (include/gymrl.h).  `running` is the caller's
-// __shared__ word.
+// The float32 observation of the float64 state s: the cast (CartPole-v1, MountainCar-v0) or (cos, sin, thdot) (Pendulum-v1)
+template <int KIND>
+__device__ __forceinline__ void episode_obs(const double (&s)[4], float* o) {
+  if constexpr (KIND == GYMRL_ENV_CARTPOLE) {
+    o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
+  } else if constexpr (KIND == GYMRL_ENV_MOUNTAINCAR) {
+    o[0] = (float)s[0]; o[1] = (float)s[1];
+  } else {
+    float ob[3];
+    pendulum_obs(s[0], s[1], ob);
+    o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
+  }
+}
+
+// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR (action(t) -> int) or GYMRL_ENV_PENDULUM (action(t) -> the torque, float).
+// Args: an argument block with E, cap, seed, stream_id0, start, returns, lengths, terminated, final_obs (include/gymrl.h).
+// `running` is the caller's __shared__ word.
 template <int KIND, class Args, class Forward, class Action>
 __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& running, const Lds& L, const int p, const int e0, const int nrows,
                                              Forward&& forward, Action&& action) {
-  constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE;
-  constexpr int D = cart ? 4 : 3, NS = cart ? 4 : 2;
+  constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE, car = KIND == GYMRL_ENV_MOUNTAINCAR;
+  constexpr int D = cart ? 4 : car ? 2 : 3, NS = cart ? 4 : 2;          // MountainCar-v0: (pos, vel)
   const int t = threadIdx.x;
   // ---- one lane per episode: the env state, the return and the length live in registers ----
   double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -55,22 +70,15 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
       for (int k = 0; k < NS; ++k) s[k] = a.start[((int64_t)p * a.E + e0 + t) * NS + k];
     } else if constexpr (cart) {
       cartpole_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
+    } else if constexpr (car) {
+      mountaincar_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
     } else {
       pendulum_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
     }
   }
   for (int it = 0; it < a.cap; ++it) {
     if (t < 64) {
-      if (active) {
-        float* o = lds + L.S + t * kMaxD;
-        if constexpr (cart) {
-          o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
-        } else {
-          float ob[3];
-          pendulum_obs(s[0], s[1], ob);
-          o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
-        }
-      }
+      if (active) episode_obs<KIND>(s, lds + L.S + t * kMaxD);
       const bool any = __ballot(active) != 0ull;
       if (t == 0) running = any ? 1 : 0;
     }
@@ -81,6 +89,9 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
       if constexpr (cart) {
         terminated = cartpole_advance(s[0], s[1], s[2], s[3], action(t));
         ret = ret + 1.0;
+      } else if constexpr (car) {
+        terminated = mountaincar_advance(s[0], s[1], action(t));
+        ret = ret + (-1.0);                 // every step, the terminating one included
       } else {
         ret = ret + (-pendulum_advance(s[0], s[1], action(t)));
       }
@@ -92,22 +103,13 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
   if (t < nrows) {
     const int64_t i = (int64_t)p * a.E + e0 + t;
     a.returns[i] = (float)ret; a.lengths[i] = len; a.terminated[i] = terminated;
-    if (a.final_obs) {
-      float* o = a.final_obs + i * D;
-      if constexpr (cart) {
-        o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
-      } else {
-        float ob[3];
-        pendulum_obs(s[0], s[1], ob);
-        o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
-      }
-    }
+    if (a.final_obs) episode_obs<KIND>(s, a.final_obs + i * D);
   }
 }
 
 inline bool aligned(const void* p, size_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) == 0; }
 
-// What both entry points refuse alike, before the first HIP call: the sizes, the stride, the streams, the outputs and their alignment
+// What the entry points refuse alike, before the first HIP call: the sizes, the stride, the streams, the outputs and their alignment
 template <class Args>
 inline bool episode_args_ok(const Args& a, int max_cap) {
   if (a.P < 1 || a.E < 1 || a.cap < 1 || a.cap > max_cap || a.stream_id0 < 0) return false;

@@ -8,6 +8,7 @@
 //                        may run; the stacked noisy head's is split into mu / sigma here)
 //
 // Bit for bit the layer-by-layer path's results (tests/test_fused_step_gpu.py).
+#include "duel_device.hpp"
 #include "slab_step_device.hpp"
 
 namespace {
@@ -39,23 +40,7 @@ struct RbWs {
   }
 };
 
-// The dueling combination of one row (lin.hip lin_fwd_kernel's GYMRL_ACT_DUELING epilogue): z[0 .. A-1] = advantage stream,
-// z[A] = value stream -> q[k] = value + (z[k] - mean(advantage)); returns the greedy action (first index of the maximum).
-// The epilogue sums the advantages with a 16-lane butterfly over zero-padded lanes: ((z0 + z1) + (z2 + 0)) for A <= 3.
-__device__ __forceinline__ int dueling_row(const float* z, int A, float* q) {
-  const float z0 = z[0], z1 = A > 1 ? z[1] : 0.0f, z2 = A > 2 ? z[2] : 0.0f;
-  const float sum = (z0 + z1) + (z2 + 0.0f);
-  const float v = z[A];
-  int bi = 0;
-  float best = 0.0f;
-  for (int k = 0; k < A; ++k) {
-    const float qv = v + (z[k] - sum / (float)A);
-    q[k] = qv;
-    if (k == 0 || qv > best) { best = qv; bi = k; }
-  }
-  return bi;
-}
-
+// (the dueling combination of one row, dueling_row: duel_device.hpp)
 constexpr int kRbMaxA = 3;
 
 // Three workgroups per 16-row slab (blockIdx.y): policy(s) — the pass the gradient flows through —, policy(s') and target(s')

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   LunarEvalArgs, MlpDesc, MlprnnParams, MountainCarEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   LunarEvalArgs, MlpDesc, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -774,6 +774,58 @@ def classic_duel_eval(kind, trunk, value, advantage, n_episodes, seed, stream_id
     a.value_w, a.value_b, a.adv_w, a.adv_b = addr[n - 2], addr[2 * n - 2], addr[n - 1], addr[2 * n - 1]
     a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
     check(lib().gymrl_classic_duel_eval(C.byref(a), _stream()), "gymrl_classic_duel_eval")
+    return out if want_final_obs else out[:3]
+
+
+# ----------------------- MountainCar-v0 policies: whole episodes in one launch ---
+MOUNTAINCAR_NET_MLP, MOUNTAINCAR_NET_DUEL_MEAN, MOUNTAINCAR_NET_DUEL_ROW = 0, 1, 2     # gymrl_mountaincar_net_eval_args.net
+
+
+def mountaincar_net_eval_shape_ok(net, n_hidden, D, A, H):
+    """What gymrl_mountaincar_net_eval takes (include/gymrl.h): a three-layer MLP (net 0: two hidden layers) or a dueling network
+    (net 1: torch's mean, net 2: the DUELING epilogue's; one or two hidden layers) on MountainCar-v0's (D, A) = (2, 3), a hidden
+    width the row-slab stages carry."""
+    return (net in (0, 1, 2) and n_hidden in ((2,) if net == 0 else (1, 2)) and (D, A) == (2, 3)
+            and 4 <= H <= 256 and H % 4 == 0)
+
+
+def mountaincar_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, value=None, flat=None, params=None, images=None,
+                         start=None, want_final_obs=False):
+    """n_episodes whole episodes of MountainCar-v0 per policy in ONE launch (include/gymrl.h gymrl_mountaincar_net_eval) ->
+    (returns f32, lengths i32, terminated u8), each [P, n_episodes], and final_obs f32[P, n_episodes, 2] when asked for.  Every
+    layer is a (weight, bias) tensor pair, a NoisyLinear's its weight_mu / bias_mu: trunk = the hidden layers (2 -> H, H -> H),
+    head = fc3 (net 0) or the advantage head (net 1 | 2), both H -> 3, value = the H -> 1 head of a dueling network.  params /
+    flat, the starts and the streams: classic_policy_eval's; start is f64[P, n_episodes, 2] = (position, velocity)."""
+    who = "mountaincar_net_eval"
+    trunk = [tuple(pair) for pair in trunk]
+    duel = net != MOUNTAINCAR_NET_MLP
+    if len(trunk) not in ((1, 2) if duel else (2,)):
+        raise ValueError(f"{who}: the trunk is {'one or two' if duel else 'two'} (weight, bias) pairs")
+    if duel != (value is not None):
+        raise ValueError(f"{who}: a dueling network (net 1 | 2) has a value head, a three-layer one (net 0) has none")
+    pairs = trunk + [tuple(head)] + ([tuple(value)] if duel else [])
+    if any(len(pair) != 2 or pair[0].dim() != 2 or pair[1].dim() != 1 or pair[1].shape[0] != pair[0].shape[0] for pair in pairs):
+        raise ValueError(f"{who}: a layer is a (weight [N, K], bias [N]) pair")
+    H, D, A = trunk[0][0].shape[0], trunk[0][0].shape[1], head[0].shape[0]
+    if len(trunk) == 2 and tuple(trunk[1][0].shape) != (H, H):
+        raise ValueError(f"{who}: the trunk is not D -> H (-> H)")
+    if head[0].shape[1] != H or (duel and tuple(value[0].shape) != (1, H)):
+        raise ValueError(f"{who}: the heads are not H -> A and H -> 1")
+    if (D, A) != (2, 3):
+        raise ValueError(f"{who}: MountainCar-v0 has 2 observations and 3 actions, the layers are {D} -> .. -> {A}")
+    tensors = [w for w, _ in pairs] + [b for _, b in pairs]
+    n, nh = len(pairs), len(trunk)
+    a = MountainCarNetEvalArgs()
+    P, stride, params, addr = _policy_addresses(who, tensors, flat, params)
+    out = _episode_io(a, P, n_episodes, 2, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
+    a.P, a.E, a.cap, a.net, a.n_hidden, a.H = P, n_episodes, cap, net, nh, H
+    for k in range(nh):
+        a.w[k], a.b[k] = addr[k], addr[n + k]
+    a.head_w, a.head_b = addr[nh], addr[n + nh]
+    if duel:
+        a.value_w, a.value_b = addr[nh + 1], addr[n + nh + 1]
+    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
+    check(lib().gymrl_mountaincar_net_eval(C.byref(a), _stream()), "gymrl_mountaincar_net_eval")
     return out if want_final_obs else out[:3]
 
 

@@ -416,6 +416,8 @@ class PrioritizedNStepBuffer:
 
 
 class RainbowDQNTrainer(PolicyEval):
+    EVAL_DUEL_COMBINE = 2              # the network's forward combines in gymrl_lin_fwd's DUELING epilogue (sum / A), not through torch
+
     def __init__(self, config):
         self.cfg = config
         if not torch.cuda.is_available() or not ops.device_ok():

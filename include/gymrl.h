@@ -42,8 +42,9 @@ enum {
   GYMRL_ENV_CARTPOLE    = 0, /* CartPole-v1   obs 4, 2 discrete actions   */
   GYMRL_ENV_PENDULUM    = 1, /* Pendulum-v1   obs 3, 1 continuous in [-2,2] */
   GYMRL_ENV_LUNARLANDER = 2, /* LunarLander-v3 obs 8, 4 discrete actions  */
-  GYMRL_ENV_MOUNTAINCAR = 3  /* MountainCar-v0 obs 2, 3 discrete actions (the steppers and gymrl_mountaincar_rule_eval only:
-                              * the fused acting, ring, rollout and policy-episode kernels refuse it with -EINVAL) */
+  GYMRL_ENV_MOUNTAINCAR = 3  /* MountainCar-v0 obs 2, 3 discrete actions (the steppers, gymrl_mountaincar_rule_eval and
+                              * gymrl_mountaincar_net_eval only: the fused acting, ring and rollout kernels and the other
+                              * policy-episode entry points refuse it with -EINVAL) */
 };
 
 /*
@@ -1768,6 +1769,47 @@ int gymrl_ndqn_act_step(const gymrl_ndqn_act_args* args, void* stream);
 size_t gymrl_ndqn_update_workspace_bytes(int B, int D, int A, int H);
 int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
 
+/* ----------------------------- MountainCar-v0 policies: whole episodes in one launch ---- */
+/*
+ * gymrl_classic_policy_eval and gymrl_classic_duel_eval (the section below: grid, lanes, uniform exit, starts, policy_stride,
+ * outputs — all as described there) for MountainCar-v0, (D, A) = (2, 3), TimeLimit 200 (csrc/eval_mountaincar.hip; the kernels
+ * and the episode loop are the ones below, stated once in csrc/eval_kernels_device.hpp and csrc/eval_episode_device.hpp).  The
+ * state (position, velocity) is float64 in the lane's registers, the observation its float32 cast, one step is
+ * csrc/env_classic_device.hpp's mountaincar_advance — the stepper's — and the return takes -1 on every step, the terminating one
+ * included.  Episode i = p * E + e starts from the reset draw of (seed, stream_id0 + e, episode 0) or from start[i].
+ *
+ *   net 0  a three-layer MLP 2 -> H -> H -> 3: n_hidden = 2, head_w / head_b = fc3, value_w / value_b NULL; the action is the
+ *          FIRST maximum of fc3's row (gymrl_epsilon_greedy's greedy branch, gymrl_categorical_sample's deterministic one).
+ *   net 1  a dueling network: a ReLU trunk of n_hidden layers (1 | 2), value_w [1][H], head_w [3][H] = the advantage head, both
+ *          in one two-item stage; q = v + (a - mean a) with the mean as ((a0 + a2) + a1) * (1 / 3) — torch's mean of a row of three — and the
+ *          first maximum of q.  A NoisyLinear layer is passed as its weight_mu / bias_mu.
+ *   net 2  the same network with the combine of gymrl_lin_fwd's GYMRL_ACT_DUELING epilogue (Rainbow's layer path):
+ *          q = v + (a - ((a0 + a1) + (a2 + 0)) / 3).  From three actions on the two means are different floats.
+ *
+ * -EINVAL before any launch: NULL args, a NULL w[0] / b[0] / head_w / head_b / returns / lengths / terminated, P < 1, E < 1, cap
+ * outside 1..200, net outside 0..2, n_hidden other than 2 with net 0 or outside {1, 2}, a non-NULL value_w / value_b with net 0 or
+ * a NULL one with net 1 | 2, a NULL w[1] / b[1] with n_hidden == 2 or a non-NULL one with n_hidden == 1, H % 4 != 0 or H outside
+ * 4..256, a negative policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, with
+ * n_hidden == 1 or with H % 16 != 0, P * E above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (the weights, images: 16
+ * bytes; start: 8; the others: 4).
+ */
+typedef struct {
+  int P, E, cap;
+  int net;                                 /* 0: three-layer MLP | 1: dueling, torch's mean | 2: dueling, the DUELING epilogue's mean */
+  int n_hidden, H;                         /* hidden layers of the trunk (net 0: 2; net 1 | 2: 1 | 2) and their width */
+  const float* w[2]; const float* b[2];    /* fc1 [H][2], fc2 [H][H] and their biases, of policy 0; entry 1 is NULL when n_hidden == 1 */
+  const float* head_w; const float* head_b;        /* net 0: fc3 [3][H], [3]; net 1 | 2: the advantage head [3][H], [3] */
+  const float* value_w; const float* value_b;      /* net 1 | 2: the value head [1][H], [1]; net 0: NULL */
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  const float* images;                     /* the forward image of fc2 (n_hidden == 2, H % 16 == 0, P == 1), or NULL: fc2 is read in place */
+  uint64_t seed; int64_t stream_id0;
+  const double* start;                     /* f64[P * E][2] (position, velocity), or NULL: the reset draw */
+  float* returns; int32_t* lengths; uint8_t* terminated;
+  float* final_obs;                        /* f32[P * E][2] or NULL */
+} gymrl_mountaincar_net_eval_args;
+size_t gymrl_mountaincar_net_eval_args_bytes(void);  /* sizeof(gymrl_mountaincar_net_eval_args) */
+int gymrl_mountaincar_net_eval(const gymrl_mountaincar_net_eval_args* args, void* stream);
+
 /* ----------------------------- classic-control policies: whole episodes in one launch ---- */
 /*
  * Replaces the eval() loops of dqn_cartpole.py:214-233, ddqn_per_cartpole.py, sac_cartpole.py, td3_pendulum.py and
@@ -1796,7 +1838,7 @@ int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
  * 4..256, a negative policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, P * E
  * above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (w[k], images: 16 bytes; start: 8; the others: 4).
  * SAC-Pendulum's greedy action tanh(mean(fc2(fc1 s))) * bound is head 1 on (fc1, fc2, mean).  Dueling networks: the entry point below.
- * Out of scope: MountainCar-v0 (LunarLander-v3 under a PPO policy: gymrl_lunar_policy_eval below).
+ * MountainCar-v0: gymrl_mountaincar_net_eval above (LunarLander-v3 under a PPO policy: gymrl_lunar_policy_eval below).
  */
 typedef struct {
   int P, E, cap;
