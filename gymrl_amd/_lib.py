@@ -336,6 +336,23 @@ class NdqnUpdateArgs(C.Structure):
                 ("loss_sum", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class EsNoiseArgs(C.Structure):
+    _c_name_ = "gymrl_es_noise_args"
+    _fields_ = [("n", C.c_int), ("k0", C.c_int), ("K", C.c_int), ("seed", C.c_uint64), ("generation", C.c_uint64), ("out", C.c_void_p)]
+
+
+class EsPerturbArgs(C.Structure):
+    _c_name_ = "gymrl_es_perturb_args"
+    _fields_ = [("n", C.c_int), ("P", C.c_int), ("stride", C.c_int64), ("sigma", C.c_float), ("seed", C.c_uint64),
+                ("generation", C.c_uint64), ("theta", C.c_void_p), ("params", C.c_void_p)]
+
+
+class EsShapeGradArgs(C.Structure):
+    _c_name_ = "gymrl_es_shape_grad_args"
+    _fields_ = [("n", C.c_int), ("P", C.c_int), ("E", C.c_int), ("sigma", C.c_float), ("seed", C.c_uint64),
+                ("generation", C.c_uint64), ("returns", C.c_void_p), ("grad", C.c_void_p), ("weights", C.c_void_p)]
+
+
 class MountainCarNetEvalArgs(C.Structure):
     _c_name_ = "gymrl_mountaincar_net_eval_args"
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("net", C.c_int), ("n_hidden", C.c_int), ("H", C.c_int),
@@ -559,6 +576,13 @@ SIGNATURES = {
     "gymrl_dsac_update": (_i, [_P(DsacUpdateArgs), _vp]),
     "gymrl_softmax_rows_fwd": (_i, [_vp, _i, _i, _vp, _vp]),
     "gymrl_softmax_rows_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "gymrl_es_pair_chunk": (_i, []),
+    "gymrl_es_noise_args_bytes": (_sz, []),
+    "gymrl_es_perturb_args_bytes": (_sz, []),
+    "gymrl_es_shape_grad_args_bytes": (_sz, []),
+    "gymrl_es_noise": (_i, [_P(EsNoiseArgs), _vp]),
+    "gymrl_es_perturb": (_i, [_P(EsPerturbArgs), _vp]),
+    "gymrl_es_shape_grad": (_i, [_P(EsShapeGradArgs), _vp]),
     "gymrl_qlearn_state_bytes": (_sz, [_i]),
     "gymrl_qlearn_train": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _u64, _i64, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_qlearn_eval": (_i, [_i, _i, _vp, _i, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp]),

@@ -70,6 +70,7 @@ enum : uint32_t {
   RNG_REPLAY    = 0x40000000u,
   RNG_NOISE     = 0x50000000u,
   RNG_SHUFFLE   = 0x60000000u,
+  RNG_ES        = 0x70000000u,   // es_noise_device.hpp (the value of tabular_device.hpp's RNG_TABULAR, whose c0 / c1 / c2 are a run's)
 };
 
 // ------------------------------------------------------ keyed permutation ---

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    LunarEvalArgs, MlpDesc, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -589,6 +589,59 @@ def env_step(kind, state, n, seed, env_id0, action, obs_out, rew_out, terminated
                                _ptr(term_obs_out, torch.float32, True), _ptr(rew_out, torch.float32), _ptr(terminated_out, torch.uint8),
                                _ptr(truncated_out, torch.uint8), _ptr(done_out, torch.uint8, True), _ptr(ep_ret_out, torch.float32, True),
                                _ptr(ep_len_out, torch.int32, True), _ptr(ep_stats, torch.float64, True), _stream()), "gymrl_env_step")
+
+
+# ------------------------------------------------- evolution strategies ---
+ES_PAIR_CHUNK = 16             # GYMRL_ES_PAIR_CHUNK: pairs per chunk of the search gradient's float64 sum (include/gymrl.h)
+ES_MAX_POPULATION = 8192
+
+
+def es_noise(n, k0, K, seed, generation, device, out=None):
+    """eps f32[K, n] of pairs k0 .. k0 + K - 1 (include/gymrl.h: the draw map): what gymrl_es_perturb and gymrl_es_shape_grad
+    draw in registers, written out for tests and tools."""
+    if out is None:
+        out = torch.empty(K, n, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != (K, n):
+        raise ValueError(f"es_noise: out is {tuple(out.shape)}, {K} pairs of {n} elements need [{K}, {n}]")
+    a = EsNoiseArgs()
+    a.n, a.k0, a.K, a.seed, a.generation, a.out = n, k0, K, seed, generation, _ptr(out, torch.float32)
+    check(lib().gymrl_es_noise(C.byref(a), _stream()), "gymrl_es_noise")
+    return out
+
+
+def es_stride(n):
+    """The narrowest row stride the evaluators take for n parameters: n rounded up to a multiple of four floats."""
+    return (n + 3) // 4 * 4
+
+
+def es_perturb(theta, sigma, seed, generation, out):
+    """out f32[P, stride] <- the mirrored population of the centre theta f32[n]: rows 2k / 2k + 1 = theta +- sigma * eps_k, ONE
+    launch; columns n .. stride - 1 of `out` are left as they are."""
+    if theta.dim() != 1 or out.dim() != 2:
+        raise ValueError("es_perturb: theta is f32[n], out f32[P, stride]")
+    a = EsPerturbArgs()
+    a.n, a.P, a.stride, a.sigma, a.seed, a.generation = theta.numel(), out.shape[0], out.shape[1], float(sigma), seed, generation
+    a.theta, a.params = _ptr(theta, torch.float32), _ptr(out, torch.float32)
+    check(lib().gymrl_es_perturb(C.byref(a), _stream()), "gymrl_es_perturb")
+    return out
+
+
+def es_shape_grad(returns, sigma, seed, generation, grad, weights=None):
+    """returns f32[P, E] of an evaluation launch -> (grad f32[n], weights f32[P]): the centred ranks of the policies' summed
+    returns and the search gradient -(1 / (P sigma)) sum_k (w_2k - w_2k+1) eps_k an Adam step DESCENDS (include/gymrl.h: the
+    summation order).  One launch up to 256 policies, two above."""
+    if returns.dim() != 2 or grad.dim() != 1:
+        raise ValueError("es_shape_grad: returns is f32[P, E], grad f32[n]")
+    P, E = returns.shape
+    if weights is None:
+        weights = torch.empty(P, dtype=torch.float32, device=returns.device)
+    elif weights.numel() != P:
+        raise ValueError(f"es_shape_grad: weights has {weights.numel()} elements for {P} policies")
+    a = EsShapeGradArgs()
+    a.n, a.P, a.E, a.sigma, a.seed, a.generation = grad.numel(), P, E, float(sigma), seed, generation
+    a.returns, a.grad, a.weights = _ptr(returns, torch.float32), _ptr(grad, torch.float32), _ptr(weights, torch.float32)
+    check(lib().gymrl_es_shape_grad(C.byref(a), _stream()), "gymrl_es_shape_grad")
+    return grad, weights
 
 
 # ------------------------------------------------------ tabular Q-learning ---

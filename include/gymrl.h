@@ -1565,6 +1565,70 @@ int gymrl_dsac_update(const gymrl_dsac_update_args* args, void* stream);
 int gymrl_softmax_rows_fwd(const float* z, int B, int A, float* p_out, void* stream);
 int gymrl_softmax_rows_bwd(const float* p, const float* g, int B, int A, float* dz_out, void* stream);
 
+/* ---- evolution strategies on the population evaluators (csrc/es.hip, csrc/es_noise_device.hpp; no reference script) --------
+ * OpenAI-ES around one evaluation launch: mirrored sampling, centred-rank fitness shaping, the search gradient for Adam.  The
+ * perturbations are drawn in registers wherever they are needed and never stored.
+ *
+ * The noise.  eps(seed, generation, pair k, element i), a standard normal float32:
+ *   r = Philox4x32-10(key = seed; c0 = i >> 2, c1 = k, c2 = generation & 0xffffffff, c3 = 0x70000000 | ((generation >> 32) & 0x0fffffff))
+ *   z0 = rho(r.x) cos(2 pi u(r.y)), z1 = rho(r.x) sin(2 pi u(r.y)), z2 = rho(r.z) cos(2 pi u(r.w)), z3 = rho(r.z) sin(2 pi u(r.w))
+ *   with rho(w) = sqrtf(-2 logf(((w >> 8) + 1) * 2^-24)), u(w) = (w >> 8) * 2^-24 (the library's reproducible logf / sincosf);
+ *   eps = z[i & 3]: four consecutive elements of a pair share one call, and all four words of the call are used.
+ * c3's tag has the value the tabular runs' draws carry; their c0 / c1 are a run id and c2 a step, and no program draws from both.
+ *
+ * gymrl_es_noise       out f32[K][n] = eps for pairs k0 .. k0 + K - 1, elements 0 .. n - 1: the window of tests and tools.
+ * gymrl_es_perturb     params f32[P][stride]: row 2k = theta + sigma * eps_k, row 2k + 1 = theta - sigma * eps_k, each ONE float32
+ *                      multiply and ONE float32 add / subtract (no fused multiply-add); columns n .. stride - 1 are not written.
+ * gymrl_es_shape_grad  returns f32[P][E] (an evaluation launch's) -> weights f32[P], grad f32[n]:
+ *   fitness  F_p = the float64 sum of returns[p][e] in ascending e
+ *   ranks    less_p = #{q: F_q < F_p}, equal_p = #{q: F_q == F_p} (p itself counted), by counting, no sort;
+ *            w_p = (float)(2 less_p + equal_p - 1) / (float)(2 (P - 1)) - 0.5f: ties share their mean rank, all-equal fitness gives
+ *            w == 0 exactly.  A NaN fitness: unspecified weights.
+ *   gradient u_k = w_2k - w_2k+1 (float32); S_i = sum_k (double)u_k * (double)eps_k[i], the pairs cut into consecutive chunks of
+ *            GYMRL_ES_PAIR_CHUNK, a chunk summed from 0.0 in ascending k, the chunk sums added to 0.0 in ascending chunk order, every
+ *            product and sum ONE float64 operation; grad[i] = (float)(-(1.0 / ((double)P * (double)sigma)) * S_i).  Negative: an
+ *            optimiser that DESCENDS grad ascends the fitness.  No atomics: the bits do not depend on the grid.
+ *   P <= 256: ONE launch (every workgroup counts the ranks itself); above: a rank launch, then the gradient's.
+ * -EINVAL before any launch: NULL args or a NULL pointer, n < 1, P odd or outside 2..8192, E < 1, K < 1, k0 < 0, k0 + K > 4096,
+ * stride < n or stride % 4 != 0, sigma <= 0 or not finite, theta / params not 16-byte aligned (the others: 4). */
+#define GYMRL_ES_PAIR_CHUNK 16
+typedef struct {
+  int n;                                   /* elements per pair */
+  int k0;                                  /* first pair */
+  int K;                                   /* pairs */
+  uint64_t seed;
+  uint64_t generation;
+  float* out;                              /* f32[K][n] */
+} gymrl_es_noise_args;
+typedef struct {
+  int n;                                   /* parameters */
+  int P;                                   /* population, even: P / 2 mirrored pairs */
+  int64_t stride;                          /* floats between rows of params: >= n, % 4 == 0 (the evaluators' policy_stride) */
+  float sigma;
+  uint64_t seed;
+  uint64_t generation;
+  const float* theta;                      /* f32[n], the centre */
+  float* params;                           /* f32[P][stride] out */
+} gymrl_es_perturb_args;
+typedef struct {
+  int n;
+  int P;
+  int E;                                   /* episodes per policy */
+  float sigma;
+  uint64_t seed;
+  uint64_t generation;
+  const float* returns;                    /* f32[P][E] */
+  float* grad;                             /* f32[n] out */
+  float* weights;                          /* f32[P] out */
+} gymrl_es_shape_grad_args;
+int gymrl_es_pair_chunk(void);               /* GYMRL_ES_PAIR_CHUNK */
+size_t gymrl_es_noise_args_bytes(void);      /* sizeof(gymrl_es_noise_args) */
+size_t gymrl_es_perturb_args_bytes(void);    /* sizeof(gymrl_es_perturb_args) */
+size_t gymrl_es_shape_grad_args_bytes(void); /* sizeof(gymrl_es_shape_grad_args) */
+int gymrl_es_noise(const gymrl_es_noise_args* args, void* stream);
+int gymrl_es_perturb(const gymrl_es_perturb_args* args, void* stream);
+int gymrl_es_shape_grad(const gymrl_es_shape_grad_args* args, void* stream);
+
 /* ---- tabular Q-learning: a population of independent runs in one launch (csrc/tabular.hip) --------------------------------
  * Replaces QLearningTrainer.train() / select_action() / update() / _shape_reward() / eval() of qlearning_frozenlake.py:56-153
  * and qlearning_cliffwalking.py:49-124 together with the gym.make(...).reset() / .step() calls inside them (:100,105 / :75,80),
