@@ -353,6 +353,20 @@ class EsShapeGradArgs(C.Structure):
                 ("generation", C.c_uint64), ("returns", C.c_void_p), ("grad", C.c_void_p), ("weights", C.c_void_p)]
 
 
+class SnesPerturbArgs(C.Structure):
+    _c_name_ = "gymrl_snes_perturb_args"
+    _fields_ = [("n", C.c_int), ("P", C.c_int), ("stride", C.c_int64), ("seed", C.c_uint64), ("generation", C.c_uint64),
+                ("mu", C.c_void_p), ("sigma", C.c_void_p), ("params", C.c_void_p)]
+
+
+class SnesTellArgs(C.Structure):
+    _c_name_ = "gymrl_snes_tell_args"
+    _fields_ = [("n", C.c_int), ("P", C.c_int), ("E", C.c_int), ("eta_mu", C.c_float), ("eta_sigma", C.c_float),
+                ("sigma_min", C.c_float), ("sigma_max", C.c_float), ("seed", C.c_uint64), ("generation", C.c_uint64),
+                ("returns", C.c_void_p), ("returns64", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p),
+                ("weights", C.c_void_p)]
+
+
 class MountainCarNetEvalArgs(C.Structure):
     _c_name_ = "gymrl_mountaincar_net_eval_args"
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("net", C.c_int), ("n_hidden", C.c_int), ("H", C.c_int),
@@ -586,6 +600,10 @@ SIGNATURES = {
     "gymrl_qlearn_state_bytes": (_sz, [_i]),
     "gymrl_qlearn_train": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _u64, _i64, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_qlearn_eval": (_i, [_i, _i, _vp, _i, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_snes_perturb_args_bytes": (_sz, []),
+    "gymrl_snes_tell_args_bytes": (_sz, []),
+    "gymrl_snes_perturb": (_i, [_P(SnesPerturbArgs), _vp]),
+    "gymrl_snes_tell": (_i, [_P(SnesTellArgs), _vp]),
     "gymrl_dqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_dqn_pack_images": (_i, [_P(DqnUpdateArgs), _vp]),
     "gymrl_dqn_args_bytes": (_sz, [_i]),

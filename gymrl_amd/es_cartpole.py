@@ -1,4 +1,4 @@
-"""Evolution strategies (OpenAI-ES) on the one-launch population evaluators — an engine addition with no reference script
+"""Evolution strategies (OpenAI-ES, or separable NES under Config.method = "snes") on the one-launch population evaluators — an engine addition with no reference script
 behind it; Config / trainer / CLI are shaped like dqn_cartpole.py's.
 
 One generation is four launches and no host synchronisation:
@@ -7,6 +7,10 @@ One generation is four launches and no host synchronisation:
     PolicyEval launch     gymrl_classic_policy_eval | gymrl_mountaincar_net_eval     P policies x E whole episodes
     OpenAIES.tell()       gymrl_es_shape_grad  returns -> centred ranks -> search gradient (two launches above 256 policies)
                           gymrl_adam_step      the centre moves
+
+Under Config.method = "snes" the learner is es.SeparableNES: gymrl_snes_perturb, the same evaluation launch, and
+gymrl_snes_tell, which moves the centre and its per-element step sizes itself — three launches, no Adam step; Config.sigma is
+the step sizes' initial value and Config.lr is not read.
 
 The policy is dqn_cartpole.py's three-layer MLP: an argmax head on CartPole-v1 and MountainCar-v0, tanh(fc3) * bound on
 Pendulum-v1.  Training episodes start from streams of their own (env ids from 1 << 41, E fresh ones per generation, the same E
@@ -18,7 +22,7 @@ import torch
 from . import ops
 from .dqn_cartpole import QNetwork
 from .envs import VecEnv
-from .es import OpenAIES
+from .es import OpenAIES, SeparableNES
 from .flat import flatten_module
 from .policy_eval import PolicyEval
 from .utils import scalar
@@ -32,11 +36,30 @@ class Config:
         self.population = 256                # even: population / 2 mirrored pairs
         self.sigma = 0.1
         self.lr = 0.03
+        self.method = "openai"               # | "snes": es.SeparableNES, a step size per parameter adapted by the learner's own launch
+        self.eta_mu = 1.0                    # "snes": the centre's learning rate
+        self.eta_sigma = None                # "snes": the step sizes' learning rate; None: (3 + ln n) / (5 sqrt n)
         self.episodes_per_policy = 16        # a workgroup of the evaluators carries 16 episodes: up to here they cost no launch time
         self.max_generations = 100
         self.log_freq = 10                   # generations between host reads of the mean population return
         self.device = "cuda"
         self.fused_eval = True               # eval() as ONE launch (csrc/eval_classic.hip); off: the step-by-step loop
+
+
+def make_learner(config, flat_params, seed):
+    """The learner Config.method names, on the trainer's flat buffer."""
+    if config.method == "openai":
+        return OpenAIES(flat_params, seed, config.population, config.sigma, config.lr)
+    if config.method == "snes":
+        return SeparableNES(flat_params, seed, config.population, config.sigma, eta_mu=config.eta_mu, eta_sigma=config.eta_sigma)
+    raise ValueError(f"ESTrainer: method is 'openai' or 'snes', not {config.method!r}")
+
+
+def check_method(rest, method):
+    """A checkpoint's learner state fits the learner that wrote it only (one written before there was a choice: OpenAI-ES's)."""
+    saved = rest.get("method", "openai")
+    if saved != method:
+        raise ValueError(f"ESTrainer: the checkpoint holds a {saved!r} learner, this trainer runs {method!r}")
 
 
 class ESTrainer(PolicyEval):
@@ -58,7 +81,7 @@ class ESTrainer(PolicyEval):
         self.policy_net = QNetwork(state_dim, action_dim, config.hidden_dim)
         torch.random.set_rng_state(g)
         self.flat_params, _ = flatten_module(self.policy_net, self.device)
-        self.es = OpenAIES(self.flat_params, self.base_seed, config.population, config.sigma, config.lr)
+        self.es = make_learner(config, self.flat_params, self.base_seed)
         self._call = self._eval_call()
         if self._call is None:
             raise ValueError(f"ESTrainer: the evaluators take no {config.env_name} policy of hidden width {config.hidden_dim} "
@@ -141,11 +164,12 @@ class ESTrainer(PolicyEval):
     def save_checkpoint(self, path):
         from .utils import checkpoint
         return checkpoint.save_agent(path, {"policy_net": self.policy_net}, {}, es_state_dict=self.es.state_dict(),
-                                     generation=self.es.generation, history=list(self.history))
+                                     generation=self.es.generation, history=list(self.history), method=self.cfg.method)
 
     def load_checkpoint(self, path):
         from .utils import checkpoint
         rest = checkpoint.load_agent(path, {"policy_net": self.policy_net}, {})
+        check_method(rest, self.cfg.method)
         self.es.load_state_dict(rest["es_state_dict"])
         self.history = [tuple(h) for h in rest.get("history", [])]
         return rest

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    LunarEvalArgs, MlpDesc, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -642,6 +642,41 @@ def es_shape_grad(returns, sigma, seed, generation, grad, weights=None):
     a.returns, a.grad, a.weights = _ptr(returns, torch.float32), _ptr(grad, torch.float32), _ptr(weights, torch.float32)
     check(lib().gymrl_es_shape_grad(C.byref(a), _stream()), "gymrl_es_shape_grad")
     return grad, weights
+
+
+def snes_perturb(mu, sigma, seed, generation, out):
+    """out f32[P, stride] <- the mirrored population of the centre mu f32[n] under the per-element step sizes sigma f32[n]:
+    rows 2k / 2k + 1 = mu +- sigma * eps_k, ONE launch; columns n .. stride - 1 of `out` are left as they are."""
+    if mu.dim() != 1 or out.dim() != 2 or tuple(sigma.shape) != tuple(mu.shape):
+        raise ValueError("snes_perturb: mu and sigma are f32[n], out f32[P, stride]")
+    a = SnesPerturbArgs()
+    a.n, a.P, a.stride, a.seed, a.generation = mu.numel(), out.shape[0], out.shape[1], seed, generation
+    a.mu, a.sigma, a.params = _ptr(mu, torch.float32), _ptr(sigma, torch.float32), _ptr(out, torch.float32)
+    check(lib().gymrl_snes_perturb(C.byref(a), _stream()), "gymrl_snes_perturb")
+    return out
+
+
+def snes_tell(returns, mu, sigma, seed, generation, eta_mu, eta_sigma, sigma_min, sigma_max, weights=None):
+    """returns [P, E] of an evaluation launch, float32 or float64 (read as it is: no cast launch) -> mu and sigma f32[n] moved
+    IN PLACE by one separable-NES step on the centred ranks of the policies' summed returns (include/gymrl.h: the sums and the
+    step), and weights f32[P].  One launch up to 256 policies, two above."""
+    if returns.dim() != 2 or mu.dim() != 1 or tuple(sigma.shape) != tuple(mu.shape):
+        raise ValueError("snes_tell: returns is [P, E], mu and sigma f32[n]")
+    if returns.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"snes_tell: returns is float32 or float64, not {returns.dtype}")
+    P, E = returns.shape
+    if weights is None:
+        weights = torch.empty(P, dtype=torch.float32, device=returns.device)
+    elif weights.numel() != P:
+        raise ValueError(f"snes_tell: weights has {weights.numel()} elements for {P} policies")
+    a = SnesTellArgs()
+    a.n, a.P, a.E, a.seed, a.generation = mu.numel(), P, E, seed, generation
+    a.eta_mu, a.eta_sigma, a.sigma_min, a.sigma_max = float(eta_mu), float(eta_sigma), float(sigma_min), float(sigma_max)
+    wide = returns.dtype == torch.float64
+    a.returns, a.returns64 = (None, _ptr(returns)) if wide else (_ptr(returns), None)
+    a.mu, a.sigma, a.weights = _ptr(mu, torch.float32), _ptr(sigma, torch.float32), _ptr(weights, torch.float32)
+    check(lib().gymrl_snes_tell(C.byref(a), _stream()), "gymrl_snes_tell")
+    return weights
 
 
 # ------------------------------------------------------ tabular Q-learning ---

@@ -1665,6 +1665,67 @@ int gymrl_qlearn_train(int env_kind, int is_slippery, int shaped, double* Q, voi
 int gymrl_qlearn_eval(int env_kind, int is_slippery, const double* Q, int n_runs, int n_episodes, uint64_t seed,
                       int64_t stream_id0, int cap, double* returns, int32_t* lengths, uint8_t* flags, void* stream);
 
+/* ---- separable NES on the population evaluators (csrc/es.hip; no reference script) ------------------------------------------
+ * The second learner on the evolution-strategies block's noise, ranks and summation contract (above the tabular runs; tests pin
+ * what follows that block, so this one stands here): a centre mu f32[n] and a step size PER ELEMENT sigma f32[n], both moved by
+ * the launch that weighs the noise.  eps, F_p, w_p and GYMRL_ES_PAIR_CHUNK are that block's.
+ *
+ * gymrl_snes_perturb  params f32[P][stride]: row 2k = mu[i] + sigma[i] * eps_k[i], row 2k + 1 = mu[i] - sigma[i] * eps_k[i], each ONE
+ *                     float32 multiply and ONE float32 add / subtract (no fused multiply-add); columns n .. stride - 1 are not
+ *                     written.
+ * gymrl_snes_tell     the evaluators' returns -> weights f32[P], and mu and sigma moved IN PLACE.  Exactly one of returns
+ *                     (f32[P][E]) and returns64 (f64[P][E], gymrl_lunar_policy_eval's) is non-NULL.
+ *   fitness  F_p = the float64 sum of row p in ascending e: for returns64 the plain double sum, for returns each term the (double)
+ *            of the float.
+ *   ranks    w_p as gymrl_es_shape_grad's, written to weights.
+ *   sums     u_k = w_2k - w_2k+1 and s_k = w_2k + w_2k+1 (float32);
+ *            Smu_i = sum_k (double)u_k * (double)eps_k[i],
+ *            Ssg_i = sum_k (double)s_k * ((double)eps_k[i] * (double)eps_k[i] - 1.0),
+ *            both under gymrl_es_shape_grad's summation contract: chunks of GYMRL_ES_PAIR_CHUNK pairs, a chunk summed from 0.0 in
+ *            ascending k, the chunk sums added to 0.0 in ascending chunk order, every product, difference and sum ONE float64
+ *            operation.  No atomics: the bits do not depend on the grid.
+ *   step     c = 4.0 / (double)P (with centred ranks sum_p |c w_p| is about 1, the usual SNES utility scale);
+ *            mu[i]    <- (float)((double)mu[i] + (double)eta_mu * ((double)sigma[i] * (c * Smu_i))), sigma[i] the value BEFORE the call;
+ *            sigma[i] <- min(max(sigma[i] * expf((float)(0.5 * (double)eta_sigma * (c * Ssg_i))), sigma_min), sigma_max)
+ *            (the library's reproducible expf; max(v, lo) = v < lo ? lo : v, min(v, hi) = v > hi ? hi : v; one float32 product).
+ *            There is no optimiser launch: the thread that closes element i's chunk sums is the only one that reads or writes
+ *            mu[i] and sigma[i].  All-equal fitness gives w == 0, both sums 0.0, expf(0) == 1: mu and sigma keep their bits
+ *            (a sigma outside the bounds is still clamped).  A NaN fitness: unspecified.
+ *   P <= 256: ONE launch (every workgroup counts the ranks itself); above: a rank launch, then the step's.
+ * -EINVAL before any launch: NULL args, a NULL mu / sigma / params / weights, both or neither of returns and returns64, n < 1,
+ * P odd or outside 2..8192, E < 1, stride < n or stride % 4 != 0, eta_mu or eta_sigma not finite, sigma_min or sigma_max not
+ * finite or !(0 < sigma_min <= sigma_max), mu / sigma / params not 16-byte aligned, returns64 not 8-byte, the others not 4-byte. */
+typedef struct {
+  int n;                                   /* parameters */
+  int P;                                   /* population, even: P / 2 mirrored pairs */
+  int64_t stride;                          /* floats between rows of params: >= n, % 4 == 0 */
+  uint64_t seed;
+  uint64_t generation;
+  const float* mu;                         /* f32[n], the centre */
+  const float* sigma;                      /* f32[n], the step size of every element */
+  float* params;                           /* f32[P][stride] out */
+} gymrl_snes_perturb_args;
+typedef struct {
+  int n;
+  int P;
+  int E;                                   /* episodes per policy */
+  float eta_mu;                            /* learning rate of the centre */
+  float eta_sigma;                         /* learning rate of the step sizes */
+  float sigma_min;                         /* 0 < sigma_min <= sigma_max */
+  float sigma_max;
+  uint64_t seed;
+  uint64_t generation;
+  const float* returns;                    /* f32[P][E], or NULL */
+  const double* returns64;                 /* f64[P][E], or NULL: exactly one of the two */
+  float* mu;                               /* f32[n], in place */
+  float* sigma;                            /* f32[n], in place */
+  float* weights;                          /* f32[P] out */
+} gymrl_snes_tell_args;
+size_t gymrl_snes_perturb_args_bytes(void);  /* sizeof(gymrl_snes_perturb_args) */
+size_t gymrl_snes_tell_args_bytes(void);     /* sizeof(gymrl_snes_tell_args) */
+int gymrl_snes_perturb(const gymrl_snes_perturb_args* args, void* stream);
+int gymrl_snes_tell(const gymrl_snes_tell_args* args, void* stream);
+
 /*
  * DQN's CartPole vector step on the same row-slab kernels (csrc/dqn_step.hip): dqn_cartpole.py's select_action :124-133 with
  * the env step and memory.push of its train loop :178-184, and update :135-168.  Discrete SAC's scheme with ONE online network
