@@ -88,6 +88,18 @@ class MlpDesc(C.Structure):
     _fields_ = [("n_stages", C.c_int), ("stage", MlpStage * MLP_MAX_STAGES)]
 
 
+class MlpPackLayer(C.Structure):
+    _c_name_ = "gymrl_mlp_pack_layer"
+    _fields_ = [("out_dim", C.c_int), ("in_dim", C.c_int), ("w_off", C.c_int64), ("b_off", C.c_int64), ("w_at", C.c_int64),
+                ("b_at", C.c_int64)]
+
+
+class MlpPackStackArgs(C.Structure):
+    _c_name_ = "gymrl_mlp_pack_stack_args"
+    _fields_ = [("P", C.c_int), ("n_layers", C.c_int), ("params", C.c_void_p), ("params_stride", C.c_int64),
+                ("packed", C.c_void_p), ("packed_stride", C.c_int64), ("layer", MlpPackLayer * MLP_MAX_STAGES)]
+
+
 class RolloutLunarArgs(C.Structure):
     _c_name_ = "gymrl_rollout_lunar_args"
     _fields_ = [("env_state", C.c_void_p), ("n_envs", C.c_int), ("seed", C.c_uint64), ("env_id0", C.c_int64),
@@ -483,6 +495,8 @@ SIGNATURES = {
     "gymrl_mlp_packed_floats": (_sz, [_i, _i]),
     "gymrl_mlp_pack": (_i, [_vp, _i, _i, _vp, _vp]),
     "gymrl_mlp_forward": (_i, [_vp, _i, _i, _P(MlpDesc), _vp]),
+    "gymrl_mlp_pack_stack_args_bytes": (_sz, []),
+    "gymrl_mlp_pack_stack": (_i, [_P(MlpPackStackArgs), _vp]),
     "gymrl_rollout_lunar": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_cartpole": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_lunar_mhc": (_i, [_P(RolloutLunarArgs), _P(MhcPolicy), _vp]),

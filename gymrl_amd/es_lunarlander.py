@@ -7,10 +7,10 @@ gymrl_lunar_policy_eval plays P policies x E whole episodes in ONE launch.  The 
 critic (no evaluator reads a value) and the alignment gaps (no layer reads them) drift like everything else and are read by
 nobody.  There is no rollout buffer, no optimiser over gradients and no env object.
 
-One generation (no host synchronisation):
+One generation (no host synchronisation, no allocation of the stack: the trainer keeps one for the run):
 
     learner.ask()               gymrl_snes_perturb | gymrl_es_perturb     the centre -> P mirrored policies
-    ops.LunarPolicyStack        gymrl_mlp_pack per layer and policy       the stack in the one-launch forward's weight layout
+    ops.LunarPolicyStack        gymrl_mlp_pack_stack, ONE launch          the stack in the one-launch forward's weight layout
     ops.lunar_policy_eval       gymrl_lunar_policy_eval                   returns f64[P, E]
     learner.tell()              "snes":   gymrl_snes_tell on the float64 returns as they are
                                 "openai": one .to(torch.float32) launch, gymrl_es_shape_grad, gymrl_adam_step — its fitness
@@ -18,7 +18,15 @@ One generation (no host synchronisation):
 
 Training episodes start from streams of their own (seed base_seed + 1_000_003, env ids from 1 << 41, E fresh ones per
 generation, the same E for every policy of a generation: common random numbers), so no training start is an eval() start
-(env ids from 1 << 40)."""
+(env ids from 1 << 40).
+
+Config.policy = "mlprnn" searches the recurrent policy instead: ppg_rnn_lunarlander.py's PSCN -> MLPRNN -> heads network at the
+one width gymrl_lunar_mlprnn_eval takes (Config.hidden_dim is not read), flattened in PPGTrainer's order (critic, trunk, auxiliary
+critic).  That evaluator reads flat parameter vectors as they are, so there is NO packing launch and no copy: ops.MlprnnPolicyStack
+(copy=False) describes the learner's population buffer where it lies and a generation is ask, evaluate, tell.  Every episode
+starts from the hidden state 0.  The observations are read RAW (norm_stats = None): an ES run keeps no running statistics, so a
+policy found here is not PPGTrainer's, which normalises — its checkpoint carries the network under a key of its own
+(`es_net_state_dict`) and its `policy`, and a file of the other policy is refused."""
 import time
 
 import torch
@@ -28,12 +36,23 @@ from .es_cartpole import check_method, make_learner
 from .flat import flatten_module
 from .ppo_lunarlander import ActorCritic
 
+POLICIES = ("mlp", "mlprnn")
+
+
+def check_policy(rest, policy):
+    """A checkpoint's network and learner state fit the policy that wrote them only (one written before there was a choice:
+    the feed-forward one's)."""
+    saved = rest.get("policy", "mlp")
+    if saved != policy:
+        raise ValueError(f"es_lunarlander.ESTrainer: the checkpoint holds a {saved!r} policy, this trainer searches {policy!r}")
+
 
 class Config:
     def __init__(self):
         self.env_name = "LunarLander-v3"
         self.seed = None
-        self.hidden_dim = 64
+        self.policy = "mlp"                  # | "mlprnn": the recurrent PSCN -> MLPRNN -> heads network, raw observations
+        self.hidden_dim = 64                 # "mlp" only
         self.method = "snes"                 # | "openai"
         self.population = 256                # even: population / 2 mirrored pairs
         self.sigma = 0.1                     # "snes": the initial step size of every parameter
@@ -58,16 +77,32 @@ class ESTrainer:
             raise ValueError(f"es_lunarlander.ESTrainer: the evaluator plays LunarLander-v3, not {config.env_name!r}")
         self.device = torch.device(config.device if ":" in str(config.device) else f"cuda:{torch.cuda.current_device()}")
         self.base_seed = 0 if config.seed is None else int(config.seed)
+        if config.policy not in POLICIES:
+            raise ValueError(f"es_lunarlander.ESTrainer: policy is one of {POLICIES}, not {config.policy!r}")
+        self.recurrent = config.policy == "mlprnn"
         state_dim, action_dim, _, _ = ops.env_dims(ops.LUNARLANDER)
         g = torch.random.get_rng_state()
         torch.manual_seed(self.base_seed)
-        self.model = ActorCritic(state_dim, action_dim, config.hidden_dim)
+        if self.recurrent:
+            from .ppg_rnn_lunarlander import ActorCriticPPG
+            self.model = ActorCriticPPG(state_dim, action_dim, hidden_size=64)
+        else:
+            self.model = ActorCritic(state_dim, action_dim, config.hidden_dim)
         torch.random.set_rng_state(g)
-        self.flat_params, _ = flatten_module(self.model, self.device, order=ppo_net.LAYOUT)
-        if not self.model._act_net():
-            raise ValueError(f"es_lunarlander.ESTrainer: the one-launch forward takes no hidden width {config.hidden_dim} "
-                             "(include/gymrl.h)")
+        if self.recurrent:
+            named = [n for n, _ in self.model.named_parameters()]
+            critic = [n for n in named if n.startswith("critic_fc.")]
+            aux = [n for n in named if n.startswith("aux_critic_fc.")]
+            trunk = [n for n in named if n not in critic and n not in aux]
+            self.flat_params, _ = flatten_module(self.model, self.device, order=critic + trunk + aux)      # PPGTrainer's
+            self._act_params = ops.mlprnn_params(self.model)       # the centre in place: views of flat_params
+        else:
+            self.flat_params, _ = flatten_module(self.model, self.device, order=ppo_net.LAYOUT)
+            if not self.model._act_net():
+                raise ValueError(f"es_lunarlander.ESTrainer: the one-launch forward takes no hidden width {config.hidden_dim} "
+                                 "(include/gymrl.h)")
         self.es = make_learner(config, self.flat_params, self.base_seed)
+        self.stack = None                    # the population in the evaluator's layout: one object for the run
         self.last_returns = None             # f64[P, E] on the device: what the last generation's launch returned
         self.history = []                    # (generation, mean population return) at the logged generations
 
@@ -81,10 +116,17 @@ class ESTrainer:
 
     @torch.no_grad()
     def step_generation(self):
-        """ask -> pack -> the evaluator's launch -> tell; nothing read back."""
-        stack = ops.LunarPolicyStack(self.model._act_net(), self.flat_params, self.es.ask())
-        returns = ops.lunar_policy_eval(stack, self.cfg.episodes_per_policy, self.base_seed + self.EVAL_SEED_OFFSET,
-                                        self.train_stream_id0(), want_terminal_obs=False)[0]
+        """ask -> pack ("mlp" only) -> the evaluator's launch -> tell; nothing read back, nothing allocated for the stack after
+        the first generation."""
+        params = self.es.ask()
+        seed, E = self.base_seed + self.EVAL_SEED_OFFSET, self.cfg.episodes_per_policy
+        if self.recurrent:
+            if self.stack is None or self.stack.buffer is not params:
+                self.stack = ops.MlprnnPolicyStack(self.model, self.flat_params, params, copy=False)
+            returns = ops.lunar_mlprnn_eval(self.stack, E, seed, self.train_stream_id0(), want_terminal_obs=False)[0]
+        else:
+            self.stack = ops.LunarPolicyStack(self.model._act_net(), self.flat_params, params, out=self.stack)
+            returns = ops.lunar_policy_eval(self.stack, E, seed, self.train_stream_id0(), want_terminal_obs=False)[0]
         self.es.tell(returns if self.cfg.method == "snes" else returns.to(torch.float32))
         self.last_returns = returns
 
@@ -111,20 +153,32 @@ class ESTrainer:
         """PPOTrainer.evaluate: -> (returns f64, lengths i32, terminated u8), numpy arrays [P, num_episodes], whole deterministic
         episodes on eval()'s streams (env id (1 << 40) + stream_offset + e) in ONE launch.  params = None: the centre (P = 1);
         params = f32[P, n]: a stack of flat parameter vectors in the layout of flat_params.  Moves nothing of the learner's."""
-        policy = self._centre_net()
         if params is not None:
             params = torch.as_tensor(params, dtype=torch.float32).to(self.device)
-            policy = ops.LunarPolicyStack(policy, self.flat_params, params.view(1, -1) if params.dim() == 1 else params)
-        out = ops.lunar_policy_eval(policy, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET,
-                                    self.EVAL_ENV_ID0 + int(stream_offset), want_terminal_obs=False, device=self.device)
+            params = params.view(1, -1) if params.dim() == 1 else params
+        seed, id0 = self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0 + int(stream_offset)
+        if self.recurrent:
+            policy = self._act_params
+            if params is not None:
+                policy = ops.MlprnnPolicyStack(self.model, self.flat_params, params[:, :self.flat_params.numel()])
+            out = ops.lunar_mlprnn_eval(policy, int(num_episodes), seed, id0, want_terminal_obs=False)
+        else:
+            policy = self._centre_net()
+            if params is not None:
+                policy = ops.LunarPolicyStack(policy, self.flat_params, params)
+            out = ops.lunar_policy_eval(policy, int(num_episodes), seed, id0, want_terminal_obs=False, device=self.device)
         return tuple(t.cpu().numpy() for t in out[:3])
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
         """The centre's returns over num_episodes deterministic episodes, ONE launch on eval()'s streams (env ids from 1 << 40)
         -> a list of floats, the float32 casts PPOTrainer.eval() lists under fused_eval."""
-        returns = ops.lunar_policy_eval(self._centre_net(), int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET,
-                                        self.EVAL_ENV_ID0, want_terminal_obs=False, device=self.device)[0]
+        seed = self.base_seed + self.EVAL_SEED_OFFSET
+        if self.recurrent:
+            returns = ops.lunar_mlprnn_eval(self._act_params, int(num_episodes), seed, self.EVAL_ENV_ID0, want_terminal_obs=False)[0]
+        else:
+            returns = ops.lunar_policy_eval(self._centre_net(), int(num_episodes), seed, self.EVAL_ENV_ID0, want_terminal_obs=False,
+                                            device=self.device)[0]
         return returns[0].to(torch.float32).tolist()
 
     def test(self):
@@ -134,14 +188,20 @@ class ESTrainer:
 
     def save_checkpoint(self, path):
         """The actor-critic under ppo_lunarlander's key (`model_state_dict`): a PPOTrainer of the same hidden width loads an
-        ES-found policy with load_checkpoint() and finds no optimiser state."""
+        ES-found policy with load_checkpoint() and finds no optimiser state.  The recurrent network goes under `es_net_state_dict`,
+        a key no other trainer reads: it was found on raw observations and PPGTrainer normalises."""
         from .utils import checkpoint
-        return checkpoint.save_agent(path, {"model": self.model}, {}, es_state_dict=self.es.state_dict(),
-                                     generation=self.es.generation, history=list(self.history), method=self.cfg.method)
+        return checkpoint.save_agent(path, {self._net_key(): self.model}, {}, es_state_dict=self.es.state_dict(),
+                                     generation=self.es.generation, history=list(self.history), method=self.cfg.method,
+                                     policy=self.cfg.policy)
+
+    def _net_key(self):
+        return "es_net" if self.recurrent else "model"
 
     def load_checkpoint(self, path):
         from .utils import checkpoint
-        rest = checkpoint.load_agent(path, {"model": self.model}, {})
+        check_policy(torch.load(path, map_location="cpu", weights_only=False), self.cfg.policy)       # before a key is missed
+        rest = checkpoint.load_agent(path, {self._net_key(): self.model}, {})
         check_method(rest, self.cfg.method)
         self.es.load_state_dict(rest["es_state_dict"])
         self.history = [tuple(h) for h in rest.get("history", [])]

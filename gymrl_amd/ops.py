@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   LunarEvalArgs, MlpDesc, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -923,13 +923,25 @@ LUNAR_MAX_STEPS = 1000
 
 class LunarPolicyStack:
     """P policies of one FusedMLP's shape for lunar_policy_eval, in ONE buffer f32[P, stride]: per row every stage's packed
-    weight (gymrl_mlp_pack's image) and then every stage's bias, each from a multiple of four floats on.  params f32[P, n]: flat
-    parameter vectors in the layout of `flat`, the buffer the network's own tensors are views of.  stride (floats, a multiple of
-    4): None = tight."""
+    weight (gymrl_mlp_pack's image) and then every stage's bias, each from a multiple of four floats on, written by ONE
+    gymrl_mlp_pack_stack launch.  params f32[P, >= n]: flat parameter vectors in the layout of `flat`, the buffer the network's
+    own tensors are views of; its rows may be strided (a learner's population buffer is read where it lies).  stride (floats, a
+    multiple of 4): None = tight.  out: a LunarPolicyStack of the same shape from an earlier call — its buffer and descriptor
+    are filled again and `out` itself is returned, nothing is allocated on the device."""
 
-    def __init__(self, fused, flat, params, stride=None):
+    def __new__(cls, fused, flat, params, stride=None, out=None):
+        if out is None:
+            return super().__new__(cls)
+        if type(out) is not cls:
+            raise ValueError("LunarPolicyStack: out is a LunarPolicyStack of an earlier call")
+        if params.dim() == 2 and params.shape[0] != out.P:
+            raise ValueError(f"LunarPolicyStack: out holds a stack of another shape ({out.P} policies, params {params.shape[0]})")
+        return out                                  # __init__ runs on it with the same arguments
+
+    def __init__(self, fused, flat, params, stride=None, out=None):
         mods = [m for m, _, _, _ in fused.stages]
-        if params.dim() != 2 or params.shape[1] < flat.numel() or params.dtype != torch.float32 or not params.is_cuda:
+        if (params.dim() != 2 or params.shape[1] < flat.numel() or params.dtype != torch.float32 or not params.is_cuda
+                or (params.shape[1] > 1 and params.stride(1) != 1)):
             raise ValueError("LunarPolicyStack: params is a stack f32[P, n] of flat buffers in the layout of `flat`, on the device")
         if any(m.bias is None for m in mods):
             raise ValueError("LunarPolicyStack: every layer carries a bias")
@@ -940,17 +952,18 @@ class LunarPolicyStack:
         sizes = [int(lib().gymrl_mlp_packed_floats(*m.weight.shape)) for m in mods] + [(m.bias.numel() + 3) // 4 * 4 for m in mods]
         at = [sum(sizes[:k]) for k in range(len(sizes))]
         tight = sum(sizes)
-        self.stride = tight if stride is None else int(stride)
-        if self.stride < tight or self.stride % 4:
-            raise ValueError(f"LunarPolicyStack: the stride is a multiple of 4 floats and at least {tight}")
-        params = params.contiguous()
-        self.P, L = params.shape[0], len(mods)
-        self.buffer = torch.zeros(self.P, self.stride, dtype=torch.float32, device=params.device)
-        for p in range(self.P):
-            for k, m in enumerate(mods):
-                W = params[p, offs[k]:offs[k] + m.weight.numel()].view(m.weight.shape)
-                mlp_pack(W, self.buffer[p, at[k]:at[k] + sizes[k]])
-                self.buffer[p, at[L + k]:at[L + k] + m.bias.numel()] = params[p, offs[L + k]:offs[L + k] + m.bias.numel()]
+        P, L = params.shape[0], len(mods)
+        shape = (P, tuple(tuple(m.weight.shape) for m in mods), params.device)
+        if out is not None:
+            if out._shape != shape or (stride is not None and int(stride) != out.stride):
+                raise ValueError("LunarPolicyStack: out holds a stack of another shape (policies, layers, stride or device)")
+        else:
+            self.stride = tight if stride is None else int(stride)
+            if self.stride < tight or self.stride % 4:
+                raise ValueError(f"LunarPolicyStack: the stride is a multiple of 4 floats and at least {tight}")
+            self.P, self._shape = P, shape
+            self.buffer = torch.zeros(P, self.stride, dtype=torch.float32, device=params.device)
+        mlp_pack_stack(params, [(*m.weight.shape, offs[k], offs[L + k], at[k], at[L + k]) for k, m in enumerate(mods)], self.buffer)
         d = MlpDesc()
         d.n_stages = L
         base = self.buffer.data_ptr()
@@ -1016,19 +1029,34 @@ class MlprnnPolicyStack:
     """P policies of one PSCN -> MLPRNN -> heads network for lunar_mlprnn_eval, in ONE buffer f32[P, stride]: row p is policy p's
     flat parameter vector.  params f32[P, n]: flat parameter vectors in the layout of `flat`, the buffer `net`'s own tensors are
     views of (the trainers' flat_params order).  stride (floats, a multiple of 4): None = n rounded up.  norm_stats f64[P, 26]
-    (RunningMeanStd.stats per policy), f64[26] (one set shared by all) or None.  `desc` points at row 0."""
+    (RunningMeanStd.stats per policy), f64[26] (one set shared by all) or None.  `desc` points at row 0.
+    copy = False describes `params` in place, with no launch: f32[P, >= n] whose rows are dense, 16-byte aligned and a multiple
+    of four floats apart (a learner's population buffer, es.ask()); `buffer` is then `params` itself, `desc` points into its
+    rows and the stack is as current as the caller keeps that tensor."""
 
-    def __init__(self, net, flat, params, norm_stats=None, stride=None):
-        if params.dim() != 2 or params.shape[1] != flat.numel() or params.dtype != torch.float32 or not params.is_cuda:
-            raise ValueError("MlprnnPolicyStack: params is a stack f32[P, n] of flat buffers in the layout of `flat`, on the device")
+    def __init__(self, net, flat, params, norm_stats=None, stride=None, copy=True):
         n = flat.numel()
         tight = (n + 3) // 4 * 4
-        self.stride = tight if stride is None else int(stride)
-        if self.stride < tight or self.stride % 4:
-            raise ValueError(f"MlprnnPolicyStack: the stride is a multiple of 4 floats and at least {tight}")
-        self.P = params.shape[0]
-        self.buffer = torch.zeros(self.P, self.stride, dtype=torch.float32, device=params.device)
-        self.buffer[:, :n] = params
+        if copy:
+            if params.dim() != 2 or params.shape[1] != n or params.dtype != torch.float32 or not params.is_cuda:
+                raise ValueError("MlprnnPolicyStack: params is a stack f32[P, n] of flat buffers in the layout of `flat`, on the device")
+            self.stride = tight if stride is None else int(stride)
+            if self.stride < tight or self.stride % 4:
+                raise ValueError(f"MlprnnPolicyStack: the stride is a multiple of 4 floats and at least {tight}")
+            self.P = params.shape[0]
+            self.buffer = torch.zeros(self.P, self.stride, dtype=torch.float32, device=params.device)
+            self.buffer[:, :n] = params
+        else:
+            if (params.dim() != 2 or params.shape[0] < 1 or params.shape[1] < n or params.dtype != torch.float32 or not params.is_cuda
+                    or (params.shape[1] > 1 and params.stride(1) != 1)):
+                raise ValueError("MlprnnPolicyStack: in place, params is f32[P, >= n] with dense rows in the layout of `flat`, "
+                                 "on the device")
+            self.P = params.shape[0]
+            self.stride = params.stride(0) if self.P > 1 else (params.shape[1] + 3) // 4 * 4
+            if self.stride < tight or self.stride % 4 or params.data_ptr() % 16 or (stride is not None and int(stride) != self.stride):
+                raise ValueError(f"MlprnnPolicyStack: in place, the rows are 16-byte aligned and a multiple of 4 floats apart, at "
+                                 f"least {tight}; `stride` is the tensor's own")
+            self.buffer = params
         own = mlprnn_params(net)
         d = MlprnnParams()
         lo, base = flat.data_ptr(), self.buffer.data_ptr()
@@ -1363,6 +1391,49 @@ def mlp_pack(W, packed=None):
     elif packed.numel() != n:
         raise ValueError("packed buffer has the wrong size")
     check(lib().gymrl_mlp_pack(_ptr(W, torch.float32), out_dim, in_dim, _ptr(packed, torch.float32), _stream()), "gymrl_mlp_pack")
+    return packed
+
+
+def _dense_rows(t, who, what):
+    """(pointer, floats between rows) of a float32 [P, n] tensor on the device whose rows are dense (they may be strided)."""
+    if t.dim() != 2 or t.shape[0] < 1:
+        raise ValueError(f"{who}: {what} is f32[P, n], got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{who}: {what} lives on the MI355X: got a CPU tensor (there is no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {what}: expected torch.float32, got {t.dtype}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{who}: the rows of {what} must be dense")
+    stride = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    if stride < t.shape[1]:
+        raise ValueError(f"{who}: the rows of {what} overlap")
+    return t.data_ptr(), stride
+
+
+def mlp_pack_stack(params, layers, packed):
+    """gymrl_mlp_pack_stack (include/gymrl.h): P flat parameter vectors x len(layers) layers -> each row of `packed` in ONE launch.
+    params f32[P, n] and packed f32[P, m], rows dense, possibly strided; layers: (out_dim, in_dim, w_off, b_off, w_at, b_at) per
+    layer, floats into a params row (the weight [out_dim, in_dim] row-major, the bias) and into a packed row (mlp_pack's image,
+    the bias padded with zeros to a multiple of four).  Floats of `packed` outside these ranges are not written.  -> packed."""
+    who = "mlp_pack_stack"
+    a = MlpPackStackArgs()
+    a.params, a.params_stride = _dense_rows(params, who, "params")
+    a.packed, a.packed_stride = _dense_rows(packed, who, "packed")
+    if packed.shape[0] != params.shape[0] or packed.device != params.device:
+        raise ValueError(f"{who}: packed holds {packed.shape[0]} rows on {packed.device}, params {params.shape[0]} on {params.device}")
+    if not 0 < len(layers) <= MLP_MAX_STAGES:
+        raise ValueError(f"{who}: 1..{MLP_MAX_STAGES} layers")
+    a.P, a.n_layers = params.shape[0], len(layers)
+    for e, (out_dim, in_dim, w_off, b_off, w_at, b_at) in zip(a.layer, layers):
+        e.out_dim, e.in_dim, e.w_off, e.b_off, e.w_at, e.b_at = (int(v) for v in (out_dim, in_dim, w_off, b_off, w_at, b_at))
+        if e.out_dim < 1 or e.in_dim < 1:
+            raise ValueError(f"{who}: a layer is {e.out_dim} x {e.in_dim}")
+        # the library holds the ranges to the strides; the LAST row ends with the tensor, not with the stride
+        if max(e.w_off + e.out_dim * e.in_dim, e.b_off + e.out_dim) > params.shape[1]:
+            raise ValueError(f"{who}: a layer's parameters end beyond a row of params ({params.shape[1]} floats)")
+        if max(e.w_at + lib().gymrl_mlp_packed_floats(e.out_dim, e.in_dim), e.b_at + (e.out_dim + 3) // 4 * 4) > packed.shape[1]:
+            raise ValueError(f"{who}: a layer's packed range ends beyond a row of packed ({packed.shape[1]} floats)")
+    check(lib().gymrl_mlp_pack_stack(C.byref(a), _stream()), "gymrl_mlp_pack_stack")
     return packed
 
 

@@ -567,6 +567,46 @@ int gymrl_mlp_pack(const float* W, int out_dim, int in_dim, float* packed, void*
 int gymrl_mlp_forward(const float* x, int n_rows, int in_dim, const gymrl_mlp_desc* desc,
                       void* stream);
 
+/* ======================================================= MLP policy stacks == */
+/*
+ * gymrl_mlp_pack for a POPULATION: P flat parameter vectors x n_layers layers into the packed layout, with the biases, in ONE
+ * launch (csrc/pack_stack.hip) — what the one-launch evaluators read as a stack of policies (gymrl_lunar_policy_eval with
+ * policy_stride = packed_stride and a gymrl_mlp_desc whose W / b point into row 0 at w_at / b_at).
+ *   Weights   for every policy p and layer k the gymrl_mlp_packed_floats(out_dim, in_dim) floats from
+ *             packed + p * packed_stride + w_at are exactly what gymrl_mlp_pack writes for the weight
+ *             params + p * params_stride + w_off (f32[out_dim][in_dim] row-major):
+ *             P[tile][kblock][lane][c] = W[16 tile + (lane & 15)][16 kblock + 4 (lane >> 4) + c], zeros beyond out_dim and
+ *             beyond in_dim, K rounded up to 64.
+ *   Biases    the out_dim floats from b_at are params[p][b_off ..]; the floats up to the next multiple of four are 0.0f.
+ *   Untouched no float of a packed row outside these 2 n_layers ranges is written: a caller's padding and the tail of a reused
+ *             buffer survive.
+ *   Copy only every float written is a copy or a zero, no arithmetic: the bits of n_layers gymrl_mlp_pack launches and bias
+ *             copies per policy (tests/test_pack_stack_gpu.py).
+ * Kernel: one thread per output float4, gridDim.y = P, gridDim.x covers a row's float4s, the layer table by value in the kernel
+ * arguments; no LDS, no atomics, no workgroup waits for another; one coalesced 16-byte store per lane; the weight reads are
+ * strided by in_dim across lanes as gymrl_mlp_pack's are (not staged through LDS).
+ * -EINVAL before any launch: NULL args, params or packed; P < 1 or P > 65535; n_layers outside 1..GYMRL_MLP_MAX_STAGES; an
+ * out_dim or in_dim < 1 or > GYMRL_MLP_MAX_WIDTH (what gymrl_mlp_forward takes between stages); a negative offset;
+ * w_off + out_dim * in_dim or b_off + out_dim beyond params_stride; w_at, b_at or packed_stride not a multiple of 4; a packed
+ * range that ends beyond packed_stride; two packed ranges of a row that overlap; packed not 16-byte aligned; params not 4-byte.
+ */
+typedef struct {
+  int out_dim, in_dim;
+  int64_t w_off, b_off;                    /* floats into a params row: W f32[out_dim][in_dim] row-major, b f32[out_dim] */
+  int64_t w_at, b_at;                      /* floats into a packed row, each % 4 == 0 */
+} gymrl_mlp_pack_layer;
+typedef struct {
+  int P;                                   /* policies, 1..65535 */
+  int n_layers;                            /* 1..GYMRL_MLP_MAX_STAGES */
+  const float* params;                     /* f32[P][params_stride]: row p = policy p's flat parameter vector */
+  int64_t params_stride;                   /* floats between rows */
+  float* packed;                           /* f32[P][packed_stride] out, 16-byte aligned */
+  int64_t packed_stride;                   /* floats between rows, % 4 == 0 */
+  gymrl_mlp_pack_layer layer[GYMRL_MLP_MAX_STAGES];
+} gymrl_mlp_pack_stack_args;
+size_t gymrl_mlp_pack_stack_args_bytes(void);  /* sizeof(gymrl_mlp_pack_stack_args) */
+int gymrl_mlp_pack_stack(const gymrl_mlp_pack_stack_args* args, void* stream);
+
 /* ======================================================== persistent rollout */
 /*
  * P4: PPOTrainer.collect_rollout — ppo_lunarlander.py:198-231 — for LunarLander-v3 as one launch per
