@@ -119,6 +119,14 @@ class LunarEvalArgs(C.Structure):
                 ("terminal_obs", C.c_void_p)]
 
 
+class LunarCollectArgs(C.Structure):
+    _c_name_ = "gymrl_lunar_collect_args"
+    _fields_ = ([("N", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("env_id0", C.c_int64), ("counter0", C.c_uint64),
+                 ("gamma", C.c_double)] +
+                [(n, C.c_void_p) for n in ("norm_stats", "reward_stats", "R", "states", "act", "logp", "value", "rew", "done",
+                                          "dw", "live", "ep_ret", "lengths")])
+
+
 class SacActorParams(C.Structure):
     _c_name_ = "gymrl_sac_actor_params"   # fc1, fc2, mean, log_std
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
@@ -504,6 +512,8 @@ SIGNATURES = {
     "gymrl_lunar_policy_eval": (_i, [_P(LunarEvalArgs), _P(MlpDesc), _vp]),
     "gymrl_lunar_mhc_eval": (_i, [_P(LunarEvalArgs), _P(MhcPolicy), _vp]),
     "gymrl_lunar_mlprnn_eval": (_i, [_P(LunarEvalArgs), _P(MlprnnParams), _vp, _i64, _vp, _vp]),
+    "gymrl_lunar_mlprnn_collect": (_i, [_P(LunarCollectArgs), _P(MlprnnParams), _vp]),
+    "gymrl_lunar_collect_args_bytes": (_sz, []),
     "gymrl_lin_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_lin_fwd": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gymrl_lin_bwd_input": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -36,4 +36,50 @@ __device__ __forceinline__ void clamped_policy(const float (&z)[A], float (&p)[A
   }
 }
 
+// Categorical(softmax(z)) of the acting step, stated once for gymrl_mlprnn_act and the one-launch recurrent collection
+// (collect_lunar_rnn.hip) -> the action; lp = its log-prob, p = softmax(z).
+//   deterministic   probs.argmax(): the first maximum
+//   else            torch.multinomial(probs / sum, 1): argmax p2 / q with the first maximum winning, q ~ Exp(1) — `noise_row`
+//                   (A explicit draws) or, without one, Philox under the keys of gymrl_categorical_sample (policy_device.hpp):
+//                   (seed, env, counter, RNG_POLICY | ...), q = -log(u) with u in (0, 1]
+template <int A>
+__device__ __forceinline__ int clamped_policy_act(const float (&z)[A], const float* __restrict__ noise_row, uint64_t seed,
+                                                  uint64_t env, uint64_t counter, int deterministic, float& lp, float (&p)[A]) {
+  float S, p2[A], L[A], c[A];
+  bool inb[A];
+  clamped_policy<A>(z, p, S, p2, L, c, inb);
+  int a = 0;
+  if (deterministic) {
+    float best = p[0];
+#pragma unroll
+    for (int k = 1; k < A; ++k) if (p[k] > best) { best = p[k]; a = k; }
+  } else {
+    float qv[A];
+    if (noise_row) {
+#pragma unroll
+      for (int k = 0; k < A; ++k) qv[k] = noise_row[k];
+    } else {
+#pragma unroll
+      for (int blk = 0; blk < (A + 3) / 4; ++blk) {
+        const u32x4 rn = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), (uint32_t)counter,
+                                    RNG_POLICY | ((uint32_t)((counter >> 32) & 0x3FFFFFu) << 2) | (uint32_t)blk);
+        const uint32_t wv[4] = {rn.x, rn.y, rn.z, rn.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (blk * 4 + k < A) qv[blk * 4 + k] = -det_logf(u01f_open0(wv[k]));
+      }
+    }
+    float best = p2[0] / qv[0];
+#pragma unroll
+    for (int k = 1; k < A; ++k) {
+      const float cand = p2[k] / qv[k];
+      if (cand > best) { best = cand; a = k; }
+    }
+  }
+  lp = L[0];
+#pragma unroll
+  for (int k = 1; k < A; ++k) if (a == k) lp = L[k];
+  return a;
+}
+
 }  // namespace gymrl

@@ -67,43 +67,11 @@ __global__ __launch_bounds__(kThreads) void mlprnn_act_kernel(const float* __res
   if (tid < kRows) {
     const int64_t row = row0 + tid;
     if (row >= N || (live && !live[row])) return;
-    float z[A], p[A], S, p2[A], L[A], c[A];
-    bool inb[A];
+    float z[A], p[A], lp;
 #pragma unroll
     for (int k = 0; k < A; ++k) z[k] = zl[tid][k];
-    clamped_policy<A>(z, p, S, p2, L, c, inb);
-    int a = 0;
-    if (deterministic) {                               // probs.argmax(): the first maximum
-      float best = p[0];
-#pragma unroll
-      for (int k = 1; k < A; ++k) if (p[k] > best) { best = p[k]; a = k; }
-    } else {                                           // torch.multinomial(probs / sum, 1): argmax p2 / q, q ~ Exp(1)
-      float qv[A];
-      if (noise_exp) {
-#pragma unroll
-        for (int k = 0; k < A; ++k) qv[k] = noise_exp[row * A + k];
-      } else {                                         // the keys of gymrl_categorical_sample (policy_device.hpp)
-        const uint64_t env = (uint64_t)(env_id0 + row);
-#pragma unroll
-        for (int blk = 0; blk < (A + 3) / 4; ++blk) {
-          const u32x4 rn = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), (uint32_t)counter,
-                                      RNG_POLICY | ((uint32_t)((counter >> 32) & 0x3FFFFFu) << 2) | (uint32_t)blk);
-          const uint32_t wv[4] = {rn.x, rn.y, rn.z, rn.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (blk * 4 + k < A) qv[blk * 4 + k] = -det_logf(u01f_open0(wv[k]));
-        }
-      }
-      float best = p2[0] / qv[0];
-#pragma unroll
-      for (int k = 1; k < A; ++k) {
-        const float cand = p2[k] / qv[k];
-        if (cand > best) { best = cand; a = k; }
-      }
-    }
-    float lp = L[0];
-#pragma unroll
-    for (int k = 1; k < A; ++k) if (a == k) lp = L[k];
+    const int a = clamped_policy_act<A>(z, noise_exp ? noise_exp + row * A : nullptr, seed, (uint64_t)(env_id0 + row), counter,
+                                        deterministic, lp, p);
     act_out[row] = a;
     logp_out[row] = lp;
     value_out[row] = zl[tid][A];

@@ -262,16 +262,7 @@ __global__ void running_norm_kernel(const float* __restrict__ x, const uint8_t* 
   for (int i = 0; valid && i < N; ++i) {
     if (live && !live[i]) continue;
     const float xv = x[(size_t)i * D + k];
-    if (update) {
-      n += 1.0;
-      if (n == 1.0) { mean = xv; std = (double)xv; }                          // :15-17
-      else {
-        const float old_mean = mean;
-        mean = old_mean + (xv - old_mean) / (float)n;                         // float32 mean (:19)
-        S = S + (double)((xv - old_mean) * (xv - mean));                      // f32 product into f64 S (:20)
-        std = sqrt(S / n);                                                    // :21
-      }
-    }
+    if (update) running_norm_update(xv, n, mean, S, std);                      // :13-21
     y[(size_t)i * D + k] = running_norm_point(xv, mean, std);                // :33
   }
   __syncthreads();          // every lane has read stats[0] before lane 0 rewrites it
@@ -288,18 +279,7 @@ __global__ void reward_scaling_kernel(const float* __restrict__ r, const uint8_t
   double S = stats[3], std = stats[4];
   for (int i = 0; i < N; ++i) {
     if (live && !live[i]) continue;
-    const double rv = (double)r[i];
-    R[i] = gamma * R[i] + rv;                                                 // :46
-    const float xv = (float)R[i];                                             // update() casts to float32 (:13)
-    n += 1.0;
-    if (n == 1.0) { mean = xv; std = (double)xv; }
-    else {
-      const float old_mean = mean;
-      mean = old_mean + (xv - old_mean) / (float)n;
-      S = S + (double)((xv - old_mean) * (xv - mean));
-      std = sqrt(S / n);
-    }
-    y[i] = (float)(rv / (std + 1e-8));                                        // :48
+    y[i] = reward_scaling_step(r[i], gamma, R[i], n, mean, S, std);           // :44-49
     if (done && done[i]) R[i] = 0.0;                                          // reset() at the next episode start
   }
   stats[0] = n; stats[2] = (double)mean; stats[3] = S; stats[4] = std;

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   LunarCollectArgs, LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -1106,6 +1106,42 @@ def lunar_mlprnn_eval(policy, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS,
     check(lib().gymrl_lunar_mlprnn_eval(C.byref(a), C.byref(desc), _ptr(norm_stats, torch.float64, True), norm_stride,
                                         _ptr(h_final, torch.float32, True), _stream()), "gymrl_lunar_mlprnn_eval")
     return out + (h_final,) if want_h_final else out
+
+
+LUNAR_COLLECT_MAX_ENVS = 16        # gymrl_lunar_mlprnn_collect: one workgroup's rows (the statistics are sequential in env order)
+
+
+def lunar_mlprnn_collect(policy, N, cap, seed, env_id0, counter0, norm_stats, reward_stats, R, gamma, out=None):
+    """One collection round of the PPG-RNN / PPO-RNN trainers as ONE launch (include/gymrl.h gymrl_lunar_mlprnn_collect): N <= 16
+    LunarLander-v3 episodes of envs env_id0 + i under `seed` from their reset until all have ended or `cap` steps have passed,
+    sampled under the Philox counters counter0 + t.  policy: mlprnn_params(net).  norm_stats f64[26], reward_stats f64[5]
+    (RunningMeanStd.stats) and R f64[N] are updated in place.  -> dict of the round's slabs in collect_round()'s layout: states
+    f32[cap + 1, N, 8], act i32 / logp f32 / value f32 / live u8 [cap + 1, N], rew f32 / done u8 / dw u8 [cap, N], ep_ret f32[N],
+    lengths i32[N]; rows of ended envs keep what they held (zeros in a fresh dict).  out: such a dict to write into."""
+    N, cap = int(N), int(cap)
+    for name, t, n in (("norm_stats", norm_stats, LUNAR_NORM_STATS), ("reward_stats", reward_stats, 5), ("R", R, N)):
+        _ptr(t, torch.float64)
+        if t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"lunar_mlprnn_collect: {name} is f64[{n}], got {tuple(t.shape)}")
+    if not 1 <= N <= LUNAR_COLLECT_MAX_ENVS:
+        raise ValueError(f"lunar_mlprnn_collect: 1 <= N <= {LUNAR_COLLECT_MAX_ENVS} envs (one workgroup), got {N}")
+    if not 1 <= cap <= LUNAR_MAX_STEPS:
+        raise ValueError(f"lunar_mlprnn_collect: 1 <= cap <= {LUNAR_MAX_STEPS}, got {cap}")
+    dev = norm_stats.device
+    shapes = {"states": ((cap + 1, N, 8), torch.float32), "act": ((cap + 1, N), torch.int32), "logp": ((cap + 1, N), torch.float32),
+              "value": ((cap + 1, N), torch.float32), "rew": ((cap, N), torch.float32), "done": ((cap, N), torch.uint8),
+              "dw": ((cap, N), torch.uint8), "live": ((cap + 1, N), torch.uint8), "ep_ret": ((N,), torch.float32),
+              "lengths": ((N,), torch.int32)}
+    if out is None:
+        out = {k: torch.zeros(*s, dtype=dt, device=dev) for k, (s, dt) in shapes.items()}
+    a = LunarCollectArgs()
+    a.N, a.cap, a.seed, a.env_id0, a.counter0, a.gamma = N, cap, int(seed), int(env_id0), int(counter0), float(gamma)
+    a.norm_stats, a.reward_stats, a.R = norm_stats.data_ptr(), reward_stats.data_ptr(), R.data_ptr()
+    for k, (s, dt) in shapes.items():
+        _need_shape(out[k], s, k)
+        setattr(a, k, _ptr(out[k], dt).value)
+    check(lib().gymrl_lunar_mlprnn_collect(C.byref(a), C.byref(policy), _stream()), "gymrl_lunar_mlprnn_collect")
+    return out
 
 
 # ============================================================== off-policy ===

@@ -60,6 +60,7 @@ class Config:
         self.num_envs = 1                  # envs stepped together; one round = one episode of each
         self.episodes_per_minibatch = 1    # G episodes per optimiser step (loss = mean over episodes); 1 = the reference
         self.fused_eval = False            # LunarLander: eval() as ONE launch (gymrl_lunar_mlprnn_eval) on the loop's own streams
+        self.fused_collect = False         # LunarLander, num_envs <= 16: a collection round as ONE launch (gymrl_lunar_mlprnn_collect)
 
 
 def initialize_weights(layer):
@@ -267,6 +268,9 @@ class PPGTrainer:
             raise ValueError(f"batch_size ({B}) must be a multiple of num_envs ({N})")
         if G < 1 or B % G:
             raise ValueError(f"batch_size ({B}) must be a multiple of episodes_per_minibatch ({G})")
+        if getattr(config, "fused_collect", False) and N > ops.LUNAR_COLLECT_MAX_ENVS:
+            raise ValueError(f"fused_collect plays a round in one workgroup: num_envs ({N}) must be at most "
+                             f"{ops.LUNAR_COLLECT_MAX_ENVS}")
         self.N, self.G = N, G
         self.device = torch.device(config.device if ":" in str(config.device) else f"cuda:{torch.cuda.current_device()}")
         self.base_seed = 0 if config.seed is None else int(config.seed)
@@ -348,7 +352,10 @@ class PPGTrainer:
     @torch.no_grad()
     def collect_round(self):
         """One round: every env plays one episode (:434-471 for N envs).  Appends the compacted episodes to the batch
-        and returns their raw returns and lengths (host lists, env order)."""
+        and returns their raw returns and lengths (host lists, env order).  With Config.fused_collect the step loop below is
+        ONE launch (gymrl_lunar_mlprnn_collect, csrc/collect_lunar_rnn.hip) that writes the same slabs, statistics and returns
+        bit for bit; the loop runs whenever the launch cannot play the round (explicit noise, another env).  self.env is not
+        stepped by the launch: every round starts with a reset, so nothing reads its state."""
         cfg, env, N, D, dev = self.cfg, self.env, self.N, self.state_dim, self.device
         # `for step in range(cfg.max_steps)` (:445): a round stops storing an env's episode after max_steps steps.  Every
         # round starts with a real reset of every env, so no cut episode has to be abandoned inside the stepper
@@ -362,11 +369,20 @@ class PPGTrainer:
         terminated, truncated = z(N, dtype=torch.uint8), z(N, dtype=torch.uint8)
         ep_ret = z(N)
         seed = self.base_seed if cfg.seed is not None else self.base_seed + 0x9E3779B1 * (self.round_count + 1)
+        c0 = self.round_count * (Tcap + 1)
+        if getattr(cfg, "fused_collect", False) and self._parity_noise is None and self._eval_fusable():
+            env.seed = seed & 0x7FFFFFFFFFFFFFFF               # what reset(seed=...) leaves: choose_action() draws under it
+            self.reward_scaler.reset()
+            slabs = dict(states=states, act=act, logp=logp, value=value, rew=rew, done=done, dw=dw, live=live, ep_ret=ep_ret,
+                         lengths=z(N, dtype=torch.int32))
+            ops.lunar_mlprnn_collect(self._act_params, N, Tcap, env.seed, env.env_id0, c0, self.state_norm.running_ms.stats,
+                                     self.reward_scaler.running_ms.stats, self.reward_scaler.R, cfg.gamma, out=slabs)
+            lengths = slabs["lengths"].cpu().numpy().astype(np.int64)
+            return self._compact(int(lengths.max()), lengths, ep_ret, states, act, rew, done, dw, logp, value)
         env.reset(raw_obs, seed=seed & 0x7FFFFFFFFFFFFFFF)
         self.reward_scaler.reset()
         hidden = z(N, 64)
         live[0].fill_(1)
-        c0 = self.round_count * (Tcap + 1)
         noise = (lambda t: self._parity_noise(self.round_count, t)) if self._parity_noise is not None else (lambda t: None)
         ops.running_norm_masked(raw_obs, live[0], self.state_norm.running_ms.stats, out=states[0])
         self._act(states[0], hidden, live[0], c0, noise(0), act[0], logp[0], value[0])
@@ -385,9 +401,12 @@ class PPGTrainer:
             t += 1
             if t % K == 0 and not bool(live[t].any()):
                 break
-        T = t
-        live_h = live[:T].cpu().numpy().astype(bool)
-        lengths = live_h.sum(0).astype(np.int64)
+        lengths = live[:t].cpu().numpy().astype(bool).sum(0).astype(np.int64)
+        return self._compact(t, lengths, ep_ret, states, act, rew, done, dw, logp, value)
+
+    def _compact(self, T, lengths, ep_ret, states, act, rew, done, dw, logp, value):
+        """The round's [T, N] slabs -> the episode-major chunk of the batch; returns the raw returns and the lengths."""
+        N, dev = self.N, self.device
         idx = np.concatenate([np.arange(n) * N + i for i, n in enumerate(lengths)])
         sel = torch.from_numpy(idx).to(dev)                  # row (t, i) of the [T, N] slabs, episode-major
         flat = lambda x, t0=0: x[t0:T + t0].reshape(T * N, *x.shape[2:]).index_select(0, sel)   # noqa: E731

@@ -33,6 +33,7 @@ class Config:
         self.num_envs = 1
         self.episodes_per_minibatch = 1
         self.fused_eval = False            # eval() as ONE launch (gymrl_lunar_mlprnn_eval), as in gymrl_amd.ppg_rnn_lunarlander
+        self.fused_collect = False         # num_envs <= 16: a collection round as ONE launch (gymrl_lunar_mlprnn_collect), likewise
 
 
 class ActorCritic(_ppg.ActorCriticPPG):

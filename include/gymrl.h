@@ -728,6 +728,40 @@ int gymrl_lunar_mhc_eval(const gymrl_lunar_eval_args* args, const struct gymrl_m
  */
 int gymrl_lunar_mlprnn_eval(const gymrl_lunar_eval_args* args, const gymrl_mlprnn_params* policy,
                             const double* norm_stats, int64_t norm_stride, float* h_final, void* stream);
+/*
+ * gymrl_lunar_mlprnn_collect: one collection round of the PPG-RNN / PPO-RNN trainers (collect_round() of
+ * ppg_rnn_lunarlander.py) as ONE launch of ONE workgroup (csrc/collect_lunar_rnn.hip): N <= 16 LunarLander-v3 episodes (envs
+ * env_id0 + i under `seed`, episode 0, gymrl_env_reset's arithmetic) from their reset until every episode has ended or `cap`
+ * steps have passed, the worlds and the GRU states (from 0) on chip throughout.  Per step t, in the loop's order: gymrl_env_step
+ * under act[t] for the envs live at t; done[t] = terminated | truncated (the env's own 1000-step limit; a `cap` below it ends
+ * the round without a done flag), dw[t] = terminated; ep_ret += reward in float32; gymrl_running_norm_masked(update = 1) over
+ * the step's (possibly terminal) observations, live rows in env order -> states[t + 1]; gymrl_reward_scaling_masked (no done
+ * flags: R is not zeroed where an episode ends) -> rew[t]; gymrl_mlprnn_act's sampling branch with counter counter0 + t + 1,
+ * masked by live at t (an env whose episode just ended gets one more forward, on its terminal state: value[t + 1] is its stored
+ * next value) -> act / logp / value[t + 1]; live[t + 1] = live[t] & !done[t].  Row 0 is the reset: states[0] the normalised
+ * first observations, act / logp / value[0] the draw with counter0.  There is no explicit-noise input.
+ *   slabs, time-major with N columns: states f32[cap + 1][N][8], act i32 / logp f32 / value f32 / live u8 [cap + 1][N],
+ *   rew f32 / done u8 / dw u8 [cap][N]; a row (t, i) is written only while env i is live (live: 1 or 0 for every t reached).
+ *   ep_ret f32[N] the raw return, lengths i32[N] the steps each env took.
+ *   norm_stats f64[2 + 3 * 8], reward_stats f64[2 + 3] (RunningMeanStd.stats) and R f64[N] are read and updated in place.
+ * Bit-identical to the step-by-step sequence above in every output.  The two statistics consume their rows one after the other
+ * in env order, which one workgroup reproduces and several cannot: N <= 16 is the limit.  The workgroup leaves on one LDS word
+ * behind a barrier every thread reaches, after at most cap + 1 iterations; no atomics, nothing waits for another workgroup.
+ * -EINVAL before any launch: NULL args, policy, member of either or output, N outside 1..16, cap outside 1..1000, env_id0 < 0,
+ * states not 16-byte, a float64 buffer not 8-byte or a 4-byte slab not 4-byte aligned, a weight gymrl_mlprnn_act reads 16 bytes
+ * at a time that is not 16-byte aligned.
+ */
+typedef struct {
+  int N, cap;
+  uint64_t seed; int64_t env_id0; uint64_t counter0;
+  double gamma;
+  double* norm_stats; double* reward_stats; double* R;
+  float* states; int32_t* act; float* logp; float* value;
+  float* rew; uint8_t* done; uint8_t* dw; uint8_t* live;
+  float* ep_ret; int32_t* lengths;
+} gymrl_lunar_collect_args;
+int gymrl_lunar_mlprnn_collect(const gymrl_lunar_collect_args* args, const gymrl_mlprnn_params* policy, void* stream);
+size_t gymrl_lunar_collect_args_bytes(void);  /* sizeof(gymrl_lunar_collect_args) */
 
 /* ================================================ low-latency Linear layers == */
 /*
