@@ -396,6 +396,11 @@ class MountainCarNetEvalArgs(C.Structure):
                 ("lengths", C.c_void_p), ("terminated", C.c_void_p), ("final_obs", C.c_void_p)]
 
 
+class AcrobotNetEvalArgs(C.Structure):
+    _c_name_ = "gymrl_acrobot_net_eval_args"
+    _fields_ = list(MountainCarNetEvalArgs._fields_)          # the same block: only the widths behind `start` / `final_obs` differ
+
+
 class ClassicEvalArgs(C.Structure):
     _c_name_ = "gymrl_classic_eval_args"
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("env_kind", C.c_int), ("head", C.c_int), ("D", C.c_int),
@@ -628,6 +633,8 @@ SIGNATURES = {
     "gymrl_snes_tell_args_bytes": (_sz, []),
     "gymrl_snes_perturb": (_i, [_P(SnesPerturbArgs), _vp]),
     "gymrl_snes_tell": (_i, [_P(SnesTellArgs), _vp]),
+    "gymrl_acrobot_net_eval_args_bytes": (_sz, []),
+    "gymrl_acrobot_net_eval": (_i, [_P(AcrobotNetEvalArgs), _vp]),
     "gymrl_dqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_dqn_pack_images": (_i, [_P(DqnUpdateArgs), _vp]),
     "gymrl_dqn_args_bytes": (_sz, [_i]),

@@ -1,4 +1,4 @@
-// env_classic.hip — CartPole-v1, Pendulum-v1 and MountainCar-v0 batched steppers + the
+// env_classic.hip — CartPole-v1, Pendulum-v1, MountainCar-v0 and Acrobot-v1 batched steppers + the
 // gymrl_env_* C-ABI dispatch (LunarLander lives in env_lunar.hip).
 //
 // Replaces gym.make(...).reset()/.step() as called from dqn_cartpole.py:176,181,
@@ -10,6 +10,7 @@
 //
 // One lane = one env; SoA state [field][N]; per-lane work is ~40 flop, so the
 // kernels are trivially HBM/launch bound (58 / 38 algorithmic bytes per env-step).
+// Acrobot-v1 is the exception: one step is an RK4 step, ~14 det_sincos per lane.
 #include "env_classic_device.hpp"
 
 using namespace gymrl;
@@ -147,6 +148,57 @@ __global__ __launch_bounds__(kEnvBlock) void mountaincar_step_kernel(
   accumulate_ep_stats(ep_stats, r.done, r.ret, r.len);
 }
 
+// -------------------------------------------------------------- Acrobot ----
+// (six floats per env: staged through LDS like Pendulum's three)
+__global__ __launch_bounds__(kEnvBlock) void acrobot_reset_kernel(void* buf, int n, uint64_t seed,
+                                                                  int64_t env_id0,
+                                                                  float* __restrict__ obs_out) {
+  __shared__ __attribute__((aligned(16))) float tile[kEnvBlock * 6];
+  AcrobotState st(buf, n);
+  const int i = blockIdx.x * kEnvBlock + threadIdx.x;
+  float o[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i < n) {
+    double s[4];
+    acrobot_draw(seed, (uint64_t)(env_id0 + i), 0u, s);
+    st.th1[i] = s[0]; st.th2[i] = s[1]; st.dth1[i] = s[2]; st.dth2[i] = s[3];
+    st.ep.ep_ret[i] = 0.0; st.ep.ep_len[i] = 0; st.ep.episode[i] = 0u;
+    acrobot_obs(s, o);
+  }
+  const int nv = min(kEnvBlock, n - blockIdx.x * kEnvBlock);
+  store_obs_tile<6>(obs_out + (size_t)blockIdx.x * kEnvBlock * 6, o, tile, threadIdx.x, nv);
+}
+
+__global__ __launch_bounds__(kEnvBlock) void acrobot_step_kernel(
+    void* buf, int n, uint64_t seed, int64_t env_id0, const int32_t* __restrict__ action,
+    float* __restrict__ obs_out, float* __restrict__ term_obs_out, float* __restrict__ rew_out,
+    uint8_t* __restrict__ terminated_out, uint8_t* __restrict__ truncated_out,
+    uint8_t* __restrict__ done_out, float* __restrict__ ep_ret_out,
+    int32_t* __restrict__ ep_len_out, double* __restrict__ ep_stats) {
+  __shared__ __attribute__((aligned(16))) float tile[kEnvBlock * 6];
+  AcrobotState st(buf, n);
+  const int i = blockIdx.x * kEnvBlock + threadIdx.x;
+  const bool valid = i < n;
+  ClassicStep<6> r;
+  r.done = false; r.ret = 0.0; r.len = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) r.o_next[k] = r.o_term[k] = 0.f;
+  if (valid) {
+    acrobot_step_one(st, i, seed, env_id0, action[i], r);
+    rew_out[i] = r.reward;
+    terminated_out[i] = r.terminated; truncated_out[i] = r.truncated;
+    if (done_out) done_out[i] = r.done;
+    if (r.done) {
+      if (ep_ret_out) ep_ret_out[i] = (float)r.ret;
+      if (ep_len_out) ep_len_out[i] = r.len;
+    }
+  }
+  const int nv = min(kEnvBlock, n - blockIdx.x * kEnvBlock);
+  const size_t base = (size_t)blockIdx.x * kEnvBlock * 6;
+  store_obs_tile<6>(obs_out + base, r.o_next, tile, threadIdx.x, nv);
+  if (term_obs_out) store_obs_tile<6>(term_obs_out + base, r.o_term, tile, threadIdx.x, nv);
+  accumulate_ep_stats(ep_stats, r.done, r.ret, r.len);
+}
+
 // Episodes a trainer abandons at its own step cap (dqn_cartpole.py:178 `for step in range(cfg.max_steps)` below the
 // env's TimeLimit): an env whose running episode has reached `cap` steps starts its next episode — no done flag, the
 // transition just stored keeps the real next observation — and reports the abandoned episode's return / length.
@@ -154,6 +206,7 @@ template <int KIND> struct StateOf;
 template <> struct StateOf<GYMRL_ENV_CARTPOLE> { using type = CartPoleState; };
 template <> struct StateOf<GYMRL_ENV_PENDULUM> { using type = PendulumState; };
 template <> struct StateOf<GYMRL_ENV_MOUNTAINCAR> { using type = MountainCarState; };
+template <> struct StateOf<GYMRL_ENV_ACROBOT> { using type = AcrobotState; };
 
 template <int KIND>
 __global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(void* buf, int n, uint64_t seed, int64_t env_id0,
@@ -183,6 +236,14 @@ __global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(void* buf, i
         float o[3];
         pendulum_obs(th, thd, o);
         obs[3 * (size_t)i] = o[0]; obs[3 * (size_t)i + 1] = o[1]; obs[3 * (size_t)i + 2] = o[2];
+      } else if constexpr (KIND == GYMRL_ENV_ACROBOT) {
+        double r[4];
+        acrobot_draw(seed, (uint64_t)(env_id0 + i), e, r);
+        st.th1[i] = r[0]; st.th2[i] = r[1]; st.dth1[i] = r[2]; st.dth2[i] = r[3];
+        float o[6];
+        acrobot_obs(r, o);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) obs[6 * (size_t)i + k] = o[k];
       } else {
         double pos, vel;
         mountaincar_draw(seed, (uint64_t)(env_id0 + i), e, pos, vel);
@@ -198,7 +259,9 @@ __global__ __launch_bounds__(kEnvBlock) void classic_abandon_kernel(void* buf, i
   accumulate_ep_stats(ep_stats, hit, ret, len);
 }
 
-inline bool classic_kind(int kind) { return kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_PENDULUM || kind == GYMRL_ENV_MOUNTAINCAR; }
+inline bool classic_kind(int kind) {
+  return kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_PENDULUM || kind == GYMRL_ENV_MOUNTAINCAR || kind == GYMRL_ENV_ACROBOT;
+}
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
@@ -219,16 +282,16 @@ int gymrl_device_ok(void) {
 }
 
 int gymrl_env_obs_dim(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 4 : kind == GYMRL_ENV_PENDULUM ? 3 : kind == GYMRL_ENV_LUNARLANDER ? 8 : kind == GYMRL_ENV_MOUNTAINCAR ? 2 : -22;
+  return kind == GYMRL_ENV_CARTPOLE ? 4 : kind == GYMRL_ENV_PENDULUM ? 3 : kind == GYMRL_ENV_LUNARLANDER ? 8 : kind == GYMRL_ENV_MOUNTAINCAR ? 2 : kind == GYMRL_ENV_ACROBOT ? 6 : -22;
 }
 int gymrl_env_act_dim(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 2 : kind == GYMRL_ENV_PENDULUM ? 1 : kind == GYMRL_ENV_LUNARLANDER ? 4 : kind == GYMRL_ENV_MOUNTAINCAR ? 3 : -22;
+  return kind == GYMRL_ENV_CARTPOLE ? 2 : kind == GYMRL_ENV_PENDULUM ? 1 : kind == GYMRL_ENV_LUNARLANDER ? 4 : kind == GYMRL_ENV_MOUNTAINCAR ? 3 : kind == GYMRL_ENV_ACROBOT ? 3 : -22;
 }
 int gymrl_env_is_discrete(int kind) {
-  return kind == GYMRL_ENV_PENDULUM ? 0 : (kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_LUNARLANDER || kind == GYMRL_ENV_MOUNTAINCAR) ? 1 : -22;
+  return kind == GYMRL_ENV_PENDULUM ? 0 : (kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_LUNARLANDER || kind == GYMRL_ENV_MOUNTAINCAR || kind == GYMRL_ENV_ACROBOT) ? 1 : -22;
 }
 int gymrl_env_max_steps(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 500 : kind == GYMRL_ENV_PENDULUM ? 200 : kind == GYMRL_ENV_LUNARLANDER ? 1000 : kind == GYMRL_ENV_MOUNTAINCAR ? 200 : -22;
+  return kind == GYMRL_ENV_CARTPOLE ? 500 : kind == GYMRL_ENV_PENDULUM ? 200 : kind == GYMRL_ENV_LUNARLANDER ? 1000 : kind == GYMRL_ENV_MOUNTAINCAR ? 200 : kind == GYMRL_ENV_ACROBOT ? 500 : -22;
 }
 
 size_t gymrl_env_state_bytes(int kind, int n_envs) {
@@ -238,6 +301,7 @@ size_t gymrl_env_state_bytes(int kind, int n_envs) {
     case GYMRL_ENV_PENDULUM: return PendulumState(nullptr, n_envs).bytes;
     case GYMRL_ENV_LUNARLANDER: return lunar_state_bytes(n_envs);
     case GYMRL_ENV_MOUNTAINCAR: return MountainCarState(nullptr, n_envs).bytes;
+    case GYMRL_ENV_ACROBOT: return AcrobotState(nullptr, n_envs).bytes;
     default: return 0;
   }
 }
@@ -262,6 +326,10 @@ int gymrl_env_reset(int kind, void* state, int n, uint64_t seed, int64_t env_id0
       hipLaunchKernelGGL(mountaincar_reset_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, s,
                          state, n, seed, env_id0, obs_out);
       break;
+    case GYMRL_ENV_ACROBOT:
+      hipLaunchKernelGGL(acrobot_reset_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, s,
+                         state, n, seed, env_id0, obs_out);
+      break;
     default: return -22;
   }
   GYMRL_CHECK_LAUNCH();
@@ -274,7 +342,8 @@ int gymrl_env_abandon(int kind, void* state, int n, uint64_t seed, int64_t env_i
   if (!classic_kind(kind)) return -22;    // no reference off-policy script runs LunarLander
   if (n == 0) return 0;
   const auto kernel = kind == GYMRL_ENV_CARTPOLE ? classic_abandon_kernel<GYMRL_ENV_CARTPOLE>
-                      : kind == GYMRL_ENV_PENDULUM ? classic_abandon_kernel<GYMRL_ENV_PENDULUM> : classic_abandon_kernel<GYMRL_ENV_MOUNTAINCAR>;
+                      : kind == GYMRL_ENV_PENDULUM ? classic_abandon_kernel<GYMRL_ENV_PENDULUM>
+                      : kind == GYMRL_ENV_ACROBOT ? classic_abandon_kernel<GYMRL_ENV_ACROBOT> : classic_abandon_kernel<GYMRL_ENV_MOUNTAINCAR>;
   hipLaunchKernelGGL(kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, (hipStream_t)stream_, state,
                      n, seed, env_id0, cap, obs_inout, flag_inout, ep_ret_out, ep_len_out, ep_stats);
   GYMRL_CHECK_LAUNCH();
@@ -317,6 +386,12 @@ int gymrl_env_step(int kind, void* state, int n, uint64_t seed, int64_t env_id0,
                         ep_stats, s);
     case GYMRL_ENV_MOUNTAINCAR:
       hipLaunchKernelGGL(mountaincar_step_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, s,
+                         state, n, seed, env_id0, (const int32_t*)action, obs_out, term_obs_out,
+                         rew_out, terminated_out, truncated_out, done_out, ep_ret_out, ep_len_out,
+                         ep_stats);
+      break;
+    case GYMRL_ENV_ACROBOT:
+      hipLaunchKernelGGL(acrobot_step_kernel, dim3(cdiv(n, kEnvBlock)), dim3(kEnvBlock), 0, s,
                          state, n, seed, env_id0, (const int32_t*)action, obs_out, term_obs_out,
                          rew_out, terminated_out, truncated_out, done_out, ep_ret_out, ep_len_out,
                          ep_stats);

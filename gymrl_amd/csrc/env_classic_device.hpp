@@ -1,6 +1,6 @@
-// env_classic_device.hpp — CartPole-v1 / Pendulum-v1 / MountainCar-v0: state layout, reset draws and ONE env's step as device functions.
+// env_classic_device.hpp — CartPole-v1 / Pendulum-v1 / MountainCar-v0 / Acrobot-v1: state layout, reset draws and ONE env's step as device functions.
 //
-// The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1" | "MountainCar-v0").step()/reset() (gymnasium classic_control, third-party:
+// The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1" | "MountainCar-v0" | "Acrobot-v1").step()/reset() (gymnasium classic_control, third-party:
 // SURVEY.md 8c.2) for one env = one lane.  Shared by the stand-alone steppers (env_classic.hip: gymrl_env_step) and the
 // fused acting kernels (offpolicy_step.hip, rainbow_step.hip, td3_step.hip: forward + draw + env step + ring append in one launch), so both produce the
 // same bits; each env's register-only core (*_advance) is shared with its one-launch episode kernel (mountaincar.hip, eval_classic.hip) in the same way.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
@@ -45,6 +45,18 @@ struct MountainCarState {
   }
 };
 
+struct AcrobotState {
+  double *th1, *th2, *dth1, *dth2;
+  EpisodeFields ep;
+  size_t bytes;
+  __host__ __device__ AcrobotState(void* buf, int n) {
+    Carver c(buf, n);
+    th1 = c.take<double>(); th2 = c.take<double>(); dth1 = c.take<double>(); dth2 = c.take<double>();
+    ep.ep_ret = c.take<double>(); ep.ep_len = c.take<int32_t>(); ep.episode = c.take<uint32_t>();
+    bytes = c.off;
+  }
+};
+
 __device__ __forceinline__ void cartpole_draw(uint64_t seed, uint64_t env, uint32_t episode,
                                               double (&s)[4]) {
   // reset: U(-0.05, 0.05)^4 in float64 (gymnasium CartPoleEnv.reset)
@@ -72,10 +84,27 @@ __device__ __forceinline__ void mountaincar_draw(uint64_t seed, uint64_t env, ui
   vel = 0.0;
 }
 
+__device__ __forceinline__ void acrobot_draw(uint64_t seed, uint64_t env, uint32_t episode, double (&s)[4]) {
+  // reset: U(-0.1, 0.1)^4 in float64 from cartpole_draw's words (gymnasium AcrobotEnv.reset; its float32 rounding of the state is not modelled)
+  const u32x4 a = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), episode, RNG_ENV_RESET | 0u);
+  const u32x4 b = philox4x32(seed, (uint32_t)env, (uint32_t)(env >> 32), episode, RNG_ENV_RESET | 1u);
+  s[0] = -0.1 + 0.2 * u01d(a.x, a.y);
+  s[1] = -0.1 + 0.2 * u01d(a.z, a.w);
+  s[2] = -0.1 + 0.2 * u01d(b.x, b.y);
+  s[3] = -0.1 + 0.2 * u01d(b.z, b.w);
+}
+
 __device__ __forceinline__ void pendulum_obs(double th, double thd, float (&o)[3]) {
   double s, c;
   det_sincos(th, &s, &c);
   o[0] = (float)c; o[1] = (float)s; o[2] = (float)thd;
+}
+
+__device__ __forceinline__ void acrobot_obs(const double (&s)[4], float (&o)[6]) {
+  double s1, c1, s2, c2;
+  det_sincos(s[0], &s1, &c1);
+  det_sincos(s[1], &s2, &c2);
+  o[0] = (float)c1; o[1] = (float)s1; o[2] = (float)c2; o[3] = (float)s2; o[4] = (float)s[2]; o[5] = (float)s[3];
 }
 
 // What one env's step hands back: the observation the policy sees next (post-reset where the episode ended), the
@@ -213,6 +242,89 @@ __device__ __forceinline__ void mountaincar_step_one(const MountainCarState& st,
     st.pos[i] = pos; st.vel[i] = vel;
     st.ep.ep_ret[i] = r.ret; st.ep.ep_len[i] = r.len;
     r.o_next[0] = r.o_term[0]; r.o_next[1] = r.o_term[1];
+  }
+}
+
+// Acrobot-v1 (gymnasium's "book" dynamics, torque_noise_max = 0), registers only.  acrobot_deriv is the right-hand side
+// f(th1, th2, dth1, dth2; a) of include/gymrl.h with the unit masses, lengths and inertias multiplied out (m1 = m2 = l1 = I1 =
+// I2 = 1, lc1 = lc2 = 0.5, g = 9.8: every folded product is exact but 1.5 * 9.8, which the compiler rounds as the host does).
+__device__ __forceinline__ void acrobot_deriv(const double (&y)[4], double a, double (&k)[4]) {
+  const double half_pi = 3.14159265358979323846 / 2.0;
+  double s2, c2, sn, c12, c1;
+  det_sincos(y[1], &s2, &c2);
+  det_sincos(y[0] + y[1] - half_pi, &sn, &c12);
+  det_sincos(y[0] - half_pi, &sn, &c1);
+  const double d1 = 0.25 + (1.25 + c2) + 1.0 + 1.0;
+  const double d2 = (0.25 + 0.5 * c2) + 1.0;
+  const double phi2 = 4.9 * c12;
+  const double phi1 = -0.5 * (y[3] * y[3]) * s2 - y[3] * y[2] * s2 + (1.5 * 9.8) * c1 + phi2;
+  const double ddth2 = (a + d2 / d1 * phi1 - 0.5 * (y[2] * y[2]) * s2 - phi2) / (1.25 - d2 * d2 / d1);
+  const double ddth1 = -(d2 * ddth2 + phi1) / d1;
+  k[0] = y[2]; k[1] = y[3]; k[2] = ddth1; k[3] = ddth2;
+}
+
+constexpr int kAcrobotWrapTrips = GYMRL_ACROBOT_WRAP_TRIPS;       // gymnasium's `while x > pi: x -= 2 pi` as a fixed trip count
+
+// One classical RK4 step over dt = 0.2, the angles wrapped into [-pi, pi], the velocities clamped to +-4 pi / +-9 pi; ->
+// terminated (the tip above the line one link length over the pivot, on the new state).  The stepper below and the policy
+// episode kernels (eval_acrobot.hip) both call it.
+__device__ __forceinline__ bool acrobot_advance(double (&s)[4], int action) {
+  const double pi = 3.14159265358979323846;
+  const double a = (double)(action - 1);
+  double k1[4], k2[4], k3[4], k4[4], y[4];
+  acrobot_deriv(s, a, k1);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = s[i] + 0.1 * k1[i];
+  acrobot_deriv(y, a, k2);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = s[i] + 0.1 * k2[i];
+  acrobot_deriv(y, a, k3);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) y[i] = s[i] + 0.2 * k3[i];
+  acrobot_deriv(y, a, k4);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s[i] = s[i] + (0.2 / 6.0) * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    double x = s[i];
+#pragma unroll
+    for (int w = 0; w < kAcrobotWrapTrips; ++w) x = x > pi ? x - 2.0 * pi : x;
+#pragma unroll
+    for (int w = 0; w < kAcrobotWrapTrips; ++w) x = x < -pi ? x + 2.0 * pi : x;
+    s[i] = x;
+  }
+  s[2] = s[2] < -4.0 * pi ? -4.0 * pi : (s[2] > 4.0 * pi ? 4.0 * pi : s[2]);
+  s[3] = s[3] < -9.0 * pi ? -9.0 * pi : (s[3] > 9.0 * pi ? 9.0 * pi : s[3]);
+  double sn, c1, c12;
+  det_sincos(s[0], &sn, &c1);
+  det_sincos(s[1] + s[0], &sn, &c12);
+  return -c1 - c12 > 1.0;
+}
+
+// Acrobot-v1: reward -1 on every step but the terminating one (0), TimeLimit 500; auto-reset into episode + 1's draw.
+__device__ __forceinline__ void acrobot_step_one(const AcrobotState& st, int i, uint64_t seed, int64_t env_id0, int action,
+                                                 ClassicStep<6>& r) {
+  double s[4] = {st.th1[i], st.th2[i], st.dth1[i], st.dth2[i]};
+  r.terminated = acrobot_advance(s, action);
+  r.len = st.ep.ep_len[i] + 1;
+  r.truncated = r.len >= 500;
+  r.done = r.terminated || r.truncated;
+  const double rew = r.terminated ? 0.0 : -1.0;
+  r.ret = st.ep.ep_ret[i] + rew;
+  r.reward = (float)rew;
+  acrobot_obs(s, r.o_term);
+  if (r.done) {
+    const uint32_t e = st.ep.episode[i] + 1u;
+    double d[4];
+    acrobot_draw(seed, (uint64_t)(env_id0 + i), e, d);
+    st.th1[i] = d[0]; st.th2[i] = d[1]; st.dth1[i] = d[2]; st.dth2[i] = d[3];
+    st.ep.ep_ret[i] = 0.0; st.ep.ep_len[i] = 0; st.ep.episode[i] = e;
+    acrobot_obs(d, r.o_next);
+  } else {
+    st.th1[i] = s[0]; st.th2[i] = s[1]; st.dth1[i] = s[2]; st.dth2[i] = s[3];
+    st.ep.ep_ret[i] = r.ret; st.ep.ep_len[i] = r.len;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r.o_next[k] = r.o_term[k];
   }
 }
 

@@ -1,6 +1,6 @@
 // eval_episode_device.hpp — the episode loop of the one-launch policy evaluation, stated once: eval_classic.hip (a three-layer MLP
-// on CartPole-v1 / Pendulum-v1), eval_duel.hip (a dueling network on CartPole-v1) and eval_mountaincar.hip (either network on
-// MountainCar-v0) instantiate it, through eval_kernels_device.hpp, with their own "policy forward" and "action" steps.
+// on CartPole-v1 / Pendulum-v1), eval_duel.hip (a dueling network on CartPole-v1), eval_mountaincar.hip and eval_acrobot.hip (either
+// network on MountainCar-v0 / Acrobot-v1) instantiate it, through eval_kernels_device.hpp, with their own "policy forward" and "action" steps.
 //
 // ONE workgroup of slab::kThreads threads carries 16 episodes of one policy from their reset to their end.  Lane t < 16 of wave 0
 // owns episode e0 + t: its float64 env state, its float64 return, its length and its flags live in registers.  Per iteration
@@ -9,8 +9,8 @@
 //                running", beside them
 //   everybody    meets at the barrier that publishes both and leaves on that word — the same for every thread of the workgroup
 //   forward()    every thread: the policy's stages over the slab, each closed by a workgroup barrier, the last one included
-//   action(t)    the running lanes: the greedy action of row t, then cartpole_advance / pendulum_advance / mountaincar_advance in
-//                registers
+//   action(t)    the running lanes: the greedy action of row t, then cartpole_advance / pendulum_advance / mountaincar_advance /
+//                acrobot_advance in registers
 //
 // A finished lane idles with its registers frozen (its slab row keeps its last observation and is computed along, unread).  No
 // __syncthreads() sits behind a per-lane or per-wave condition, nothing waits for another workgroup, there are no atomics, inside
@@ -34,13 +34,19 @@ struct EpisodeSlot {
   }
 };
 
-// The float32 observation of the float64 state s: the cast (CartPole-v1, MountainCar-v0) or (cos, sin, thdot) (Pendulum-v1)
+// The float32 observation of the float64 state s: the cast (CartPole-v1, MountainCar-v0), (cos, sin, thdot) (Pendulum-v1) or
+// the two links' (cos, sin) and the velocities (Acrobot-v1)
 template <int KIND>
 __device__ __forceinline__ void episode_obs(const double (&s)[4], float* o) {
   if constexpr (KIND == GYMRL_ENV_CARTPOLE) {
     o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
   } else if constexpr (KIND == GYMRL_ENV_MOUNTAINCAR) {
     o[0] = (float)s[0]; o[1] = (float)s[1];
+  } else if constexpr (KIND == GYMRL_ENV_ACROBOT) {
+    float ob[6];
+    acrobot_obs(s, ob);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = ob[k];
   } else {
     float ob[3];
     pendulum_obs(s[0], s[1], ob);
@@ -48,14 +54,14 @@ __device__ __forceinline__ void episode_obs(const double (&s)[4], float* o) {
   }
 }
 
-// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR (action(t) -> int) or GYMRL_ENV_PENDULUM (action(t) -> the torque, float).
+// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR, GYMRL_ENV_ACROBOT (action(t) -> int) or GYMRL_ENV_PENDULUM (action(t) -> the torque, float).
 // Args: an argument block with E, cap, seed, stream_id0, start, returns, lengths, terminated, final_obs (include/gymrl.h).
 // `running` is the caller's __shared__ word.
 template <int KIND, class Args, class Forward, class Action>
 __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& running, const Lds& L, const int p, const int e0, const int nrows,
                                              Forward&& forward, Action&& action) {
-  constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE, car = KIND == GYMRL_ENV_MOUNTAINCAR;
-  constexpr int D = cart ? 4 : car ? 2 : 3, NS = cart ? 4 : 2;          // MountainCar-v0: (pos, vel)
+  constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE, car = KIND == GYMRL_ENV_MOUNTAINCAR, acro = KIND == GYMRL_ENV_ACROBOT;
+  constexpr int D = cart ? 4 : car ? 2 : acro ? 6 : 3, NS = cart || acro ? 4 : 2;          // MountainCar-v0: (pos, vel)
   const int t = threadIdx.x;
   // ---- one lane per episode: the env state, the return and the length live in registers ----
   double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -72,6 +78,8 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
       cartpole_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
     } else if constexpr (car) {
       mountaincar_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
+    } else if constexpr (acro) {
+      acrobot_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
     } else {
       pendulum_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
     }
@@ -92,6 +100,9 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
       } else if constexpr (car) {
         terminated = mountaincar_advance(s[0], s[1], action(t));
         ret = ret + (-1.0);                 // every step, the terminating one included
+      } else if constexpr (acro) {
+        terminated = acrobot_advance(s, action(t));
+        ret = ret + (terminated ? 0.0 : -1.0);  // every step but the terminating one
       } else {
         ret = ret + (-pendulum_advance(s[0], s[1], action(t)));
       }

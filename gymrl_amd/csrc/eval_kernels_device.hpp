@@ -1,13 +1,13 @@
 // eval_kernels_device.hpp — the two episode kernels of the classic-control policy evaluation, stated once per network shape:
 //
-//   classic_eval_kernel   a three-layer MLP D -> H -> H -> A under an argmax head (CartPole-v1, MountainCar-v0) or a tanh head
+//   classic_eval_kernel   a three-layer MLP D -> H -> H -> A under an argmax head (CartPole-v1, MountainCar-v0, Acrobot-v1) or a tanh head
 //                         (Pendulum-v1)
 //   duel_eval_kernel      a dueling network: a ReLU trunk of one or two layers, a value head and an advantage head in ONE
-//                         two-item stage, the combine, the first maximum (CartPole-v1, MountainCar-v0)
+//                         two-item stage, the combine, the first maximum (CartPole-v1, MountainCar-v0, Acrobot-v1)
 //
 // Both are templates over the env kind and the ARGUMENT BLOCK of the entry point that launches them: eval_classic.hip
-// (gymrl_classic_eval_args), eval_duel.hip (gymrl_classic_duel_eval_args) and eval_mountaincar.hip
-// (gymrl_mountaincar_net_eval_args) name the same tensors differently, and mlp3_of / duel_of below read them out.  The episode
+// (gymrl_classic_eval_args), eval_duel.hip (gymrl_classic_duel_eval_args), eval_mountaincar.hip
+// (gymrl_mountaincar_net_eval_args) and eval_acrobot.hip (gymrl_acrobot_net_eval_args) name the same tensors differently, and mlp3_of / duel_of below read them out.  The episode
 // loop is eval_episode_device.hpp's run_episodes; what is stated here is one step's policy forward and its action.
 //
 // Register pressure: the tensors' pointers pass through an empty asm inside the forward, so that the stages' per-lane operand
@@ -29,16 +29,20 @@ template <int KIND> struct EvalDims;
 template <> struct EvalDims<GYMRL_ENV_CARTPOLE> { static constexpr int D = 4, A = 2; };
 template <> struct EvalDims<GYMRL_ENV_PENDULUM> { static constexpr int D = 3, A = 1; };
 template <> struct EvalDims<GYMRL_ENV_MOUNTAINCAR> { static constexpr int D = 2, A = 3; };
+template <> struct EvalDims<GYMRL_ENV_ACROBOT> { static constexpr int D = 6, A = 3; };
 
 // policy 0's tensors as the kernels name them
 struct Mlp3 { const float *w0, *w1, *w2, *b0, *b1, *b2; };
 __device__ __forceinline__ Mlp3 mlp3_of(const gymrl_classic_eval_args& a) { return Mlp3{a.w[0], a.w[1], a.w[2], a.b[0], a.b[1], a.b[2]}; }
 __device__ __forceinline__ Mlp3 mlp3_of(const gymrl_mountaincar_net_eval_args& a) { return Mlp3{a.w[0], a.w[1], a.head_w, a.b[0], a.b[1], a.head_b}; }
+__device__ __forceinline__ Mlp3 mlp3_of(const gymrl_acrobot_net_eval_args& a) { return Mlp3{a.w[0], a.w[1], a.head_w, a.b[0], a.b[1], a.head_b}; }
 struct DuelNet { const float *w0, *b0, *w1, *b1, *wv, *bv, *wa, *ba; };
 __device__ __forceinline__ DuelNet duel_of(const gymrl_classic_duel_eval_args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.adv_w, a.adv_b}; }
 __device__ __forceinline__ DuelNet duel_of(const gymrl_mountaincar_net_eval_args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.head_w, a.head_b}; }
 
-// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR (the first maximum of fc3's row) or GYMRL_ENV_PENDULUM (tanh * a.bound);
+__device__ __forceinline__ DuelNet duel_of(const gymrl_acrobot_net_eval_args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.head_w, a.head_b}; }
+
+// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR, GYMRL_ENV_ACROBOT (the first maximum of fc3's row) or GYMRL_ENV_PENDULUM (tanh * a.bound);
 // HC: the hidden width the instance is built for (0: a.H)
 template <int HC, int KIND, class Args>
 __global__ __launch_bounds__(kThreads) void classic_eval_kernel(const Args a) {

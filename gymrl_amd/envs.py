@@ -1,4 +1,4 @@
-"""Device-resident batched environments (CartPole-v1 / Pendulum-v1 / LunarLander-v3 / MountainCar-v0).
+"""Device-resident batched environments (CartPole-v1 / Pendulum-v1 / LunarLander-v3 / MountainCar-v0 / Acrobot-v1).
 
 Stands where `gym.make(name)` stands in the reference trainers
 (ppo_lunarlander.py:160, dqn_cartpole.py:94, rainbow_dqn_cartpole.py:270,

@@ -4,7 +4,7 @@ behind it; Config / trainer / CLI are shaped like dqn_cartpole.
 One generation is four launches and no host synchronisation:
 
     OpenAIES.ask()        gymrl_es_perturb     the centre -> P mirrored policies, f32[P, stride]
-    PolicyEval launch     gymrl_classic_policy_eval | gymrl_mountaincar_net_eval     P policies x E whole episodes
+    PolicyEval launch     gymrl_classic_policy_eval | gymrl_mountaincar_net_eval | gymrl_acrobot_net_eval     P policies x E whole episodes
     OpenAIES.tell()       gymrl_es_shape_grad  returns -> centred ranks -> search gradient (two launches above 256 policies)
                           gymrl_adam_step      the centre moves
 
@@ -12,7 +12,7 @@ Under Config.method = "snes" the learner is es.SeparableNES: gymrl
 gymrl_snes_tell, which moves the centre and its per-element step sizes itself — three launches, no Adam step; Config.sigma is
 the step sizes' initial value and Config.lr is not read.
 
-The policy is dqn_cartpole.py's three-layer MLP: an argmax head on CartPole-v1 and MountainCar-v0, tanh(fc3) * bound on
+The policy is dqn_cartpole.py's three-layer MLP: an argmax head on CartPole-v1, MountainCar-v0 and Acrobot-v1, tanh(fc3) * bound on
 Pendulum-v1.  Training episodes start from streams of their own (env ids from 1 << 41, E fresh ones per generation, the same E
 for every policy of a generation), so no training start is an eval() start."""
 import time
@@ -30,7 +30,7 @@ from .utils import scalar
 
 class Config:
     def __init__(self):
-        self.env_name = "CartPole-v1"        # | "Pendulum-v1" | "MountainCar-v0"
+        self.env_name = "CartPole-v1"        # | "Pendulum-v1" | "MountainCar-v0" | "Acrobot-v1"
         self.seed = None
         self.hidden_dim = 64
         self.population = 256                # even: population / 2 mirrored pairs
@@ -72,7 +72,7 @@ class ESTrainer(PolicyEval):
         self.device = torch.device(config.device if ":" in str(config.device) else f"cuda:{torch.cuda.current_device()}")
         self.base_seed = 0 if config.seed is None else int(config.seed)
         kind = ops.ENV_KINDS.get(config.env_name)
-        if kind not in (ops.CARTPOLE, ops.PENDULUM, ops.MOUNTAINCAR):
+        if kind not in (ops.CARTPOLE, ops.PENDULUM, ops.MOUNTAINCAR, ops.ACROBOT):
             raise ValueError(f"ESTrainer: no population evaluator for {config.env_name!r}")
         state_dim, action_dim, self.discrete, _ = ops.env_dims(kind)
         self.action_bound = 2.0 if kind == ops.PENDULUM else 0.0          # Pendulum-v1's max torque

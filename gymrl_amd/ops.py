@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   LunarCollectArgs, LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   LunarCollectArgs, LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, AcrobotNetEvalArgs, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -558,7 +558,9 @@ def soft_update(target, source, tau):
 
 # -------------------------------------------------------------------- env ---
 CARTPOLE, PENDULUM, LUNARLANDER, MOUNTAINCAR = 0, 1, 2, 3
-ENV_KINDS = {"CartPole-v1": CARTPOLE, "Pendulum-v1": PENDULUM, "LunarLander-v3": LUNARLANDER, "MountainCar-v0": MOUNTAINCAR}
+ACROBOT = 5                    # 4 is left free for MountainCar's continuous sibling (include/gymrl.h): every entry point refuses it
+ENV_KINDS = {"CartPole-v1": CARTPOLE, "Pendulum-v1": PENDULUM, "LunarLander-v3": LUNARLANDER, "MountainCar-v0": MOUNTAINCAR,
+             "Acrobot-v1": ACROBOT}
 
 
 def env_dims(kind):
@@ -884,7 +886,14 @@ def mountaincar_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, va
     layer is a (weight, bias) tensor pair, a NoisyLinear's its weight_mu / bias_mu: trunk = the hidden layers (2 -> H, H -> H),
     head = fc3 (net 0) or the advantage head (net 1 | 2), both H -> 3, value = the H -> 1 head of a dueling network.  params /
     flat, the starts and the streams: classic_policy_eval's; start is f64[P, n_episodes, 2] = (position, velocity)."""
-    who = "mountaincar_net_eval"
+    return _net_eval("mountaincar_net_eval", "MountainCar-v0", (2, 3), 2, MountainCarNetEvalArgs, net, trunk, head, n_episodes, seed,
+                     stream_id0, cap, value, flat, params, images, start, want_final_obs)
+
+
+def _net_eval(who, env, dims, nst, Args, net, trunk, head, n_episodes, seed, stream_id0, cap, value, flat, params, images, start,
+              want_final_obs):
+    """mountaincar_net_eval / acrobot_net_eval: one argument block, two entry points (gymrl_<who>); dims = the env's (D, A), nst
+    the float64 fields of a start state."""
     trunk = [tuple(pair) for pair in trunk]
     duel = net != MOUNTAINCAR_NET_MLP
     if len(trunk) not in ((1, 2) if duel else (2,)):
@@ -899,13 +908,16 @@ def mountaincar_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, va
         raise ValueError(f"{who}: the trunk is not D -> H (-> H)")
     if head[0].shape[1] != H or (duel and tuple(value[0].shape) != (1, H)):
         raise ValueError(f"{who}: the heads are not H -> A and H -> 1")
-    if (D, A) != (2, 3):
-        raise ValueError(f"{who}: MountainCar-v0 has 2 observations and 3 actions, the layers are {D} -> .. -> {A}")
+    if (D, A) != dims:
+        raise ValueError(f"{who}: {env} has {dims[0]} observations and {dims[1]} actions, the layers are {D} -> .. -> {A}")
+    n_pol = params.shape[0] if params is not None and params.dim() == 2 else 1
+    if start is not None and tuple(start.shape) != (n_pol, n_episodes, nst):      # before any pointer is handed out
+        raise ValueError(f"{who}: start is {tuple(start.shape)}, {n_pol} policies x {n_episodes} episodes need [{n_pol}, {n_episodes}, {nst}]")
     tensors = [w for w, _ in pairs] + [b for _, b in pairs]
     n, nh = len(pairs), len(trunk)
-    a = MountainCarNetEvalArgs()
+    a = Args()
     P, stride, params, addr = _policy_addresses(who, tensors, flat, params)
-    out = _episode_io(a, P, n_episodes, 2, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
+    out = _episode_io(a, P, n_episodes, nst, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
     a.P, a.E, a.cap, a.net, a.n_hidden, a.H = P, n_episodes, cap, net, nh, H
     for k in range(nh):
         a.w[k], a.b[k] = addr[k], addr[n + k]
@@ -913,8 +925,30 @@ def mountaincar_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, va
     if duel:
         a.value_w, a.value_b = addr[nh + 1], addr[n + nh + 1]
     a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
-    check(lib().gymrl_mountaincar_net_eval(C.byref(a), _stream()), "gymrl_mountaincar_net_eval")
+    check(getattr(lib(), "gymrl_" + who)(C.byref(a), _stream()), "gymrl_" + who)
     return out if want_final_obs else out[:3]
+
+
+# ----------------------- Acrobot-v1 policies: whole episodes in one launch ---
+ACROBOT_MAX_STEPS = 500
+
+
+def acrobot_net_eval_shape_ok(net, n_hidden, D, A, H):
+    """What gymrl_acrobot_net_eval takes (include/gymrl.h): mountaincar_net_eval_shape_ok's networks on Acrobot-v1's
+    (D, A) = (6, 3)."""
+    return (net in (0, 1, 2) and n_hidden in ((2,) if net == 0 else (1, 2)) and (D, A) == (6, 3)
+            and 4 <= H <= 256 and H % 4 == 0)
+
+
+def acrobot_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, value=None, flat=None, params=None, images=None,
+                     start=None, want_final_obs=False, kind=ACROBOT):
+    """mountaincar_net_eval on Acrobot-v1 (include/gymrl.h gymrl_acrobot_net_eval): the same networks (the MOUNTAINCAR_NET_*
+    values of `net`), layers and outputs with trunk[0] = 6 -> H, final_obs f32[P, n_episodes, 6] and start f64[P, n_episodes, 4] =
+    (th1, th2, dth1, dth2).  `kind` is what PolicyEval's call carries to tell the two entry points apart."""
+    if kind != ACROBOT:
+        raise ValueError(f"acrobot_net_eval: env kind {kind} is not Acrobot-v1's")
+    return _net_eval("acrobot_net_eval", "Acrobot-v1", (6, 3), 4, AcrobotNetEvalArgs, net, trunk, head, n_episodes, seed,
+                     stream_id0, cap, value, flat, params, images, start, want_final_obs)
 
 
 # ---------------------- LunarLander-v3 PPO policies: whole episodes in one launch ---

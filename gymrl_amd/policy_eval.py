@@ -1,10 +1,10 @@
 """Evaluation of a trainer's policy as whole episodes in ONE launch (csrc/eval_classic.hip; csrc/eval_duel.hip, §4q;
-csrc/eval_mountaincar.hip, §4t).
+csrc/eval_mountaincar.hip, §4t; csrc/eval_acrobot.hip, §4y).
 
 The reference's eval() (dqn_cartpole.py:214-235 and its siblings) plays num_episodes episodes one after another under
 select_action(deterministic=True).  The trainers here play them side by side on a VecEnv, one host iteration per env step;
 with Config.fused_eval the same episodes — the same start draws, the same actions, the same returns — are one kernel
-launch.  Three entry points serve nine trainers:
+launch.  Four entry points serve nine trainers:
 
   gymrl_classic_policy_eval   a three-layer MLP: CartPole-v1 under an argmax head (DQN, DDQN+PER, discrete SAC), Pendulum-v1 under
                               a tanh head (TD3, DDPG; SAC-Pendulum's tanh(mean(fc2(fc1 s))) * bound through evaluate() only:
@@ -16,6 +16,7 @@ launch.  Three entry points serve nine trainers:
                               three-layer ones as net 0, dueling ones with the combine their trainer declares in
                               EVAL_DUEL_COMBINE — 1: torch's mean, sum * (1 / 3) (dueling DDQN+PER, NoisyNet); 2: the layer
                               kernels' DUELING epilogue, sum / 3 (Rainbow).  With three actions the two are different floats
+  gymrl_acrobot_net_eval      Acrobot-v1 (env_name = "Acrobot-v1"): the same six trainers, the same three nets, (D, A) = (6, 3)
 
 Every shape the entry points refuse (hidden 260, another action count) keeps the loop.  LunarLander-v3 has a
 launch of its own on the two PPO trainers themselves (csrc/eval_lunar.hip, DESIGN §4r: other streams, a float64 return, a
@@ -44,12 +45,15 @@ class PolicyEval:
 
     def _eval_call(self):
         """The launch's fixed arguments — ops.classic_policy_eval's, ops.classic_duel_eval's (`trunk` is among them) or, on
-        MountainCar-v0, ops.mountaincar_net_eval's (`net` is among them) — or None where the entry points would refuse the shape."""
+        MountainCar-v0 and Acrobot-v1, ops.mountaincar_net_eval's / ops.acrobot_net_eval's (`net` is among them) — or None where the entry points would refuse the shape."""
         kind = ops.ENV_KINDS.get(self.cfg.env_name)
         if kind is None:
             return None
         if kind == ops.MOUNTAINCAR:
-            return self._eval_call_mountaincar()
+            return self._eval_call_net(kind, ops.mountaincar_net_eval_shape_ok)
+        if kind == ops.ACROBOT:
+            call = self._eval_call_net(kind, ops.acrobot_net_eval_shape_ok)
+            return None if call is None else dict(call, kind=kind)      # what tells _eval_launch the two entry points apart
         pol = self._eval_policy()
         if pol is not None:
             (fc1, fc2, fc3), flat, head, bound = pol
@@ -66,8 +70,9 @@ class PolicyEval:
             return None
         return dict(kind=kind, trunk=trunk, value=value, advantage=advantage, cap=ops.env_dims(kind)[3], flat=flat)
 
-    def _eval_call_mountaincar(self):
-        """_eval_call() on MountainCar-v0: a three-layer policy is net 0, a dueling one the combine the trainer declares."""
+    def _eval_call_net(self, kind, shape_ok):
+        """_eval_call() on MountainCar-v0 / Acrobot-v1: a three-layer policy is net 0, a dueling one the combine the trainer
+        declares."""
         pair = lambda m: (m.weight, m.bias)     # noqa: E731
         pol = self._eval_policy()
         if pol is not None:
@@ -82,14 +87,15 @@ class PolicyEval:
             trunk, value, top, flat = duel
             net = self.EVAL_DUEL_COMBINE
         (H, D), A = trunk[0][0].shape, top[0].shape[0]
-        if not ops.mountaincar_net_eval_shape_ok(net, len(trunk), D, A, H):
+        if not shape_ok(net, len(trunk), D, A, H):
             return None
-        return dict(net=net, trunk=trunk, head=top, value=value, cap=ops.env_dims(ops.MOUNTAINCAR)[3], flat=flat)
+        return dict(net=net, trunk=trunk, head=top, value=value, cap=ops.env_dims(kind)[3], flat=flat)
 
     @staticmethod
     def _eval_launch(call, **kw):
         """One launch of the entry point the call's arguments belong to."""
-        fn = ops.mountaincar_net_eval if "net" in call else ops.classic_duel_eval if "trunk" in call else ops.classic_policy_eval
+        fn = (ops.acrobot_net_eval if call.get("kind") == ops.ACROBOT and "net" in call else
+              ops.mountaincar_net_eval if "net" in call else ops.classic_duel_eval if "trunk" in call else ops.classic_policy_eval)
         return fn(**kw, **call)
 
     def _eval_fused(self, num_episodes):
@@ -113,7 +119,7 @@ class PolicyEval:
         call = self._eval_call()
         if call is None:
             raise RuntimeError(f"{type(self).__name__}.evaluate: gymrl_classic_policy_eval / gymrl_classic_duel_eval / "
-                               "gymrl_mountaincar_net_eval take no such policy (include/gymrl.h)")
+                               "gymrl_mountaincar_net_eval / gymrl_acrobot_net_eval take no such policy (include/gymrl.h)")
         if params is not None:
             params = torch.as_tensor(params, dtype=torch.float32).to(self.device)
             params = params.view(1, -1) if params.dim() == 1 else params.contiguous()

@@ -42,10 +42,13 @@ enum {
   GYMRL_ENV_CARTPOLE    = 0, /* CartPole-v1   obs 4, 2 discrete actions   */
   GYMRL_ENV_PENDULUM    = 1, /* Pendulum-v1   obs 3, 1 continuous in [-2,2] */
   GYMRL_ENV_LUNARLANDER = 2, /* LunarLander-v3 obs 8, 4 discrete actions  */
-  GYMRL_ENV_MOUNTAINCAR = 3  /* MountainCar-v0 obs 2, 3 discrete actions (the steppers, gymrl_mountaincar_rule_eval and
+  GYMRL_ENV_MOUNTAINCAR = 3, /* MountainCar-v0 obs 2, 3 discrete actions (the steppers, gymrl_mountaincar_rule_eval and
                               * gymrl_mountaincar_net_eval only: the fused acting, ring and rollout kernels and the other
                               * policy-episode entry points refuse it with -EINVAL) */
+  /* 4 is left free for MountainCar's continuous sibling (MountainCarContinuous-v0, not built): every entry point refuses it */
+  GYMRL_ENV_ACROBOT     = 5  /* Acrobot-v1 obs 6, 3 discrete actions (the steppers and gymrl_acrobot_net_eval only, like kind 3) */
 };
+#define GYMRL_ACROBOT_WRAP_TRIPS 8   /* Acrobot-v1: trips of each angle-wrapping loop (the rule below) */
 
 /*
  * Batched env stepper.  Replaces gym.make / env.reset / env.step as used by
@@ -58,13 +61,45 @@ enum {
  *   CartPole-v1  f64 x, f64 x_dot, f64 theta, f64 theta_dot, f64 ep_ret, i32 ep_len, u32 episode
  *   Pendulum-v1  f64 theta, f64 theta_dot, f64 ep_ret, i32 ep_len, u32 episode
  *   MountainCar-v0  f64 position, f64 velocity, f64 ep_ret, i32 ep_len, u32 episode
+ *   Acrobot-v1   f64 theta1, f64 theta2, f64 dtheta1, f64 dtheta2, f64 ep_ret, i32 ep_len, u32 episode
  * (float64 like gymnasium's own state; tests/test_classic_micro_gpu.py writes states through this layout, and a
  * checkpoint of a running vector is a copy of the buffer).  LunarLander: 144 dwords per env, word-major.
+ */
+
+/*
+ * Acrobot-v1, the rule (gymnasium is no dependency of this library: what follows is the specification, after gymnasium's published
+ * AcrobotEnv in its "book" variant with torque_noise_max = 0).  Everything is IEEE float64, no operation is contracted into an
+ * fma, sin / cos are csrc/gymrl_device.hpp's det_sincos, and an expression is evaluated left to right in exactly the grouping
+ * written here, so that a host restatement (tests/acrobot_ref.py) reproduces every bit.
+ *   state   y = (th1, th2, dth1, dth2);  torque a = (double)(action - 1), action in {0, 1, 2}
+ *   f(y; a) (m1 = m2 = l1 = I1 = I2 = 1, lc1 = lc2 = 0.5, g = 9.8 multiplied out; 14.7 stands for the double 1.5 * 9.8):
+ *     s2 = sin(th2), c2 = cos(th2), c12 = cos((th1 + th2) - pi / 2), c1 = cos(th1 - pi / 2)
+ *     d1    = ((0.25 + (1.25 + c2)) + 1.0) + 1.0
+ *     d2    = (0.25 + 0.5 * c2) + 1.0
+ *     phi2  = 4.9 * c12
+ *     phi1  = ((((-0.5 * (dth2 * dth2)) * s2) - ((dth2 * dth1) * s2)) + 14.7 * c1) + phi2
+ *     ddth2 = (((a + (d2 / d1) * phi1) - ((0.5 * (dth1 * dth1)) * s2)) - phi2) / (1.25 - (d2 * d2) / d1)
+ *     ddth1 = (-(d2 * ddth2 + phi1)) / d1
+ *     f     = (dth1, dth2, ddth1, ddth2)
+ *   step    one classical RK4 step over dt = 0.2, per component:
+ *     k1 = f(y), k2 = f(y + 0.1 * k1), k3 = f(y + 0.1 * k2), k4 = f(y + 0.2 * k3)
+ *     y' = y + (0.2 / 6.0) * (((k1 + 2.0 * k2) + 2.0 * k3) + k4)
+ *   then    th1, th2: GYMRL_ACROBOT_WRAP_TRIPS times `x = x > pi ? x - 2.0 * pi : x`, then as many times
+ *           `x = x < -pi ? x + 2.0 * pi : x` — gymnasium's two while loops with a fixed trip count: from a state inside the
+ *           velocity box an angle moves by less than 9 pi in a step (at the box's corners), so five trips do
+ *           (tests/test_acrobot_ref.py); an angle handed in through `start` more than 16 pi outside stays outside.  dth1 is clamped to +-4.0 * pi, dth2 to
+ *           +-9.0 * pi (x < lo ? lo : x > hi ? hi : x).
+ *   end     terminated = ((-cos(th1)) - cos(th2 + th1)) > 1.0 on the new state; reward -1, and 0 on the terminating step;
+ *           TimeLimit 500 (truncated = length >= 500).
+ *   obs     the float32 casts of (cos th1, sin th1, cos th2, sin th2, dth1, dth2)
+ *   reset   y[k] = -0.1 + 0.2 * u_k, the four u_k taken from the Philox words exactly as CartPole-v1's reset takes them (two
+ *           calls, RNG_ENV_RESET | 0 and | 1).  gymnasium rounds the reset state to float32; like CartPole-v1's, that rounding
+ *           is deliberately not modelled.
  */
 int    gymrl_env_obs_dim(int kind);
 int    gymrl_env_act_dim(int kind);     /* #discrete actions, or continuous dim */
 int    gymrl_env_is_discrete(int kind);
-int    gymrl_env_max_steps(int kind);   /* TimeLimit: 500 / 200 / 1000 / 200 */
+int    gymrl_env_max_steps(int kind);   /* TimeLimit: 500 / 200 / 1000 / 200 / (kind 5) 500 */
 size_t gymrl_env_state_bytes(int kind, int n_envs);
 
 /* (Re)initialise every env: episode counter := 0, draws from the counter-based
@@ -96,7 +131,7 @@ int gymrl_env_step(int kind, void* state, int n_envs, uint64_t seed, int64_t env
  * Call after gymrl_env_step: every env whose running episode has reached `cap` steps starts its next episode;
  * obs_inout [N, obs] rows of those envs become the reset observation, flag_inout u8[N] (or NULL) is OR-ed with 1
  * for them, ep_ret_out / ep_len_out / ep_stats receive the abandoned episode as gymrl_env_step would for a
- * finished one.  CartPole-v1, Pendulum-v1 and MountainCar-v0 (no reference off-policy script runs LunarLander: -EINVAL). */
+ * finished one.  CartPole-v1, Pendulum-v1, MountainCar-v0 and Acrobot-v1 (no reference off-policy script runs LunarLander: -EINVAL). */
 int gymrl_env_abandon(int kind, void* state, int n_envs, uint64_t seed, int64_t env_id0, int cap,
                       float* obs_inout, uint8_t* flag_inout, float* ep_ret_out, int32_t* ep_len_out,
                       double* ep_stats, void* stream);
@@ -106,7 +141,7 @@ int gymrl_env_abandon(int kind, void* state, int n_envs, uint64_t seed, int64_t 
  * episode in a spare slot of `state`; gymrl_env_step then swaps it in when the episode ends
  * instead of running the reset inside the step.  Results are bit-identical with or without
  * it.  Intended for a side stream (it may overlap later gymrl_env_step calls on the same
- * state); a no-op for CartPole / Pendulum / MountainCar. */
+ * state); a no-op for CartPole / Pendulum / MountainCar / Acrobot. */
 int gymrl_env_refill(int kind, void* state, int n_envs, uint64_t seed, int64_t env_id0,
                      void* stream);
 
@@ -1800,6 +1835,34 @@ size_t gymrl_snes_tell_args_bytes(void);     /* sizeof(gymrl_snes_tell_args) */
 int gymrl_snes_perturb(const gymrl_snes_perturb_args* args, void* stream);
 int gymrl_snes_tell(const gymrl_snes_tell_args* args, void* stream);
 
+/* ----------------------------- Acrobot-v1 policies: whole episodes in one launch ---- */
+/*
+ * gymrl_mountaincar_net_eval (below: the three nets, the trunk, policy_stride, images, the outputs — all as described there) for
+ * Acrobot-v1, (D, A) = (6, 3), TimeLimit 500 (csrc/eval_acrobot.hip; the same kernels of csrc/eval_kernels_device.hpp and the
+ * same episode loop of csrc/eval_episode_device.hpp, instantiated for env kind 5).  The state (th1, th2, dth1, dth2) is float64
+ * in the lane's registers, the observation the six float32 of the rule at the head of this file, one step is csrc/
+ * env_classic_device.hpp's acrobot_advance — the stepper's RK4 step — on the 16 lanes of the first wave, and the return takes -1 on
+ * every step but a terminating one.  Episode i = p * E + e starts from the reset draw of (seed, stream_id0 + e, episode 0) or from
+ * start[i].
+ * -EINVAL before any launch: gymrl_mountaincar_net_eval's list with cap outside 1..500.
+ */
+typedef struct {
+  int P, E, cap;
+  int net;                                 /* 0: three-layer MLP | 1: dueling, torch's mean | 2: dueling, the DUELING epilogue's mean */
+  int n_hidden, H;                         /* hidden layers of the trunk (net 0: 2; net 1 | 2: 1 | 2) and their width */
+  const float* w[2]; const float* b[2];    /* fc1 [H][6], fc2 [H][H] and their biases, of policy 0; entry 1 is NULL when n_hidden == 1 */
+  const float* head_w; const float* head_b;        /* net 0: fc3 [3][H], [3]; net 1 | 2: the advantage head [3][H], [3] */
+  const float* value_w; const float* value_b;      /* net 1 | 2: the value head [1][H], [1]; net 0: NULL */
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  const float* images;                     /* the forward image of fc2 (n_hidden == 2, H % 16 == 0, P == 1), or NULL: fc2 is read in place */
+  uint64_t seed; int64_t stream_id0;
+  const double* start;                     /* f64[P * E][4] (th1, th2, dth1, dth2), or NULL: the reset draw */
+  float* returns; int32_t* lengths; uint8_t* terminated;
+  float* final_obs;                        /* f32[P * E][6] or NULL */
+} gymrl_acrobot_net_eval_args;
+size_t gymrl_acrobot_net_eval_args_bytes(void);  /* sizeof(gymrl_acrobot_net_eval_args) */
+int gymrl_acrobot_net_eval(const gymrl_acrobot_net_eval_args* args, void* stream);
+
 /*
  * DQN's CartPole vector step on the same row-slab kernels (csrc/dqn_step.hip): dqn_cartpole.py's select_action :124-133 with
  * the env step and memory.push of its train loop :178-184, and update :135-168.  Discrete SAC's scheme with ONE online network
@@ -2037,7 +2100,7 @@ int gymrl_mountaincar_net_eval(const gymrl_mountaincar_net_eval_args* args, void
  * 4..256, a negative policy_stride or one that is not a multiple of 4, policy_stride == 0 with P > 1, images with P > 1, P * E
  * above INT32_MAX, stream_id0 < 0, a pointer that is not aligned (w[k], images: 16 bytes; start: 8; the others: 4).
  * SAC-Pendulum's greedy action tanh(mean(fc2(fc1 s))) * bound is head 1 on (fc1, fc2, mean).  Dueling networks: the entry point below.
- * MountainCar-v0: gymrl_mountaincar_net_eval above (LunarLander-v3 under a PPO policy: gymrl_lunar_policy_eval below).
+ * MountainCar-v0: gymrl_mountaincar_net_eval above, Acrobot-v1: gymrl_acrobot_net_eval further up (LunarLander-v3 under a PPO policy: gymrl_lunar_policy_eval below).
  */
 typedef struct {
   int P, E, cap;
