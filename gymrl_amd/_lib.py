@@ -119,6 +119,13 @@ class LunarEvalArgs(C.Structure):
                 ("terminal_obs", C.c_void_p)]
 
 
+class ClassicPpoEvalArgs(C.Structure):
+    _c_name_ = "gymrl_classic_ppo_eval_args"
+    _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("env_kind", C.c_int), ("seed", C.c_uint64),
+                ("stream_id0", C.c_int64), ("policy_stride", C.c_int64), ("returns", C.c_void_p), ("lengths", C.c_void_p),
+                ("terminated", C.c_void_p), ("final_obs", C.c_void_p)]
+
+
 class LunarCollectArgs(C.Structure):
     _c_name_ = "gymrl_lunar_collect_args"
     _fields_ = ([("N", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("env_id0", C.c_int64), ("counter0", C.c_uint64),
@@ -512,6 +519,7 @@ SIGNATURES = {
     "gymrl_mlp_pack_stack": (_i, [_P(MlpPackStackArgs), _vp]),
     "gymrl_rollout_lunar": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_cartpole": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
+    "gymrl_rollout_classic": (_i, [_i, _P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_lunar_mhc": (_i, [_P(RolloutLunarArgs), _P(MhcPolicy), _vp]),
     "gymrl_lunar_eval_args_bytes": (_sz, []),
     "gymrl_lunar_policy_eval": (_i, [_P(LunarEvalArgs), _P(MlpDesc), _vp]),
@@ -519,6 +527,8 @@ SIGNATURES = {
     "gymrl_lunar_mlprnn_eval": (_i, [_P(LunarEvalArgs), _P(MlprnnParams), _vp, _i64, _vp, _vp]),
     "gymrl_lunar_mlprnn_collect": (_i, [_P(LunarCollectArgs), _P(MlprnnParams), _vp]),
     "gymrl_lunar_collect_args_bytes": (_sz, []),
+    "gymrl_classic_ppo_eval_args_bytes": (_sz, []),
+    "gymrl_classic_ppo_eval": (_i, [_P(ClassicPpoEvalArgs), _P(MlpDesc), _vp]),
     "gymrl_lin_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_lin_fwd": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gymrl_lin_bwd_input": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1,0 +1,64 @@
+// classic_ppo_device.hpp — what PPO's one-launch kernels on the classic-control envs share: rollout_classic.hip (the persistent
+// rollout) and eval_classic_ppo.hip (whole evaluation episodes) are templates over ClassicEnv<KIND>, and both entry points refuse
+// the same policy descriptors.
+//
+//   ClassicEnv<KIND>   CartPole-v1 (4 observations, 2 actions), MountainCar-v0 (2, 3), Acrobot-v1 (6, 3): the widths, the view of
+//                      the env state buffer, ONE env's step with auto-reset (env_classic_device.hpp: gymrl_env_step's arithmetic),
+//                      the TimeLimit, and the vector an observation row of the slab is stored with — 16 bytes are one float4,
+//                      8 and 24 bytes are one and three float2.
+//   ppo_desc_ok        the policy is gymrl_mlp_forward's stage table on the env's observation: logits [A] then value [1] as its
+//                      two dst == -1 stages.
+#pragma once
+#include "env_classic_device.hpp"
+#include "mlp_device.hpp"
+
+namespace gymrl {
+namespace {
+
+template <int KIND> struct ClassicEnv;
+template <> struct ClassicEnv<GYMRL_ENV_CARTPOLE> {
+  static constexpr int kObs = 4, kActions = 2, kMaxSteps = 500;
+  using State = CartPoleState;
+  using ObsVec = float4;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<4>& r) {
+    cartpole_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+template <> struct ClassicEnv<GYMRL_ENV_MOUNTAINCAR> {
+  static constexpr int kObs = 2, kActions = 3, kMaxSteps = 200;
+  using State = MountainCarState;
+  using ObsVec = float2;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<2>& r) {
+    mountaincar_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+template <> struct ClassicEnv<GYMRL_ENV_ACROBOT> {
+  static constexpr int kObs = 6, kActions = 3, kMaxSteps = 500;
+  using State = AcrobotState;
+  using ObsVec = float2;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<6>& r) {
+    acrobot_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+
+// the policy must be a 2-output network on the env's observation: logits [n_act] then value [1]
+inline bool ppo_desc_ok(const gymrl_mlp_desc* policy, int n_obs, int n_act) {
+  int outs = 0, cols = 0;
+  if (!policy || policy->n_stages <= 0 || policy->n_stages > GYMRL_MLP_MAX_STAGES) return false;
+  for (int s = 0; s < policy->n_stages; ++s) {
+    const gymrl_mlp_stage& st = policy->stage[s];
+    if (!st.W || st.in_dim <= 0 || st.out_dim <= 0 || st.in_dim > GYMRL_MLP_MAX_WIDTH || st.src < -1 || st.src > 2 ||
+        st.dst < -1 || st.dst > 2 || (st.dst >= 0 && (st.dst == st.src || st.out_dim > GYMRL_MLP_MAX_WIDTH)) ||
+        (st.src < 0 && st.in_dim != n_obs) || st.act < GYMRL_ACT_NONE || st.act > GYMRL_ACT_RELU ||
+        (reinterpret_cast<uintptr_t>(st.W) & 15))
+      return false;
+    if (st.dst < 0) {
+      if ((outs == 0 && st.out_dim != n_act) || (outs == 1 && st.out_dim != 1) || outs > 1) return false;
+      ++outs; cols += st.out_dim;
+    }
+  }
+  return outs == 2 && cols <= mlp::kHeadStride;
+}
+
+}  // namespace
+}  // namespace gymrl

@@ -5,14 +5,14 @@
 // ONE workgroup of slab::kThreads threads carries 16 episodes of one policy from their reset to their end.  Lane t < 16 of wave 0
 // owns episode e0 + t: its float64 env state, its float64 return, its length and its flags live in registers.  Per iteration
 //
-//   wave 0       puts the float32 observation of every running lane's state into L.S and writes ONE LDS word, "is anybody still
-//                running", beside them
+//   wave 0       puts the float32 observation of every running lane's state into its row of the forward's input (the caller says
+//                where the 16 rows lie: a pointer and a pitch) and writes ONE LDS word, "is anybody still running", beside them
 //   everybody    meets at the barrier that publishes both and leaves on that word — the same for every thread of the workgroup
 //   forward()    every thread: the policy's stages over the slab, each closed by a workgroup barrier, the last one included
 //   action(t)    the running lanes: the greedy action of row t, then cartpole_advance / pendulum_advance / mountaincar_advance /
 //                acrobot_advance in registers
 //
-// A finished lane idles with its registers frozen (its slab row keeps its last observation and is computed along, unread).  No
+// A finished lane idles with its registers frozen (its input row keeps its last observation and is computed along, unread).  No
 // __syncthreads() sits behind a per-lane or per-wave condition, nothing waits for another workgroup, there are no atomics, inside
 // the loop global memory is only READ, and the trip count is at most a.cap.
 #pragma once
@@ -54,12 +54,20 @@ __device__ __forceinline__ void episode_obs(const double (&s)[4], float* o) {
   }
 }
 
+// An argument block's explicit starts f64[P][E][NS], or nullptr where the block has no such member (gymrl_classic_ppo_eval_args)
+template <class Args>
+__device__ __forceinline__ auto episode_starts(const Args& a, int) -> decltype(a.start) { return a.start; }
+template <class Args>
+__device__ __forceinline__ const double* episode_starts(const Args&, long) { return nullptr; }
+
 // KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR, GYMRL_ENV_ACROBOT (action(t) -> int) or GYMRL_ENV_PENDULUM (action(t) -> the torque, float).
-// Args: an argument block with E, cap, seed, stream_id0, start, returns, lengths, terminated, final_obs (include/gymrl.h).
-// `running` is the caller's __shared__ word.
+// Args: an argument block with E, cap, seed, stream_id0, returns (float or double), lengths, terminated, final_obs and, optionally,
+// start (include/gymrl.h).  obs_rows / pitch: the 16 rows the forward reads the observations from, `pitch` floats apart — the
+// slab's L.S at kMaxD (eval_kernels_device.hpp) or mlp::forward_tile's input tile at mlp::kInStride (eval_classic_ppo.hip); all
+// `pitch` columns of the 16 rows are zeroed here once.  `running` is the caller's __shared__ word.
 template <int KIND, class Args, class Forward, class Action>
-__device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& running, const Lds& L, const int p, const int e0, const int nrows,
-                                             Forward&& forward, Action&& action) {
+__device__ __forceinline__ void run_episodes(const Args& a, float* obs_rows, const int pitch, int& running, const int p, const int e0,
+                                             const int nrows, Forward&& forward, Action&& action) {
   constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE, car = KIND == GYMRL_ENV_MOUNTAINCAR, acro = KIND == GYMRL_ENV_ACROBOT;
   constexpr int D = cart ? 4 : car ? 2 : acro ? 6 : 3, NS = cart || acro ? 4 : 2;          // MountainCar-v0: (pos, vel)
   const int t = threadIdx.x;
@@ -69,11 +77,11 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
   int len = 0;
   bool terminated = false, active = t < nrows;
   if (t < 16)
-    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = 0.0f;     // rows beyond the episodes and columns beyond D stay zero
+    for (int k = 0; k < pitch; ++k) obs_rows[t * pitch + k] = 0.0f;      // rows beyond the episodes and columns beyond D stay zero
   if (active) {
-    if (a.start) {
+    if (const double* start = episode_starts(a, 0)) {
 #pragma unroll
-      for (int k = 0; k < NS; ++k) s[k] = a.start[((int64_t)p * a.E + e0 + t) * NS + k];
+      for (int k = 0; k < NS; ++k) s[k] = start[((int64_t)p * a.E + e0 + t) * NS + k];
     } else if constexpr (cart) {
       cartpole_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
     } else if constexpr (car) {
@@ -86,7 +94,7 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
   }
   for (int it = 0; it < a.cap; ++it) {
     if (t < 64) {
-      if (active) episode_obs<KIND>(s, lds + L.S + t * kMaxD);
+      if (active) episode_obs<KIND>(s, obs_rows + t * pitch);
       const bool any = __ballot(active) != 0ull;
       if (t == 0) running = any ? 1 : 0;
     }
@@ -109,11 +117,11 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* lds, int& run
       len += 1;
       active = !terminated && len < a.cap;
     }
-    // (the next iteration's stores to L.S and `running` follow forward()'s closing barrier; their last readers sit in front of it)
+    // (the next iteration's stores to the input rows and `running` follow forward()'s closing barrier; their last readers sit in front of it)
   }
   if (t < nrows) {
     const int64_t i = (int64_t)p * a.E + e0 + t;
-    a.returns[i] = (float)ret; a.lengths[i] = len; a.terminated[i] = terminated;
+    a.returns[i] = (decltype(+a.returns[i]))ret; a.lengths[i] = len; a.terminated[i] = terminated;
     if (a.final_obs) episode_obs<KIND>(s, a.final_obs + i * D);
   }
 }

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void classic_eval_kernel(const Args a) {
   const float* img = (a.images && (H & 15) == 0) ? a.images : nullptr;
   const int R = GYMRL_ACT_RELU, kD = kMaxD, kA = kMaxA;
   run_episodes<KIND>(
-      a, lds, running, L, p, e0, nrows,
+      a, lds + L.S, kD, running, p, e0, nrows,
       [=]() {
         const float *v0 = w0, *v1 = w1, *v2 = w2, *c0 = b0, *c1 = b1, *c2 = b2, *im = img;
         // (the pointers pass through an empty asm: see the register-pressure note at the head of this file)
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void duel_eval_kernel(const Args a) {
   const float* img = (NH == 2 && a.images && (H & 15) == 0) ? a.images : nullptr;
   const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
   run_episodes<KIND>(
-      a, lds, running, L, p, e0, nrows,
+      a, lds + L.S, kD, running, p, e0, nrows,
       [=]() {
         const float *v0 = w0, *c0 = b0, *v1 = w1, *c1 = b1, *vv = wv, *cv = bv, *va = wa, *ca = ba, *im = img;
         // (the pointers pass through an empty asm: see the register-pressure note at the head of this file)

@@ -1,7 +1,7 @@
-// rollout_classic.hip — PPO's collect_rollout (ppo_lunarlander.py:198-231) for CartPole-v1 as ONE persistent launch per
-// chunk of vector steps: rollout_lunar.hip's scheme with the classic-control stepper in place of the Box2D one.
+// rollout_classic.hip — PPO's collect_rollout (ppo_lunarlander.py:198-231) for CartPole-v1, MountainCar-v0 and Acrobot-v1 as ONE
+// persistent launch per chunk of vector steps: rollout_lunar.hip's scheme with the classic-control stepper in place of the Box2D one.
 //
-// Step by step, a CartPole vector step is the policy forward + the sample kernel + cartpole_step_kernel: three launches
+// Step by step, a classic-control vector step is the policy forward + the sample kernel + the env's step kernel: three launches
 // of a few microseconds of work each, i.e. the launch floor.  Nothing couples two workgroups inside a rollout (frozen
 // weights, independent envs), so a workgroup owns its 16 envs for `nsteps` steps: all four waves run the policy forward of
 // the 16 observations (mlp_device.hpp: f32 MFMA, logits and value stay in LDS), then lanes 0..15 of wave 0 fold step
@@ -9,9 +9,11 @@
 // gymrl_categorical_sample), step their env (env_classic_device.hpp: the arithmetic of gymrl_env_step), write the slab
 // rows and put the next observation into the forward's LDS input.  Every arithmetic piece is the device function the
 // step-by-step path launches: the slab is bit-identical to collect_rollout() without this kernel
-// (tests/test_hip_parity.py::test_persistent_rollout_cartpole_bit_identical_to_stepwise).
-#include "env_classic_device.hpp"
-#include "mlp_device.hpp"
+// (tests/test_hip_parity.py::test_persistent_rollout_cartpole_bit_identical_to_stepwise, tests/test_rollout_classic_gpu.py).
+//
+// The kernel is ONE template over classic_ppo_device.hpp's ClassicEnv<KIND>: the observation width, the action count, the state
+// view, the step function and the vector an observation row is stored with are the env's, everything else is shared.
+#include "classic_ppo_device.hpp"
 #include "policy_device.hpp"
 
 using namespace gymrl;
@@ -20,13 +22,18 @@ namespace M = gymrl::mlp;
 namespace {
 
 constexpr int kThreads = M::kWaves * 64;
-constexpr int kActions = 2, kObs = 4;
 constexpr int kGaeChunk = 16;        // == gymrl_gae_chunk() (gae.hip kBlkTC)
 constexpr int kDynFloats = M::kBufs * M::kRows * M::kStride + M::kRows * M::kInStride + M::kRows * M::kHeadStride;
 constexpr int kDynBytes = 96 * 1024; // > 80 KB: one workgroup per CU (as mlp_forward_kernel)
 static_assert(kDynFloats * 4 <= kDynBytes, "LDS carve-up");
 
-__global__ __launch_bounds__(kThreads) void rollout_cartpole_kernel(gymrl_rollout_lunar_args a, gymrl_mlp_desc d) {
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void rollout_classic_kernel(gymrl_rollout_lunar_args a, gymrl_mlp_desc d) {
+  using Env = ClassicEnv<KIND>;
+  using ObsVec = typename Env::ObsVec;
+  constexpr int kObs = Env::kObs, kActions = Env::kActions;
+  constexpr int kObsVecs = kObs * (int)sizeof(float) / (int)sizeof(ObsVec);
+  static_assert(kObsVecs * sizeof(ObsVec) == kObs * sizeof(float), "an observation row is whole store vectors");
   extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
   float (*lds)[M::kRows * M::kStride] = reinterpret_cast<float (*)[M::kRows * M::kStride]>(dyn_lds);
   float* xin = dyn_lds + M::kBufs * M::kRows * M::kStride;
@@ -37,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void rollout_cartpole_kernel(gymrl_rollou
   const int t_end = a.t0 + a.nsteps;
   const int row = lane, i = m0 + row;                              // wave 0's view: one lane per env (lanes 0..15)
   const bool valid = row < M::kRows && i < N;
-  const CartPoleState st(a.env_state, N);
+  const typename Env::State st(a.env_state, N);
   const double gl = (double)(float)(a.gamma * a.lam);              // NEP-50 float32 decay (see gae.hip)
 
   for (int e = tid; e < M::kRows * M::kInStride; e += kThreads) xin[e] = 0.0f;
@@ -53,7 +60,7 @@ __global__ __launch_bounds__(kThreads) void rollout_cartpole_kernel(gymrl_rollou
     M::forward_tile(d, lds, xin, head, m0, N, tid, 0u);
     __syncthreads();                                // logits / value of the 16 rows are in `head`
     if (wave == 0) {
-      ClassicStep<4> r;
+      ClassicStep<kObs> r;
       r.done = false; r.ret = 0.0; r.len = 0;
       if (valid) {
         const float v = head[row * M::kHeadStride + kActions];
@@ -74,12 +81,17 @@ __global__ __launch_bounds__(kThreads) void rollout_cartpole_kernel(gymrl_rollou
           const int act = categorical_pick<kActions>(z, a.noise_exp ? a.noise_exp + o * kActions : nullptr, a.seed,
                                                      (uint64_t)(a.env_id0 + i), a.counter0 + (uint64_t)t, 0, lp, H);
           a.act[o] = act; a.logp[o] = lp;
-          cartpole_step_one(st, i, a.seed, a.env_id0, act, r);
+          Env::step(st, i, a.seed, a.env_id0, act, r);
           a.rew[o] = r.reward;
           a.done[o] = r.done;
           if (a.ep_ret && r.done) a.ep_ret[o] = (float)r.ret;
           float* on = a.obs + ((size_t)(t + 1) * N + i) * kObs;
-          reinterpret_cast<float4*>(on)[0] = make_float4(r.o_next[0], r.o_next[1], r.o_next[2], r.o_next[3]);
+          if constexpr (kObsVecs == 1 && sizeof(ObsVec) == 16) {
+            reinterpret_cast<float4*>(on)[0] = make_float4(r.o_next[0], r.o_next[1], r.o_next[2], r.o_next[3]);
+          } else {
+#pragma unroll
+            for (int k = 0; k < kObsVecs; ++k) reinterpret_cast<float2*>(on)[k] = make_float2(r.o_next[2 * k], r.o_next[2 * k + 1]);
+          }
 #pragma unroll
           for (int k = 0; k < kObs; ++k) xin[row * M::kInStride + k] = r.o_next[k];     // next policy input: the forward's LDS tile
         }
@@ -90,39 +102,45 @@ __global__ __launch_bounds__(kThreads) void rollout_cartpole_kernel(gymrl_rollou
   }
 }
 
+// what every kind's entry refuses alike, before any launch: the slabs, the step window, the GAE pair, the row's alignment, the policy
+template <int KIND>
+bool rollout_args_ok(const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc* policy) {
+  using Env = ClassicEnv<KIND>;
+  if (!a || !policy || !a->env_state || !a->obs || !a->act || !a->logp || !a->val || !a->rew || !a->done ||
+      !a->next_value || a->n_envs <= 0 || a->T <= 0 || a->t0 < 0 || a->nsteps < 0 || a->t0 + a->nsteps > a->T)
+    return false;
+  if (a->gae_running && !a->gae_workspace) return false;
+  if (reinterpret_cast<uintptr_t>(a->obs) & (sizeof(typename Env::ObsVec) - 1)) return false;
+  return ppo_desc_ok(policy, Env::kObs, Env::kActions);
+}
+
+template <int KIND>
+int rollout_launch(const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc* policy, void* stream) {
+  if (!rollout_args_ok<KIND>(a, policy)) return -22;
+  if (a->nsteps == 0 && a->t0 != a->T) return 0;
+  static bool attr_set = false;
+  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_classic_kernel<KIND>}, kDynBytes)) return rc;
+  const int blocks = (a->n_envs + M::kRows - 1) / M::kRows;
+  hipLaunchKernelGGL(rollout_classic_kernel<KIND>, dim3(blocks), dim3(kThreads), kDynBytes, (hipStream_t)stream, *a, *policy);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 int gymrl_rollout_cartpole(const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc* policy, void* stream) {
-  if (!a || !policy || !a->env_state || !a->obs || !a->act || !a->logp || !a->val || !a->rew || !a->done ||
-      !a->next_value || a->n_envs <= 0 || a->T <= 0 || a->t0 < 0 || a->nsteps < 0 || a->t0 + a->nsteps > a->T)
-    return -22;
-  if (a->gae_running && !a->gae_workspace) return -22;
-  if (reinterpret_cast<uintptr_t>(a->obs) & 15) return -22;
-  // the policy must be a 2-output network on the CartPole observation: logits [2] then value [1]
-  int outs = 0, cols = 0;
-  if (policy->n_stages <= 0 || policy->n_stages > GYMRL_MLP_MAX_STAGES) return -22;
-  for (int s = 0; s < policy->n_stages; ++s) {
-    const gymrl_mlp_stage& st = policy->stage[s];
-    if (!st.W || st.in_dim <= 0 || st.out_dim <= 0 || st.in_dim > GYMRL_MLP_MAX_WIDTH || st.src < -1 || st.src > 2 ||
-        st.dst < -1 || st.dst > 2 || (st.dst >= 0 && (st.dst == st.src || st.out_dim > GYMRL_MLP_MAX_WIDTH)) ||
-        (st.src < 0 && st.in_dim != kObs) || st.act < GYMRL_ACT_NONE || st.act > GYMRL_ACT_RELU ||
-        (reinterpret_cast<uintptr_t>(st.W) & 15))
-      return -22;
-    if (st.dst < 0) {
-      if ((outs == 0 && st.out_dim != kActions) || (outs == 1 && st.out_dim != 1) || outs > 1) return -22;
-      ++outs; cols += st.out_dim;
-    }
+  return rollout_launch<GYMRL_ENV_CARTPOLE>(a, policy, stream);
+}
+
+int gymrl_rollout_classic(int env_kind, const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc* policy, void* stream) {
+  switch (env_kind) {
+    case GYMRL_ENV_CARTPOLE: return rollout_launch<GYMRL_ENV_CARTPOLE>(a, policy, stream);
+    case GYMRL_ENV_MOUNTAINCAR: return rollout_launch<GYMRL_ENV_MOUNTAINCAR>(a, policy, stream);
+    case GYMRL_ENV_ACROBOT: return rollout_launch<GYMRL_ENV_ACROBOT>(a, policy, stream);
+    default: return -22;
   }
-  if (outs != 2 || cols > M::kHeadStride) return -22;
-  if (a->nsteps == 0 && a->t0 != a->T) return 0;
-  static bool attr_set = false;
-  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_cartpole_kernel}, kDynBytes)) return rc;
-  const int blocks = (a->n_envs + M::kRows - 1) / M::kRows;
-  hipLaunchKernelGGL(rollout_cartpole_kernel, dim3(blocks), dim3(kThreads), kDynBytes, (hipStream_t)stream, *a, *policy);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
+from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, ClassicPpoEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    LunarCollectArgs, LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, AcrobotNetEvalArgs, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
@@ -1037,6 +1037,37 @@ def lunar_policy_eval(policy, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS,
     return out
 
 
+CLASSIC_PPO_EVAL_CAPS = {CARTPOLE: 500, MOUNTAINCAR: 200, ACROBOT: 500}       # kind -> the env's TimeLimit
+
+
+def classic_ppo_eval(kind, policy, n_episodes, seed, stream_id0, cap=None, want_final_obs=False, device=None):
+    """n_episodes whole CartPole-v1 / MountainCar-v0 / Acrobot-v1 episodes per policy under the first maximum of the PPO
+    actor-critic's logits, in ONE launch (include/gymrl.h gymrl_classic_ppo_eval) -> (returns f64, lengths i32, terminated u8,
+    final_obs f32[..., D] | None), each [P, n_episodes].  policy: a nn.FusedMLP (logits [A] then value [1]; P = 1, the weights as
+    its last refresh() packed them) or a LunarPolicyStack of such networks.  cap: None = the env's TimeLimit.  Episode e of every
+    policy is the first episode of env stream_id0 + e under `seed`."""
+    if kind not in CLASSIC_PPO_EVAL_CAPS:
+        raise ValueError(f"classic_ppo_eval: env kind {kind} is not CartPole-v1's, MountainCar-v0's or Acrobot-v1's")
+    if isinstance(policy, LunarPolicyStack):
+        P, stride, desc, dev = policy.P, policy.stride, policy.desc, policy.buffer.device
+    else:
+        dev = device if device is not None else policy.stages[0][0].weight.device
+        P, stride, desc = 1, 0, policy.descriptor(16, dev)
+    D = ROLLOUT_CLASSIC_DIMS[kind][0]
+    n_episodes = int(n_episodes)
+    returns = torch.empty(P, n_episodes, dtype=torch.float64, device=dev)
+    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
+    terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
+    final = torch.empty(P, n_episodes, D, dtype=torch.float32, device=dev) if want_final_obs else None
+    a = ClassicPpoEvalArgs()
+    a.P, a.E, a.cap, a.env_kind = P, n_episodes, CLASSIC_PPO_EVAL_CAPS[kind] if cap is None else int(cap), kind
+    a.seed, a.stream_id0, a.policy_stride = seed, stream_id0, stride
+    a.returns, a.lengths, a.terminated = _ptr(returns), _ptr(lengths), _ptr(terminated)
+    a.final_obs = _ptr(final, torch.float32, True)
+    check(lib().gymrl_classic_ppo_eval(C.byref(a), C.byref(desc), _stream()), "gymrl_classic_ppo_eval")
+    return returns, lengths, terminated, final
+
+
 def lunar_mhc_eval(policy_desc, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS, want_terminal_obs=True, device=None):
     """lunar_policy_eval for PPO-full's mHC network: policy_desc is a filled _lib.MhcPolicy (its `image` as the caller left it:
     None reads the parameters in place), one policy."""
@@ -1724,9 +1755,29 @@ def rollout_lunar(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, va
     check(lib().gymrl_rollout_lunar(C.byref(a), C.byref(policy_desc), _stream()), "gymrl_rollout_lunar")
 
 
-def rollout_cartpole(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, policy_desc,
-                     T, t0, nsteps, gamma, lam, noise_exp=None, gae_running=None, gae_workspace=None, ep_stats=None):
-    """gymrl_rollout_cartpole: the persistent rollout for PPO on CartPole-v1 (obs [T+1, N, 4], two actions)."""
+ROLLOUT_CLASSIC_DIMS = {CARTPOLE: (4, 2), MOUNTAINCAR: (2, 3), ACROBOT: (6, 3)}      # kind -> (observations, actions)
+
+
+def _rollout_classic_args(what, kind, env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, T, t0,
+                          nsteps, gamma, lam, noise_exp, gae_running, gae_workspace, ep_stats):
+    """The argument block of gymrl_rollout_cartpole / gymrl_rollout_classic; the slabs' shapes are checked against the kind's
+    (observations, actions) before any pointer is taken."""
+    if kind not in ROLLOUT_CLASSIC_DIMS:
+        raise ValueError(f"{what}: env kind {kind} is not CartPole-v1's, MountainCar-v0's or Acrobot-v1's")
+    D, A = ROLLOUT_CLASSIC_DIMS[kind]
+    if n_envs < 1 or T < 1 or tuple(obs.shape) != (T + 1, n_envs, D):
+        raise ValueError(f"{what}: obs is f32[T + 1, N, {D}] = {(T + 1, n_envs, D)}, not {tuple(obs.shape)}")
+    for name, t in (("act", act), ("logp", logp), ("val", val), ("rew", rew), ("done", done), ("ep_ret", ep_ret)):
+        if t is not None and tuple(t.shape) != (T, n_envs):
+            raise ValueError(f"{what}: {name} is [T, N] = {(T, n_envs)}, not {tuple(t.shape)}")
+    if next_value.numel() != n_envs:
+        raise ValueError(f"{what}: next_value is f32[N] = {n_envs}, not {tuple(next_value.shape)}")
+    if noise_exp is not None and tuple(noise_exp.shape) != (T, n_envs, A):
+        raise ValueError(f"{what}: noise_exp is f32[T, N, {A}] = {(T, n_envs, A)}, not {tuple(noise_exp.shape)}")
+    if gae_running is not None and tuple(gae_running.shape) != (2, n_envs):
+        raise ValueError(f"{what}: gae_running is f64[2, N] = {(2, n_envs)}, not {tuple(gae_running.shape)}")
+    if env_state.numel() * env_state.element_size() < int(lib().gymrl_env_state_bytes(kind, n_envs)):
+        raise ValueError(f"{what}: env_state is smaller than gymrl_env_state_bytes({kind}, {n_envs})")
     a = RolloutLunarArgs()
     a.env_state, a.n_envs, a.seed, a.env_id0, a.counter0 = _ptr(env_state).value, n_envs, seed, env_id0, counter0
     a.obs, a.act, a.logp = _ptr(obs, torch.float32).value, _ptr(act, torch.int32).value, _ptr(logp, torch.float32).value
@@ -1736,7 +1787,24 @@ def rollout_cartpole(env_state, n_envs, seed, env_id0, counter0, obs, act, logp,
     a.gae_running, a.gae_workspace = _ptr(gae_running, torch.float64, True).value, _ptr(gae_workspace, None, True).value
     a.gamma, a.lam, a.ep_stats = gamma, lam, _ptr(ep_stats, torch.float64, True).value
     a.T, a.t0, a.nsteps = T, t0, nsteps
+    return a
+
+
+def rollout_cartpole(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, policy_desc,
+                     T, t0, nsteps, gamma, lam, noise_exp=None, gae_running=None, gae_workspace=None, ep_stats=None):
+    """gymrl_rollout_cartpole: the persistent rollout for PPO on CartPole-v1 (obs [T+1, N, 4], two actions)."""
+    a = _rollout_classic_args("rollout_cartpole", CARTPOLE, env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done,
+                              ep_ret, next_value, T, t0, nsteps, gamma, lam, noise_exp, gae_running, gae_workspace, ep_stats)
     check(lib().gymrl_rollout_cartpole(C.byref(a), C.byref(policy_desc), _stream()), "gymrl_rollout_cartpole")
+
+
+def rollout_classic(kind, env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, policy_desc,
+                    T, t0, nsteps, gamma, lam, noise_exp=None, gae_running=None, gae_workspace=None, ep_stats=None):
+    """gymrl_rollout_classic: the persistent rollout for PPO on CartPole-v1, MountainCar-v0 or Acrobot-v1 (obs [T+1, N, D], A
+    actions: ROLLOUT_CLASSIC_DIMS[kind]); rollout_cartpole's arguments behind the env kind."""
+    a = _rollout_classic_args("rollout_classic", kind, env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done,
+                              ep_ret, next_value, T, t0, nsteps, gamma, lam, noise_exp, gae_running, gae_workspace, ep_stats)
+    check(lib().gymrl_rollout_classic(kind, C.byref(a), C.byref(policy_desc), _stream()), "gymrl_rollout_classic")
 
 
 def rollout_lunar_mhc(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, policy_desc,

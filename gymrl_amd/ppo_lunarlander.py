@@ -62,7 +62,8 @@ class Config:
         self.fused_policy_forward = True  # rollout forward = one gymrl_mlp_forward launch (False: per-layer torch)
         self.fused_update = True          # update = ppo_net.FusedActorCriticUpdate.step(): hand-written f32-MFMA GEMMs + fused
                                           # HBM passes, hidden_dim 64 / 128 / 256 (False or another shape: torch autograd)
-        self.persistent_rollout = True    # LunarLander: whole chunks of vector steps in one launch (gymrl_rollout_lunar)
+        self.persistent_rollout = True    # LunarLander: whole chunks of vector steps in one launch (gymrl_rollout_lunar); CartPole,
+                                          # MountainCar, Acrobot: the same (gymrl_rollout_cartpole / gymrl_rollout_classic)
         self.rollout_chunk = 0            # vector steps per persistent launch (0: the whole rollout in one launch —
                                           # every extra launch boundary waits for the slowest workgroup again)
         self.rollout_refill = True        # persistent rollout: wave 1 prepares every env's next episode while wave 0 steps
@@ -70,7 +71,8 @@ class Config:
                                           # Bit-identical to the eager loop, but measured SLOWER at bench shape (update 889 vs 881
                                           # ms, A/B in one call: the host already runs ~19 launches ahead of 2.8 ms of kernels,
                                           # and the graph executor's 4-7 us per kernel node exceed the eager queue's gaps)
-        self.fused_eval = False           # LunarLander: eval() as ONE launch (gymrl_lunar_policy_eval) on the loop's own streams, acting on
+        self.fused_eval = False           # LunarLander (gymrl_lunar_policy_eval), CartPole / MountainCar / Acrobot (gymrl_classic_ppo_eval):
+                                          # eval() as ONE launch on the loop's own streams, acting on
                                           # act_forward's logits — the forward the persistent rollout trains under; eval()'s loop runs
                                           # torch's layers, which can differ from it in a logit's last place
         self.solved_reward = 200.0
@@ -378,11 +380,12 @@ class PPOTrainer:
         return self._next_value
 
     def _persistent_ok(self):
-        """gymrl_rollout_lunar / gymrl_rollout_cartpole cover: the built-in LunarLander and CartPole envs, a policy the
-        one-launch forward supports."""
+        """gymrl_rollout_lunar / gymrl_rollout_cartpole / gymrl_rollout_classic cover: the built-in LunarLander, CartPole,
+        MountainCar and Acrobot envs, a policy the one-launch forward supports."""
         cfg, env = self.cfg, self.env
         return (cfg.persistent_rollout and cfg.fused_policy_forward and isinstance(env, VecEnv)
-                and (env.kind, self.action_dim) in ((ops.LUNARLANDER, 4), (ops.CARTPOLE, 2)) and bool(self.model._act_net()))
+                and (env.kind, self.action_dim) in ((ops.LUNARLANDER, 4), (ops.CARTPOLE, 2), (ops.MOUNTAINCAR, 3), (ops.ACROBOT, 3))
+                and bool(self.model._act_net()))
 
     def _collect_rollout_persistent(self, counter0, noise, fuse_gae):
         """:198-231 as ceil(T / rollout_chunk) launches: every workgroup runs its 16 envs through the whole chunk
@@ -404,6 +407,8 @@ class PPOTrainer:
                           gae_workspace=self._gae_ws if fuse_gae else None, ep_stats=env.ep_stats)
             if env.kind == ops.CARTPOLE:
                 ops.rollout_cartpole(*common, **online)
+            elif env.kind in (ops.MOUNTAINCAR, ops.ACROBOT):
+                ops.rollout_classic(env.kind, *common, **online)
             else:
                 ops.rollout_lunar(*common, **online, wg_ticks=self._wg_ticks, refill=getattr(cfg, "rollout_refill", True),
                                   gae_carry=carry)
@@ -663,10 +668,18 @@ class PPOTrainer:
 
     EVAL_SEED_OFFSET, EVAL_ENV_ID0 = 1_000_003, 1 << 40      # eval()'s env streams: seed base_seed + 1_000_003, env ids from 1 << 40
 
+    _EVAL_KINDS = {ops.LUNARLANDER: 4, ops.CARTPOLE: 2, ops.MOUNTAINCAR: 3, ops.ACROBOT: 3}     # kind -> actions: what the one-launch evaluations take
+
+    def _eval_kind(self):
+        """The env kind of the one-launch evaluation (gymrl_lunar_policy_eval: LunarLander; gymrl_classic_ppo_eval: CartPole,
+        MountainCar, Acrobot), or None for any other env."""
+        kind = ops.ENV_KINDS.get(self.cfg.env_name)
+        return kind if self._EVAL_KINDS.get(kind) == self.action_dim else None
+
     def _eval_net(self):
-        """The one-launch forward gymrl_lunar_policy_eval acts on (weights packed as they are now), or None: an env other than the
-        built-in LunarLander, or a network FusedMLP.supported refuses."""
-        if ops.ENV_KINDS.get(self.cfg.env_name) != ops.LUNARLANDER or self.action_dim != 4:
+        """The one-launch forward gymrl_lunar_policy_eval / gymrl_classic_ppo_eval act on (weights packed as they are now), or
+        None: an env neither entry point takes, or a network FusedMLP.supported refuses."""
+        if self._eval_kind() is None:
             return None
         net = self.model._act_net()
         if not net:
@@ -678,21 +691,27 @@ class PPOTrainer:
     def evaluate(self, num_episodes, params=None, stream_offset=0):
         """-> (returns f64, lengths i32, terminated u8), numpy arrays [P, num_episodes]: whole deterministic episodes on eval()'s
         streams (episode e: seed base_seed + 1_000_003, env id (1 << 40) + stream_offset + e), every policy from the same starts,
-        in ONE launch (csrc/eval_lunar.hip) whatever Config.fused_eval says.  params = None: the trainer's own policy (P = 1);
+        in ONE launch (csrc/eval_lunar.hip; CartPole / MountainCar / Acrobot: csrc/eval_classic_ppo.hip) whatever Config.fused_eval says.  params = None: the trainer's own policy (P = 1);
         params = f32[P, n]: a stack of flat parameter vectors in the layout of flat_params.  The actions are the first maxima of
         act_forward's logits (gymrl_mlp_forward's bits).  Moves neither the rollout's counters, nor self.env, the buffer or the
         optimiser.  Raises where the entry point takes no such policy."""
         net = self._eval_net()
         if net is None:
-            raise RuntimeError("PPOTrainer.evaluate: gymrl_lunar_policy_eval takes LunarLander-v3 under a network the one-launch "
-                               "forward supports (include/gymrl.h)")
+            raise RuntimeError("PPOTrainer.evaluate: gymrl_lunar_policy_eval takes LunarLander-v3 and gymrl_classic_ppo_eval CartPole-v1, "
+                               "MountainCar-v0 and Acrobot-v1 under a network the one-launch forward supports (include/gymrl.h)")
         policy = net
         if params is not None:
             params = torch.as_tensor(params, dtype=torch.float32).to(self.device)
             policy = ops.LunarPolicyStack(net, self.flat_params, params.view(1, -1) if params.dim() == 1 else params)
-        out = ops.lunar_policy_eval(policy, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET,
-                                    self.EVAL_ENV_ID0 + int(stream_offset), want_terminal_obs=False, device=self.device)
+        out = self._eval_launch(policy, int(num_episodes), int(stream_offset))
         return tuple(t.cpu().numpy() for t in out[:3])
+
+    def _eval_launch(self, policy, num_episodes, stream_offset=0):
+        """The one launch of evaluate() / eval() for this trainer's env -> (returns f64, lengths, terminated, None), each [P, E]."""
+        kind, seed, id0 = self._eval_kind(), self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0 + stream_offset
+        if kind == ops.LUNARLANDER:
+            return ops.lunar_policy_eval(policy, num_episodes, seed, id0, want_terminal_obs=False, device=self.device)
+        return ops.classic_ppo_eval(kind, policy, num_episodes, seed, id0, device=self.device)
 
     def _eval_fused(self, num_episodes):
         """eval(num_episodes) as one launch -> the list the loop returns, or None: fused_eval is off, the test hook supplies the env,
@@ -702,15 +721,14 @@ class PPOTrainer:
         net = self._eval_net()
         if net is None:
             return None
-        returns = ops.lunar_policy_eval(net, int(num_episodes), self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0,
-                                        want_terminal_obs=False, device=self.device)[0]
+        returns = self._eval_launch(net, int(num_episodes))[0]
         return returns[0].to(torch.float32).tolist()           # the loop's ep_ret_out: the float32 cast of the float64 return
 
     @torch.no_grad()
     def eval(self, num_episodes=10):
         """:368-399: deterministic (argmax) episodes — run as `num_episodes` parallel envs,
         each contributing its first finished episode.  With Config.fused_eval the same episodes are ONE launch
-        (gymrl_lunar_policy_eval) that reproduces this loop run on act_forward (gymrl_mlp_forward) bit for bit; the loop below
+        (gymrl_lunar_policy_eval; CartPole / MountainCar / Acrobot: gymrl_classic_ppo_eval) that reproduces this loop run on act_forward (gymrl_mlp_forward) bit for bit; the loop below
         runs torch's library layers, whose logits can differ from act_forward's in the last place — argmax makes a different
         action rare, not impossible, so the two lists are not promised equal."""
         rewards = self._eval_fused(num_episodes)

@@ -699,6 +699,15 @@ int gymrl_rollout_lunar(const gymrl_rollout_lunar_args* args, const gymrl_mlp_de
  * `wg_ticks` are ignored.  A step by step CartPole vector step is three launches at the launch floor; here a workgroup
  * keeps its 16 envs for the whole chunk.  Bit-identical to gymrl_mlp_forward -> gymrl_categorical_sample -> gymrl_env_step. */
 int gymrl_rollout_cartpole(const gymrl_rollout_lunar_args* args, const gymrl_mlp_desc* policy, void* stream);
+/* The same rollout for PPO on any of the discrete classic-control envs (csrc/rollout_classic.hip: one kernel template, one
+ * instantiation per env): env_kind is GYMRL_ENV_CARTPOLE (D = 4 observations, A = 2 actions), GYMRL_ENV_MOUNTAINCAR (2, 3) or
+ * GYMRL_ENV_ACROBOT (6, 3).  The argument block is gymrl_rollout_cartpole's, with the same ignored fields: obs f32[T+1][N][D],
+ * noise_exp f32[T][N][A] or NULL, env_state is gymrl_env_state_bytes(env_kind, n_envs); the policy's two dst == -1 stages are
+ * logits [A] then value [1].  With GYMRL_ENV_CARTPOLE it is gymrl_rollout_cartpole's launch.  Bit-identical to gymrl_mlp_forward
+ * -> gymrl_categorical_sample -> gymrl_env_step.  -EINVAL before any launch: everything gymrl_rollout_cartpole refuses, any other
+ * kind, a descriptor whose input width is not D or whose logit width is not A, and an `obs` that is not aligned to the store of
+ * an observation row: 16 bytes (CartPole-v1: one float4) or 8 bytes (the other two: one and three float2). */
+int gymrl_rollout_classic(int env_kind, const gymrl_rollout_lunar_args* args, const gymrl_mlp_desc* policy, void* stream);
 /* The same persistent rollout for PPO-full (ppo_full_lunarlander.py collect_experience :440-505): the policy is the mHC network
  * (gymrl_mhc_policy, declared with gymrl_mhc_policy_forward below; obs_dim 8, n_act 4), `ent` receives the behaviour policy's
  * entropy, and with gae_running2 / lam2 both decoupled-lambda chunk maps are composed (the actor's with `lam`, then the critic's).
@@ -797,6 +806,41 @@ typedef struct {
 } gymrl_lunar_collect_args;
 int gymrl_lunar_mlprnn_collect(const gymrl_lunar_collect_args* args, const gymrl_mlprnn_params* policy, void* stream);
 size_t gymrl_lunar_collect_args_bytes(void);  /* sizeof(gymrl_lunar_collect_args) */
+
+/* ------------------------------ classic-control PPO policies: whole episodes in one launch ---- */
+/*
+ * gymrl_lunar_policy_eval's contract for PPOTrainer on CartPole-v1, MountainCar-v0 and Acrobot-v1 (csrc/eval_classic_ppo.hip):
+ * P policies x E deterministic episodes in ONE launch, the grid is P * ceil(E / 16) workgroups of 256 threads.  A workgroup
+ * carries 16 episodes of one policy from the in-kernel reset to their end: lanes 0..15 of wave 0 keep the float64 env state, the
+ * float64 return and the length in registers (the episode loop of gymrl_classic_policy_eval further down), all four waves run the
+ * policy forward (gymrl_mlp_forward's stages; stages that only feed the value are not run), the action is the FIRST maximum of the
+ * logits (gymrl_categorical_sample's deterministic branch).  No atomics, nothing waits for another workgroup, no random draw;
+ * global memory is written once, when the workgroup's episodes have ended.
+ *
+ * env_kind is GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR or GYMRL_ENV_ACROBOT; the policy is gymrl_rollout_classic's descriptor for
+ * that kind (their `out` pointers are ignored).  Policy p reads every stage's W and b p * policy_stride floats behind policy 0's
+ * (0: P == 1).  Episode i = p * E + e is the first episode of env stream_id0 + e under `seed` — the SAME starts for every policy,
+ * env e of a gymrl_env_reset with env_id0 = stream_id0.  It ends with terminated = 1 when the env says so, with terminated = 0
+ * when its length reaches `cap`.
+ *
+ * Outputs, each [P * E]: returns (float64: the sum of the float32 rewards in step order), lengths, terminated, final_obs
+ * [P * E][D] (optional) the observation after the last step (the terminal one, not the next episode's first).  Bit-identical to
+ * the step-by-step sequence gymrl_mlp_forward -> gymrl_categorical_sample(deterministic) -> gymrl_env_step.
+ * -EINVAL before any launch: NULL args / policy / returns / lengths / terminated, P < 1, E < 1, P * E above INT32_MAX, cap < 1 or
+ * above the kind's TimeLimit (500 / 200 / 500), stream_id0 < 0, a negative policy_stride or one that is not a multiple of 4,
+ * policy_stride == 0 with P > 1, a pointer that is not aligned (returns: 8 bytes; lengths: 4; final_obs: 8), any other kind, and
+ * every descriptor gymrl_rollout_classic refuses for the kind.
+ */
+typedef struct {
+  int P, E, cap;
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE | GYMRL_ENV_MOUNTAINCAR | GYMRL_ENV_ACROBOT */
+  uint64_t seed; int64_t stream_id0;
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  double* returns; int32_t* lengths; uint8_t* terminated;
+  float* final_obs;                        /* f32[P * E][D] or NULL */
+} gymrl_classic_ppo_eval_args;
+size_t gymrl_classic_ppo_eval_args_bytes(void);  /* sizeof(gymrl_classic_ppo_eval_args) */
+int gymrl_classic_ppo_eval(const gymrl_classic_ppo_eval_args* args, const gymrl_mlp_desc* policy, void* stream);
 
 /* ================================================ low-latency Linear layers == */
 /*
