@@ -1,5 +1,7 @@
 // env_lunar.hip — LunarLander-v3 batched stepper: kernels and launchers (the solver itself is in
 // env_lunar_device.hpp, which carries the design notes).
+#include <cstdlib>
+
 #include "env_lunar_device.hpp"
 
 using namespace gymrl;
@@ -46,9 +48,10 @@ __global__ __launch_bounds__(kEnvBlock) void lunar_step_kernel(
     float* __restrict__ obs_out, float* __restrict__ term_obs_out, float* __restrict__ rew_out,
     uint8_t* __restrict__ terminated_out, uint8_t* __restrict__ truncated_out,
     uint8_t* __restrict__ done_out, float* __restrict__ ep_ret_out,
-    int32_t* __restrict__ ep_len_out, double* __restrict__ ep_stats) {
+    int32_t* __restrict__ ep_len_out, double* __restrict__ ep_stats, int general_sweep) {
   __shared__ uint32_t lds_words[kLdsWords * kEnvBlock];
-  const Lds lds{lds_words + threadIdx.x};
+  Lds lds{lds_words + threadIdx.x};
+  lds.general_sweep = general_sweep != 0;
   const LunarState st(buf, n);
   const int role = threadIdx.x & 3;
   const int i = blockIdx.x * kEnvsPerBlock + (threadIdx.x >> 2);
@@ -83,9 +86,13 @@ int lunar_step(void* state, int n, uint64_t seed, int64_t env_id0, const int32_t
                float* obs_out, float* term_obs_out, float* rew_out, uint8_t* terminated_out,
                uint8_t* truncated_out, uint8_t* done_out, float* ep_ret_out, int32_t* ep_len_out,
                double* ep_stats, hipStream_t s) {
+  // GYMRL_LUNAR_GENERAL_SWEEP=1: every step runs the general velocity-sweep body instead of the one chosen per wave-step
+  // (tests/test_lunar_sweep_variants.py steps the same envs both ways and compares every state word)
+  const char* gs = getenv("GYMRL_LUNAR_GENERAL_SWEEP");
+  const int general_sweep = gs && gs[0] == '1';
   hipLaunchKernelGGL(lunar_step_kernel, dim3(cdiv(n, kEnvsPerBlock)), dim3(kEnvBlock), 0, s, state, n, seed,
                      env_id0, action, obs_out, term_obs_out, rew_out, terminated_out, truncated_out,
-                     done_out, ep_ret_out, ep_len_out, ep_stats);
+                     done_out, ep_ret_out, ep_len_out, ep_stats, general_sweep);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

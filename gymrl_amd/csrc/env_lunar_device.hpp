@@ -116,6 +116,7 @@ struct Lds {
   unsigned long long* envp = nullptr;   // probe build: this lane's env's counters, [3][envn]: steps with a contact of its own, its own
   int envn = 0;                         // position iterations, steps on which the WAVE ran the contact sweeps
 #endif
+  bool general_sweep = false;   // test switch (wave-uniform): every wave-step with a contact runs the general sweep body
   __device__ __forceinline__ float& mf(int s, int f) const { return reinterpret_cast<float*>(w)[(s * kMfWords + f) * kEnvBlock]; }
   __device__ __forceinline__ uint32_t& mu(int s, int f) const { return w[(s * kMfWords + f) * kEnvBlock]; }
   __device__ __forceinline__ float& vc(int s, int f) const { return reinterpret_cast<float*>(w)[(2 * kMfWords + s * kVcWords + f) * kEnvBlock]; }
@@ -156,6 +157,8 @@ struct World {
   uint32_t flags;           // bit0 leg0 ground contact, bit1 leg1, bit2 game_over, bit3 has prev_shaping, bit4 asleep
   float prev_shaping;
 };
+
+template <bool B> struct SweepFlag { static constexpr bool value = B; };   // compile-time switch of a sweep-loop variant
 
 __device__ __forceinline__ float cross2(float ax, float ay, float bx, float by) { return ax * by - ay * bx; }
 __device__ __forceinline__ float dot2(float ax, float ay, float bx, float by) { return ax * bx + ay * by; }
@@ -782,16 +785,37 @@ __device__ __forceinline__ void world_step(World& W, const Lds& lds, int role, i
   };
 #undef SB
 #undef USEL
-  auto contacts = [&]() {
+  // The contact half of a sweep: each lane solves its own body's slots (lane = body), so the velocities are transposed
+  // from the joint solve's layout (lane = component) and back.  A transposed word is a quad broadcast selected by the lane's
+  // role: v_cndmask_b32 takes a DPP operand when its mask is VCC, so one instruction broadcasts AND selects — the role masks
+  // are lane patterns (constants), moved into VCC once per three selects (11 instructions per direction instead of 15 / 18).
+  // The first DPP read of a word follows the word's producer by two issue slots or more: VB[1] is long written when the
+  // joints end, me.vx is written seven instructions before a contact block ends and the block opens with the VCC move;
+  // lane 3 of VA / VB is left holding lane 0's vx: no lane of the quad ever reads lane 3 (kRot1, kRot2, kSwap01, 0xAA, R * 0x55).
+  unsigned long long role_not1 = 0xDDDDDDDDDDDDDDDDull, role_not2 = 0xBBBBBBBBBBBBBBBBull, role_12 = 0x6666666666666666ull;
+  asm volatile("" : "+s"(role_not1), "+s"(role_not2), "+s"(role_12));   // keep them SGPR pairs (the compiler would rebuild the constants in the loop)
+#define QSEL3(d, s, R) "v_cndmask_b32_dpp " d ", " s ", " d ", vcc quad_perm:[" R "," R "," R "," R "] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define QMOV3(d, s, R) "v_mov_b32_dpp " d ", " s " quad_perm:[" R "," R "," R "," R "] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+  // TWO / SLOT1 (compile-time): whether any lane of the WAVE solves a two-point manifold / has a second slot on this step.
+  // A body without them is the general body with the code no lane can reach removed, nothing else.
+  auto contacts = [&](auto two_, auto slot1_) {
+    constexpr bool TWO = decltype(two_)::value, SLOT1 = decltype(slot1_)::value;
+    const unsigned long long m_not1 = role_not1, m_not2 = role_not2, m_12 = role_12;
     // contacts: each lane solves its own body's slots, then the quad exchanges velocities
     if (any_contact) {
       Body me;                                  // only the velocities are touched in a sweep
       me.cx = me.cy = me.a = 0.0f;
-      me.vx = sel3(mb, quad_bcast<0>(VA), quad_bcast<0>(VB[0]), quad_bcast<0>(VB[1]));
-      me.vy = sel3(mb, quad_bcast<1>(VA), quad_bcast<1>(VB[0]), quad_bcast<1>(VB[1]));
-      me.w = sel3(mb, quad_bcast<2>(VA), quad_bcast<2>(VB[0]), quad_bcast<2>(VB[1]));
+      // me.(vx, vy, w) = component (0, 1, 2) of body mb: VB[1]'s, replaced by VB[0]'s on role 1 and by VA's on roles 0 and 3
+      asm(QMOV3("%0", "%5", "0") QMOV3("%1", "%5", "1") QMOV3("%2", "%5", "2")
+          "s_mov_b64 vcc, %6\n\t"
+          QSEL3("%0", "%4", "0") QSEL3("%1", "%4", "1") QSEL3("%2", "%4", "2")
+          "s_mov_b64 vcc, %7\n\t"
+          QSEL3("%0", "%3", "0") QSEL3("%1", "%3", "1") QSEL3("%2", "%3", "2")
+          : "=&v"(me.vx), "=&v"(me.vy), "=&v"(me.w)
+          : "v"(VA), "v"(VB[0]), "v"(VB[1]), "s"(m_not1), "s"(m_12)
+          : "vcc");
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
+      for (int s = 0; s < (SLOT1 ? 2 : 1); ++s) {
         const int vcount = vcn[s];
         if (vcount > 0) {
           const float nx = vcf[s][VC_NX - 1], ny = vcf[s][VC_NY - 1], tx = ny, ty = -nx;
@@ -808,7 +832,7 @@ __device__ __forceinline__ void world_step(World& W, const Lds& lds, int role, i
             me.vx += mB_ * Px; me.vy += mB_ * Py;
             me.w += iB_ * cross2(rx0, ry0, Px, Py);
           }
-          if (vcount == 2) {  // friction, point 1
+          if (TWO && vcount == 2) {  // friction, point 1
             const float dvx = me.vx + (-me.w * ry1), dvy = me.vy + (me.w * rx1);
             const float vt = dot2(dvx, dvy, tx, ty);
             float lam = vcf[s][VC_TM1 - 1] * (-vt);
@@ -819,7 +843,7 @@ __device__ __forceinline__ void world_step(World& W, const Lds& lds, int role, i
             me.vx += mB_ * Px; me.vy += mB_ * Py;
             me.w += iB_ * cross2(rx1, ry1, Px, Py);
           }
-          if (vcount == 1) {
+          if (!TWO || vcount == 1) {
             const float dvx = me.vx + (-me.w * ry0), dvy = me.vy + (me.w * rx0);
             const float vn = dot2(dvx, dvy, nx, ny);
             float lam = -vcf[s][VC_NM0 - 1] * vn;
@@ -863,21 +887,40 @@ __device__ __forceinline__ void world_step(World& W, const Lds& lds, int role, i
             }
           }
           vim[s][0] = ni0; vim[s][1] = ti0;
-          if (vcount == 2) { vim[s][2] = ni1; vim[s][3] = ti1; }
+          if (TWO && vcount == 2) { vim[s][2] = ni1; vim[s][3] = ti1; }
         }
       }
-      VA = lane3(quad_bcast<0>(me.vx), quad_bcast<0>(me.vy), quad_bcast<0>(me.w));
-      VB[0] = lane3(quad_bcast<1>(me.vx), quad_bcast<1>(me.vy), quad_bcast<1>(me.w));
-      VB[1] = lane3(quad_bcast<2>(me.vx), quad_bcast<2>(me.vy), quad_bcast<2>(me.w));
+      // back to lane = component: lane r of VA / VB[0] / VB[1] takes component r of lane 0's / 1's / 2's body
+      asm("s_mov_b64 vcc, %6\n\t"
+          QMOV3("%0", "%3", "0") QMOV3("%1", "%3", "1") QMOV3("%2", "%3", "2")
+          QSEL3("%0", "%4", "0") QSEL3("%1", "%4", "1") QSEL3("%2", "%4", "2")
+          "s_mov_b64 vcc, %7\n\t"
+          QSEL3("%0", "%5", "0") QSEL3("%1", "%5", "1") QSEL3("%2", "%5", "2")
+          : "=&v"(VA), "=&v"(VB[0]), "=&v"(VB[1])
+          : "v"(me.vx), "v"(me.vy), "v"(me.w), "s"(m_not1), "s"(m_not2)
+          : "vcc");
     }
   };
-  // a wave without a single contact (most steps of most workgroups) runs the sweeps without the per-sweep test
+#undef QSEL3
+#undef QMOV3
+  // One loop per kind of wave-step, chosen once per step from ballots every lane of the wave takes part in: no contact in
+  // the wave (most steps of most workgroups: the joints alone, no per-sweep test); contacts, but no two-point manifold in
+  // the wave (a lander resting on its legs: one clamp per manifold, no block-solver code) with or without a second slot;
+  // the general body.  `lds.general_sweep` (the stepper's test switch) sends every contact wave-step to the general body.
+  const bool wave_two = __builtin_amdgcn_ballot_w64(vcn[0] == 2 || vcn[1] == 2) != 0ull || lds.general_sweep;
+  const bool wave_slot1 = __builtin_amdgcn_ballot_w64(vcn[1] > 0) != 0ull;
   if (__builtin_amdgcn_ballot_w64(any_contact) == 0ull) {
 #pragma nounroll
     for (int it = 0; it < kVelIters; ++it) joints();
+  } else if (wave_two) {
+#pragma nounroll
+    for (int it = 0; it < kVelIters; ++it) { joints(); contacts(SweepFlag<true>{}, SweepFlag<true>{}); }
+  } else if (wave_slot1) {
+#pragma nounroll
+    for (int it = 0; it < kVelIters; ++it) { joints(); contacts(SweepFlag<false>{}, SweepFlag<true>{}); }
   } else {
 #pragma nounroll
-    for (int it = 0; it < kVelIters; ++it) { joints(); contacts(); }
+    for (int it = 0; it < kVelIters; ++it) { joints(); contacts(SweepFlag<false>{}, SweepFlag<false>{}); }
   }
   B[0].vx = quad_bcast<0>(VA); B[0].vy = quad_bcast<1>(VA); B[0].w = quad_bcast<2>(VA);
 #pragma unroll
