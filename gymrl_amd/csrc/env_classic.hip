@@ -281,18 +281,19 @@ int gymrl_device_ok(void) {
   return __builtin_strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : 0;
 }
 
-int gymrl_env_obs_dim(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 4 : kind == GYMRL_ENV_PENDULUM ? 3 : kind == GYMRL_ENV_LUNARLANDER ? 8 : kind == GYMRL_ENV_MOUNTAINCAR ? 2 : kind == GYMRL_ENV_ACROBOT ? 6 : -22;
-}
-int gymrl_env_act_dim(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 2 : kind == GYMRL_ENV_PENDULUM ? 1 : kind == GYMRL_ENV_LUNARLANDER ? 4 : kind == GYMRL_ENV_MOUNTAINCAR ? 3 : kind == GYMRL_ENV_ACROBOT ? 3 : -22;
-}
+// (observations, actions, TimeLimit) of a kind: the classic-control envs' from ClassicDims (env_classic_device.hpp); nobody's: -22
+#define GYMRL_CLASSIC_DIM(kind, member)                                            \
+  ((kind) == GYMRL_ENV_CARTPOLE ? ClassicDims<GYMRL_ENV_CARTPOLE>::member          \
+   : (kind) == GYMRL_ENV_PENDULUM ? ClassicDims<GYMRL_ENV_PENDULUM>::member        \
+   : (kind) == GYMRL_ENV_MOUNTAINCAR ? ClassicDims<GYMRL_ENV_MOUNTAINCAR>::member  \
+   : (kind) == GYMRL_ENV_ACROBOT ? ClassicDims<GYMRL_ENV_ACROBOT>::member : -22)
+int gymrl_env_obs_dim(int kind) { return kind == GYMRL_ENV_LUNARLANDER ? 8 : GYMRL_CLASSIC_DIM(kind, kObs); }
+int gymrl_env_act_dim(int kind) { return kind == GYMRL_ENV_LUNARLANDER ? 4 : GYMRL_CLASSIC_DIM(kind, kActions); }
 int gymrl_env_is_discrete(int kind) {
   return kind == GYMRL_ENV_PENDULUM ? 0 : (kind == GYMRL_ENV_CARTPOLE || kind == GYMRL_ENV_LUNARLANDER || kind == GYMRL_ENV_MOUNTAINCAR || kind == GYMRL_ENV_ACROBOT) ? 1 : -22;
 }
-int gymrl_env_max_steps(int kind) {
-  return kind == GYMRL_ENV_CARTPOLE ? 500 : kind == GYMRL_ENV_PENDULUM ? 200 : kind == GYMRL_ENV_LUNARLANDER ? 1000 : kind == GYMRL_ENV_MOUNTAINCAR ? 200 : kind == GYMRL_ENV_ACROBOT ? 500 : -22;
-}
+int gymrl_env_max_steps(int kind) { return kind == GYMRL_ENV_LUNARLANDER ? 1000 : GYMRL_CLASSIC_DIM(kind, kMaxSteps); }
+#undef GYMRL_CLASSIC_DIM
 
 size_t gymrl_env_state_bytes(int kind, int n_envs) {
   if (n_envs <= 0) return 0;

@@ -3,11 +3,20 @@
 // The arithmetic of gym.make("CartPole-v1" | "Pendulum-v1" | "MountainCar-v0" | "Acrobot-v1").step()/reset() (gymnasium classic_control, third-party:
 // SURVEY.md 8c.2) for one env = one lane.  Shared by the stand-alone steppers (env_classic.hip: gymrl_env_step) and the
 // fused acting kernels (offpolicy_step.hip, rainbow_step.hip, td3_step.hip: forward + draw + env step + ring append in one launch), so both produce the
-// same bits; each env's register-only core (*_advance) is shared with its one-launch episode kernel (mountaincar.hip, eval_classic.hip) in the same way.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
+// same bits; each env's register-only core (*_advance) is shared with its one-launch episode kernels (mountaincar.hip; EpisodeEnv at the end of this file) in the same way.  State is float64 like gymnasium's, observations are the float32 cast; sin / cos are det_sincos.
 #pragma once
 #include "env_common.hpp"
 
 namespace gymrl {
+
+// The widths and the TimeLimit of an env kind, written here and nowhere else under csrc/: observations, actions (Pendulum-v1: the
+// one torque), float64 fields of a state, gymnasium's max_episode_steps.  The steppers below, the size queries (env_classic.hip),
+// the episode kernels (EpisodeEnv at the end of this file) and PPO's kernels (classic_ppo_device.hpp: ClassicEnv) read them.
+template <int KIND> struct ClassicDims;
+template <> struct ClassicDims<GYMRL_ENV_CARTPOLE> { static constexpr int kObs = 4, kActions = 2, kState = 4, kMaxSteps = 500; };
+template <> struct ClassicDims<GYMRL_ENV_PENDULUM> { static constexpr int kObs = 3, kActions = 1, kState = 2, kMaxSteps = 200; };
+template <> struct ClassicDims<GYMRL_ENV_MOUNTAINCAR> { static constexpr int kObs = 2, kActions = 3, kState = 2, kMaxSteps = 200; };
+template <> struct ClassicDims<GYMRL_ENV_ACROBOT> { static constexpr int kObs = 6, kActions = 3, kState = 4, kMaxSteps = 500; };
 
 struct CartPoleState {
   double *x, *xd, *th, *thd;
@@ -134,13 +143,13 @@ __device__ __forceinline__ bool cartpole_advance(double& x, double& xd, double& 
   return x < -2.4 || x > 2.4 || th < -th_lim || th > th_lim;
 }
 
-// CartPole-v1: reward 1 on every step including the terminating one, TimeLimit 500; auto-reset into episode + 1's draw.
+// CartPole-v1: reward 1 on every step including the terminating one, the TimeLimit; auto-reset into episode + 1's draw.
 __device__ __forceinline__ void cartpole_step_one(const CartPoleState& st, int i, uint64_t seed, int64_t env_id0, int action,
                                                   ClassicStep<4>& r) {
   double x = st.x[i], xd = st.xd[i], th = st.th[i], thd = st.thd[i];
   r.terminated = cartpole_advance(x, xd, th, thd, action);
   r.len = st.ep.ep_len[i] + 1;
-  r.truncated = r.len >= 500;
+  r.truncated = r.len >= ClassicDims<GYMRL_ENV_CARTPOLE>::kMaxSteps;
   r.done = r.terminated || r.truncated;
   r.ret = st.ep.ep_ret[i] + 1.0;
   r.reward = 1.0f;
@@ -180,14 +189,14 @@ __device__ __forceinline__ double pendulum_advance(double& th, double& thd, floa
   return cost;
 }
 
-// Pendulum-v1: never terminates, TimeLimit 200; auto-reset into episode + 1's draw.
+// Pendulum-v1: never terminates, the TimeLimit; auto-reset into episode + 1's draw.
 __device__ __forceinline__ void pendulum_step_one(const PendulumState& st, int i, uint64_t seed, int64_t env_id0, float action,
                                                   ClassicStep<3>& r) {
   double nth = st.th[i], nthd = st.thd[i];
   const double cost = pendulum_advance(nth, nthd, action);
   r.len = st.ep.ep_len[i] + 1;
   r.terminated = false;
-  r.truncated = r.len >= 200;
+  r.truncated = r.len >= ClassicDims<GYMRL_ENV_PENDULUM>::kMaxSteps;
   r.done = r.truncated;
   r.ret = st.ep.ep_ret[i] + (-cost);
   r.reward = (float)(-cost);
@@ -220,13 +229,13 @@ __device__ __forceinline__ bool mountaincar_advance(double& pos, double& vel, in
   return pos >= 0.5 && vel >= 0.0;
 }
 
-// MountainCar-v0: reward -1 on every step including the terminating one, TimeLimit 200; auto-reset into episode + 1's draw.
+// MountainCar-v0: reward -1 on every step including the terminating one, the TimeLimit; auto-reset into episode + 1's draw.
 __device__ __forceinline__ void mountaincar_step_one(const MountainCarState& st, int i, uint64_t seed, int64_t env_id0, int action,
                                                      ClassicStep<2>& r) {
   double pos = st.pos[i], vel = st.vel[i];
   r.terminated = mountaincar_advance(pos, vel, action);
   r.len = st.ep.ep_len[i] + 1;
-  r.truncated = r.len >= 200;
+  r.truncated = r.len >= ClassicDims<GYMRL_ENV_MOUNTAINCAR>::kMaxSteps;
   r.done = r.terminated || r.truncated;
   r.ret = st.ep.ep_ret[i] + (-1.0);
   r.reward = -1.0f;
@@ -267,7 +276,7 @@ constexpr int kAcrobotWrapTrips = GYMRL_ACROBOT_WRAP_TRIPS;       // gymnasium's
 
 // One classical RK4 step over dt = 0.2, the angles wrapped into [-pi, pi], the velocities clamped to +-4 pi / +-9 pi; ->
 // terminated (the tip above the line one link length over the pivot, on the new state).  The stepper below and the policy
-// episode kernels (eval_acrobot.hip) both call it.
+// episode kernels (EpisodeEnv below) both call it.
 __device__ __forceinline__ bool acrobot_advance(double (&s)[4], int action) {
   const double pi = 3.14159265358979323846;
   const double a = (double)(action - 1);
@@ -301,13 +310,13 @@ __device__ __forceinline__ bool acrobot_advance(double (&s)[4], int action) {
   return -c1 - c12 > 1.0;
 }
 
-// Acrobot-v1: reward -1 on every step but the terminating one (0), TimeLimit 500; auto-reset into episode + 1's draw.
+// Acrobot-v1: reward -1 on every step but the terminating one (0), the TimeLimit; auto-reset into episode + 1's draw.
 __device__ __forceinline__ void acrobot_step_one(const AcrobotState& st, int i, uint64_t seed, int64_t env_id0, int action,
                                                  ClassicStep<6>& r) {
   double s[4] = {st.th1[i], st.th2[i], st.dth1[i], st.dth2[i]};
   r.terminated = acrobot_advance(s, action);
   r.len = st.ep.ep_len[i] + 1;
-  r.truncated = r.len >= 500;
+  r.truncated = r.len >= ClassicDims<GYMRL_ENV_ACROBOT>::kMaxSteps;
   r.done = r.terminated || r.truncated;
   const double rew = r.terminated ? 0.0 : -1.0;
   r.ret = st.ep.ep_ret[i] + rew;
@@ -327,5 +336,65 @@ __device__ __forceinline__ void acrobot_step_one(const AcrobotState& st, int i, 
     for (int k = 0; k < 6; ++k) r.o_next[k] = r.o_term[k];
   }
 }
+
+// What an env kind is to the one-launch episode kernels (eval_episode_device.hpp: run_episodes): ClassicDims, the action its policy
+// hands over (an index, or Pendulum-v1's float torque), and three register-only pieces on the lane's float64 state s[kState] —
+//
+//   draw      the reset of the stream's first episode (the steppers' draw at episode 0)
+//   obs       the float32 observation of s, o[kObs]
+//   advance   one step under `action`, the undiscounted reward added to `ret` in float64 as the stepper above adds it; -> terminated
+//
+// A fifth env is one more ClassicDims and one more EpisodeEnv; the loop, the kernels and the launcher take it as a template argument.
+template <int KIND> struct EpisodeEnv;
+template <> struct EpisodeEnv<GYMRL_ENV_CARTPOLE> : ClassicDims<GYMRL_ENV_CARTPOLE> {
+  using Action = int;
+  static __device__ __forceinline__ void draw(uint64_t seed, uint64_t stream, double (&s)[4]) { cartpole_draw(seed, stream, 0u, s); }
+  static __device__ __forceinline__ void obs(const double (&s)[4], float* o) {
+    o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
+  }
+  static __device__ __forceinline__ bool advance(double (&s)[4], int action, double& ret) {
+    const bool terminated = cartpole_advance(s[0], s[1], s[2], s[3], action);
+    ret = ret + 1.0;
+    return terminated;
+  }
+};
+template <> struct EpisodeEnv<GYMRL_ENV_PENDULUM> : ClassicDims<GYMRL_ENV_PENDULUM> {
+  using Action = float;
+  static __device__ __forceinline__ void draw(uint64_t seed, uint64_t stream, double (&s)[4]) { pendulum_draw(seed, stream, 0u, s[0], s[1]); }
+  static __device__ __forceinline__ void obs(const double (&s)[4], float* o) {
+    float ob[3];
+    pendulum_obs(s[0], s[1], ob);
+    o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
+  }
+  static __device__ __forceinline__ bool advance(double (&s)[4], float action, double& ret) {
+    ret = ret + (-pendulum_advance(s[0], s[1], action));
+    return false;
+  }
+};
+template <> struct EpisodeEnv<GYMRL_ENV_MOUNTAINCAR> : ClassicDims<GYMRL_ENV_MOUNTAINCAR> {
+  using Action = int;
+  static __device__ __forceinline__ void draw(uint64_t seed, uint64_t stream, double (&s)[4]) { mountaincar_draw(seed, stream, 0u, s[0], s[1]); }
+  static __device__ __forceinline__ void obs(const double (&s)[4], float* o) { o[0] = (float)s[0]; o[1] = (float)s[1]; }
+  static __device__ __forceinline__ bool advance(double (&s)[4], int action, double& ret) {
+    const bool terminated = mountaincar_advance(s[0], s[1], action);
+    ret = ret + (-1.0);                 // every step, the terminating one included
+    return terminated;
+  }
+};
+template <> struct EpisodeEnv<GYMRL_ENV_ACROBOT> : ClassicDims<GYMRL_ENV_ACROBOT> {
+  using Action = int;
+  static __device__ __forceinline__ void draw(uint64_t seed, uint64_t stream, double (&s)[4]) { acrobot_draw(seed, stream, 0u, s); }
+  static __device__ __forceinline__ void obs(const double (&s)[4], float* o) {
+    float ob[6];
+    acrobot_obs(s, ob);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) o[k] = ob[k];
+  }
+  static __device__ __forceinline__ bool advance(double (&s)[4], int action, double& ret) {
+    const bool terminated = acrobot_advance(s, action);
+    ret = ret + (terminated ? 0.0 : -1.0);  // every step but the terminating one
+    return terminated;
+  }
+};
 
 }  // namespace gymrl

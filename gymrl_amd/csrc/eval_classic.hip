@@ -24,10 +24,22 @@ namespace {
 using namespace gymrl;
 using namespace gymrl::slab;
 
-// KIND: GYMRL_ENV_CARTPOLE (head 0, D = 4, A = 2) or GYMRL_ENV_PENDULUM (head 1, D = 3, A = 1); HC: the hidden width the instance is built for (0: a.H)
+using Args = gymrl_classic_eval_args;
+using Kernel = void (*)(const Args);
+
+// KIND: GYMRL_ENV_CARTPOLE (head 0) or GYMRL_ENV_PENDULUM (head 1); wide: the instance built for hidden width 256 (else: a.H).
 // One step's policy forward and its action: eval_kernels_device.hpp's classic_eval_kernel, on this entry point's argument block.
-template <int HC, int KIND>
-constexpr auto kernel = classic_eval_kernel<HC, KIND, gymrl_classic_eval_args>;
+template <int KIND>
+Kernel kernel(bool wide) { return wide ? classic_eval_kernel<256, KIND, Args> : classic_eval_kernel<0, KIND, Args>; }
+Kernel pick(bool wide, int pendulum) { return pendulum ? kernel<GYMRL_ENV_PENDULUM>(wide) : kernel<GYMRL_ENV_CARTPOLE>(wide); }
+
+// the block's cap, head and widths are the env's
+template <int KIND>
+bool shape_ok(const Args& a) {
+  using Env = EpisodeEnv<KIND>;
+  constexpr int head = std::is_same<typename Env::Action, int>::value ? kHeadArgmax : kHeadTanh;
+  return episode_args_ok(a, Env::kMaxSteps) && a.head == head && a.D == Env::kObs && a.A == Env::kActions;
+}
 
 }  // namespace
 
@@ -37,28 +49,14 @@ size_t gymrl_classic_eval_args_bytes(void) { return sizeof(gymrl_classic_eval_ar
 
 int gymrl_classic_policy_eval(const gymrl_classic_eval_args* args, void* stream) {
   if (!args) return -22;
-  const gymrl_classic_eval_args& a = *args;
+  const Args& a = *args;
   const bool cart = a.env_kind == GYMRL_ENV_CARTPOLE;
   if (!cart && a.env_kind != GYMRL_ENV_PENDULUM) return -22;
-  if (!episode_args_ok(a, cart ? 500 : 200)) return -22;
-  if (cart ? (a.head != kHeadArgmax || a.D != 4 || a.A != 2) : (a.head != kHeadTanh || a.D != 3 || a.A != 1)) return -22;
+  if (!(cart ? shape_ok<GYMRL_ENV_CARTPOLE>(a) : shape_ok<GYMRL_ENV_PENDULUM>(a))) return -22;
   if (!slab_shape_ok(1, 1, a.D, a.A, a.H)) return -22;
-  if (!all_set({a.w[0], a.w[1], a.w[2], a.b[0], a.b[1], a.b[2]})) return -22;
-  for (int k = 0; k < 3; ++k)
-    if (!aligned(a.w[k], 16) || !aligned(a.b[k], 4)) return -22;
+  if (!layers_ok({{a.w[0], a.b[0], true}, {a.w[1], a.b[1], true}, {a.w[2], a.b[2], true}})) return -22;
   static bool lds_set = false;
-  if (const int rc = set_max_lds_once(lds_set, {(const void*)kernel<0, GYMRL_ENV_CARTPOLE>, (const void*)kernel<256, GYMRL_ENV_CARTPOLE>,
-                                                (const void*)kernel<0, GYMRL_ENV_PENDULUM>, (const void*)kernel<256, GYMRL_ENV_PENDULUM>},
-                                      (int)lds_bytes(256, 2)))
-    return rc;
-  const dim3 grid((unsigned)(a.P * ((a.E + 15) / 16))), block(kThreads);
-  const size_t smem = lds_bytes(a.H, 2);
-  hipStream_t st = (hipStream_t)stream;
-  const bool wide = a.H == 256;           // the instances built for the reference's hidden width
-  if (cart) hipLaunchKernelGGL((wide ? kernel<256, GYMRL_ENV_CARTPOLE> : kernel<0, GYMRL_ENV_CARTPOLE>), grid, block, smem, st, a);
-  else hipLaunchKernelGGL((wide ? kernel<256, GYMRL_ENV_PENDULUM> : kernel<0, GYMRL_ENV_PENDULUM>), grid, block, smem, st, a);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
+  return launch_episodes<2>(a, stream, lds_set, cart ? 0 : 1, 2, pick);
 }
 
 }  // extern "C"

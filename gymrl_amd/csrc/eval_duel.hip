@@ -23,10 +23,15 @@ namespace {
 using namespace gymrl;
 using namespace gymrl::slab;
 
+using Args = gymrl_classic_duel_eval_args;
+using Env = EpisodeEnv<GYMRL_ENV_CARTPOLE>;
+using Kernel = void (*)(const Args);
+
 // NH: hidden layers of the trunk (1 | 2); HC: the hidden width the instance is built for (0: a.H).  One step's policy forward and
 // its action: eval_kernels_device.hpp's duel_eval_kernel on this entry point's argument block, CartPole-v1, duel_combine.
 template <int HC, int NH>
-constexpr auto kernel = duel_eval_kernel<HC, NH, GYMRL_ENV_CARTPOLE, kCombineMean, gymrl_classic_duel_eval_args>;
+constexpr auto kernel = duel_eval_kernel<HC, NH, GYMRL_ENV_CARTPOLE, kCombineMean, Args>;
+Kernel pick(bool wide, int two) { return two ? (wide ? kernel<256, 2> : kernel<0, 2>) : (wide ? kernel<256, 1> : kernel<0, 1>); }
 
 }  // namespace
 
@@ -36,32 +41,17 @@ size_t gymrl_classic_duel_eval_args_bytes(void) { return sizeof(gymrl_classic_du
 
 int gymrl_classic_duel_eval(const gymrl_classic_duel_eval_args* args, void* stream) {
   if (!args) return -22;
-  const gymrl_classic_duel_eval_args& a = *args;
-  if (a.env_kind != GYMRL_ENV_CARTPOLE || a.D != 4 || a.A != 2) return -22;       // duel_combine's order is pinned for two actions
-  if (!episode_args_ok(a, 500)) return -22;
+  const Args& a = *args;
+  // duel_combine's order is pinned for two actions
+  if (a.env_kind != GYMRL_ENV_CARTPOLE || a.D != Env::kObs || a.A != Env::kActions) return -22;
+  if (!episode_args_ok(a, Env::kMaxSteps)) return -22;
   if (a.n_hidden != 1 && a.n_hidden != 2) return -22;
   if (!slab_shape_ok(1, 1, a.D, a.A, a.H)) return -22;
   const bool two = a.n_hidden == 2;
-  if (!all_set({a.w[0], a.b[0], a.value_w, a.value_b, a.adv_w, a.adv_b})) return -22;
-  if (two ? !all_set({a.w[1], a.b[1]}) : (a.w[1] || a.b[1] || a.images)) return -22;       // one hidden layer: no fc2, so no image of it
-  if (a.images && (a.H & 15) != 0) return -22;
-  for (const float* w : {a.w[0], a.w[1], a.value_w, a.adv_w})
-    if (!aligned(w, 16)) return -22;
-  for (const float* b : {a.b[0], a.b[1], a.value_b, a.adv_b})
-    if (!aligned(b, 4)) return -22;
+  if (!layers_ok({{a.w[0], a.b[0], true}, {a.w[1], a.b[1], two}, {a.value_w, a.value_b, true}, {a.adv_w, a.adv_b, true}})) return -22;
+  if (!fc2_image_ok(a.images, two, a.H)) return -22;
   static bool lds_set = false;
-  if (const int rc = set_max_lds_once(lds_set, {(const void*)kernel<0, 1>, (const void*)kernel<256, 1>,
-                                                (const void*)kernel<0, 2>, (const void*)kernel<256, 2>},
-                                      (int)lds_bytes(256, 2)))
-    return rc;
-  const dim3 grid((unsigned)(a.P * ((a.E + 15) / 16))), block(kThreads);
-  const size_t smem = lds_bytes(a.H, a.n_hidden);
-  hipStream_t st = (hipStream_t)stream;
-  const bool wide = a.H == 256;           // the instances built for the reference's hidden width
-  if (two) hipLaunchKernelGGL((wide ? kernel<256, 2> : kernel<0, 2>), grid, block, smem, st, a);
-  else hipLaunchKernelGGL((wide ? kernel<256, 1> : kernel<0, 1>), grid, block, smem, st, a);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
+  return launch_episodes<2>(a, stream, lds_set, two ? 1 : 0, a.n_hidden, pick);
 }
 
 }  // extern "C"

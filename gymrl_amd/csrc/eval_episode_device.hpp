@@ -1,6 +1,7 @@
 // eval_episode_device.hpp — the episode loop of the one-launch policy evaluation, stated once: eval_classic.hip (a three-layer MLP
-// on CartPole-v1 / Pendulum-v1), eval_duel.hip (a dueling network on CartPole-v1), eval_mountaincar.hip and eval_acrobot.hip (either
-// network on MountainCar-v0 / Acrobot-v1) instantiate it, through eval_kernels_device.hpp, with their own "policy forward" and "action" steps.
+// on CartPole-v1 / Pendulum-v1), eval_duel.hip (a dueling network on CartPole-v1) and eval_net.hip (either network on
+// MountainCar-v0 / Acrobot-v1) instantiate it, through eval_kernels_device.hpp, with their own "policy forward" and "action" steps;
+// eval_classic_ppo.hip with PPO's.  What an env is comes from EpisodeEnv<KIND> (env_classic_device.hpp) alone.
 //
 // ONE workgroup of slab::kThreads threads carries 16 episodes of one policy from their reset to their end.  Lane t < 16 of wave 0
 // owns episode e0 + t: its float64 env state, its float64 return, its length and its flags live in registers.  Per iteration
@@ -9,8 +10,7 @@
 //                where the 16 rows lie: a pointer and a pitch) and writes ONE LDS word, "is anybody still running", beside them
 //   everybody    meets at the barrier that publishes both and leaves on that word — the same for every thread of the workgroup
 //   forward()    every thread: the policy's stages over the slab, each closed by a workgroup barrier, the last one included
-//   action(t)    the running lanes: the greedy action of row t, then cartpole_advance / pendulum_advance / mountaincar_advance /
-//                acrobot_advance in registers
+//   action(t)    the running lanes: the greedy action of row t, then EpisodeEnv<KIND>::advance in registers
 //
 // A finished lane idles with its registers frozen (its input row keeps its last observation and is computed along, unread).  No
 // __syncthreads() sits behind a per-lane or per-wave condition, nothing waits for another workgroup, there are no atomics, inside
@@ -34,33 +34,13 @@ struct EpisodeSlot {
   }
 };
 
-// The float32 observation of the float64 state s: the cast (CartPole-v1, MountainCar-v0), (cos, sin, thdot) (Pendulum-v1) or
-// the two links' (cos, sin) and the velocities (Acrobot-v1)
-template <int KIND>
-__device__ __forceinline__ void episode_obs(const double (&s)[4], float* o) {
-  if constexpr (KIND == GYMRL_ENV_CARTPOLE) {
-    o[0] = (float)s[0]; o[1] = (float)s[1]; o[2] = (float)s[2]; o[3] = (float)s[3];
-  } else if constexpr (KIND == GYMRL_ENV_MOUNTAINCAR) {
-    o[0] = (float)s[0]; o[1] = (float)s[1];
-  } else if constexpr (KIND == GYMRL_ENV_ACROBOT) {
-    float ob[6];
-    acrobot_obs(s, ob);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) o[k] = ob[k];
-  } else {
-    float ob[3];
-    pendulum_obs(s[0], s[1], ob);
-    o[0] = ob[0]; o[1] = ob[1]; o[2] = ob[2];
-  }
-}
-
 // An argument block's explicit starts f64[P][E][NS], or nullptr where the block has no such member (gymrl_classic_ppo_eval_args)
 template <class Args>
 __device__ __forceinline__ auto episode_starts(const Args& a, int) -> decltype(a.start) { return a.start; }
 template <class Args>
 __device__ __forceinline__ const double* episode_starts(const Args&, long) { return nullptr; }
 
-// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR, GYMRL_ENV_ACROBOT (action(t) -> int) or GYMRL_ENV_PENDULUM (action(t) -> the torque, float).
+// KIND: an env kind with an EpisodeEnv (env_classic_device.hpp); action(t) -> its Action, an index or Pendulum-v1's torque.
 // Args: an argument block with E, cap, seed, stream_id0, returns (float or double), lengths, terminated, final_obs and, optionally,
 // start (include/gymrl.h).  obs_rows / pitch: the 16 rows the forward reads the observations from, `pitch` floats apart — the
 // slab's L.S at kMaxD (eval_kernels_device.hpp) or mlp::forward_tile's input tile at mlp::kInStride (eval_classic_ppo.hip); all
@@ -68,8 +48,8 @@ __device__ __forceinline__ const double* episode_starts(const Args&, long) { ret
 template <int KIND, class Args, class Forward, class Action>
 __device__ __forceinline__ void run_episodes(const Args& a, float* obs_rows, const int pitch, int& running, const int p, const int e0,
                                              const int nrows, Forward&& forward, Action&& action) {
-  constexpr bool cart = KIND == GYMRL_ENV_CARTPOLE, car = KIND == GYMRL_ENV_MOUNTAINCAR, acro = KIND == GYMRL_ENV_ACROBOT;
-  constexpr int D = cart ? 4 : car ? 2 : acro ? 6 : 3, NS = cart || acro ? 4 : 2;          // MountainCar-v0: (pos, vel)
+  using Env = EpisodeEnv<KIND>;
+  constexpr int D = Env::kObs, NS = Env::kState;
   const int t = threadIdx.x;
   // ---- one lane per episode: the env state, the return and the length live in registers ----
   double s[4] = {0.0, 0.0, 0.0, 0.0};
@@ -82,19 +62,13 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* obs_rows, con
     if (const double* start = episode_starts(a, 0)) {
 #pragma unroll
       for (int k = 0; k < NS; ++k) s[k] = start[((int64_t)p * a.E + e0 + t) * NS + k];
-    } else if constexpr (cart) {
-      cartpole_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
-    } else if constexpr (car) {
-      mountaincar_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
-    } else if constexpr (acro) {
-      acrobot_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s);
     } else {
-      pendulum_draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), 0u, s[0], s[1]);
+      Env::draw(a.seed, (uint64_t)(a.stream_id0 + e0 + t), s);
     }
   }
   for (int it = 0; it < a.cap; ++it) {
     if (t < 64) {
-      if (active) episode_obs<KIND>(s, obs_rows + t * pitch);
+      if (active) Env::obs(s, obs_rows + t * pitch);
       const bool any = __ballot(active) != 0ull;
       if (t == 0) running = any ? 1 : 0;
     }
@@ -102,18 +76,7 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* obs_rows, con
     if (!running) break;                  // one word, the same for every thread of the workgroup
     forward();
     if (active) {
-      if constexpr (cart) {
-        terminated = cartpole_advance(s[0], s[1], s[2], s[3], action(t));
-        ret = ret + 1.0;
-      } else if constexpr (car) {
-        terminated = mountaincar_advance(s[0], s[1], action(t));
-        ret = ret + (-1.0);                 // every step, the terminating one included
-      } else if constexpr (acro) {
-        terminated = acrobot_advance(s, action(t));
-        ret = ret + (terminated ? 0.0 : -1.0);  // every step but the terminating one
-      } else {
-        ret = ret + (-pendulum_advance(s[0], s[1], action(t)));
-      }
+      terminated = Env::advance(s, action(t), ret);
       len += 1;
       active = !terminated && len < a.cap;
     }
@@ -122,7 +85,7 @@ __device__ __forceinline__ void run_episodes(const Args& a, float* obs_rows, con
   if (t < nrows) {
     const int64_t i = (int64_t)p * a.E + e0 + t;
     a.returns[i] = (decltype(+a.returns[i]))ret; a.lengths[i] = len; a.terminated[i] = terminated;
-    if (a.final_obs) episode_obs<KIND>(s, a.final_obs + i * D);
+    if (a.final_obs) Env::obs(s, a.final_obs + i * D);
   }
 }
 
@@ -137,6 +100,37 @@ inline bool episode_args_ok(const Args& a, int max_cap) {
   if (a.images && a.P != 1) return false;
   if (!all_set({a.returns, a.lengths, a.terminated})) return false;
   return aligned(a.images, 16) && aligned(a.start, 8) && aligned(a.returns, 4) && aligned(a.lengths, 4) && aligned(a.final_obs, 4);
+}
+
+// One layer of policy 0 as an argument block names it.  A layer the network has is both tensors, the weight on 16 bytes and the
+// bias on 4; one it has not (a second hidden layer, a value head) is neither.
+struct EvalLayer { const float *w, *b; bool present; };
+inline bool layers_ok(std::initializer_list<EvalLayer> layers) {
+  for (const EvalLayer& l : layers)
+    if (l.present ? !(l.w && l.b && aligned(l.w, 16) && aligned(l.b, 4)) : (l.w || l.b)) return false;
+  return true;
+}
+// `images` is fc2's forward image: of a trunk that has an fc2, at a width that has an image
+inline bool fc2_image_ok(const float* images, bool two, int H) { return !images || (two && (H & 15) == 0); }
+
+// The launch of the checked block `a`.  pick(wide, v) -> the kernel instance of variant v (which network, on which env: the
+// entry point's own numbering, N_VARIANTS of them) built for hidden width 256 (wide) or for any a.H.  The first call raises the
+// dynamic-LDS ceiling of EVERY instance pick can answer with, so the list cannot fall behind the launch.
+template <int N_VARIANTS, class Args, class Pick>
+inline int launch_episodes(const Args& a, void* stream, bool& lds_set, int variant, int n_hidden, Pick&& pick) {
+  if (!lds_set) {
+    const void* all[2 * N_VARIANTS];
+    for (int v = 0; v < N_VARIANTS; ++v) {
+      all[2 * v] = (const void*)pick(false, v);
+      all[2 * v + 1] = (const void*)pick(true, v);
+    }
+    if (const int rc = set_max_lds_once(lds_set, all, all + 2 * N_VARIANTS, (int)lds_bytes(256, 2))) return rc;
+  }
+  const dim3 grid((unsigned)(a.P * ((a.E + 15) / 16))), block(kThreads);
+  const bool wide = a.H == 256;           // the instances built for the reference's hidden width
+  hipLaunchKernelGGL(pick(wide, variant), grid, block, lds_bytes(a.H, n_hidden), (hipStream_t)stream, a);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // namespace

@@ -5,15 +5,17 @@
 //   duel_eval_kernel      a dueling network: a ReLU trunk of one or two layers, a value head and an advantage head in ONE
 //                         two-item stage, the combine, the first maximum (CartPole-v1, MountainCar-v0, Acrobot-v1)
 //
-// Both are templates over the env kind and the ARGUMENT BLOCK of the entry point that launches them: eval_classic.hip
-// (gymrl_classic_eval_args), eval_duel.hip (gymrl_classic_duel_eval_args), eval_mountaincar.hip
-// (gymrl_mountaincar_net_eval_args) and eval_acrobot.hip (gymrl_acrobot_net_eval_args) name the same tensors differently, and mlp3_of / duel_of below read them out.  The episode
-// loop is eval_episode_device.hpp's run_episodes; what is stated here is one step's policy forward and its action.
+// Both are templates over the env kind (EpisodeEnv<KIND>, env_classic_device.hpp: the widths and the action type) and the
+// ARGUMENT BLOCK of the entry point that launches them: eval_classic.hip (gymrl_classic_eval_args), eval_duel.hip
+// (gymrl_classic_duel_eval_args) and eval_net.hip (gymrl_mountaincar_net_eval_args, gymrl_acrobot_net_eval_args: one set of
+// fields) name the same tensors differently, and mlp3_of / duel_of below read them out.  The episode loop is
+// eval_episode_device.hpp's run_episodes; what is stated here is one step's policy forward and its action.
 //
 // Register pressure: the tensors' pointers pass through an empty asm inside the forward, so that the stages' per-lane operand
 // addresses are formed again in every iteration — hoisted out of the loop they were 47 spilled registers, reloaded from scratch
 // memory step by step.
 #pragma once
+#include <type_traits>
 #include "duel_device.hpp"
 #include "eval_episode_device.hpp"
 
@@ -24,33 +26,27 @@ namespace {
 constexpr int kHeadArgmax = 0, kHeadTanh = 1;
 constexpr int kCombineMean = 1, kCombineRow = 2;       // duel_combine (torch's mean) | dueling_row (Rainbow's epilogue)
 
-// (obs dim, actions) of an env kind's episode kernels
-template <int KIND> struct EvalDims;
-template <> struct EvalDims<GYMRL_ENV_CARTPOLE> { static constexpr int D = 4, A = 2; };
-template <> struct EvalDims<GYMRL_ENV_PENDULUM> { static constexpr int D = 3, A = 1; };
-template <> struct EvalDims<GYMRL_ENV_MOUNTAINCAR> { static constexpr int D = 2, A = 3; };
-template <> struct EvalDims<GYMRL_ENV_ACROBOT> { static constexpr int D = 6, A = 3; };
-
-// policy 0's tensors as the kernels name them
+// policy 0's tensors as the kernels name them: a block with head_w (the net entry points': fc3 or the advantage head), or the
+// CartPole / Pendulum blocks' own names
 struct Mlp3 { const float *w0, *w1, *w2, *b0, *b1, *b2; };
 __device__ __forceinline__ Mlp3 mlp3_of(const gymrl_classic_eval_args& a) { return Mlp3{a.w[0], a.w[1], a.w[2], a.b[0], a.b[1], a.b[2]}; }
-__device__ __forceinline__ Mlp3 mlp3_of(const gymrl_mountaincar_net_eval_args& a) { return Mlp3{a.w[0], a.w[1], a.head_w, a.b[0], a.b[1], a.head_b}; }
-__device__ __forceinline__ Mlp3 mlp3_of(const gymrl_acrobot_net_eval_args& a) { return Mlp3{a.w[0], a.w[1], a.head_w, a.b[0], a.b[1], a.head_b}; }
+template <class Args>
+__device__ __forceinline__ Mlp3 mlp3_of(const Args& a) { return Mlp3{a.w[0], a.w[1], a.head_w, a.b[0], a.b[1], a.head_b}; }
 struct DuelNet { const float *w0, *b0, *w1, *b1, *wv, *bv, *wa, *ba; };
 __device__ __forceinline__ DuelNet duel_of(const gymrl_classic_duel_eval_args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.adv_w, a.adv_b}; }
-__device__ __forceinline__ DuelNet duel_of(const gymrl_mountaincar_net_eval_args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.head_w, a.head_b}; }
+template <class Args>
+__device__ __forceinline__ DuelNet duel_of(const Args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.head_w, a.head_b}; }
 
-__device__ __forceinline__ DuelNet duel_of(const gymrl_acrobot_net_eval_args& a) { return DuelNet{a.w[0], a.b[0], a.w[1], a.b[1], a.value_w, a.value_b, a.head_w, a.head_b}; }
-
-// KIND: GYMRL_ENV_CARTPOLE, GYMRL_ENV_MOUNTAINCAR, GYMRL_ENV_ACROBOT (the first maximum of fc3's row) or GYMRL_ENV_PENDULUM (tanh * a.bound);
+// KIND: an env whose Action is an index (the first maximum of fc3's row) or a float (Pendulum-v1: tanh * a.bound);
 // HC: the hidden width the instance is built for (0: a.H)
 template <int HC, int KIND, class Args>
 __global__ __launch_bounds__(kThreads) void classic_eval_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int running;                 // the loop's exit word: written by wave 0, read by everybody behind the barrier
   const Lds L;
-  constexpr bool argmax = KIND != GYMRL_ENV_PENDULUM;
-  constexpr int D = EvalDims<KIND>::D, A = EvalDims<KIND>::A;
+  using Env = EpisodeEnv<KIND>;
+  constexpr bool argmax = std::is_same<typename Env::Action, int>::value;
+  constexpr int D = Env::kObs, A = Env::kActions;
   const int H = HC ? HC : a.H, ld = lin::slab_ld(H);
   const int X0 = L.big, X1 = X0 + 16 * ld;
   const int groups = (a.E + 15) / 16;
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void duel_eval_kernel(const Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   __shared__ int running;                 // the loop's exit word: written by wave 0, read by everybody behind the barrier
   const Lds L;
-  constexpr int D = EvalDims<KIND>::D, A = EvalDims<KIND>::A;
+  constexpr int D = EpisodeEnv<KIND>::kObs, A = EpisodeEnv<KIND>::kActions;
   const int H = HC ? HC : a.H, ld = lin::slab_ld(H);
   const int X0 = L.big, X1 = X0 + 16 * ld, Xh = NH == 2 ? X1 : X0;       // Xh: the slab the heads read
   const int groups = (a.E + 15) / 16;

@@ -25,12 +25,15 @@ namespace gymrl {
 
 // the dynamic-LDS ceiling of a unit's kernels, set by the first call that gets here (`done`: the call site's own static flag);
 // 0 or the C ABI's -1000 - hipError
-static inline int set_max_lds_once(bool& done, std::initializer_list<const void*> kernels, int bytes) {
+static inline int set_max_lds_once(bool& done, const void* const* first, const void* const* last, int bytes) {
   if (done) return 0;
-  for (const void* f : kernels)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1000 - (int)hipGetLastError();
+  for (; first != last; ++first)
+    if (hipFuncSetAttribute(*first, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1000 - (int)hipGetLastError();
   done = true;
   return 0;
+}
+static inline int set_max_lds_once(bool& done, std::initializer_list<const void*> kernels, int bytes) {
+  return set_max_lds_once(done, kernels.begin(), kernels.end(), bytes);
 }
 
 // ---------------------------------------------------------------- Philox ---

@@ -561,6 +561,13 @@ CARTPOLE, PENDULUM, LUNARLANDER, MOUNTAINCAR = 0, 1, 2, 3
 ACROBOT = 5                    # 4 is left free for MountainCar's continuous sibling (include/gymrl.h): every entry point refuses it
 ENV_KINDS = {"CartPole-v1": CARTPOLE, "Pendulum-v1": PENDULUM, "LunarLander-v3": LUNARLANDER, "MountainCar-v0": MOUNTAINCAR,
              "Acrobot-v1": ACROBOT}
+# kind -> (name, observations, actions, float64 fields of a state, TimeLimit) of the classic-control envs, stated here once on
+# this side of the C ABI: the episode evaluators' shape rules, start states and caps and PPO's rollout widths below read it.  The
+# library's own statement is csrc/env_classic_device.hpp (ClassicDims); tests/test_episode_eval_refusals.py holds this table
+# against env_dims() and against the largest cap every entry point takes.  (Not read from env_dims() here: the constants derived
+# below exist at import, before the library is loaded.)
+EPISODE_ENVS = {CARTPOLE: ("CartPole-v1", 4, 2, 4, 500), PENDULUM: ("Pendulum-v1", 3, 1, 2, 200),
+                MOUNTAINCAR: ("MountainCar-v0", 2, 3, 2, 200), ACROBOT: ("Acrobot-v1", 6, 3, 4, 500)}
 
 
 def env_dims(kind):
@@ -725,7 +732,7 @@ def qlearn_eval(kind, Q, n_episodes, seed, stream_id0, cap, is_slippery=False):
 
 # ------------------------------------------- MountainCar-v0 rule baseline ---
 MOUNTAINCAR_RULE_COEFS = (-0.09, 0.25, 0.03, 0.3, 0.9, 0.008, -0.07, 0.38, 0.07)     # mountaincar_baseline.py:37-40
-MOUNTAINCAR_MAX_STEPS = 200
+MOUNTAINCAR_MAX_STEPS = EPISODE_ENVS[MOUNTAINCAR][4]
 
 
 def mountaincar_rule_eval(n_episodes, seed, stream_id0, cap, device, coefs=None, start=None, want_final_state=False):
@@ -752,13 +759,43 @@ def mountaincar_rule_eval(n_episodes, seed, stream_id0, cap, device, coefs=None,
 
 # ----------------------- classic-control policies: whole episodes in one launch ---
 CLASSIC_HEAD_ARGMAX, CLASSIC_HEAD_TANH = 0, 1
-CLASSIC_EVAL_SHAPES = {0: (CLASSIC_HEAD_ARGMAX, 4, 2), 1: (CLASSIC_HEAD_TANH, 3, 1)}     # env kind -> (head, D, A)
+CLASSIC_EVAL_HEADS = {CARTPOLE: CLASSIC_HEAD_ARGMAX, PENDULUM: CLASSIC_HEAD_TANH}     # gymrl_classic_policy_eval's env kinds
+MOUNTAINCAR_NET_MLP, MOUNTAINCAR_NET_DUEL_MEAN, MOUNTAINCAR_NET_DUEL_ROW = 0, 1, 2     # gymrl_mountaincar_net_eval_args.net
+ACROBOT_MAX_STEPS = EPISODE_ENVS[ACROBOT][4]
+
+
+def _eval_widths_ok(kind, D, A, H):
+    """The layers are the env's (D, A) at a hidden width the row-slab stages carry."""
+    return kind in EPISODE_ENVS and (D, A) == EPISODE_ENVS[kind][1:3] and 4 <= H <= 256 and H % 4 == 0
 
 
 def classic_eval_shape_ok(kind, head, D, A, H):
     """What gymrl_classic_policy_eval takes (include/gymrl.h): CartPole-v1 under an argmax head, Pendulum-v1 under a tanh head,
     a hidden width the row-slab stages carry."""
-    return CLASSIC_EVAL_SHAPES.get(kind) == (head, D, A) and 4 <= H <= 256 and H % 4 == 0
+    return kind in CLASSIC_EVAL_HEADS and CLASSIC_EVAL_HEADS[kind] == head and _eval_widths_ok(kind, D, A, H)
+
+
+def classic_duel_eval_shape_ok(kind, n_hidden, D, A, H):
+    """What gymrl_classic_duel_eval takes (include/gymrl.h): CartPole-v1, a trunk of one or two hidden layers, two actions, a hidden
+    width the row-slab stages carry."""
+    return kind == CARTPOLE and n_hidden in (1, 2) and _eval_widths_ok(kind, D, A, H)
+
+
+def net_eval_shape_ok(kind, net, n_hidden, D, A, H):
+    """What gymrl_mountaincar_net_eval / gymrl_acrobot_net_eval take (include/gymrl.h): a three-layer MLP (net 0: two hidden
+    layers) or a dueling network (net 1: torch's mean, net 2: the DUELING epilogue's; one or two hidden layers) on the env's
+    (D, A), a hidden width the row-slab stages carry."""
+    return net in (0, 1, 2) and n_hidden in ((2,) if net == 0 else (1, 2)) and _eval_widths_ok(kind, D, A, H)
+
+
+def mountaincar_net_eval_shape_ok(net, n_hidden, D, A, H):
+    """net_eval_shape_ok on MountainCar-v0's (D, A) = (2, 3)."""
+    return net_eval_shape_ok(MOUNTAINCAR, net, n_hidden, D, A, H)
+
+
+def acrobot_net_eval_shape_ok(net, n_hidden, D, A, H):
+    """net_eval_shape_ok on Acrobot-v1's (D, A) = (6, 3)."""
+    return net_eval_shape_ok(ACROBOT, net, n_hidden, D, A, H)
 
 
 def lin_fwd_image(W):
@@ -792,10 +829,8 @@ def _policy_addresses(who, tensors, flat, params):
     return params.shape[0], params.shape[1], params, [base + 4 * o for o in offs]
 
 
-def _episode_io(a, P, n_episodes, nst, D, seed, stream_id0, start, want_final_obs, dev):
+def _episode_io(a, P, n_episodes, D, seed, stream_id0, start, want_final_obs, dev):
     """The starts and the outputs of an episode launch's argument block -> (returns, lengths, terminated, final_obs | None)."""
-    if start is not None and tuple(start.shape) != (P, n_episodes, nst):
-        raise ValueError(f"start is {tuple(start.shape)}, {P} policies x {n_episodes} episodes need [{P}, {n_episodes}, {nst}]")
     returns = torch.empty(P, n_episodes, dtype=torch.float32, device=dev)
     lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
     terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
@@ -806,6 +841,61 @@ def _episode_io(a, P, n_episodes, nst, D, seed, stream_id0, start, want_final_ob
     return returns, lengths, terminated, final
 
 
+# wrapper (its entry point is gymrl_<wrapper>) -> the argument block; where the top layer (fc3 or the advantage head) goes, an index
+# into w[] / b[] or the prefix of <prefix>_w / <prefix>_b; which of n_hidden / D / A the block states; whether the layers' (D, A)
+# are held against the env's here (the CartPole / Pendulum entry points leave that to the library).  The trunk is w[k] / b[k] and
+# the value head value_w / value_b in every block.
+_EVAL_ENTRIES = {"classic_policy_eval": (ClassicEvalArgs, 2, ("D", "A"), False),
+                 "classic_duel_eval": (ClassicDuelEvalArgs, "adv", ("n_hidden", "D", "A"), False),
+                 "mountaincar_net_eval": (MountainCarNetEvalArgs, "head", ("n_hidden",), True),
+                 "acrobot_net_eval": (AcrobotNetEvalArgs, "head", ("n_hidden",), True)}
+
+
+def _episode_eval(who, kind, trunk, top, value, scalars, n_episodes, seed, stream_id0, cap, flat, params, images, start,
+                  want_final_obs):
+    """What the four wrappers share: the layers — (weight, bias) pairs: trunk D -> H (-> H), top H -> A, value H -> 1 or None —
+    are checked, addressed (policy 0's, _policy_addresses) and written into the block _EVAL_ENTRIES[who] names next to the
+    wrapper's own `scalars`, the outputs are allocated and gymrl_<who> is called -> (returns f32, lengths i32, terminated u8),
+    each [P, n_episodes], and final_obs f32[P, n_episodes, D] when asked for."""
+    Args, top_at, stated, env_checked = _EVAL_ENTRIES[who]
+    if kind not in EPISODE_ENVS:
+        raise ValueError(f"{who}: env kind {kind} has no episode evaluator")
+    env, env_D, env_A, nst, _ = EPISODE_ENVS[kind]
+    pairs = [tuple(pair) for pair in trunk] + [tuple(top)] + ([tuple(value)] if value is not None else [])
+    if any(len(pair) != 2 or pair[0].dim() != 2 or pair[1].dim() != 1 or pair[1].shape[0] != pair[0].shape[0] for pair in pairs):
+        raise ValueError(f"{who}: a layer is a (weight [N, K], bias [N]) pair")
+    n, nh = len(pairs), len(trunk)
+    (H, D), A = pairs[0][0].shape, top[0].shape[0]
+    if nh == 2 and tuple(pairs[1][0].shape) != (H, H):
+        raise ValueError(f"{who}: the trunk is not D -> H (-> H)")
+    if top[0].shape[1] != H or (value is not None and tuple(value[0].shape) != (1, H)):
+        raise ValueError(f"{who}: the heads are not H -> A and H -> 1")
+    if env_checked and (D, A) != (env_D, env_A):
+        raise ValueError(f"{who}: {env} has {env_D} observations and {env_A} actions, the layers are {D} -> .. -> {A}")
+    n_pol = params.shape[0] if params is not None and params.dim() == 2 else 1
+    if start is not None and tuple(start.shape) != (n_pol, n_episodes, nst):      # before any pointer is handed out
+        raise ValueError(f"{who}: start is {tuple(start.shape)}, {n_pol} policies x {n_episodes} episodes need [{n_pol}, {n_episodes}, {nst}]")
+    tensors = [w for w, _ in pairs] + [b for _, b in pairs]
+    a = Args()
+    P, stride, params, addr = _policy_addresses(who, tensors, flat, params)
+    out = _episode_io(a, P, n_episodes, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
+    a.P, a.E, a.cap, a.H = P, n_episodes, cap, H
+    for name, v in dict(scalars, **{k: v for k, v in (("n_hidden", nh), ("D", D), ("A", A)) if k in stated}).items():
+        setattr(a, name, v)
+    for k in range(nh):
+        a.w[k], a.b[k] = addr[k], addr[n + k]
+    if isinstance(top_at, int):
+        a.w[top_at], a.b[top_at] = addr[nh], addr[n + nh]
+    else:
+        setattr(a, top_at + "_w", addr[nh])
+        setattr(a, top_at + "_b", addr[n + nh])
+    if value is not None:
+        a.value_w, a.value_b = addr[nh + 1], addr[n + nh + 1]
+    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
+    check(getattr(lib(), "gymrl_" + who)(C.byref(a), _stream()), "gymrl_" + who)
+    return out if want_final_obs else out[:3]
+
+
 def classic_policy_eval(kind, layers, n_episodes, seed, stream_id0, cap, head, bound=0.0, flat=None, params=None, images=None,
                         start=None, want_final_obs=False):
     """n_episodes whole episodes of CartPole-v1 / Pendulum-v1 per policy in ONE launch (include/gymrl.h
@@ -814,26 +904,9 @@ def classic_policy_eval(kind, layers, n_episodes, seed, stream_id0, cap, head, b
     the layers' own tensors.  params = f32[P, n]: P flat parameter buffers in the layout of `flat`, the buffer the layers'
     tensors are views of (n >= flat.numel(); rows are padded here to a multiple of four floats).  Episode e of every policy starts
     from the reset draw of (seed, stream_id0 + e), or from start f64[P, n_episodes, 4 | 2]."""
-    fc1, fc2, fc3 = layers
-    H, D, A = fc1.weight.shape[0], fc1.weight.shape[1], fc3.weight.shape[0]
-    if tuple(fc2.weight.shape) != (H, H) or fc3.weight.shape[1] != H:
-        raise ValueError("classic_policy_eval: the layers are not D -> H -> H -> A")
-    tensors = [fc1.weight, fc2.weight, fc3.weight, fc1.bias, fc2.bias, fc3.bias]
-    a = ClassicEvalArgs()
-    P, stride, params, addr = _policy_addresses("classic_policy_eval", tensors, flat, params)
-    out = _episode_io(a, P, n_episodes, 4 if kind == CARTPOLE else 2, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
-    a.P, a.E, a.cap, a.env_kind, a.head, a.D, a.A, a.H, a.bound = P, n_episodes, cap, kind, head, D, A, H, float(bound)
-    for k in range(3):
-        a.w[k], a.b[k] = addr[k], addr[3 + k]
-    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
-    check(lib().gymrl_classic_policy_eval(C.byref(a), _stream()), "gymrl_classic_policy_eval")
-    return out if want_final_obs else out[:3]
-
-
-def classic_duel_eval_shape_ok(kind, n_hidden, D, A, H):
-    """What gymrl_classic_duel_eval takes (include/gymrl.h): CartPole-v1, a trunk of one or two hidden layers, two actions, a hidden
-    width the row-slab stages carry."""
-    return kind == CARTPOLE and n_hidden in (1, 2) and (D, A) == (4, 2) and 4 <= H <= 256 and H % 4 == 0
+    fc1, fc2, fc3 = ((m.weight, m.bias) for m in layers)
+    return _episode_eval("classic_policy_eval", kind, [fc1, fc2], fc3, None, dict(env_kind=kind, head=head, bound=float(bound)),
+                         n_episodes, seed, stream_id0, cap, flat, params, images, start, want_final_obs)
 
 
 def classic_duel_eval(kind, trunk, value, advantage, n_episodes, seed, stream_id0, cap, flat=None, params=None, images=None,
@@ -842,41 +915,20 @@ def classic_duel_eval(kind, trunk, value, advantage, n_episodes, seed, stream_id
     Every layer is a (weight, bias) tensor pair — a NoisyLinear passes its weight_mu / bias_mu as they are: trunk = one or two pairs
     (D -> H, H -> H), value = the H -> 1 head, advantage = the H -> A head.  params / flat: classic_policy_eval's offset scheme; the
     stride shifts every pointer, so whatever else lies in a row (a noisy layer's sigmas) travels unused."""
-    trunk = [tuple(pair) for pair in trunk]
     if len(trunk) not in (1, 2):
         raise ValueError("classic_duel_eval: the trunk is one or two (weight, bias) pairs")
-    pairs = trunk + [tuple(value), tuple(advantage)]
-    if any(len(pair) != 2 or pair[0].dim() != 2 or pair[1].dim() != 1 or pair[1].shape[0] != pair[0].shape[0] for pair in pairs):
-        raise ValueError("classic_duel_eval: a layer is a (weight [N, K], bias [N]) pair")
-    H, D, A = trunk[0][0].shape[0], trunk[0][0].shape[1], advantage[0].shape[0]
-    if len(trunk) == 2 and tuple(trunk[1][0].shape) != (H, H):
-        raise ValueError("classic_duel_eval: the trunk is not D -> H (-> H)")
-    if tuple(value[0].shape) != (1, H) or advantage[0].shape[1] != H:
-        raise ValueError("classic_duel_eval: the heads are not H -> 1 and H -> A")
-    tensors = [w for w, _ in pairs] + [b for _, b in pairs]
-    n = len(pairs)
-    a = ClassicDuelEvalArgs()
-    P, stride, params, addr = _policy_addresses("classic_duel_eval", tensors, flat, params)
-    out = _episode_io(a, P, n_episodes, 4, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
-    a.P, a.E, a.cap, a.env_kind, a.n_hidden, a.D, a.A, a.H = P, n_episodes, cap, kind, len(trunk), D, A, H
-    for k in range(len(trunk)):
-        a.w[k], a.b[k] = addr[k], addr[n + k]
-    a.value_w, a.value_b, a.adv_w, a.adv_b = addr[n - 2], addr[2 * n - 2], addr[n - 1], addr[2 * n - 1]
-    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
-    check(lib().gymrl_classic_duel_eval(C.byref(a), _stream()), "gymrl_classic_duel_eval")
-    return out if want_final_obs else out[:3]
+    return _episode_eval("classic_duel_eval", kind, trunk, advantage, value, dict(env_kind=kind), n_episodes, seed, stream_id0, cap,
+                         flat, params, images, start, want_final_obs)
 
 
-# ----------------------- MountainCar-v0 policies: whole episodes in one launch ---
-MOUNTAINCAR_NET_MLP, MOUNTAINCAR_NET_DUEL_MEAN, MOUNTAINCAR_NET_DUEL_ROW = 0, 1, 2     # gymrl_mountaincar_net_eval_args.net
-
-
-def mountaincar_net_eval_shape_ok(net, n_hidden, D, A, H):
-    """What gymrl_mountaincar_net_eval takes (include/gymrl.h): a three-layer MLP (net 0: two hidden layers) or a dueling network
-    (net 1: torch's mean, net 2: the DUELING epilogue's; one or two hidden layers) on MountainCar-v0's (D, A) = (2, 3), a hidden
-    width the row-slab stages carry."""
-    return (net in (0, 1, 2) and n_hidden in ((2,) if net == 0 else (1, 2)) and (D, A) == (2, 3)
-            and 4 <= H <= 256 and H % 4 == 0)
+def _net_eval(who, kind, net, trunk, head, value, *rest):
+    """mountaincar_net_eval / acrobot_net_eval: the trunk and the value head a `net` has."""
+    duel = net != MOUNTAINCAR_NET_MLP
+    if len(trunk) not in ((1, 2) if duel else (2,)):
+        raise ValueError(f"{who}: the trunk is {'one or two' if duel else 'two'} (weight, bias) pairs")
+    if duel != (value is not None):
+        raise ValueError(f"{who}: a dueling network (net 1 | 2) has a value head, a three-layer one (net 0) has none")
+    return _episode_eval(who, kind, trunk, head, value, dict(net=net), *rest)
 
 
 def mountaincar_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, value=None, flat=None, params=None, images=None,
@@ -886,58 +938,8 @@ def mountaincar_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, va
     layer is a (weight, bias) tensor pair, a NoisyLinear's its weight_mu / bias_mu: trunk = the hidden layers (2 -> H, H -> H),
     head = fc3 (net 0) or the advantage head (net 1 | 2), both H -> 3, value = the H -> 1 head of a dueling network.  params /
     flat, the starts and the streams: classic_policy_eval's; start is f64[P, n_episodes, 2] = (position, velocity)."""
-    return _net_eval("mountaincar_net_eval", "MountainCar-v0", (2, 3), 2, MountainCarNetEvalArgs, net, trunk, head, n_episodes, seed,
-                     stream_id0, cap, value, flat, params, images, start, want_final_obs)
-
-
-def _net_eval(who, env, dims, nst, Args, net, trunk, head, n_episodes, seed, stream_id0, cap, value, flat, params, images, start,
-              want_final_obs):
-    """mountaincar_net_eval / acrobot_net_eval: one argument block, two entry points (gymrl_<who>); dims = the env's (D, A), nst
-    the float64 fields of a start state."""
-    trunk = [tuple(pair) for pair in trunk]
-    duel = net != MOUNTAINCAR_NET_MLP
-    if len(trunk) not in ((1, 2) if duel else (2,)):
-        raise ValueError(f"{who}: the trunk is {'one or two' if duel else 'two'} (weight, bias) pairs")
-    if duel != (value is not None):
-        raise ValueError(f"{who}: a dueling network (net 1 | 2) has a value head, a three-layer one (net 0) has none")
-    pairs = trunk + [tuple(head)] + ([tuple(value)] if duel else [])
-    if any(len(pair) != 2 or pair[0].dim() != 2 or pair[1].dim() != 1 or pair[1].shape[0] != pair[0].shape[0] for pair in pairs):
-        raise ValueError(f"{who}: a layer is a (weight [N, K], bias [N]) pair")
-    H, D, A = trunk[0][0].shape[0], trunk[0][0].shape[1], head[0].shape[0]
-    if len(trunk) == 2 and tuple(trunk[1][0].shape) != (H, H):
-        raise ValueError(f"{who}: the trunk is not D -> H (-> H)")
-    if head[0].shape[1] != H or (duel and tuple(value[0].shape) != (1, H)):
-        raise ValueError(f"{who}: the heads are not H -> A and H -> 1")
-    if (D, A) != dims:
-        raise ValueError(f"{who}: {env} has {dims[0]} observations and {dims[1]} actions, the layers are {D} -> .. -> {A}")
-    n_pol = params.shape[0] if params is not None and params.dim() == 2 else 1
-    if start is not None and tuple(start.shape) != (n_pol, n_episodes, nst):      # before any pointer is handed out
-        raise ValueError(f"{who}: start is {tuple(start.shape)}, {n_pol} policies x {n_episodes} episodes need [{n_pol}, {n_episodes}, {nst}]")
-    tensors = [w for w, _ in pairs] + [b for _, b in pairs]
-    n, nh = len(pairs), len(trunk)
-    a = Args()
-    P, stride, params, addr = _policy_addresses(who, tensors, flat, params)
-    out = _episode_io(a, P, n_episodes, nst, D, seed, stream_id0, start, want_final_obs, tensors[0].device)
-    a.P, a.E, a.cap, a.net, a.n_hidden, a.H = P, n_episodes, cap, net, nh, H
-    for k in range(nh):
-        a.w[k], a.b[k] = addr[k], addr[n + k]
-    a.head_w, a.head_b = addr[nh], addr[n + nh]
-    if duel:
-        a.value_w, a.value_b = addr[nh + 1], addr[n + nh + 1]
-    a.policy_stride, a.images = stride, _ptr(images, torch.float32, True)
-    check(getattr(lib(), "gymrl_" + who)(C.byref(a), _stream()), "gymrl_" + who)
-    return out if want_final_obs else out[:3]
-
-
-# ----------------------- Acrobot-v1 policies: whole episodes in one launch ---
-ACROBOT_MAX_STEPS = 500
-
-
-def acrobot_net_eval_shape_ok(net, n_hidden, D, A, H):
-    """What gymrl_acrobot_net_eval takes (include/gymrl.h): mountaincar_net_eval_shape_ok's networks on Acrobot-v1's
-    (D, A) = (6, 3)."""
-    return (net in (0, 1, 2) and n_hidden in ((2,) if net == 0 else (1, 2)) and (D, A) == (6, 3)
-            and 4 <= H <= 256 and H % 4 == 0)
+    return _net_eval("mountaincar_net_eval", MOUNTAINCAR, net, trunk, head, value, n_episodes, seed, stream_id0, cap, flat, params,
+                     images, start, want_final_obs)
 
 
 def acrobot_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, value=None, flat=None, params=None, images=None,
@@ -947,8 +949,8 @@ def acrobot_net_eval(net, trunk, head, n_episodes, seed, stream_id0, cap, value=
     (th1, th2, dth1, dth2).  `kind` is what PolicyEval's call carries to tell the two entry points apart."""
     if kind != ACROBOT:
         raise ValueError(f"acrobot_net_eval: env kind {kind} is not Acrobot-v1's")
-    return _net_eval("acrobot_net_eval", "Acrobot-v1", (6, 3), 4, AcrobotNetEvalArgs, net, trunk, head, n_episodes, seed,
-                     stream_id0, cap, value, flat, params, images, start, want_final_obs)
+    return _net_eval("acrobot_net_eval", ACROBOT, net, trunk, head, value, n_episodes, seed, stream_id0, cap, flat, params, images,
+                     start, want_final_obs)
 
 
 # ---------------------- LunarLander-v3 PPO policies: whole episodes in one launch ---
@@ -1037,7 +1039,7 @@ def lunar_policy_eval(policy, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS,
     return out
 
 
-CLASSIC_PPO_EVAL_CAPS = {CARTPOLE: 500, MOUNTAINCAR: 200, ACROBOT: 500}       # kind -> the env's TimeLimit
+CLASSIC_PPO_EVAL_CAPS = {kind: EPISODE_ENVS[kind][4] for kind in (CARTPOLE, MOUNTAINCAR, ACROBOT)}       # kind -> the env's TimeLimit
 
 
 def classic_ppo_eval(kind, policy, n_episodes, seed, stream_id0, cap=None, want_final_obs=False, device=None):
@@ -1755,7 +1757,7 @@ def rollout_lunar(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, va
     check(lib().gymrl_rollout_lunar(C.byref(a), C.byref(policy_desc), _stream()), "gymrl_rollout_lunar")
 
 
-ROLLOUT_CLASSIC_DIMS = {CARTPOLE: (4, 2), MOUNTAINCAR: (2, 3), ACROBOT: (6, 3)}      # kind -> (observations, actions)
+ROLLOUT_CLASSIC_DIMS = {kind: EPISODE_ENVS[kind][1:3] for kind in (CARTPOLE, MOUNTAINCAR, ACROBOT)}      # kind -> (observations, actions)
 
 
 def _rollout_classic_args(what, kind, env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, T, t0,

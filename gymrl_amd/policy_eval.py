@@ -1,5 +1,5 @@
 """Evaluation of a trainer's policy as whole episodes in ONE launch (csrc/eval_classic.hip; csrc/eval_duel.hip, §4q;
-csrc/eval_mountaincar.hip, §4t; csrc/eval_acrobot.hip, §4y).
+csrc/eval_net.hip, §4t and §4y; what an env is to all of them: §4aa).
 
 The reference's eval() (dqn_cartpole.py:214-235 and its siblings) plays num_episodes episodes one after another under
 select_action(deterministic=True).  The trainers here play them side by side on a VecEnv, one host iteration per env step;
@@ -49,18 +49,15 @@ class PolicyEval:
         kind = ops.ENV_KINDS.get(self.cfg.env_name)
         if kind is None:
             return None
-        if kind == ops.MOUNTAINCAR:
-            return self._eval_call_net(kind, ops.mountaincar_net_eval_shape_ok)
-        if kind == ops.ACROBOT:
-            call = self._eval_call_net(kind, ops.acrobot_net_eval_shape_ok)
-            return None if call is None else dict(call, kind=kind)      # what tells _eval_launch the two entry points apart
+        if kind in (ops.MOUNTAINCAR, ops.ACROBOT):
+            return self._eval_call_net(kind)
         pol = self._eval_policy()
         if pol is not None:
             (fc1, fc2, fc3), flat, head, bound = pol
             H, D, A = fc1.weight.shape[0], fc1.weight.shape[1], fc3.weight.shape[0]
             if not ops.classic_eval_shape_ok(kind, head, D, A, H):
                 return None
-            return dict(kind=kind, layers=(fc1, fc2, fc3), cap=ops.env_dims(kind)[3], head=head, bound=bound, flat=flat)
+            return dict(kind=kind, layers=(fc1, fc2, fc3), cap=ops.EPISODE_ENVS[kind][4], head=head, bound=bound, flat=flat)
         duel = self._eval_duel_policy()
         if duel is None:
             return None
@@ -68,11 +65,11 @@ class PolicyEval:
         (H, D), A = trunk[0][0].shape, advantage[0].shape[0]
         if not ops.classic_duel_eval_shape_ok(kind, len(trunk), D, A, H):
             return None
-        return dict(kind=kind, trunk=trunk, value=value, advantage=advantage, cap=ops.env_dims(kind)[3], flat=flat)
+        return dict(kind=kind, trunk=trunk, value=value, advantage=advantage, cap=ops.EPISODE_ENVS[kind][4], flat=flat)
 
-    def _eval_call_net(self, kind, shape_ok):
+    def _eval_call_net(self, kind):
         """_eval_call() on MountainCar-v0 / Acrobot-v1: a three-layer policy is net 0, a dueling one the combine the trainer
-        declares."""
+        declares.  The call is the keyword arguments of the env's own wrapper, so only Acrobot-v1's carries `kind`."""
         pair = lambda m: (m.weight, m.bias)     # noqa: E731
         pol = self._eval_policy()
         if pol is not None:
@@ -87,13 +84,15 @@ class PolicyEval:
             trunk, value, top, flat = duel
             net = self.EVAL_DUEL_COMBINE
         (H, D), A = trunk[0][0].shape, top[0].shape[0]
-        if not shape_ok(net, len(trunk), D, A, H):
+        if not ops.net_eval_shape_ok(kind, net, len(trunk), D, A, H):
             return None
-        return dict(net=net, trunk=trunk, head=top, value=value, cap=ops.env_dims(kind)[3], flat=flat)
+        call = dict(net=net, trunk=trunk, head=top, value=value, cap=ops.EPISODE_ENVS[kind][4], flat=flat)
+        return dict(call, kind=kind) if kind == ops.ACROBOT else call
 
     @staticmethod
     def _eval_launch(call, **kw):
-        """One launch of the entry point the call's arguments belong to."""
+        """One launch of the wrapper the call's keyword arguments are of.  A call is nothing but those arguments — callers hand it,
+        or a dict rebuilt from it, to the wrapper themselves — so the wrapper is read off the names it uses."""
         fn = (ops.acrobot_net_eval if call.get("kind") == ops.ACROBOT and "net" in call else
               ops.mountaincar_net_eval if "net" in call else ops.classic_duel_eval if "trunk" in call else ops.classic_policy_eval)
         return fn(**kw, **call)

@@ -1882,7 +1882,7 @@ int gymrl_snes_tell(const gymrl_snes_tell_args* args, void* stream);
 /* ----------------------------- Acrobot-v1 policies: whole episodes in one launch ---- */
 /*
  * gymrl_mountaincar_net_eval (below: the three nets, the trunk, policy_stride, images, the outputs — all as described there) for
- * Acrobot-v1, (D, A) = (6, 3), TimeLimit 500 (csrc/eval_acrobot.hip; the same kernels of csrc/eval_kernels_device.hpp and the
+ * Acrobot-v1, (D, A) = (6, 3), TimeLimit 500 (csrc/eval_net.hip; the same kernels of csrc/eval_kernels_device.hpp and the
  * same episode loop of csrc/eval_episode_device.hpp, instantiated for env kind 5).  The state (th1, th2, dth1, dth2) is float64
  * in the lane's registers, the observation the six float32 of the rule at the head of this file, one step is csrc/
  * env_classic_device.hpp's acrobot_advance — the stepper's RK4 step — on the 16 lanes of the first wave, and the return takes -1 on
@@ -2078,7 +2078,7 @@ int gymrl_ndqn_update(const gymrl_ndqn_update_args* args, void* stream);
 /* ----------------------------- MountainCar-v0 policies: whole episodes in one launch ---- */
 /*
  * gymrl_classic_policy_eval and gymrl_classic_duel_eval (the section below: grid, lanes, uniform exit, starts, policy_stride,
- * outputs — all as described there) for MountainCar-v0, (D, A) = (2, 3), TimeLimit 200 (csrc/eval_mountaincar.hip; the kernels
+ * outputs — all as described there) for MountainCar-v0, (D, A) = (2, 3), TimeLimit 200 (csrc/eval_net.hip; the kernels
  * and the episode loop are the ones below, stated once in csrc/eval_kernels_device.hpp and csrc/eval_episode_device.hpp).  The
  * state (position, velocity) is float64 in the lane's registers, the observation its float32 cast, one step is
  * csrc/env_classic_device.hpp's mountaincar_advance — the stepper's — and the return takes -1 on every step, the terminating one

@@ -1,4 +1,4 @@
-"""Whole evaluation episodes of Acrobot-v1 in one launch (csrc/eval_acrobot.hip: gymrl_acrobot_net_eval) against the loop they
+"""Whole evaluation episodes of Acrobot-v1 in one launch (csrc/eval_net.hip: gymrl_acrobot_net_eval) against the loop they
 replace: a VecEnv("Acrobot-v1") on the same streams stepped under the trainer's own select_action(deterministic=True), first
 episode per env.  Four trainers cover the networks: DQN (net 0), dueling DDQN+PER (net 1, one hidden layer), NoisyNet dueling DQN
 (net 1, two) and Rainbow (net 2, two); net 2 on one hidden layer has no trainer and is checked against the two-layer launch with an

@@ -1,4 +1,4 @@
-"""Whole evaluation episodes of MountainCar-v0 in one launch (csrc/eval_mountaincar.hip: gymrl_mountaincar_net_eval) against the
+"""Whole evaluation episodes of MountainCar-v0 in one launch (csrc/eval_net.hip: gymrl_mountaincar_net_eval) against the
 loop they replace: a VecEnv("MountainCar-v0") on the same streams stepped under the trainer's own
 select_action(deterministic=True), first episode per env.  Six trainers: three three-layer networks (net 0), two dueling ones
 that combine through torch's mean (net 1) and Rainbow, which combines in the layer kernels' DUELING epilogue (net 2).  The

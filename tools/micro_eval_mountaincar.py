@@ -1,6 +1,6 @@
 """Time of a policy evaluation on MountainCar-v0, both ways the trainers can run it.
 
-  * one gymrl_mountaincar_net_eval launch (csrc/eval_mountaincar.hip): device events around `--batch` back-to-back launches of the
+  * one gymrl_mountaincar_net_eval launch (csrc/eval_net.hip): device events around `--batch` back-to-back launches of the
     same shape after a warm-up batch, per-launch median and minimum over `--repeats` such batches (tools/micro_eval_classic.py's
     method).  Shapes: 1 policy x 10 episodes at hidden 64 and 256; 1 policy x 4096 and 8 policies x 4096 episodes at hidden 256;
     with and without the forward image of fc2 where P = 1;
