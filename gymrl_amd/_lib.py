@@ -567,6 +567,7 @@ SIGNATURES = {
     "gymrl_heads_fwd_tanh": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "gymrl_heads_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "gymrl_heads_loss_blocks": (_i, [_i64, _i]),
+    "gymrl_ppo_update_shape_ok": (_i, [_i, _i, _i]),
     "gymrl_heads_loss_fwd_bwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PPOCfg), _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp]),
     "gymrl_gemm_workspace_bytes": (_sz, []),

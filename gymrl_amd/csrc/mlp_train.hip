@@ -107,6 +107,12 @@ __device__ __forceinline__ void load_row(float (&xv)[D], const float* __restrict
       const f32x4 v = *reinterpret_cast<const f32x4*>(p + d);
       xv[d] = v[0]; xv[d + 1] = v[1]; xv[d + 2] = v[2]; xv[d + 3] = v[3];
     }
+  } else if constexpr (D == 6) {       // a row starts at a multiple of 24 bytes from a 16-byte-aligned base
+#pragma unroll
+    for (int d = 0; d < D; d += 2) {
+      const float2 v = *reinterpret_cast<const float2*>(p + d);
+      xv[d] = v.x; xv[d + 1] = v.y;
+    }
   } else {
 #pragma unroll
     for (int d = 0; d < D; ++d) xv[d] = p[d];
@@ -439,20 +445,23 @@ __global__ __launch_bounds__(kTB) void heads_finalize_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------ F3+L1+B4 -
-// heads_fwd_tanh + ppo_loss + heads_bwd as ONE pass over Zac [B, 512] (pre-activations of actor.0 | critic.0,
-// C = 256: a row is one wavefront x float4 + float4).  A wave takes kRB rows at a time: tanh, the A + 1 head dot
-// products reduced with the forward pass's butterfly, lane k keeps row k's logits and value; then ONE evaluation of
-// the clipped-surrogate loss for the kRB rows (ppo_loss_row, one row per lane: the bits of ppo_loss_kernel — done
-// per row it would be 250 instructions replicated over the row's 64 lanes, more than the rest of the pass); then row
-// k's dlogits / dv are read back from lane k (v_readlane) and turned into dZac — written in place over the
-// pre-activations — and into heads_bwd's register accumulators.  One read and one write of 2 KB per row instead of
-// two reads and a write plus the logits / dlogits round trip.  partial row: as heads_bwd_kernel;
-// met_parts[block][5] (f64).
+// heads_fwd_tanh + ppo_loss + heads_bwd as ONE pass over Zac [B, 2C] (pre-activations of actor.0 | critic.0), C in
+// {64, 128, 256}: a row is lpr = C / 4 lanes x (float4 + float4), a wave-load is rpw = 64 / lpr rows.  A wave takes a
+// batch of kRB wave-loads = kRB * rpw rows at a time (32 / 16 / 8): tanh, the A + 1 head dot products reduced inside the
+// row's lpr lanes with the forward pass's butterfly, and row (k, r_in) of the batch — row r0 + k * rpw + r_in — leaves its
+// logits and value in lane k * rpw + r_in; then ONE evaluation of the clipped-surrogate loss for the batch
+// (ppo_loss_row, one row per lane: the bits of ppo_loss_kernel — done per row it would be 250 instructions replicated
+// over the row's lanes, more than the rest of the pass); then every lane fetches its row's dlogits / dv back from lane
+// k * rpw + r_in (C = 256: one row per wave-load, so v_readlane with a uniform index; narrower: the lanes of a wave-load
+// belong to rpw rows, so ds_bpermute) and turns them into dZac — written in place over the pre-activations — and into
+// heads_bwd's register accumulators.  One read and one write of 8C bytes per row instead of two reads and a write plus
+// the logits / dlogits round trip.  Rows past B in the last batch are loaded from row B - 1 and contribute nothing: the
+// test is per row group (wave-uniform at C = 256).  partial row: as heads_bwd_kernel; met_parts[block][5] (f64).
 constexpr int kRB = 8;
 __device__ __forceinline__ float lane_bcast(float v, int k) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
 }
-template <int A>
+template <int A, int C>
 __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, const float* __restrict__ bac,
                                                          const float* __restrict__ Wa2, const float* __restrict__ ba2,
                                                          const float* __restrict__ Wc2, const float* __restrict__ bc2,
@@ -460,7 +469,8 @@ __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, 
                                                          const float* __restrict__ adv, const float* __restrict__ ret,
                                                          const double* __restrict__ adv_moments, gymrl_ppo_cfg cfg,
                                                          float* __restrict__ partials, double* __restrict__ met_parts) {
-  constexpr int C = 256;
+  static_assert(C == 64 || C == 128 || C == 256, "a row is 16, 32 or 64 lanes");
+  constexpr int lpr = C / 4, rpw = 64 / lpr, kBatch = kRB * rpw;
   extern __shared__ float sm[];
   __shared__ double s_norm[2];
   __shared__ double s_met[5][kTB / 64];
@@ -476,7 +486,7 @@ __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, 
     s_norm[0] = mean; s_norm[1] = sd;
   }
   __syncthreads();
-  const RowMap m(C, threadIdx.x & 63);               // lpr = 64: c4 = lane, one row per wave-load
+  const RowMap m(C, threadIdx.x & 63);               // C = 256: c4 = lane, one row per wave-load
   const int lane = threadIdx.x & 63;
   float wa[A][4], wc[4];
 #pragma unroll
@@ -500,19 +510,20 @@ __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, 
   for (int i = 0; i < NACC; ++i) acc[i] = 0.0f;
   double met[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   const float invB = 1.0f / (float)B;
-  const int64_t nbatch = (B + kRB - 1) / kRB;
+  const int64_t nbatch = (B + kBatch - 1) / kBatch;
   for (int64_t bt = (int64_t)blockIdx.x * (kTB / 64) + (threadIdx.x >> 6); bt < nbatch; bt += (int64_t)gridDim.x * (kTB / 64)) {
-    const int64_t r0 = bt * kRB;
+    const int64_t r0 = bt * kBatch;
     f32x4 ha[kRB], hc[kRB];
 #pragma unroll
     for (int k = 0; k < kRB; ++k) {
-      const int64_t rr = r0 + k < B ? r0 + k : B - 1;
+      const int64_t row = r0 + k * rpw + m.r_in;
+      const int64_t rr = row < B ? row : B - 1;
       const size_t o = (size_t)rr * 2 * C + 4 * m.c4;
       ha[k] = *reinterpret_cast<const f32x4*>(Zac + o);
       hc[k] = *reinterpret_cast<const f32x4*>(Zac + o + C);
     }
-    // the loss inputs of row r0 + lane (lanes >= kRB and rows past the end: a valid row, results unused)
-    const int64_t rl = (lane < kRB && r0 + lane < B) ? r0 + lane : r0;
+    // the loss inputs of row r0 + lane (lanes >= kBatch and rows past the end: a valid row, results unused)
+    const int64_t rl = (lane < kBatch && r0 + lane < B) ? r0 + lane : r0;
     const int a_r = act[rl];
     const float lpo = logp_old[rl], rt = ret[rl];
     float ad = adv[rl];
@@ -537,30 +548,45 @@ __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, 
         for (int j = 0; j < 4; ++j) s = fmaf(hc[k][j], wc[j], s);
         p[A] = s;
       }
-      for (int off = 32; off > 0; off >>= 1) {
+      for (int off = lpr / 2; off > 0; off >>= 1) {
 #pragma unroll
         for (int a = 0; a <= A; ++a) p[a] += __shfl_xor(p[a], off, 64);
       }
-      if (lane == k) {
+      // every lane of the row holds the sums: C = 256 keeps row k in lane k; narrower, the row's lane c4 == k keeps it
+      // (lane r_in * lpr + k) and one permute after the loop moves the batch to lanes k * rpw + r_in
+      if (m.c4 == k) {
 #pragma unroll
         for (int a = 0; a < A; ++a) z[a] = p[a] + hb[a];
         v = p[A] + hb[A];
       }
     }
+    if constexpr (rpw > 1) {
+      const int src = (lane % rpw) * lpr + lane / rpw;      // lanes >= kBatch read past the kept lanes: results unused
+#pragma unroll
+      for (int a = 0; a < A; ++a) z[a] = __shfl(z[a], src, 64);
+      v = __shfl(v, src, 64);
+    }
     float dl[A], dvr, m_obj, m_val, m_ent, m_clip, m_kl;
     if (adv_moments) ad = (float)(((double)ad - s_norm[0]) / s_norm[1]);
     ppo_loss_row<A>(z, v, a_r, lpo, ad, rt, invB, cfg, dl, dvr, m_obj, m_val, m_ent, m_clip, m_kl);
-    if (lane < kRB && r0 + lane < B) {
+    if (lane < kBatch && r0 + lane < B) {
       met[0] += -(double)m_obj; met[1] += (double)m_val; met[2] += (double)m_ent;
       met[3] += (double)m_clip; met[4] += (double)m_kl;
     }
 #pragma unroll
     for (int k = 0; k < kRB; ++k) {
-      if (r0 + k < B) {                      // wave-uniform
-        float dk[A];
+      float dk[A], dvk;
+      if constexpr (rpw > 1) {               // all lanes take part in the permute, live or not
 #pragma unroll
-        for (int a = 0; a < A; ++a) dk[a] = lane_bcast(dl[a], k);
-        const float dvk = lane_bcast(dvr, k);
+        for (int a = 0; a < A; ++a) dk[a] = __shfl(dl[a], k * rpw + m.r_in, 64);
+        dvk = __shfl(dvr, k * rpw + m.r_in, 64);
+      }
+      if (r0 + k * rpw + m.r_in < B) {       // per row group; C = 256: wave-uniform
+        if constexpr (rpw == 1) {
+#pragma unroll
+          for (int a = 0; a < A; ++a) dk[a] = lane_bcast(dl[a], k);
+          dvk = lane_bcast(dvr, k);
+        }
         f32x4 za, zc;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -579,7 +605,7 @@ __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, 
 #pragma unroll
         for (int a = 0; a < A; ++a) acc[12 + 4 * A + a] += dk[a];
         acc[12 + 4 * A + A] += dvk;
-        const size_t o = (size_t)(r0 + k) * 2 * C + 4 * m.c4;
+        const size_t o = (size_t)(r0 + k * rpw + m.r_in) * 2 * C + 4 * m.c4;
         *reinterpret_cast<f32x4*>(Zac + o) = za;
         *reinterpret_cast<f32x4*>(Zac + o + C) = zc;
       }
@@ -636,6 +662,41 @@ __global__ __launch_bounds__(kTB) void update_finalize_kernel(const UpdFinArgs a
   else smallk_finalize_body(a.parts_1, a.nb_1, a.C, a.D, a.dW1, a.db1, b - a.b_h);
 }
 
+// the fused update's shapes, stated once: hidden width C, observation width D, action count A
+inline bool heads_loss_cols(int C) { return C == 64 || C == 128 || C == 256; }
+inline bool update_obs(int D) { return D == 2 || D == 3 || D == 4 || D == 6 || D == 8; }
+inline bool update_actions(int A) { return A == 2 || A == 3 || A == 4; }
+
+// blocks of heads_loss_kernel<A, C>: a wave takes batches of kRB wave-loads = kRB * (64 / (C / 4)) rows
+inline int heads_loss_grid(int64_t B, int C) {
+  const int batch = kRB * (64 / (C / 4));
+  const int64_t nb = ((B + batch - 1) / batch + (kTB / 64) - 1) / (kTB / 64);
+  return (int)(nb < kMaxBlocks ? (nb < 1 ? 1 : nb) : kMaxBlocks);
+}
+
+template <int A>
+void launch_heads_loss(dim3 grid, int C, hipStream_t s, bool parts_only, float* Zac, int64_t B, const float* bac,
+                              const float* Wa2, const float* ba2, const float* Wc2, const float* bc2, const int32_t* act,
+                              const float* logp_old, const float* adv, const float* ret, const double* adv_moments,
+                              const gymrl_ppo_cfg& cfg, float* parts, double* metric_parts, float* dbac, float* dWa2,
+                              float* dba2, float* dWc2, float* dbc2) {
+  constexpr int NV = (8 + 4 * A + 4 + 4 * ((A + 1 + 3) / 4)) / 4;
+  const dim3 block(kTB);
+  const size_t lds = sm_bytes(C, NV);
+  if (C == 256)
+    hipLaunchKernelGGL((heads_loss_kernel<A, 256>), grid, block, lds, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret,
+                       adv_moments, cfg, parts, metric_parts);
+  else if (C == 128)
+    hipLaunchKernelGGL((heads_loss_kernel<A, 128>), grid, block, lds, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret,
+                       adv_moments, cfg, parts, metric_parts);
+  else
+    hipLaunchKernelGGL((heads_loss_kernel<A, 64>), grid, block, lds, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret,
+                       adv_moments, cfg, parts, metric_parts);
+  if (!parts_only)
+    hipLaunchKernelGGL(heads_finalize_kernel<A>, dim3((NV * C + kFinE - 1) / kFinE), block, 0, s, parts, (int)grid.x, C, dbac, dWa2,
+                       dWc2, dba2, dbc2);
+}
+
 }  // namespace
 
 extern "C" {
@@ -656,6 +717,7 @@ int gymrl_linear_tanh_smallk(const float* x, const float* W, const float* b, int
     case 2: hipLaunchKernelGGL(linear_tanh_smallk_kernel<2>, grid, block, 0, s, x, W, b, B, C, out); break;
     case 3: hipLaunchKernelGGL(linear_tanh_smallk_kernel<3>, grid, block, 0, s, x, W, b, B, C, out); break;
     case 4: hipLaunchKernelGGL(linear_tanh_smallk_kernel<4>, grid, block, 0, s, x, W, b, B, C, out); break;
+    case 6: hipLaunchKernelGGL(linear_tanh_smallk_kernel<6>, grid, block, 0, s, x, W, b, B, C, out); break;
     case 8: hipLaunchKernelGGL(linear_tanh_smallk_kernel<8>, grid, block, 0, s, x, W, b, B, C, out); break;
     default: return -22;
   }
@@ -672,6 +734,7 @@ int gymrl_linear_smallk(const float* x, const float* W, const float* b, int64_t 
     case 2: hipLaunchKernelGGL((linear_tanh_smallk_kernel<2, false>), grid, block, 0, s, x, W, b, B, C, out); break;
     case 3: hipLaunchKernelGGL((linear_tanh_smallk_kernel<3, false>), grid, block, 0, s, x, W, b, B, C, out); break;
     case 4: hipLaunchKernelGGL((linear_tanh_smallk_kernel<4, false>), grid, block, 0, s, x, W, b, B, C, out); break;
+    case 6: hipLaunchKernelGGL((linear_tanh_smallk_kernel<6, false>), grid, block, 0, s, x, W, b, B, C, out); break;
     case 8: hipLaunchKernelGGL((linear_tanh_smallk_kernel<8, false>), grid, block, 0, s, x, W, b, B, C, out); break;
     default: return -22;
   }
@@ -718,6 +781,7 @@ int gymrl_linear_smallk_bwd(const float* dH, const float* H, const float* x, int
     case 2: hipLaunchKernelGGL(linear_smallk_bwd_kernel<2>, grid, block, sm_bytes(C, 3), s, dH, H, x, B, C, parts, W, b); break;
     case 3: hipLaunchKernelGGL(linear_smallk_bwd_kernel<3>, grid, block, sm_bytes(C, 4), s, dH, H, x, B, C, parts, W, b); break;
     case 4: hipLaunchKernelGGL(linear_smallk_bwd_kernel<4>, grid, block, sm_bytes(C, 5), s, dH, H, x, B, C, parts, W, b); break;
+    case 6: hipLaunchKernelGGL(linear_smallk_bwd_kernel<6>, grid, block, sm_bytes(C, 7), s, dH, H, x, B, C, parts, W, b); break;
     case 8: hipLaunchKernelGGL(linear_smallk_bwd_kernel<8>, grid, block, sm_bytes(C, 9), s, dH, H, x, B, C, parts, W, b); break;
     default: return -22;
   }
@@ -737,6 +801,7 @@ int gymrl_heads_fwd_tanh(float* Zac, int64_t B, int C, int A, const float* bac, 
   const int64_t want = (B + rows_per_block - 1) / rows_per_block;
   const dim3 grid((unsigned)(want < 8 * kMaxBlocks ? (want < 1 ? 1 : want) : 8 * kMaxBlocks)), block(kTB);
   if (A == 4) hipLaunchKernelGGL(heads_fwd_tanh_kernel<4>, grid, block, 0, s, Zac, B, C, bac, Wa2, ba2, Wc2, bc2, logits, value, store_h);
+  else if (A == 3) hipLaunchKernelGGL(heads_fwd_tanh_kernel<3>, grid, block, 0, s, Zac, B, C, bac, Wa2, ba2, Wc2, bc2, logits, value, store_h);
   else if (A == 2) hipLaunchKernelGGL(heads_fwd_tanh_kernel<2>, grid, block, 0, s, Zac, B, C, bac, Wa2, ba2, Wc2, bc2, logits, value, store_h);
   else return -22;
   GYMRL_CHECK_LAUNCH();
@@ -770,14 +835,11 @@ int gymrl_heads_bwd(const float* Hac, const float* dlogits, const float* dv, int
   return 0;
 }
 
-static int heads_loss_grid(int64_t B) {
-  const int64_t nb = ((B + kRB - 1) / kRB + (kTB / 64) - 1) / (kTB / 64);
-  return (int)(nb < kMaxBlocks ? (nb < 1 ? 1 : nb) : kMaxBlocks);
-}
+int gymrl_ppo_update_shape_ok(int C, int D, int A) { return heads_loss_cols(C) && update_obs(D) && update_actions(A) ? 1 : 0; }
 
 int gymrl_heads_loss_blocks(int64_t B, int C) {
-  if (B <= 0 || C != 256) return 0;
-  return heads_loss_grid(B);
+  if (B <= 0 || !heads_loss_cols(C)) return 0;
+  return heads_loss_grid(B, C);
 }
 
 int gymrl_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* bac, const float* Wa2, const float* ba2,
@@ -789,29 +851,20 @@ int gymrl_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* b
   const bool parts_only = !dbac && !dWa2 && !dba2 && !dWc2 && !dbc2;
   if (!Zac || !Wa2 || !Wc2 || !act || !logp_old || !adv || !ret || !cfg ||
       (!parts_only && (!dbac || !dWa2 || !dba2 || !dWc2 || !dbc2)) ||
-      !metric_parts || !workspace || B <= 0 || C != 256 || !al16(Zac) || (bac && !al16(bac)))
+      !metric_parts || !workspace || B <= 0 || !heads_loss_cols(C) || !update_actions(A) || !al16(Zac) || (bac && !al16(bac)))
     return -22;
   hipStream_t s = (hipStream_t)stream;
-  const int nb = heads_loss_grid(B);
+  const dim3 grid(heads_loss_grid(B, C));
   float* parts = (float*)workspace;
-  const dim3 grid(nb), block(kTB);
-  if (A == 4) {
-    constexpr int NV = (8 + 16 + 4 + 8) / 4;
-    hipLaunchKernelGGL(heads_loss_kernel<4>, grid, block, sm_bytes(C, NV), s, Zac, B, bac, Wa2, ba2, Wc2, bc2, act,
-                       logp_old, adv, ret, adv_moments, *cfg, parts, metric_parts);
-    if (!parts_only)
-      hipLaunchKernelGGL(heads_finalize_kernel<4>, dim3((NV * C + kFinE - 1) / kFinE), block, 0, s, parts, nb, C, dbac, dWa2,
-                         dWc2, dba2, dbc2);
-  } else if (A == 2) {
-    constexpr int NV = (8 + 8 + 4 + 4) / 4;
-    hipLaunchKernelGGL(heads_loss_kernel<2>, grid, block, sm_bytes(C, NV), s, Zac, B, bac, Wa2, ba2, Wc2, bc2, act,
-                       logp_old, adv, ret, adv_moments, *cfg, parts, metric_parts);
-    if (!parts_only)
-      hipLaunchKernelGGL(heads_finalize_kernel<2>, dim3((NV * C + kFinE - 1) / kFinE), block, 0, s, parts, nb, C, dbac, dWa2,
-                         dWc2, dba2, dbc2);
-  } else {
-    return -22;
-  }
+  if (A == 4)
+    launch_heads_loss<4>(grid, C, s, parts_only, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, adv_moments, *cfg, parts,
+                         metric_parts, dbac, dWa2, dba2, dWc2, dbc2);
+  else if (A == 3)
+    launch_heads_loss<3>(grid, C, s, parts_only, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, adv_moments, *cfg, parts,
+                         metric_parts, dbac, dWa2, dba2, dWc2, dbc2);
+  else
+    launch_heads_loss<2>(grid, C, s, parts_only, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, adv_moments, *cfg, parts,
+                         metric_parts, dbac, dWa2, dba2, dWc2, dbc2);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
@@ -819,7 +872,7 @@ int gymrl_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* b
 int gymrl_update_finalize(int64_t B, int C, int A, int D, const void* ws_dw_ac, float* dWac, const void* ws_dw_2, float* dW2,
                           float* db2, const void* ws_heads, float* dbac, float* dWa2, float* dba2, float* dWc2, float* dbc2,
                           const void* ws_smallk, float* dW1, float* db1, void* stream) {
-  if (B <= 0 || C != 256 || (A != 2 && A != 4) || (D != 2 && D != 3 && D != 4 && D != 8) || !ws_dw_ac || !dWac || !ws_dw_2 ||
+  if (B <= 0 || C != 256 || !update_actions(A) || !update_obs(D) || !ws_dw_ac || !dWac || !ws_dw_2 ||
       !dW2 || !db2 || !ws_heads || !dbac || !dWa2 || !dba2 || !dWc2 || !dbc2 || !ws_smallk || !dW1 || !db1 || !al16(dWac) ||
       !al16(dW2) || !al16(ws_dw_ac) || !al16(ws_dw_2))
     return -22;
@@ -829,7 +882,7 @@ int gymrl_update_finalize(int64_t B, int C, int A, int D, const void* ws_dw_ac, 
   fin::tn_geometry(B, C, &a.slices_2, &rps);
   a.parts_ac = (const float*)((const char*)ws_dw_ac + fin::kColsumBytes); a.dWac = dWac;
   a.cs_2 = (const float*)ws_dw_2; a.parts_2 = (const float*)((const char*)ws_dw_2 + fin::kColsumBytes); a.dW2 = dW2; a.db2 = db2;
-  a.parts_h = (const float*)ws_heads; a.nb_h = heads_loss_grid(B);
+  a.parts_h = (const float*)ws_heads; a.nb_h = heads_loss_grid(B, C);
   a.dbac = dbac; a.dWa2 = dWa2; a.dWc2 = dWc2; a.dba2 = dba2; a.dbc2 = dbc2;
   a.parts_1 = (const float*)ws_smallk; a.nb_1 = grid_for(B, C); a.D = D; a.dW1 = dW1; a.db1 = db1;
   a.C = C;
@@ -840,6 +893,7 @@ int gymrl_update_finalize(int64_t B, int C, int A, int D, const void* ws_dw_ac, 
   a.b_h = a.b_cs + (NV * C + kFinE - 1) / kFinE;
   const int total = a.b_h + ((D + 1) * C + kFinE - 1) / kFinE;
   if (A == 4) hipLaunchKernelGGL(update_finalize_kernel<4>, dim3(total), dim3(kTB), 0, (hipStream_t)stream, a);
+  else if (A == 3) hipLaunchKernelGGL(update_finalize_kernel<3>, dim3(total), dim3(kTB), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(update_finalize_kernel<2>, dim3(total), dim3(kTB), 0, (hipStream_t)stream, a);
   GYMRL_CHECK_LAUNCH();
   return 0;

@@ -32,11 +32,19 @@ def capture(graph):
     until then by a caller's frame); destroying that trainer's captured graphs releases their private memory pool, and a
     device free while a stream is capturing is an error that surfaces inside a destructor — the process aborts.
     (torch's context manager collects once on entry; an additional explicit gc.collect() in front of it was measured to
-    make the graph captured afterwards 35 % slower to replay — Rainbow 0.36 -> 0.49 ms per vector step — so there is none.)"""
+    make the graph captured afterwards 35 % slower to replay — Rainbow 0.36 -> 0.49 ms per vector step — so there is none.)
+
+    Under an RCCL process group the capture is thread-local.  ProcessGroupNCCL's watchdog thread polls the events of the
+    collectives launched before the capture (hipEventQuery); under the default global mode that call from ANOTHER thread
+    is an error while this thread captures ("operation not permitted when stream is capturing"), the watchdog throws and
+    the process aborts — whenever a poll happens to fall inside a capture (PPO-full captures right behind its eager
+    all-reduce).  Thread-local mode refuses the same calls from the capturing thread only; the graph is the same."""
+    from . import dist as gdist
+    mode = "thread_local" if gdist.backend() == "nccl" else "global"
     was_enabled = gc.isenabled()
     gc.disable()
     try:
-        with torch.cuda.graph(graph):
+        with torch.cuda.graph(graph, capture_error_mode=mode):
             yield
     finally:
         if was_enabled:

@@ -1576,7 +1576,7 @@ def mlp_train_workspace(C_, D, A, device):
 
 
 def linear_tanh_smallk(x, W, b, out):
-    """out = tanh(x W^T + b) for a first layer with in_features in {2,3,4,8} (shared.0 + Tanh)."""
+    """out = tanh(x W^T + b) for a first layer with in_features in {2,3,4,6,8} (shared.0 + Tanh)."""
     B, D = x.shape
     check(lib().gymrl_linear_tanh_smallk(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True), B, D, W.shape[0],
                                          _ptr(out, torch.float32), _stream()), "gymrl_linear_tanh_smallk")
@@ -1584,7 +1584,7 @@ def linear_tanh_smallk(x, W, b, out):
 
 
 def linear_smallk(x, W, b, out):
-    """out = x W^T + b for a first layer with in_features in {2,3,4,8} and a power-of-two width (no activation)."""
+    """out = x W^T + b for a first layer with in_features in {2,3,4,6,8} and a power-of-two width (no activation)."""
     B, D = x.shape
     check(lib().gymrl_linear_smallk(_ptr(x, torch.float32), _ptr(W, torch.float32), _ptr(b, torch.float32, True), B, D, W.shape[0],
                                     _ptr(out, torch.float32), _stream()), "gymrl_linear_smallk")
@@ -1634,6 +1634,11 @@ def heads_bwd(Hac, dlogits, dv, Wa2, Wc2, dZac, dbac, dWa2, dba2, dWc2, dbc2, wo
 
 def heads_loss_blocks(B, C_=256):
     return int(lib().gymrl_heads_loss_blocks(B, C_))
+
+
+def ppo_update_shape_ok(C_, D, A):
+    """gymrl_ppo_update_shape_ok: the (hidden, obs_dim, actions) the fused PPO update covers.  Host only."""
+    return bool(lib().gymrl_ppo_update_shape_ok(C_, D, A))
 
 
 def heads_loss_fwd_bwd(Zac, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, cfg, adv_moments, dbac, dWa2, dba2, dWc2,

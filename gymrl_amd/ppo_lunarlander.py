@@ -61,7 +61,8 @@ class Config:
         self.gae_carry_in_rollout = True  # LunarLander's persistent rollout also runs the scan's carry pass at its tail (same bits; one launch fewer)
         self.fused_policy_forward = True  # rollout forward = one gymrl_mlp_forward launch (False: per-layer torch)
         self.fused_update = True          # update = ppo_net.FusedActorCriticUpdate.step(): hand-written f32-MFMA GEMMs + fused
-                                          # HBM passes, hidden_dim 64 / 128 / 256 (False or another shape: torch autograd)
+                                          # HBM passes, hidden_dim 64 / 128 / 256, obs 2 / 3 / 4 / 6 / 8, 2-4 actions: every env of
+                                          # this trainer at those widths (False or another shape: torch autograd)
         self.persistent_rollout = True    # LunarLander: whole chunks of vector steps in one launch (gymrl_rollout_lunar); CartPole,
                                           # MountainCar, Acrobot: the same (gymrl_rollout_cartpole / gymrl_rollout_classic)
         self.rollout_chunk = 0            # vector steps per persistent launch (0: the whole rollout in one launch —

@@ -8,9 +8,11 @@ the GEMM libraries are not on this path.
               Zac = H2 [Wa1;Wc1]^T + [ba1;bc1]        gymrl_linear_fwd (N = 2 hidden, bias only: the heads pass applies
                                                       the tanh where the VALU is idle)
     loss+heads  dZac (in place), dbac, dWa2, dba2, dWc2, dbc2, metrics
-                                                      hidden 256: gymrl_heads_loss_fwd_bwd, ONE pass over Zac;
-                                                      hidden 64 / 128: gymrl_heads_fwd_tanh -> gymrl_ppo_loss_fwd_bwd ->
-                                                      gymrl_heads_bwd (the same per-row arithmetic as three passes)
+                                                      hidden 256, and three actions at every width:
+                                                      gymrl_heads_loss_fwd_bwd, ONE pass over Zac;
+                                                      hidden 64 / 128 with 2 or 4 actions: gymrl_heads_fwd_tanh ->
+                                                      gymrl_ppo_loss_fwd_bwd -> gymrl_heads_bwd (the same per-row
+                                                      arithmetic as three passes; gymrl_heads_bwd takes no A = 3)
     backward  d[Wa1;Wc1] = dZac^T H2                  gymrl_linear_bwd_weight (hidden 256) / gymrl_lin_bwd_weight
               dZ2 = (dZac [Wa1;Wc1]) (1 - H2^2)       gymrl_linear_bwd_input, tanh' in the epilogue
               dW2 = dZ2^T H1, db2 = colsum dZ2        gymrl_linear_bwd_weight / gymrl_lin_bwd_weight (+ bias gradient)
@@ -41,8 +43,9 @@ def supported(model):
     H = model.shared[0].out_features
     D = model.shared[0].in_features
     A = model.actor[2].out_features
+    # H in {64, 128, 256}, D in {2, 3, 4, 6, 8}, A in {2, 3, 4}: the library states the gate (gymrl_ppo_update_shape_ok).
     # multiples of 64 keep flatten_module's 64-float padding from separating actor.0 / critic.0
-    return (H in (64, 128, 256) and D in (2, 3, 4, 8) and A in (2, 4)
+    return (ops.ppo_update_shape_ok(H, D, A)
             and model.shared[2].out_features == H and model.actor[0].out_features == H
             and model.critic[0].out_features == H)
 
@@ -78,7 +81,10 @@ class FusedActorCriticUpdate:
         self.dH2 = torch.empty(R, H, device=dev)
         self.dH1 = torch.empty(R, H, device=dev)
         self.timers = None      # bench.py: KernelTimers bracketing every launch
-        self.one_pass_heads = H == 256           # gymrl_heads_loss_fwd_bwd (a row = one 64-lane load of 4 columns per lane)
+        # two independent choices.  The heads: gymrl_heads_loss_fwd_bwd (one pass) at hidden 256 and wherever A = 3, which
+        # gymrl_heads_bwd does not take.  The weight gradients: the 256-deep GEMM (gemm_ws) at hidden 256, the narrow
+        # kernels of lin.hip (lin_ws) below it.
+        self.one_pass_heads = H == 256 or self.A == 3
         self.gemm_ws = ops.gemm_workspace(dev) if H == 256 else None
         # the five batch reductions' second halves as ONE launch at the end of step() (gymrl_update_finalize) instead of five
         # behind their producers: every producer then keeps its partials in a workspace of its own until that launch
@@ -90,6 +96,7 @@ class FusedActorCriticUpdate:
             self.value = torch.empty(R, 1, device=dev)
             self.dlogits = torch.empty(R, self.A, device=dev)
             self.dvalue = torch.empty(R, device=dev)
+        if H != 256:
             self.lin_ws = ops.lin_workspace(R, 2 * H, H, 1, dev) if R > 512 else None
 
     def _timed(self, name, units, fn, *args, **kw):
@@ -124,15 +131,12 @@ class FusedActorCriticUpdate:
         heads = (m.actor[2].weight, m.actor[2].bias, m.critic[2].weight, m.critic[2].bias)
         hgrads = (m.actor[2].weight.grad, m.actor[2].bias.grad, m.critic[2].weight.grad, m.critic[2].bias.grad)
         # (multi-rank: bucket 1 of the gradient all-reduce leaves in the middle of step(): its gradients are finalized at once)
-        defer = self.defer_finalize and self.one_pass_heads and reducer is None
-        if self.one_pass_heads and defer:
-            t("heads_loss_fwd_bwd", B, ops.heads_loss_fwd_bwd, Zac, None, *heads, act, logp_old, adv, ret, loss_cfg, adv_moments,
-              None, None, None, None, None, metric_parts, self.ws)
-            t("gemm_dw_512", B, ops.linear_bwd_weight, Zac, H2, None, ws)
-        elif self.one_pass_heads:
-            t("heads_loss_fwd_bwd", B, ops.heads_loss_fwd_bwd, Zac, None, *heads, act, logp_old, adv, ret, loss_cfg, adv_moments,
-              self.dbac, *hgrads, metric_parts, self.ws)
-            t("gemm_dw_512", B, ops.linear_bwd_weight, Zac, H2, self.dWac, ws)
+        wide = H == 256                                   # weight gradients: the 256-deep GEMM / lin.hip's narrow kernels
+        defer = self.defer_finalize and self.one_pass_heads and wide and reducer is None
+        if self.one_pass_heads:
+            dbac, hg = (None, (None,) * 4) if defer else (self.dbac, hgrads)
+            t("heads_loss_fwd_bwd" + sfx, B, ops.heads_loss_fwd_bwd, Zac, None, *heads, act, logp_old, adv, ret, loss_cfg, adv_moments,
+              dbac, *hg, metric_parts, self.ws)
         else:
             logits, value, dl, dv = self.logits[:B], self.value[:B], self.dlogits[:B], self.dvalue[:B]
             # the GEMM added [ba1;bc1]: the heads read pre-activations, recompute their tanh in backward, write dZac in place
@@ -141,13 +145,16 @@ class FusedActorCriticUpdate:
               adv_moments=adv_moments, dlogits_out=dl, dvalue_out=dv, workspace=metric_parts)
             t("heads_bwd" + sfx, B, ops.heads_bwd, Zac, dl, dv, heads[0], heads[2], Zac, self.dbac, hgrads[0], hgrads[1],
               hgrads[2], hgrads[3], self.ws, True, None)
+        if wide:
+            t("gemm_dw_512", B, ops.linear_bwd_weight, Zac, H2, None if defer else self.dWac, ws)
+        else:
             t(f"lin_dw_{2 * H}", B, ops.lin_bwd_weight, Zac, None, H2, self.dWac, workspace=self.lin_ws)
         if reducer is not None:
             reducer.launch(1)
         t(f"gemm_dx_{2 * H}_tanhbwd", B, ops.linear_bwd_input, Zac, self.Wac, H2, dZ2)
         if defer:
             t("gemm_dw_256_db", B, ops.linear_bwd_weight, dZ2, H1, None, self.gemm_ws2, None, True)
-        elif self.one_pass_heads:
+        elif wide:
             t("gemm_dw_256_db", B, ops.linear_bwd_weight, dZ2, H1, W2.grad, ws, m.shared[2].bias.grad)
         else:
             t(f"lin_dw_{H}_db", B, ops.lin_bwd_weight, dZ2, None, H1, W2.grad, m.shared[2].bias.grad, workspace=self.lin_ws)

@@ -1078,7 +1078,7 @@ int gymrl_mhc_policy_forward(const gymrl_mhc_policy* p, const float* obs, int B,
  * C a power of two in 16..256.  workspace: gymrl_mlp_train_workspace_bytes(C, D, A) bytes.
  * Column reductions are deterministic (fixed-order f64 finalize over per-workgroup partials).
  *
- *   linear_tanh_smallk : out = tanh(x W^T + b), x [B, D], W [C, D], D in {2,3,4,8}
+ *   linear_tanh_smallk : out = tanh(x W^T + b), x [B, D], W [C, D], D in {2,3,4,6,8}
  *                        (shared.0: Linear(obs, hidden) + Tanh)
  *   tanh_inplace       : z <- tanh(z + bias[col]) on n floats = rows of C columns (bias NULL: none) after a
  *                        library GEMM; the bias rides on this pass, the GEMM runs without an epilogue
@@ -1110,7 +1110,7 @@ int gymrl_mhc_policy_forward(const gymrl_mhc_policy* p, const float* obs, int B,
 size_t gymrl_mlp_train_workspace_bytes(int C, int D, int A);
 int gymrl_linear_tanh_smallk(const float* x, const float* W, const float* b, int64_t B, int D, int C,
                              float* out, void* stream);
-/* The same launch without the tanh: out [B, C] = x [B, D] W[C, D]^T + b (D in {2, 3, 4, 8}, C a power of two >= 4), one fmaf chain
+/* The same launch without the tanh: out [B, C] = x [B, D] W[C, D]^T + b (D in {2, 3, 4, 6, 8}, C a power of two >= 4), one fmaf chain
  * per output in ascending d — PPO-full's input projection (ppo_full_lunarlander.py:236: Linear(obs, 128)) at 524 288-row
  * micro-batches, where the 16 x 16-tile layer kernel writes its 268 MB in 64-byte pieces (152 us; this one: 16-byte stores). */
 int gymrl_linear_smallk(const float* x, const float* W, const float* b, int64_t B, int D, int C, float* out, void* stream);
@@ -1130,10 +1130,10 @@ int gymrl_heads_bwd(const float* Hac, const float* dlogits, const float* dv, int
 
 /*
  * heads_loss_fwd_bwd : gymrl_heads_fwd_tanh + gymrl_ppo_loss_fwd_bwd + gymrl_heads_bwd as ONE pass over
- *   Zac [B, 512] (C == 256): per row tanh(Zac + bac), logits / value from the two heads, the clipped-surrogate loss of
+ *   Zac [B, 2C] (C in {64, 128, 256}, A in {2, 3, 4}): per row tanh(Zac + bac), logits / value from the two heads, the clipped-surrogate loss of
  *   ppo_lunarlander.py:278-300 (advantage normalised on load from adv_moments as in gymrl_ppo_loss_fwd_bwd; act /
  *   logp_old / adv / ret are the minibatch's rows in order, i.e. already gathered), and the heads' backward: dZac
- *   overwrites Zac in place; dbac [512], dWa2 [A, 256], dba2 [A], dWc2 [256], dbc2 [1] as gymrl_heads_bwd.
+ *   overwrites Zac in place; dbac [2C], dWa2 [A, C], dba2 [A], dWc2 [C], dbc2 [1] as gymrl_heads_bwd.
  *   metric_parts: f64[gymrl_heads_loss_blocks(B, C)][5] block partials of (policy loss, value loss, entropy,
  *   clip fraction, approx KL) sums — reduce with gymrl_reduce_rows.  Same arithmetic per row as the three
  *   separate passes (one shared device function each), so gradients and metrics are bit-identical to them.
@@ -1141,6 +1141,10 @@ int gymrl_heads_bwd(const float* Hac, const float* dlogits, const float* dv, int
 /* (gradient outputs: all five non-NULL, or all five NULL = "block partials only": they stay in `workspace` for
  *  gymrl_update_finalize below; gymrl_linear_smallk_bwd takes dW = db = NULL and gymrl_linear_bwd_weight dW = NULL the same way) */
 int gymrl_heads_loss_blocks(int64_t B, int C);
+/* 1 where the fused PPO update (ppo_net.FusedActorCriticUpdate) covers an ActorCritic of hidden width C, observation width D
+ * and A actions: C in {64, 128, 256}, D in {2, 3, 4, 6, 8}, A in {2, 3, 4}; 0 otherwise.  Host only.  (A = 3 takes
+ * gymrl_heads_loss_fwd_bwd at every width: gymrl_heads_bwd stays A in {2, 4}.) */
+int gymrl_ppo_update_shape_ok(int C, int D, int A);
 int gymrl_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* bac, const float* Wa2,
                              const float* ba2, const float* Wc2, const float* bc2, const int32_t* act,
                              const float* logp_old, const float* adv, const float* ret,
@@ -1206,7 +1210,7 @@ int gymrl_linear_bwd_weight(const float* dY, const float* X, int64_t B, int N, i
  * (gymrl_heads_loss_fwd_bwd with its five outputs NULL) and of the first layer's (gymrl_linear_smallk_bwd, dW = db = NULL) —
  * each left in the workspace handed to that call (FOUR DIFFERENT workspaces: a deferred reduction's partials must survive
  * until this launch).  Every block runs the body of the kernel it replaces: same loads, same float64 sums in the same order,
- * outputs bit-identical to the five separate launches (tests/test_update_path_gpu.py).  C = 256, A in {2, 4}, D in {2, 3, 4, 8}.
+ * outputs bit-identical to the five separate launches (tests/test_update_path_gpu.py).  C = 256, A in {2, 3, 4}, D in {2, 3, 4, 6, 8}.
  */
 int gymrl_update_finalize(int64_t B, int C, int A, int D, const void* ws_dw_ac, float* dWac, const void* ws_dw_2, float* dW2,
                           float* db2, const void* ws_heads, float* dbac, float* dWa2, float* dba2, float* dWc2, float* dbc2,
