@@ -130,7 +130,54 @@ float orc_tanhf(float x) {
   p = fmaf(p, z, -5.37397155531e-2f);
   p = fmaf(p, z, 1.33314422036e-1f);
   p = fmaf(p, z, -3.33332819422e-1f);
-  return fmaf(p * z, x, x);
+  return copysignf(fmaf(p * z, x, x), x);   /* x = -0: the fma gives (-0)(-0) + (-0) = +0 */
+}
+
+/* The twin of det_tanhf_sel (gymrl_device.hpp): both ranges evaluated and selected, operation for operation.  The same
+ * bits as orc_tanhf for every input, NaN included (a NaN fails `a >= 0.625f` and leaves through the polynomial):
+ * tools/check_det_f32.c compares the two over all 2^32 patterns. */
+float orc_tanhf_sel(float x) {
+  const float a = fabsf(x);
+  const float t = fminf(a, 9.0f);
+  const float xx = t + t;
+  float n = rintf(xx * 1.44269504088896341f);
+  float r = fmaf(n, -0.693359375f, xx);
+  r = fmaf(n, 2.12194440e-4f, r);
+  float pe = 1.9875691500e-4f;
+  pe = fmaf(pe, r, 1.3981999507e-3f);
+  pe = fmaf(pe, r, 8.3334519073e-3f);
+  pe = fmaf(pe, r, 4.1665795894e-2f);
+  pe = fmaf(pe, r, 1.6666665459e-1f);
+  pe = fmaf(pe, r, 5.0000001201e-1f);
+  const float e = ldexpf(fmaf(pe, r * r, r) + 1.0f, (int)n);
+  float big = 1.0f - 2.0f / (e + 1.0f);
+  big = a > 9.0f ? 1.0f : big;
+  big = x < 0.0f ? -big : big;
+  const float z = x * x;
+  float p = -5.70498872745e-3f;
+  p = fmaf(p, z, 2.06390887954e-2f);
+  p = fmaf(p, z, -5.37397155531e-2f);
+  p = fmaf(p, z, 1.33314422036e-1f);
+  p = fmaf(p, z, -3.33332819422e-1f);
+  const float small = copysignf(fmaf(p * z, x, x), x);
+  return a >= 0.625f ? big : small;
+}
+
+/* One of the functions above over an array (the test suite sweeps millions of inputs; a ctypes call each is too slow).
+ * op: 0 exp, 1 log, 2 tanh (branchy), 3 sincos (out = sin, out2 = cos), 4 tanh (select form),
+ *     5 sigmoid = 1 / (1 + exp(-x)), det_sigmoidf's expression; any other op fills out with NaN.  out2 is written by op 3 only. */
+void orc_map_f32(int op, const float* x, int64_t n, float* out, float* out2) {
+  for (int64_t i = 0; i < n; ++i) {
+    switch (op) {
+      case 0: out[i] = orc_expf(x[i]); break;
+      case 1: out[i] = orc_logf(x[i]); break;
+      case 2: out[i] = orc_tanhf(x[i]); break;
+      case 3: orc_sincosf(x[i], out + i, out2 + i); break;
+      case 4: out[i] = orc_tanhf_sel(x[i]); break;
+      case 5: out[i] = 1.0f / (1.0f + orc_expf(-x[i])); break;
+      default: out[i] = NAN; break;
+    }
+  }
 }
 
 /* ------------------------------------------------------------------ MLP ---

@@ -57,19 +57,29 @@ def _i32(a):
 
 
 # ------------------------------------------------------------------ math ----
+MAP_EXP, MAP_LOG, MAP_TANH, MAP_SINCOS, MAP_TANH_SEL, MAP_SIGMOID = range(6)
+
+
+def map_f32(op, x):
+    """orc_map_f32: one of the reproducible f32 functions over an array, in one call.  MAP_SINCOS returns (sin, cos)."""
+    shape = np.shape(x)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    out2 = np.empty_like(x) if op == MAP_SINCOS else None
+    lib().orc_map_f32(C.c_int(int(op)), _p(x), C.c_int64(x.size), _p(out), _p(out2))
+    return (out.reshape(shape), out2.reshape(shape)) if op == MAP_SINCOS else out.reshape(shape)
+
+
 def expf(x):
-    L = lib()
-    return np.array([L.orc_expf(float(v)) for v in np.asarray(x, np.float32).ravel()], np.float32).reshape(np.shape(x))
+    return map_f32(MAP_EXP, x)
 
 
 def logf(x):
-    L = lib()
-    return np.array([L.orc_logf(float(v)) for v in np.asarray(x, np.float32).ravel()], np.float32).reshape(np.shape(x))
+    return map_f32(MAP_LOG, x)
 
 
 def tanhf(x):
-    L = lib()
-    return np.array([L.orc_tanhf(float(v)) for v in np.asarray(x, np.float32).ravel()], np.float32).reshape(np.shape(x))
+    return map_f32(MAP_TANH, x)
 
 
 def linear_act(x, W, b, act=0):
@@ -144,15 +154,7 @@ def mlp_forward(x, stages):
 
 
 def sincosf(x):
-    L = lib()
-    xs = np.asarray(x, np.float32).ravel()
-    s = np.empty_like(xs)
-    c = np.empty_like(xs)
-    ss, cc = C.c_float(), C.c_float()
-    for i, v in enumerate(xs):
-        L.orc_sincosf(C.c_float(float(v)), C.byref(ss), C.byref(cc))
-        s[i], c[i] = ss.value, cc.value
-    return s.reshape(np.shape(x)), c.reshape(np.shape(x))
+    return map_f32(MAP_SINCOS, x)
 
 
 def philox(key, c0, c1, c2, c3):

@@ -1,39 +1,25 @@
 """Plain numpy float32 restatement of gymrl_amd/csrc/lstm_cell_device.hpp, operation by operation (TEST INFRASTRUCTURE).
 
-exp and tanh are the built oracle library's orc_expf / orc_tanhf (the bits of det_expf and det_tanhf_sel), taken through
-ctypes; everything else is IEEE float32 arithmetic, which numpy evaluates exactly as the header writes it (the kernels
+exp and tanh are the built oracle library's orc_expf / orc_tanhf_sel (the bits of det_expf and det_tanhf_sel), taken through
+tests/det_math_ref.py; everything else is IEEE float32 arithmetic, which numpy evaluates exactly as the header writes it (the kernels
 are built with -ffp-contract=off and correctly rounded division).  Also a window / episode recurrence with float64 gate
 products, like oracle.gru_forward, and its reverse.
 """
-import ctypes as C
-
 import numpy as np
+
+import det_math_ref
 
 _F = np.float32
 _ONE = _F(1.0)
 
 
-def _lib():
-    from oracle import oracle as orc
-    L = orc.lib()
-    for name in ("orc_expf", "orc_tanhf"):
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = C.c_float, [C.c_float]
-    return L
-
-
-def _map(fn, x):
-    x = np.asarray(x, _F)
-    return np.array([fn(float(v)) for v in x.ravel()], _F).reshape(x.shape)
-
-
 def expf(x):
-    return _map(_lib().orc_expf, x)
+    return det_math_ref.expf(x)
 
 
 def tanhf(x):
     """det_tanhf_sel"""
-    return _map(_lib().orc_tanhf, x)
+    return det_math_ref.tanhf_sel(x)
 
 
 def sigmoidf(x):
