@@ -627,6 +627,7 @@ SIGNATURES = {
     "gymrl_dsac_pack_images": (_i, [_P(DsacUpdateArgs), _vp]),
     "gymrl_dsac_args_bytes": (_sz, [_i]),
     "gymrl_dsac_act_step": (_i, [_P(DsacActArgs), _vp]),
+    "gymrl_dsac_act_step_classic": (_i, [_P(DsacActArgs), _vp]),
     "gymrl_dsac_update": (_i, [_P(DsacUpdateArgs), _vp]),
     "gymrl_softmax_rows_fwd": (_i, [_vp, _i, _i, _vp, _vp]),
     "gymrl_softmax_rows_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
@@ -650,6 +651,7 @@ SIGNATURES = {
     "gymrl_dqn_pack_images": (_i, [_P(DqnUpdateArgs), _vp]),
     "gymrl_dqn_args_bytes": (_sz, [_i]),
     "gymrl_dqn_act_step": (_i, [_P(DqnActArgs), _vp]),
+    "gymrl_dqn_act_step_classic": (_i, [_P(DqnActArgs), _vp]),
     "gymrl_dqn_update": (_i, [_P(DqnUpdateArgs), _vp]),
     "gymrl_ddqn_update_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_ddqn_pack_images": (_i, [_P(DdqnUpdateArgs), _vp]),

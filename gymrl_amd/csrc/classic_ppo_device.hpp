@@ -2,10 +2,9 @@
 // rollout) and eval_classic_ppo.hip (whole evaluation episodes) are templates over ClassicEnv<KIND>, and both entry points refuse
 // the same policy descriptors.
 //
-//   ClassicEnv<KIND>   CartPole-v1, MountainCar-v0, Acrobot-v1: the widths and the TimeLimit (kObs, kActions, kMaxSteps: ClassicDims
-//                      of env_classic_device.hpp), the view of the env state buffer, ONE env's step with auto-reset
-//                      (env_classic_device.hpp: gymrl_env_step's arithmetic), and the vector an observation row of the slab is
-//                      stored with — 16 bytes are one float4, 8 and 24 bytes are one and three float2.
+//   ClassicEnv<KIND>   (env_classic_device.hpp, which the DQN-family act kernels read it from as well) CartPole-v1, MountainCar-v0,
+//                      Acrobot-v1: the widths and the TimeLimit, the view of the env state buffer, ONE env's step with auto-reset, and
+//                      the vector an observation row of the slab is stored with.
 //   ppo_desc_ok        the policy is gymrl_mlp_forward's stage table on the env's observation: logits [A] then value [1] as its
 //                      two dst == -1 stages.
 #pragma once
@@ -14,29 +13,6 @@
 
 namespace gymrl {
 namespace {
-
-template <int KIND> struct ClassicEnv;
-template <> struct ClassicEnv<GYMRL_ENV_CARTPOLE> : ClassicDims<GYMRL_ENV_CARTPOLE> {
-  using State = CartPoleState;
-  using ObsVec = float4;
-  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<4>& r) {
-    cartpole_step_one(st, i, seed, env_id0, action, r);
-  }
-};
-template <> struct ClassicEnv<GYMRL_ENV_MOUNTAINCAR> : ClassicDims<GYMRL_ENV_MOUNTAINCAR> {
-  using State = MountainCarState;
-  using ObsVec = float2;
-  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<2>& r) {
-    mountaincar_step_one(st, i, seed, env_id0, action, r);
-  }
-};
-template <> struct ClassicEnv<GYMRL_ENV_ACROBOT> : ClassicDims<GYMRL_ENV_ACROBOT> {
-  using State = AcrobotState;
-  using ObsVec = float2;
-  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<6>& r) {
-    acrobot_step_one(st, i, seed, env_id0, action, r);
-  }
-};
 
 // the policy must be a 2-output network on the env's observation: logits [n_act] then value [1]
 inline bool ppo_desc_ok(const gymrl_mlp_desc* policy, int n_obs, int n_act) {

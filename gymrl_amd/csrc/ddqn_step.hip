@@ -346,7 +346,7 @@ int gymrl_ddqn_update(const gymrl_ddqn_update_args* args, void* stream_) {
 int gymrl_ddqn_duel_act_step(const gymrl_dqn_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_dqn_act_args& a = *args;
-  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
   if (const int rc = ddqn_set_lds_attr()) return rc;
   hipLaunchKernelGGL(a.H == 256 ? ddqn_duel_act_kernel<256> : ddqn_duel_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 1), (hipStream_t)stream_, a);
   GYMRL_CHECK_LAUNCH();

@@ -120,8 +120,9 @@ __global__ __launch_bounds__(kThreads) void dqn_r1_kernel(const gymrl_dqn_update
   bwd_stage(lds, {BwdItem{Z0, ld, H, p.w[1], H, -1, nullptr, P1, ld, R, -1, 0, ws.Z1, H, im.pb}}, row0, nrows);      // (the last stage: no barrier behind it)
 }
 
-// ---- acting: the policy net's Q values, the epsilon-greedy choice (gymrl_epsilon_greedy's keys), CartPole step, replay row ----
-template <int HC>
+// ---- acting: the policy net's Q values, the epsilon-greedy choice (gymrl_epsilon_greedy's keys), the env's step, replay row ----
+// KIND: CartPole-v1 (gymrl_dqn_act_step, and gymrl_dqn_act_step_classic's kind 0), MountainCar-v0, Acrobot-v1
+template <int HC, int KIND>
 __global__ __launch_bounds__(kThreads) void dqn_act_kernel(const gymrl_dqn_act_args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds L;
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void dqn_act_kernel(const gymrl_dqn_act_a
   fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.policy.w[0], a.policy.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);
   fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, a.policy.w[1], a.policy.b[1], X1, ld, nullptr, 0, R, 0.0f, 0.0f, pf)}, row0, nrows);
   fwd_one(lds, {fwd_item(X1, ld, -1, 0, H, H, A, a.policy.w[2], a.policy.b[2], L.Mean, kA, nullptr, 0, GYMRL_ACT_NONE)}, row0, nrows);
-  // one lane per env: the choice, CartPole step with auto-reset, replay row (the first wave: 16 lanes busy)
+  // one lane per env: the choice, the env's step with auto-reset, replay row (the first wave: 16 lanes busy)
   if (t < 64) {
     int act = 0;
     if (t < nrows) {
@@ -148,7 +149,19 @@ __global__ __launch_bounds__(kThreads) void dqn_act_kernel(const gymrl_dqn_act_a
       act = epsilon_greedy_pick(lds + L.Mean + t * kMaxA, A, a.u ? a.u + (size_t)(row0 + t) * 2 : nullptr, a.seed,
                                 (uint64_t)(a.env_id0 + row0 + t), counter, eps);
     }
-    cartpole_act_tail(a, lds, L, t, row0, nrows, act);
+    classic_act_tail<KIND>(a, lds, L, t, row0, nrows, act);
+  }
+}
+// the instance of (hidden width, env kind); nullptr for a kind without one
+using DqnActKernel = void (*)(const gymrl_dqn_act_args);
+template <int KIND>
+DqnActKernel dqn_act_instance(bool wide) { return wide ? dqn_act_kernel<256, KIND> : dqn_act_kernel<0, KIND>; }
+DqnActKernel dqn_act_pick(int env_kind, bool wide) {
+  switch (env_kind) {
+    case GYMRL_ENV_CARTPOLE: return dqn_act_instance<GYMRL_ENV_CARTPOLE>(wide);
+    case GYMRL_ENV_MOUNTAINCAR: return dqn_act_instance<GYMRL_ENV_MOUNTAINCAR>(wide);
+    case GYMRL_ENV_ACROBOT: return dqn_act_instance<GYMRL_ENV_ACROBOT>(wide);
+    default: return nullptr;
   }
 }
 
@@ -161,18 +174,37 @@ size_t gymrl_dqn_args_bytes(int which) { return which == 0 ? sizeof(gymrl_dqn_ac
 
 static int dqn_set_lds_attr() {
   static bool done = false;
-  return set_max_lds_once(done, {(const void*)dqn_r1_kernel<0>, (const void*)dqn_r1_kernel<256>, (const void*)dqn_act_kernel<0>,
-                                 (const void*)dqn_act_kernel<256>}, (int)lds_bytes(256, 4));
+  return set_max_lds_once(done, {(const void*)dqn_r1_kernel<0>, (const void*)dqn_r1_kernel<256>, (const void*)dqn_act_pick(GYMRL_ENV_CARTPOLE, false),
+                                 (const void*)dqn_act_pick(GYMRL_ENV_CARTPOLE, true)}, (int)lds_bytes(256, 4));
+}
+// (the MountainCar and Acrobot instances: raised on gymrl_dqn_act_step_classic's first call, so that a CartPole run's set-up is the parent's)
+static int dqn_set_lds_attr_classic() {
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)dqn_act_pick(GYMRL_ENV_MOUNTAINCAR, false), (const void*)dqn_act_pick(GYMRL_ENV_MOUNTAINCAR, true),
+                                 (const void*)dqn_act_pick(GYMRL_ENV_ACROBOT, false), (const void*)dqn_act_pick(GYMRL_ENV_ACROBOT, true)}, (int)lds_bytes(256, 4));
+}
+static int dqn_act_launch(const gymrl_dqn_act_args& a, void* stream_) {
+  hipLaunchKernelGGL(dqn_act_pick(a.env_kind, a.H == 256), dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
 }
 
 int gymrl_dqn_act_step(const gymrl_dqn_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_dqn_act_args& a = *args;
-  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
   if (const int rc = dqn_set_lds_attr()) return rc;
-  hipLaunchKernelGGL(a.H == 256 ? dqn_act_kernel<256> : dqn_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
+  return dqn_act_launch(a, stream_);
+}
+
+// the same launch for the env kind the block names: CartPole-v1, MountainCar-v0 or Acrobot-v1, each with its own (D, A)
+int gymrl_dqn_act_step_classic(const gymrl_dqn_act_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_dqn_act_args& a = *args;
+  if (!classic_act_kind_ok(a.env_kind) || !act_args_ok(a, a.env_kind, /*refuse_neg_cursor=*/true) || !net_ok(a.policy)) return -22;
+  if (const int rc = dqn_set_lds_attr()) return rc;
+  if (const int rc = dqn_set_lds_attr_classic()) return rc;
+  return dqn_act_launch(a, stream_);
 }
 
 static bool dqn_update_args_ok(const gymrl_dqn_update_args& a) {

@@ -256,8 +256,9 @@ __global__ __launch_bounds__(256) void dsac_dw2_kernel(const Dw2 a) {
   sac_dw_body(a.d[second], second ? (int)blockIdx.x - a.na : (int)blockIdx.x, second ? (int)gridDim.x - a.na : a.na, sm);
 }
 
-// ---- acting: actor logits, the categorical draw (gymrl_categorical_sample's keys), CartPole step, replay row ----
-template <int HC>
+// ---- acting: actor logits, the categorical draw (gymrl_categorical_sample's keys), the env's step, replay row ----
+// KIND: CartPole-v1 (gymrl_dsac_act_step, and gymrl_dsac_act_step_classic's kind 0), MountainCar-v0, Acrobot-v1
+template <int HC, int KIND>
 __global__ __launch_bounds__(kThreads) void dsac_act_kernel(const gymrl_dsac_act_args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds L;
@@ -275,17 +276,32 @@ __global__ __launch_bounds__(kThreads) void dsac_act_kernel(const gymrl_dsac_act
   fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.actor.w[0], a.actor.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);
   fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, a.actor.w[1], a.actor.b[1], X1, ld, nullptr, 0, R, 0.0f, 0.0f, af)}, row0, nrows);
   fwd_one(lds, {fwd_item(X1, ld, -1, 0, H, H, A, a.actor.w[2], a.actor.b[2], L.Mean, kA, nullptr, 0, GYMRL_ACT_NONE)}, row0, nrows);
-  // one lane per env: the draw, CartPole step with auto-reset, replay row (the first wave: 16 lanes busy)
+  // one lane per env: the draw, the env's step with auto-reset, replay row (the first wave: 16 lanes busy)
   if (t < 64) {
+    constexpr int kActs = ClassicDims<KIND>::kActions;
     int act = 0;
     if (t < nrows) {
-      const float z[2] = {lds[L.Mean + t * kMaxA], lds[L.Mean + t * kMaxA + 1]};
+      float z[kActs];
+#pragma unroll
+      for (int k = 0; k < kActs; ++k) z[k] = lds[L.Mean + t * kMaxA + k];
       const uint64_t counter = a.counter_dev ? a.counter_dev[0] : a.counter;
       float lp, ent;
-      act = categorical_pick<2>(z, a.noise_exp ? a.noise_exp + (size_t)(row0 + t) * 2 : nullptr, a.seed, (uint64_t)(a.env_id0 + row0 + t),
-                                counter, 0, lp, ent);
+      act = categorical_pick<kActs>(z, a.noise_exp ? a.noise_exp + (size_t)(row0 + t) * kActs : nullptr, a.seed, (uint64_t)(a.env_id0 + row0 + t),
+                                 counter, 0, lp, ent);
     }
-    cartpole_act_tail(a, lds, L, t, row0, nrows, act);
+    classic_act_tail<KIND>(a, lds, L, t, row0, nrows, act);
+  }
+}
+// the instance of (hidden width, env kind); nullptr for a kind without one
+using DsacActKernel = void (*)(const gymrl_dsac_act_args);
+template <int KIND>
+DsacActKernel dsac_act_instance(bool wide) { return wide ? dsac_act_kernel<256, KIND> : dsac_act_kernel<0, KIND>; }
+DsacActKernel dsac_act_pick(int env_kind, bool wide) {
+  switch (env_kind) {
+    case GYMRL_ENV_CARTPOLE: return dsac_act_instance<GYMRL_ENV_CARTPOLE>(wide);
+    case GYMRL_ENV_MOUNTAINCAR: return dsac_act_instance<GYMRL_ENV_MOUNTAINCAR>(wide);
+    case GYMRL_ENV_ACROBOT: return dsac_act_instance<GYMRL_ENV_ACROBOT>(wide);
+    default: return nullptr;
   }
 }
 
@@ -309,17 +325,36 @@ size_t gymrl_dsac_args_bytes(int which) { return which == 0 ? sizeof(gymrl_dsac_
 static int dsac_set_lds_attr() {
   static bool done = false;
   return set_max_lds_once(done, {(const void*)dsac_r1_kernel<0>, (const void*)dsac_r1_kernel<256>, (const void*)dsac_r3_kernel<0>, (const void*)dsac_r3_kernel<256>,
-                                 (const void*)dsac_act_kernel<0>, (const void*)dsac_act_kernel<256>}, (int)lds_bytes(256, 6));
+                                 (const void*)dsac_act_pick(GYMRL_ENV_CARTPOLE, false), (const void*)dsac_act_pick(GYMRL_ENV_CARTPOLE, true)}, (int)lds_bytes(256, 6));
+}
+// (the MountainCar and Acrobot instances: raised on gymrl_dsac_act_step_classic's first call, so that a CartPole run's set-up is the parent's)
+static int dsac_set_lds_attr_classic() {
+  static bool done = false;
+  return set_max_lds_once(done, {(const void*)dsac_act_pick(GYMRL_ENV_MOUNTAINCAR, false), (const void*)dsac_act_pick(GYMRL_ENV_MOUNTAINCAR, true),
+                                 (const void*)dsac_act_pick(GYMRL_ENV_ACROBOT, false), (const void*)dsac_act_pick(GYMRL_ENV_ACROBOT, true)}, (int)lds_bytes(256, 6));
+}
+static int dsac_act_launch(const gymrl_dsac_act_args& a, void* stream_) {
+  hipLaunchKernelGGL(dsac_act_pick(a.env_kind, a.H == 256), dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
 }
 
 int gymrl_dsac_act_step(const gymrl_dsac_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_dsac_act_args& a = *args;
-  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
   if (const int rc = dsac_set_lds_attr()) return rc;
-  hipLaunchKernelGGL(a.H == 256 ? dsac_act_kernel<256> : dsac_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
-  GYMRL_CHECK_LAUNCH();
-  return 0;
+  return dsac_act_launch(a, stream_);
+}
+
+// the same launch for the env kind the block names: CartPole-v1, MountainCar-v0 or Acrobot-v1, each with its own (D, A)
+int gymrl_dsac_act_step_classic(const gymrl_dsac_act_args* args, void* stream_) {
+  if (!args) return -22;
+  const gymrl_dsac_act_args& a = *args;
+  if (!classic_act_kind_ok(a.env_kind) || !act_args_ok(a, a.env_kind, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
+  if (const int rc = dsac_set_lds_attr()) return rc;
+  if (const int rc = dsac_set_lds_attr_classic()) return rc;
+  return dsac_act_launch(a, stream_);
 }
 
 static bool dsac_update_args_ok(const gymrl_dsac_update_args& a) {

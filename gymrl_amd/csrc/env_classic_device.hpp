@@ -337,6 +337,33 @@ __device__ __forceinline__ void acrobot_step_one(const AcrobotState& st, int i, 
   }
 }
 
+// What an env kind is to the kernels that STEP it inside a launch of their own — PPO's rollout and evaluation (classic_ppo_device.hpp)
+// and the DQN-family act kernels (slab_step_device.hpp: classic_act_tail): ClassicDims, the view of the env state buffer, ONE env's
+// step with auto-reset (gymrl_env_step's arithmetic, above), and the vector an observation row of PPO's slab is stored with — 16
+// bytes are one float4, 8 and 24 bytes are one and three float2.
+template <int KIND> struct ClassicEnv;
+template <> struct ClassicEnv<GYMRL_ENV_CARTPOLE> : ClassicDims<GYMRL_ENV_CARTPOLE> {
+  using State = CartPoleState;
+  using ObsVec = float4;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<4>& r) {
+    cartpole_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+template <> struct ClassicEnv<GYMRL_ENV_MOUNTAINCAR> : ClassicDims<GYMRL_ENV_MOUNTAINCAR> {
+  using State = MountainCarState;
+  using ObsVec = float2;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<2>& r) {
+    mountaincar_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+template <> struct ClassicEnv<GYMRL_ENV_ACROBOT> : ClassicDims<GYMRL_ENV_ACROBOT> {
+  using State = AcrobotState;
+  using ObsVec = float2;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<6>& r) {
+    acrobot_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+
 // What an env kind is to the one-launch episode kernels (eval_episode_device.hpp: run_episodes): ClassicDims, the action its policy
 // hands over (an index, or Pendulum-v1's float torque), and three register-only pieces on the lane's float64 state s[kState] —
 //

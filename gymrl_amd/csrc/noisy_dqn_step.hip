@@ -329,7 +329,7 @@ int gymrl_ndqn_combine(const gymrl_ndqn_combine_args* args, void* stream_) {
 int gymrl_ndqn_act_step(const gymrl_ndqn_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_ndqn_act_args& a = *args;
-  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, 4, 2, /*refuse_neg_cursor=*/true) || !a.workspace) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_CARTPOLE, /*refuse_neg_cursor=*/true) || !a.workspace) return -22;
   if (const int rc = ndqn_set_lds_attr()) return rc;
   NdqnWs ws;
   NdqnWs::carve(&ws, align256(const_cast<void*>(a.workspace)), 1, a.D, a.A, a.H);

@@ -504,7 +504,7 @@ size_t gymrl_sac_args_bytes(int which) { return which == 0 ? sizeof(gymrl_sac_ac
 int gymrl_sac_act_step(const gymrl_sac_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_sac_act_args& a = *args;
-  if (!act_args_ok(a, GYMRL_ENV_PENDULUM, 3, 1, /*refuse_neg_cursor=*/false) || !net_ok(a.actor)) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_PENDULUM, /*refuse_neg_cursor=*/false) || !net_ok(a.actor)) return -22;
   static bool done = false;
   if (const int rc = set_max_lds_once(done, {(const void*)sac_act_kernel<0>, (const void*)sac_act_kernel<256>}, (int)lds_bytes(256, 4))) return rc;
   hipLaunchKernelGGL(a.H == 256 ? sac_act_kernel<256> : sac_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 4), (hipStream_t)stream_, a);

@@ -58,11 +58,31 @@ inline bool net_ok(const Net& n, int layers = (int)(sizeof(Net::w) / sizeof(void
 }
 template <class Args>
 inline bool ring_ok(const Args& a) { return all_set({a.r_state, a.r_action, a.r_reward, a.r_next, a.r_flag}); }
-// an act step's env, I/O and ring: the env kind with its fixed D and A; refuse_neg_cursor: SAC's act step has never looked at the cursor
+// the fixed (D, A) of the env kinds an act kernel steps (ClassicDims of env_classic_device.hpp); {0, 0}, which no argument block
+// passes, for every other kind
+struct ActDims { int D, A; };
+template <int KIND>
+constexpr ActDims act_dims_of() { return ActDims{ClassicDims<KIND>::kObs, ClassicDims<KIND>::kActions}; }
+inline ActDims act_env_dims(int env_kind) {
+  switch (env_kind) {
+    case GYMRL_ENV_CARTPOLE: return act_dims_of<GYMRL_ENV_CARTPOLE>();
+    case GYMRL_ENV_PENDULUM: return act_dims_of<GYMRL_ENV_PENDULUM>();
+    case GYMRL_ENV_MOUNTAINCAR: return act_dims_of<GYMRL_ENV_MOUNTAINCAR>();
+    case GYMRL_ENV_ACROBOT: return act_dims_of<GYMRL_ENV_ACROBOT>();
+    default: return ActDims{0, 0};
+  }
+}
+// an act step's env, I/O and ring: the env kind the entry point steps, with that kind's D and A; refuse_neg_cursor: SAC's act step
+// has never looked at the cursor
 template <class Args>
-inline bool act_args_ok(const Args& a, int env_kind, int D, int A, bool refuse_neg_cursor) {
-  return a.N > 0 && slab_shape_ok(1, 1, a.D, a.A, a.H) && a.env_kind == env_kind && a.D == D && a.A == A &&
+inline bool act_args_ok(const Args& a, int env_kind, bool refuse_neg_cursor) {
+  const ActDims dims = act_env_dims(env_kind);
+  return a.N > 0 && slab_shape_ok(1, 1, a.D, a.A, a.H) && a.env_kind == env_kind && a.D == dims.D && a.A == dims.A &&
          all_set({a.env_state, a.obs, a.obs_out}) && ring_ok(a) && a.cap >= a.N && !(refuse_neg_cursor && a.cursor < 0);
+}
+// the kinds gymrl_dqn_act_step_classic / gymrl_dsac_act_step_classic have an instance for (ops.FUSED_ACT_KINDS)
+inline bool classic_act_kind_ok(int env_kind) {
+  return env_kind == GYMRL_ENV_CARTPOLE || env_kind == GYMRL_ENV_MOUNTAINCAR || env_kind == GYMRL_ENV_ACROBOT;
 }
 // an update's replay rows: the caller's list, (where idx_dev_counts) the device's draw record, or a keyed draw over idx_size >= B rows
 template <class Args>
@@ -652,19 +672,24 @@ __device__ __forceinline__ void pendulum_act_tail(const Args& a, const float* ld
   accumulate_ep_stats(a.ep_stats, r.done && ok, r.ret, r.len);
 }
 
-// The same tail for CartPole under a discrete action: the step with auto-reset, the ring row {state, int32 action word, reward,
-// TERMINAL observation, done} at (cursor + i) % cap, the outputs env.step(..., done_out, term_obs_out, ep_ret_out) + memory.push
-// write.  (Rainbow's tail pushes into an n-step window between the step and the ring row and keeps its own copy.)
-template <class Args>
-__device__ __forceinline__ void cartpole_act_tail(const Args& a, const float* lds, const Lds& L, int t, int row0, int nrows, int act) {
+// The same tail for a classic-control env under a discrete action, KIND = CartPole-v1, MountainCar-v0 or Acrobot-v1 (ClassicEnv of
+// env_classic_device.hpp: the stepper's own arithmetic and auto-reset): the ring row {state, uint32 action word, reward, TERMINAL
+// observation, done} at (cursor + i) % cap, the outputs env.step(..., done_out, term_obs_out, ep_ret_out) + memory.push write.  The
+// row loops run over the kind's own width (ClassicDims::kObs) and unroll per env — but for CartPole, whose instance keeps the run-time
+// a.D (== 4: act_args_ok) it has always looped over, so that the kernels a CartPole run launches stay instruction for instruction
+// what they were (DESIGN 4ad has what the constant width would change there).  (Rainbow's tail pushes into an n-step window between
+// the step and the ring row and keeps its own copy.)
+template <int KIND, class Args>
+__device__ __forceinline__ void classic_act_tail(const Args& a, const float* lds, const Lds& L, int t, int row0, int nrows, int act) {
+  using Env = ClassicEnv<KIND>;
+  const int D = KIND == GYMRL_ENV_CARTPOLE ? a.D : (int)Env::kObs;
   const bool ok = t < nrows;
-  const int D = a.D;
-  ClassicStep<4> r;
+  ClassicStep<Env::kObs> r;
   r.done = false; r.ret = 0.0; r.len = 0;
   if (ok) {
     const int i = row0 + t;
-    const CartPoleState st(a.env_state, a.N);
-    cartpole_step_one(st, i, a.env_seed, a.env_id0, act, r);
+    const typename Env::State st(a.env_state, a.N);
+    Env::step(st, i, a.env_seed, a.env_id0, act, r);
     const int64_t cursor = a.cursor_dev ? a.cursor_dev[0] : a.cursor;
     const int64_t row = (cursor + i) % a.cap;
     for (int k = 0; k < D; ++k) {
@@ -681,6 +706,11 @@ __device__ __forceinline__ void cartpole_act_tail(const Args& a, const float* ld
     if (r.done && a.ep_ret_out) a.ep_ret_out[i] = (float)r.ret;
   }
   accumulate_ep_stats(a.ep_stats, r.done && ok, r.ret, r.len);
+}
+// its CartPole instance, under the name the two-action kernels (ddqn_step.hip's dueling act, noisy_dqn_step.hip) call
+template <class Args>
+__device__ __forceinline__ void cartpole_act_tail(const Args& a, const float* lds, const Lds& L, int t, int row0, int nrows, int act) {
+  classic_act_tail<GYMRL_ENV_CARTPOLE>(a, lds, L, t, row0, nrows, act);
 }
 
 // All weight images (f32[n][H*H]) from the parameters as they are (after load_state_dict / a checkpoint / a hard target copy /

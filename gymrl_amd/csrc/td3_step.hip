@@ -294,7 +294,7 @@ static int td3_set_lds_attr() {
 int gymrl_td3_act_step(const gymrl_td3_act_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_td3_act_args& a = *args;
-  if (!act_args_ok(a, GYMRL_ENV_PENDULUM, 3, 1, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
+  if (!act_args_ok(a, GYMRL_ENV_PENDULUM, /*refuse_neg_cursor=*/true) || !net_ok(a.actor)) return -22;
   if (const int rc = td3_set_lds_attr()) return rc;
   hipLaunchKernelGGL(a.H == 256 ? td3_act_kernel<256> : td3_act_kernel<0>, dim3((a.N + 15) / 16), dim3(kThreads), lds_bytes(a.H, 2), (hipStream_t)stream_, a);
   GYMRL_CHECK_LAUNCH();

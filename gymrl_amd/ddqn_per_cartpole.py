@@ -10,7 +10,8 @@ into the tree inside update().  ddqn_per_duel_cartpole.py imports everything her
 
 With Config.fused_step the update's forward chains, TD target and input-gradient chain are gymrl_ddqn_update's row launch
 (csrc/ddqn_step.hip) and acting is gymrl_dqn_act_step (the dueling net: gymrl_ddqn_duel_act_step); the default is the
-layer-by-layer path.
+layer-by-layer path.  On MountainCar-v0 and Acrobot-v1 (`env_name`) the non-dueling trainer acts through
+gymrl_dqn_act_step_classic (ops.FUSED_ACT_KINDS); the dueling one, whose kernels are two-action ones, trains layer by layer there.
 """
 import numpy as np
 import torch
@@ -279,7 +280,8 @@ class DDQNPERTrainer(DQNTrainer):
             img = (ops.dqn_images(cfg.hidden_dim, self.device)              # (the dueling net has no H x H layer: no images)
                    if getattr(cfg, "fused_images", True) and not self.DUELING else None)
             act = (ops.ddqn_act_args(env, self._layers(self.policy_net), m.ring, m.capacity, img)
-                   if isinstance(env, VecEnv) and env.kind == ops.CARTPOLE else None)
+                   if isinstance(env, VecEnv) and env.kind in ops.FUSED_ACT_KINDS       # (the dueling act kernel: two actions,
+                   and (not self.DUELING or env.kind == ops.CARTPOLE) else None)        # and so CartPole only)
             ws = ops.ddqn_update_workspace(cfg.batch_size, D, A, cfg.hidden_dim, self.device)
             upd = ops.ddqn_update_args(cfg.batch_size, D, A, self._layers(self.policy_net), self._layers(self.target_net),
                                        self.optimizer, m.ring, cfg.gamma, self._td, self._loss, ws, img, dueling=self.DUELING)

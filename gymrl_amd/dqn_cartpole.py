@@ -8,7 +8,8 @@ the TD target + MSE loss forward/backward and the grad-clamp(+-1) + Adam step ar
 kernels behind the C-ABI; the three Linear layers run through PyTorch-ROCm.
 
 With Config.fused_step the vector step is gymrl_dqn_act_step + gymrl_dqn_update (csrc/dqn_step.hip: one launch to act,
-two to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described above.
+two to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described above.  On
+MountainCar-v0 and Acrobot-v1 (`env_name`) the act launch is gymrl_dqn_act_step_classic (ops.FUSED_ACT_KINDS).
 """
 import copy
 from collections import deque
@@ -222,10 +223,11 @@ class DQNTrainer(WeightImages, PolicyEval):
                 and ops.dqn_fused_shape_ok(cfg.batch_size, m.ring[0].shape[1], self.action_dim, cfg.hidden_dim))
 
     def _fused_ok(self):
-        """The whole vector step fused: the update AND acting + env step + replay row (gymrl_dqn_act_step steps CartPole
-        itself and has no `abandon`: the trainer's own step cap must not cut an episode short; one update per step)."""
+        """The whole vector step fused: the update AND acting + env step + replay row (the act launch steps CartPole-v1,
+        MountainCar-v0 or Acrobot-v1 itself and has no `abandon`: the trainer's own step cap must not cut an episode short; one
+        update per step)."""
         cfg, env = self.cfg, self.env
-        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind == ops.CARTPOLE
+        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind in ops.FUSED_ACT_KINDS
                 and cfg.max_steps >= env.max_steps and cfg.updates_per_step == 1 and self.memory.capacity >= env.n)
 
     def _fused_args(self):
@@ -234,7 +236,7 @@ class DQNTrainer(WeightImages, PolicyEval):
             D, A = m.ring[0].shape[1], self.action_dim
             img = ops.dqn_images(cfg.hidden_dim, self.device) if getattr(cfg, "fused_images", True) else None
             act = (ops.dqn_act_args(env, self.policy_net, m.ring, m.capacity, img)
-                   if isinstance(env, VecEnv) and env.kind == ops.CARTPOLE else None)
+                   if isinstance(env, VecEnv) and env.kind in ops.FUSED_ACT_KINDS else None)
             ws = ops.dqn_update_workspace(cfg.batch_size, D, A, cfg.hidden_dim, self.device)
             upd = ops.dqn_update_args(cfg.batch_size, D, A, self.policy_net, self.target_net, self.optimizer, m.ring, cfg.gamma,
                                       self._loss, ws, img)

@@ -568,6 +568,8 @@ ENV_KINDS = {"CartPole-v1": CARTPOLE, "Pendulum-v1": PENDULUM, "LunarLander-v3":
 # below exist at import, before the library is loaded.)
 EPISODE_ENVS = {CARTPOLE: ("CartPole-v1", 4, 2, 4, 500), PENDULUM: ("Pendulum-v1", 3, 1, 2, 200),
                 MOUNTAINCAR: ("MountainCar-v0", 2, 3, 2, 200), ACROBOT: ("Acrobot-v1", 6, 3, 4, 500)}
+# the env kinds the DQN-family act launches step themselves (dqn_act_step, dsac_act_step: csrc/slab_step_device.hpp classic_act_tail)
+FUSED_ACT_KINDS = (CARTPOLE, MOUNTAINCAR, ACROBOT)
 
 
 def env_dims(kind):
@@ -2303,6 +2305,12 @@ def _set_act_env(a, env, actor, ring, cap, images):
     a.cap, a.images = cap, _addr(images)
 
 
+def _classic_act_entry(name, kind):
+    """The entry point of an act launch on env kind `kind`: CartPole-v1 keeps the one it has always called, MountainCar-v0 and
+    Acrobot-v1 (FUSED_ACT_KINDS) take its `_classic` sibling; any other kind goes to `name`, which refuses it."""
+    return name + "_classic" if kind in FUSED_ACT_KINDS and kind != CARTPOLE else name
+
+
 def _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, outs):
     """An act step's per-call fields; outs = (action_out, rew_out, done_out, ep_ret_out, ep_stats), each a tensor or None."""
     a.env_seed = env.seed                              # reset(seed=...) may have moved it
@@ -2560,9 +2568,10 @@ def dsac_act_args(env, actor, ring, cap, images=None):
 
 
 def dsac_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, noise_exp=None, seed=0, counter=0, counter_dev=None,
-                  action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None):
+                  action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None, entry=None):
     """gymrl_dsac_act_step: actor logits on obs [N, D], the categorical draw (noise_exp = f32[N, A] Exp(1) draws or None:
-    gymrl_categorical_sample's Philox keys under (seed, counter)), CartPole step with auto-reset, replay rows at
+    gymrl_categorical_sample's Philox keys under (seed, counter)), the env's step with auto-reset (CartPole-v1; MountainCar-v0
+    and Acrobot-v1 through gymrl_dsac_act_step_classic, or whichever of the two `entry` names), replay rows at
     (cursor + env) % cap — ONE launch."""
     if tuple(obs.shape) != (a.N, a.D) or tuple(obs_out.shape) != (a.N, a.D):
         raise ValueError(f"dsac_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
@@ -2573,7 +2582,8 @@ def dsac_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, noise_exp=Non
     _set_act_io(a, env, obs, obs_out, cursor, cursor_dev, (action_out, rew_out, done_out, ep_ret_out, ep_stats))
     a.noise_exp = _addr(noise_exp)
     a.seed, a.counter, a.counter_dev = seed, counter, _addr(counter_dev)
-    check(lib().gymrl_dsac_act_step(C.byref(a), _stream()), "gymrl_dsac_act_step")
+    entry = entry or _classic_act_entry("gymrl_dsac_act_step", a.env_kind)
+    check(getattr(lib(), entry)(C.byref(a), _stream()), entry)
 
 
 def dsac_update_args(B, D, A, actor, critic1, critic2, critic1_target, critic2_target, actor_opt, critic1_opt, critic2_opt, ring,
@@ -2656,10 +2666,11 @@ def dqn_act_args(env, policy, ring, cap, images=None):
 
 def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, cursor_dev=None, u=None, seed=0, counter=0,
                  counter_dev=None, action_out=None, rew_out=None, done_out=None, ep_ret_out=None, ep_stats=None,
-                 entry="gymrl_dqn_act_step"):
+                 entry=None):
     """gymrl_dqn_act_step: policy net on obs [N, D], the epsilon-greedy choice (u = f32[N, 2] uniforms or None:
     gymrl_epsilon_greedy's Philox keys under (seed, counter); epsilon rounded to float32 as epsilon_greedy() passes it, or
-    epsilon_dev = f32[1] on the device), CartPole step with auto-reset, replay rows at (cursor + env) % cap — ONE launch."""
+    epsilon_dev = f32[1] on the device), the env's step with auto-reset (CartPole-v1; MountainCar-v0 and Acrobot-v1 through
+    gymrl_dqn_act_step_classic), replay rows at (cursor + env) % cap — ONE launch.  entry: another kernel on the same block."""
     if tuple(obs.shape) != (a.N, a.D) or tuple(obs_out.shape) != (a.N, a.D):
         raise ValueError(f"dqn_act_step: obs {tuple(obs.shape)} / obs_out {tuple(obs_out.shape)}, expected {(a.N, a.D)}")
     if u is not None and (u.dtype != torch.float32 or u.numel() != a.N * 2 or not u.is_contiguous()):
@@ -2670,6 +2681,7 @@ def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, 
     a.u = _addr(u)
     a.seed, a.counter, a.counter_dev = seed, counter, _addr(counter_dev)
     a.epsilon, a.epsilon_dev = float(epsilon), _addr(epsilon_dev)
+    entry = entry or _classic_act_entry("gymrl_dqn_act_step", a.env_kind)
     check(getattr(lib(), entry)(C.byref(a), _stream()), entry)
 
 

@@ -4,7 +4,8 @@ Actor :70-80 (softmax output), Critic :83-93 (Q per action), SACTrainer :96-329 
 soft_update :140-145, update :148-227, train / eval / test).
 
 With Config.fused_step the vector step is gymrl_dsac_act_step + gymrl_dsac_update (csrc/dsac_step.hip: one launch to act,
-four to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described next.
+four to update, sixteen steps replayed as one hipGraph); the default is the layer-by-layer path described next.  On
+MountainCar-v0 and Acrobot-v1 (`env_name`) the act launch is gymrl_dsac_act_step_classic (ops.FUSED_ACT_KINDS).
 
 Underneath: CartPole instances step on the GPU; replay ring, categorical draw, soft-Bellman target, both
 critic losses, the actor loss's forward + dL/dprobs, the float32 log_alpha Adam step, three fused Adam steps
@@ -154,10 +155,10 @@ class SACTrainer(WeightImages, PolicyEval):
                 and ops.dsac_fused_shape_ok(cfg.batch_size, m.ring[0].shape[1], self.action_dim, cfg.hidden_dim))
 
     def _fused_ok(self):
-        """The whole vector step fused: the update AND acting + env step + replay row (gymrl_dsac_act_step steps CartPole
-        itself and has no `abandon`: the trainer's own step cap must not cut an episode short)."""
+        """The whole vector step fused: the update AND acting + env step + replay row (the act launch steps CartPole-v1,
+        MountainCar-v0 or Acrobot-v1 itself and has no `abandon`: the trainer's own step cap must not cut an episode short)."""
         cfg, env = self.cfg, self.env
-        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind == ops.CARTPOLE
+        return (self._fused_update_ok() and isinstance(env, VecEnv) and env.kind in ops.FUSED_ACT_KINDS
                 and cfg.max_steps >= env.max_steps and self.memory.capacity >= env.n)
 
     def _fused_args(self):
@@ -166,7 +167,7 @@ class SACTrainer(WeightImages, PolicyEval):
             D, A = m.ring[0].shape[1], self.action_dim
             img = ops.dsac_images(cfg.hidden_dim, self.device) if getattr(cfg, "fused_images", True) else None
             act = (ops.dsac_act_args(env, self.actor, m.ring, m.capacity, img)
-                   if isinstance(env, VecEnv) and env.kind == ops.CARTPOLE else None)
+                   if isinstance(env, VecEnv) and env.kind in ops.FUSED_ACT_KINDS else None)
             ws = ops.dsac_update_workspace(cfg.batch_size, D, A, cfg.hidden_dim, self.device)
             upd = ops.dsac_update_args(cfg.batch_size, D, A, self.actor, self.critic1, self.critic2, self.critic1_target,
                                        self.critic2_target, self.actor_optim, self.critic1_optim, self.critic2_optim, m.ring,

@@ -1672,11 +1672,12 @@ int gymrl_td3_update(const gymrl_td3_update_args* args, void* stream);
  *               temperature step on the finished entropy sum (:211-217)
  * Results are the layer-by-layer path's bits when that path runs its softmax through gymrl_softmax_rows_fwd / _bwd
  * (tests/test_dsac_fused_step_gpu.py).  Limits: H % 4 == 0, H <= 256, D <= 8, A <= 4, B <= 256 (-22 otherwise, before any
- * launch: the trainer stays on the layer path); CartPole-v1 (D = 4, A = 2) for the act step.
+ * launch: the trainer stays on the layer path); CartPole-v1 (D = 4, A = 2) for the act step, MountainCar-v0 and Acrobot-v1
+ * through gymrl_dsac_act_step_classic.
  */
 typedef struct {
   int N, D, A, H;
-  int env_kind;                            /* GYMRL_ENV_CARTPOLE */
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE; the _classic entry point: also GYMRL_ENV_MOUNTAINCAR | GYMRL_ENV_ACROBOT */
   void* env_state; uint64_t env_seed; int64_t env_id0;
   const float* obs; float* obs_out;        /* f32[N, D] in / next observations out (post-reset where an episode ended) */
   const float* noise_exp;                  /* f32[N, A] Exp(1) draws, or NULL: gymrl_categorical_sample's Philox keys */
@@ -1716,6 +1717,10 @@ size_t gymrl_dsac_update_workspace_bytes(int B, int D, int A, int H);
 int gymrl_dsac_pack_images(const gymrl_dsac_update_args* args, void* stream);
 size_t gymrl_dsac_args_bytes(int which);     /* sizeof(gymrl_dsac_act_args) (0) / sizeof(gymrl_dsac_update_args) (1) */
 int gymrl_dsac_act_step(const gymrl_dsac_act_args* args, void* stream);
+/* gymrl_dsac_act_step for the env kind args->env_kind names: GYMRL_ENV_CARTPOLE (D = 4, A = 2; the launch above), GYMRL_ENV_MOUNTAINCAR
+ * (D = 2, A = 3) or GYMRL_ENV_ACROBOT (D = 6, A = 3), the stepper's own arithmetic and auto-reset in the same launch.  -22 for every
+ * other kind, for a (D, A) that is not the kind's, and for what gymrl_dsac_act_step refuses. */
+int gymrl_dsac_act_step_classic(const gymrl_dsac_act_args* args, void* stream);
 int gymrl_dsac_update(const gymrl_dsac_update_args* args, void* stream);
 /* The softmax of csrc/softmax_device.hpp over the rows of z f32[B, A] (A <= 8) and its backward dz = p (g - sum g p): what
  * ops.softmax_rows runs in place of F.softmax (sac_cartpole.py:70-80) under Config.kernel_softmax. */
@@ -1929,11 +1934,12 @@ int gymrl_acrobot_net_eval(const gymrl_acrobot_net_eval_args* args, void* stream
  *               (:162-166; gymrl_adam_step's arithmetic); the loss sum in gymrl_dqn_td_loss's order (B <= 256: one block's)
  *   The target network is read only: the hard copy (:193-194) stays with the caller, as does rebuilding the images after it.
  * Results are the layer-by-layer path's bits (tests/test_dqn_fused_step_gpu.py).  Limits: H % 4 == 0, H <= 256, D <= 8, A <= 4,
- * B <= 256 (-22 otherwise, before any launch: the trainer stays on the layer path); CartPole-v1 (D = 4, A = 2) for the act step.
+ * B <= 256 (-22 otherwise, before any launch: the trainer stays on the layer path); CartPole-v1 (D = 4, A = 2) for the act step,
+ * MountainCar-v0 and Acrobot-v1 through gymrl_dqn_act_step_classic.
  */
 typedef struct {
   int N, D, A, H;
-  int env_kind;                            /* GYMRL_ENV_CARTPOLE */
+  int env_kind;                            /* GYMRL_ENV_CARTPOLE; the _classic entry point: also GYMRL_ENV_MOUNTAINCAR | GYMRL_ENV_ACROBOT */
   void* env_state; uint64_t env_seed; int64_t env_id0;
   const float* obs; float* obs_out;        /* f32[N, D] in / next observations out (post-reset where an episode ended) */
   const float* u;                          /* f32[N, 2] uniforms {explore?, which action}, or NULL: gymrl_epsilon_greedy's Philox keys */
@@ -1968,6 +1974,11 @@ size_t gymrl_dqn_update_workspace_bytes(int B, int D, int A, int H);
 int gymrl_dqn_pack_images(const gymrl_dqn_update_args* args, void* stream);
 size_t gymrl_dqn_args_bytes(int which);      /* sizeof(gymrl_dqn_act_args) (0) / sizeof(gymrl_dqn_update_args) (1) */
 int gymrl_dqn_act_step(const gymrl_dqn_act_args* args, void* stream);
+/* gymrl_dqn_act_step for the env kind args->env_kind names: GYMRL_ENV_CARTPOLE (D = 4, A = 2; the launch above), GYMRL_ENV_MOUNTAINCAR
+ * (D = 2, A = 3) or GYMRL_ENV_ACROBOT (D = 6, A = 3), the stepper's own arithmetic and auto-reset in the same launch; u stays
+ * f32[N, 2] (u0 against epsilon, u1 the exploring action min((int)(u1 * A), A - 1)).  -22 for every other kind, for a (D, A) that is not
+ * the kind's, and for what gymrl_dqn_act_step refuses.  gymrl_dqn_update and the non-dueling gymrl_ddqn_update take these shapes. */
+int gymrl_dqn_act_step_classic(const gymrl_dqn_act_args* args, void* stream);
 int gymrl_dqn_update(const gymrl_dqn_update_args* args, void* stream);
 
 /*

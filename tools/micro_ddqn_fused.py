@@ -10,7 +10,10 @@ captures the graphs; then `--runs` timed train(max_vector_steps=steps) calls, ea
 device synchronise; the figure is the MEDIAN run.  The variants of a shape alternate inside each of `--pairs` rounds, so that a
 drift of the machine falls on all of them.  Each trainer gets an episode_rewards deque of 99 entries, which the stop rule (it
 asks for 100) never accepts; every line carries its count of optimiser steps, which must equal the steps asked for.  A run
-with no GPU fails: there is no CPU figure.  Lines are appended to --out as JSON."""
+with no GPU fails: there is no CPU figure.  Lines are appended to --out as JSON.
+--env_name MountainCar-v0 | Acrobot-v1 times the same loops on those envs (the fused act launch is gymrl_dqn_act_step_classic /
+gymrl_dsac_act_step_classic there); every line then carries "env".  The default, CartPole-v1, prints the lines it always printed.
+The dueling variants are two-action kernels: they are left out on those envs."""
 import argparse
 import collections
 import json
@@ -22,12 +25,15 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = [(8192, 64, 256, 1024), (64, 64, 256, 2048), (1, 64, 256, 2048)]      # (N, B, hidden, timed steps)
+DEFAULT_ENV = "CartPole-v1"
+ENV = DEFAULT_ENV              # --env_name
 
 
 def _make(module, trainer, N, B, H, fused):
     import importlib
     mod = importlib.import_module("gymrl_amd." + module)
     cfg = mod.Config()
+    cfg.env_name = ENV
     cfg.num_envs, cfg.batch_size, cfg.hidden_dim, cfg.seed = N, B, H, 0
     cfg.max_episodes, cfg.use_graphs, cfg.fused_step = 10 ** 9, True, fused
     cfg.memory_capacity = max(cfg.memory_capacity, 4 * N)
@@ -46,13 +52,19 @@ VARIANTS = {"ddqn_layer_graphed": ("ddqn_per_cartpole", "DDQNPERTrainer", False)
 def main():
     import torch
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default=",".join(VARIANTS))
+    ap.add_argument("--variants", default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--pairs", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=48)
     ap.add_argument("--tag", default="this")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--env_name", default=DEFAULT_ENV)
     args = ap.parse_args()
+    global ENV
+    ENV = args.env_name
+    env_key = {} if ENV == DEFAULT_ENV else {"env": ENV}
+    if args.variants is None:
+        args.variants = ",".join(v for v in VARIANTS if ENV == DEFAULT_ENV or not v.startswith("duel_"))
     if not torch.cuda.is_available():
         raise SystemExit("micro_ddqn_fused: needs an MI355X; there is no CPU figure")
     box = f"1x {torch.cuda.get_device_name(0)}, torch {torch.__version__}"
@@ -79,7 +91,7 @@ def main():
                 chunk = getattr(tr, "_chunk", None)
                 lines.append(dict(what="vector_step", variant=name, tree=args.tag, N=N, B=B, H=H, steps=steps,
                                   ms_per_step=round(statistics.median(runs), 4), ms_per_step_runs=[round(r, 4) for r in runs],
-                                  chunk_graph=bool(chunk is not None and chunk.graph is not None), updates=done, box=box, pair=pair))
+                                  chunk_graph=bool(chunk is not None and chunk.graph is not None), updates=done, box=box, pair=pair, **env_key))
                 print(json.dumps(lines[-1]), flush=True)
         ms = {n: [ln["ms_per_step"] for ln in lines if ln.get("variant") == n and ln["N"] == N] for n in trainers}
         for net in ("ddqn", "duel"):
@@ -88,7 +100,7 @@ def main():
                 over = [round(a / b, 3) for a, b in zip(ms[f"{net}_fused"], ms.get("dqn_fused", []))]
                 lines.append(dict(what="comparison", net=net, tree=args.tag, N=N, B=B, H=H, layer_ms=ms[f"{net}_layer_graphed"],
                                   fused_ms=ms[f"{net}_fused"], dqn_fused_ms=ms.get("dqn_fused"), speedup_per_pair=sp,
-                                  fused_over_dqn_fused=over, fused_wins_every_pair=all(s > 1.0 for s in sp)))
+                                  fused_over_dqn_fused=over, fused_wins_every_pair=all(s > 1.0 for s in sp), **env_key))
                 print(json.dumps(lines[-1]), flush=True)
         del trainers
     if args.out:

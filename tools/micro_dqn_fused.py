@@ -10,7 +10,9 @@ Method: one trainer per variant; a warm-up train() call fills the ring, loads th
 is the MEDIAN run.  The variants of a shape alternate inside each of `--pairs` rounds, so that a drift of the machine falls on
 all of them.  DQN solves CartPole within the timed window, and train() would return where mean(last 100) >= 495: the
 tool gives each DQN trainer an episode_rewards deque of 99 entries, which the stop rule (it asks for 100) never accepts; every line
-carries its count of optimiser steps, which must equal the steps asked for.  A run with no GPU fails: there is no CPU figure.  Lines are appended to --out as JSON."""
+carries its count of optimiser steps, which must equal the steps asked for.  A run with no GPU fails: there is no CPU figure.  Lines are appended to --out as JSON.
+--env_name MountainCar-v0 | Acrobot-v1 times the same loops on those envs (the fused act launch is gymrl_dqn_act_step_classic /
+gymrl_dsac_act_step_classic there); every line then carries "env".  The default, CartPole-v1, prints the lines it always printed."""
 import argparse
 import collections
 import json
@@ -22,11 +24,14 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = [(8192, 64, 256, 2048), (1, 64, 256, 4096), (64, 64, 256, 4096)]      # (N, B, hidden, timed steps): the flagship width, the reference's N, a small vector
+DEFAULT_ENV = "CartPole-v1"
+ENV = DEFAULT_ENV              # --env_name
 
 
 def _dqn(N, B, H, fused):
     from gymrl_amd import dqn_cartpole
     cfg = dqn_cartpole.Config()
+    cfg.env_name = ENV
     cfg.num_envs, cfg.batch_size, cfg.hidden_dim, cfg.seed = N, B, H, 0
     cfg.max_episodes, cfg.use_graphs, cfg.fused_step = 10 ** 9, True, fused
     cfg.memory_capacity = max(cfg.memory_capacity, 4 * N)
@@ -38,6 +43,7 @@ def _dqn(N, B, H, fused):
 def _dsac(N, B, H, fused):
     from gymrl_amd import sac_cartpole
     cfg = sac_cartpole.Config()
+    cfg.env_name = ENV
     cfg.num_envs, cfg.batch_size, cfg.hidden_dim, cfg.seed = N, B, H, 0
     cfg.max_episodes, cfg.use_graphs, cfg.fused_step = 10 ** 9, True, fused
     cfg.memory_capacity = max(cfg.memory_capacity, 4 * N)
@@ -60,7 +66,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=48)
     ap.add_argument("--tag", default="this")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--env_name", default=DEFAULT_ENV)
     args = ap.parse_args()
+    global ENV
+    ENV = args.env_name
+    env_key = {} if ENV == DEFAULT_ENV else {"env": ENV}
     if not torch.cuda.is_available():
         raise SystemExit("micro_dqn_fused: needs an MI355X; there is no CPU figure")
     box = f"1x {torch.cuda.get_device_name(0)}, torch {torch.__version__}"
@@ -89,13 +99,13 @@ def main():
                 lines.append(dict(what="vector_step", variant=name, tree=args.tag, N=N, B=B, H=H, steps=steps,
                                   ms_per_step=round(statistics.median(runs), 4), ms_per_step_runs=[round(r, 4) for r in runs],
                                   chunk_graph=bool(chunk is not None and chunk.graph is not None),
-                                  updates=count() - before, box=box, pair=pair))
+                                  updates=count() - before, box=box, pair=pair, **env_key))
                 print(json.dumps(lines[-1]), flush=True)
         if "dqn_layer_graphed" in trainers and "dqn_fused" in trainers:
             ms = {n: [ln["ms_per_step"] for ln in lines if ln.get("variant") == n and ln["N"] == N] for n in trainers}
             sp = [round(a / b, 3) for a, b in zip(ms["dqn_layer_graphed"], ms["dqn_fused"])]
             lines.append(dict(what="comparison", tree=args.tag, N=N, B=B, H=H, layer_ms=ms["dqn_layer_graphed"], fused_ms=ms["dqn_fused"],
-                              dsac_fused_ms=ms.get("dsac_fused"), speedup_per_pair=sp, fused_wins_every_pair=all(s > 1.0 for s in sp)))
+                              dsac_fused_ms=ms.get("dsac_fused"), speedup_per_pair=sp, fused_wins_every_pair=all(s > 1.0 for s in sp), **env_key))
             print(json.dumps(lines[-1]), flush=True)
         del trainers
     if args.out:
