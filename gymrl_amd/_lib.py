@@ -112,6 +112,16 @@ class RolloutLunarArgs(C.Structure):
                 ("refill", C.c_int), ("gae_carry", C.c_int)]
 
 
+class RolloutPendulumArgs(C.Structure):
+    _c_name_ = "gymrl_rollout_pendulum_args"
+    _fields_ = [("env_state", C.c_void_p), ("n_envs", C.c_int), ("seed", C.c_uint64), ("env_id0", C.c_int64),
+                ("counter0", C.c_uint64), ("obs", C.c_void_p), ("act", C.c_void_p), ("logp", C.c_void_p),
+                ("val", C.c_void_p), ("rew", C.c_void_p), ("done", C.c_void_p), ("ep_ret", C.c_void_p),
+                ("next_value", C.c_void_p), ("log_std", C.c_void_p), ("noise_normal", C.c_void_p), ("reward_scale", C.c_float),
+                ("gae_running", C.c_void_p), ("gae_workspace", C.c_void_p), ("gamma", C.c_double), ("lam", C.c_double),
+                ("ep_stats", C.c_void_p), ("T", C.c_int), ("t0", C.c_int), ("nsteps", C.c_int)]
+
+
 class LunarEvalArgs(C.Structure):
     _c_name_ = "gymrl_lunar_eval_args"
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("stream_id0", C.c_int64),
@@ -124,6 +134,13 @@ class ClassicPpoEvalArgs(C.Structure):
     _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("env_kind", C.c_int), ("seed", C.c_uint64),
                 ("stream_id0", C.c_int64), ("policy_stride", C.c_int64), ("returns", C.c_void_p), ("lengths", C.c_void_p),
                 ("terminated", C.c_void_p), ("final_obs", C.c_void_p)]
+
+
+class PendulumPpoEvalArgs(C.Structure):
+    _c_name_ = "gymrl_pendulum_ppo_eval_args"
+    _fields_ = [("P", C.c_int), ("E", C.c_int), ("cap", C.c_int), ("seed", C.c_uint64), ("stream_id0", C.c_int64),
+                ("policy_stride", C.c_int64), ("returns", C.c_void_p), ("lengths", C.c_void_p), ("terminated", C.c_void_p),
+                ("final_obs", C.c_void_p)]
 
 
 class LunarCollectArgs(C.Structure):
@@ -473,6 +490,7 @@ SIGNATURES = {
     "gymrl_env_abandon": (_i, [_i, _vp, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_env_refill": (_i, [_i, _vp, _i, _u64, _i64, _vp]),
     "gymrl_categorical_sample": (_i, [_vp, _vp, _vp, _u64, _u64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _P(GaeOnline), _vp]),
+    "gymrl_gaussian_sample": (_i, [_vp, _vp, _vp, _vp, _u64, _u64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _P(GaeOnline), _vp]),
     "gymrl_gae_online_flush": (_i, [_P(GaeOnline), _vp, _i, _vp]),
     "gymrl_gae_chunk": (_i, []),
     "gymrl_gae_workspace_bytes": (_sz, [_i, _i]),
@@ -484,6 +502,8 @@ SIGNATURES = {
     "gymrl_moments": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "gymrl_normalize": (_i, [_vp, _i64, _vp, _i, _d, _vp]),
     "gymrl_ppo_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(PPOCfg), _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_ppo_gauss_loss_workspace_bytes": (_sz, [_i, _i]),
+    "gymrl_ppo_gauss_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(PPOCfg), _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "gymrl_loss_blocks": (_i, [_i]),
     "gymrl_reduce_rows": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "gymrl_ppo_full_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _P(PPOFullCfg), _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -520,6 +540,8 @@ SIGNATURES = {
     "gymrl_rollout_lunar": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_cartpole": (_i, [_P(RolloutLunarArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_classic": (_i, [_i, _P(RolloutLunarArgs), _P(MlpDesc), _vp]),
+    "gymrl_rollout_pendulum_args_bytes": (_sz, []),
+    "gymrl_rollout_pendulum": (_i, [_P(RolloutPendulumArgs), _P(MlpDesc), _vp]),
     "gymrl_rollout_lunar_mhc": (_i, [_P(RolloutLunarArgs), _P(MhcPolicy), _vp]),
     "gymrl_lunar_eval_args_bytes": (_sz, []),
     "gymrl_lunar_policy_eval": (_i, [_P(LunarEvalArgs), _P(MlpDesc), _vp]),
@@ -529,6 +551,8 @@ SIGNATURES = {
     "gymrl_lunar_collect_args_bytes": (_sz, []),
     "gymrl_classic_ppo_eval_args_bytes": (_sz, []),
     "gymrl_classic_ppo_eval": (_i, [_P(ClassicPpoEvalArgs), _P(MlpDesc), _vp]),
+    "gymrl_pendulum_ppo_eval_args_bytes": (_sz, []),
+    "gymrl_pendulum_ppo_eval": (_i, [_P(PendulumPpoEvalArgs), _P(MlpDesc), _vp]),
     "gymrl_lin_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gymrl_lin_fwd": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gymrl_lin_bwd_input": (_i, [_P(LinItem), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

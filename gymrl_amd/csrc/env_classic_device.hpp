@@ -340,7 +340,7 @@ __device__ __forceinline__ void acrobot_step_one(const AcrobotState& st, int i, 
 // What an env kind is to the kernels that STEP it inside a launch of their own — PPO's rollout and evaluation (classic_ppo_device.hpp)
 // and the DQN-family act kernels (slab_step_device.hpp: classic_act_tail): ClassicDims, the view of the env state buffer, ONE env's
 // step with auto-reset (gymrl_env_step's arithmetic, above), and the vector an observation row of PPO's slab is stored with — 16
-// bytes are one float4, 8 and 24 bytes are one and three float2.
+// bytes are one float4, 8 and 24 bytes are one and three float2, Pendulum-v1's 12 bytes are three floats.
 template <int KIND> struct ClassicEnv;
 template <> struct ClassicEnv<GYMRL_ENV_CARTPOLE> : ClassicDims<GYMRL_ENV_CARTPOLE> {
   using State = CartPoleState;
@@ -361,6 +361,15 @@ template <> struct ClassicEnv<GYMRL_ENV_ACROBOT> : ClassicDims<GYMRL_ENV_ACROBOT
   using ObsVec = float2;
   static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, int action, ClassicStep<6>& r) {
     acrobot_step_one(st, i, seed, env_id0, action, r);
+  }
+};
+// Pendulum-v1 (PPO's Gaussian rollout only): the action is the float torque, and a 12-byte observation row is three scalar stores —
+// row i starts 12 i bytes into the slab, so nothing wider than 4 bytes is aligned for every i.
+template <> struct ClassicEnv<GYMRL_ENV_PENDULUM> : ClassicDims<GYMRL_ENV_PENDULUM> {
+  using State = PendulumState;
+  using ObsVec = float;
+  static __device__ __forceinline__ void step(const State& st, int i, uint64_t seed, int64_t env_id0, float action, ClassicStep<3>& r) {
+    pendulum_step_one(st, i, seed, env_id0, action, r);
   }
 };
 

@@ -2,6 +2,8 @@
 //
 //   P2  gymrl_categorical_sample       ppo_lunarlander.py:92-104
 //   L1  gymrl_ppo_loss_fwd_bwd         ppo_lunarlander.py:110-117, 278-300, 309-322
+//   P2g gymrl_gaussian_sample          the diagonal-Gaussian head's draw (include/gymrl.h "Gaussian policy")
+//   L1g gymrl_ppo_gauss_loss_fwd_bwd   L1 under that head: gradients to mu, value and log_std
 //   L3  gymrl_ppo_full_loss_fwd_bwd    ppo_full_lunarlander.py:575-652
 //
 // One lane = one sample; the A (<= 8) logits of a sample live in registers, the
@@ -13,6 +15,7 @@
 // reproduce integer action draws exactly.
 #include "gymrl_device.hpp"
 #include "policy_device.hpp"
+#include "gauss_policy_device.hpp"
 #include "../../include/gymrl.h"
 
 using namespace gymrl;
@@ -74,6 +77,30 @@ __global__ __launch_bounds__(kBlock) void categorical_sample_kernel(
   if (value_out && value_in) value_out[i] = value_in[i];
 }
 
+// P2g: the Gaussian head's draw, one lane per row; the same optional producer side of GAE as above
+template <int A>
+__global__ __launch_bounds__(kBlock) void gaussian_sample_kernel(
+    const float* __restrict__ mu, const float* __restrict__ log_std, const float* __restrict__ value_in,
+    const float* __restrict__ noise_normal, uint64_t seed, uint64_t counter, int64_t env_id0, int n,
+    int deterministic, float* __restrict__ act_out, float* __restrict__ logp_out,
+    float* __restrict__ ent_out, float* __restrict__ value_out, OnlineGae og) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  if (og.rew_prev)
+    gae_online_compose(og.rew_prev[i], og.done_prev[i], og.val_prev[i], value_in[i], og.gamma, og.gl, og.first,
+                       og.last, og.running, og.agg_row, n, i);
+  float m[A], a[A], H, lp;
+#pragma unroll
+  for (int k = 0; k < A; ++k) m[k] = mu[(size_t)i * A + k];
+  gaussian_pick<A>(m, log_std, noise_normal ? noise_normal + (size_t)i * A : nullptr, seed, (uint64_t)(env_id0 + i), counter,
+                   deterministic, a, lp, H);
+#pragma unroll
+  for (int k = 0; k < A; ++k) act_out[(size_t)i * A + k] = a[k];
+  logp_out[i] = lp;
+  if (ent_out) ent_out[i] = H;
+  if (value_out && value_in) value_out[i] = value_in[i];
+}
+
 // ---------------------------------------------------------------- L1 loss ---
 template <int A>
 __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(
@@ -123,6 +150,101 @@ __global__ __launch_bounds__(kBlock) void ppo_loss_kernel(
     met[4] += (double)m_kl;
   }
   if (partials) block_partials<5, kBlock>(met, partials);
+}
+
+// ------------------------------------------------------- L1g: Gaussian loss ---
+// ppo_loss_kernel's scheme, one row per lane.  The metric sums go the way they go there (per-thread float64 over the grid-stride
+// loop, one partial row per workgroup).  The log_std gradient is a sum over the batch that TRAINING reads, so its order is fixed by
+// B alone, not by the grid: rows [256 j, 256 j + 256) form segment j, a workgroup walks whole segments, a segment's float64 sum
+// (lanes of a wave by shuffle, the four waves in order) lands in dls_parts[j][A], and gauss_dls_finalize_kernel adds the segments.
+template <int A>
+__global__ __launch_bounds__(kBlock) void ppo_gauss_loss_kernel(
+    const float* __restrict__ mu, const float* __restrict__ log_std, const float* __restrict__ value,
+    const int32_t* __restrict__ idx, const float* __restrict__ act, const float* __restrict__ logp_old,
+    const float* __restrict__ adv, const float* __restrict__ ret, const double* __restrict__ adv_moments, int B,
+    gymrl_ppo_cfg cfg, float* __restrict__ dmu_out, float* __restrict__ dvalue_out, double* __restrict__ dls_parts,
+    double* __restrict__ partials) {
+  double met[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  __shared__ double s_norm[2];
+  __shared__ double s_dls[A][kBlock / 64];
+  if (adv_moments && threadIdx.x == 0) {
+    const double cnt = adv_moments[0];
+    const double mean = adv_moments[1] / cnt;
+    double var = adv_moments[2] / cnt - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    s_norm[0] = mean; s_norm[1] = sqrt(var) + 1e-8;
+  }
+  __syncthreads();
+  float ls[A];
+#pragma unroll
+  for (int k = 0; k < A; ++k) ls[k] = log_std[k];
+  const int nseg = (B + kBlock - 1) / kBlock;
+  const float invB = 1.0f / (float)B;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int seg = blockIdx.x; seg < nseg; seg += gridDim.x) {        // (the same trip count for every thread of the workgroup)
+    const int b = seg * kBlock + threadIdx.x;
+    float dls[A];
+#pragma unroll
+    for (int k = 0; k < A; ++k) dls[k] = 0.0f;
+    if (b < B) {
+      float m[A], a[A], dm[A], dvo, m_obj, m_val, m_ent, m_clip, m_kl;
+      const int i = idx ? idx[b] : b;
+#pragma unroll
+      for (int k = 0; k < A; ++k) { m[k] = mu[(size_t)b * A + k]; a[k] = act[(size_t)i * A + k]; }
+      float ad = adv[i];
+      if (adv_moments) ad = (float)(((double)ad - s_norm[0]) / s_norm[1]);
+      ppo_gauss_loss_row<A>(m, ls, value[b], a, logp_old[i], ad, ret[i], invB, cfg, dm, dls, dvo, m_obj, m_val, m_ent, m_clip, m_kl);
+#pragma unroll
+      for (int k = 0; k < A; ++k) dmu_out[(size_t)b * A + k] = dm[k];
+      dvalue_out[b] = dvo;
+      met[0] += -(double)m_obj;
+      met[1] += (double)m_val;
+      met[2] += (double)m_ent;
+      met[3] += (double)m_clip;
+      met[4] += (double)m_kl;
+    }
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+      const double s = wave_sum((double)dls[k]);
+      if (lane == 0) s_dls[k][wid] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < A) {
+      double s = 0.0;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) s += s_dls[threadIdx.x][w];
+      dls_parts[(size_t)seg * A + threadIdx.x] = s;
+    }
+    __syncthreads();                                                // s_dls is free for the next segment
+  }
+  if (partials) block_partials<5, kBlock>(met, partials);
+}
+
+// dlog_std_out[k] = (float) sum_j dls_parts[j][k]: lane t adds segments t, t + 256, ... in ascending order, then the block's fixed tree
+template <int A>
+__global__ __launch_bounds__(kBlock) void gauss_dls_finalize_kernel(const double* __restrict__ dls_parts, int nseg,
+                                                                    float* __restrict__ dlog_std_out) {
+  __shared__ double sm[A][kBlock / 64];
+  double v[A];
+#pragma unroll
+  for (int k = 0; k < A; ++k) v[k] = 0.0;
+  for (int j = threadIdx.x; j < nseg; j += kBlock) {
+#pragma unroll
+    for (int k = 0; k < A; ++k) v[k] += dls_parts[(size_t)j * A + k];
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < A; ++k) {
+    const double s = wave_sum(v[k]);
+    if (lane == 0) sm[k][wid] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) s += sm[threadIdx.x][w];
+    dlog_std_out[threadIdx.x] = (float)s;
+  }
 }
 
 // ---------------------------------------------------------------- L3 loss ---
@@ -403,6 +525,19 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
     default: return -22;                  \
   }
 
+#define DISPATCH_GAUSS_A(A_, CALL)        \
+  switch (A_) {                           \
+    case 1: { constexpr int A = 1; CALL; } break; \
+    case 2: { constexpr int A = 2; CALL; } break; \
+    case 3: { constexpr int A = 3; CALL; } break; \
+    case 4: { constexpr int A = 4; CALL; } break; \
+    case 5: { constexpr int A = 5; CALL; } break; \
+    case 6: { constexpr int A = 6; CALL; } break; \
+    case 7: { constexpr int A = 7; CALL; } break; \
+    case 8: { constexpr int A = 8; CALL; } break; \
+    default: return -22;                  \
+  }
+
 extern "C" {
 
 int gymrl_categorical_sample(const float* logits, const float* value_in, const float* noise_exp,
@@ -441,6 +576,34 @@ int gymrl_categorical_sample(const float* logits, const float* value_in, const f
   return 0;
 }
 
+int gymrl_gaussian_sample(const float* mu, const float* log_std, const float* value_in, const float* noise_normal,
+                          uint64_t seed, uint64_t counter, int64_t env_id0, int n, int act_dim, int deterministic,
+                          float* act_out, float* logp_out, float* ent_out, float* value_out, const gymrl_gae_online* online,
+                          void* stream_) {
+  if (!mu || !log_std || !act_out || !logp_out || n < 0 || act_dim < 1 || act_dim > 8) return -22;
+  if (n == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  OnlineGae og{};
+  if (online) {
+    if (!value_in || !online->rew_prev || !online->done_prev || !online->val_prev || !online->running ||
+        !online->gae_workspace || online->t_prev < 0 || online->t_prev >= online->T || online->running2)
+      return -22;
+    const int tc = gymrl_gae_chunk();
+    og.rew_prev = online->rew_prev; og.done_prev = online->done_prev; og.val_prev = online->val_prev;
+    og.running = online->running;
+    og.agg_row = (double2*)online->gae_workspace + (size_t)(online->t_prev / tc) * n;
+    og.gamma = online->gamma; og.gl = (double)(float)(online->gamma * online->lam);
+    og.first = (online->t_prev % tc) == 0;
+    og.last = (online->t_prev % tc) == tc - 1 || online->t_prev == online->T - 1;
+  }
+  DISPATCH_GAUSS_A(act_dim,
+                   hipLaunchKernelGGL(gaussian_sample_kernel<A>, dim3(cdiv(n, kBlock)), dim3(kBlock), 0, stream, mu, log_std,
+                                      value_in, noise_normal, seed, counter, env_id0, n, deterministic, act_out, logp_out,
+                                      ent_out, value_out, og));
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
 int gymrl_ppo_loss_fwd_bwd(const float* logits, const float* value, const int32_t* idx,
                            const int32_t* act, const float* logp_old, const float* adv,
                            const float* ret, const double* adv_moments, int B, int n_actions,
@@ -461,6 +624,42 @@ int gymrl_ppo_loss_fwd_bwd(const float* logits, const float* value, const int32_
   if (metrics_sum)
     hipLaunchKernelGGL(metrics_finalize_kernel<5>, dim3(1), dim3(kBlock), 0, stream, parts, nb,
                        metrics_sum);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+size_t gymrl_ppo_gauss_loss_workspace_bytes(int B, int act_dim) {
+  if (B < 0 || act_dim < 1 || act_dim > 8) return 0;
+  return (size_t)(cdiv(B, kBlock) > 0 ? cdiv(B, kBlock) : 1) * (size_t)act_dim * sizeof(double);
+}
+
+int gymrl_ppo_gauss_loss_fwd_bwd(const float* mu, const float* log_std, const float* value, const int32_t* idx,
+                                 const float* act, const float* logp_old, const float* adv, const float* ret,
+                                 const double* adv_moments, int B, int act_dim, const gymrl_ppo_cfg* cfg_host, float* dmu_out,
+                                 float* dvalue_out, float* dlog_std_out, double* metrics_sum, void* workspace,
+                                 void* dls_workspace, int grid_blocks, void* stream_) {
+  if (!mu || !log_std || !value || !act || !logp_old || !adv || !ret || !cfg_host || !dmu_out || !dvalue_out ||
+      !dlog_std_out || !dls_workspace || B < 0 || act_dim < 1 || act_dim > 8 || grid_blocks < 0 || (metrics_sum && !workspace) ||
+      (reinterpret_cast<uintptr_t>(dls_workspace) & 7) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+    return -22;
+  if (B == 0) return 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  const gymrl_ppo_cfg cfg = *cfg_host;
+  const int nseg = cdiv(B, kBlock);
+  int nb = nseg < kMaxLossBlocks ? nseg : kMaxLossBlocks;       // == gymrl_loss_blocks(B): the rows of the metric partials
+  if (grid_blocks > 0 && grid_blocks < nb) {
+    if (workspace && !metrics_sum) return -22;                   // a narrower grid writes fewer metric rows than a caller's table has
+    nb = grid_blocks;
+  }
+  double* parts = (double*)workspace;
+  double* dls_parts = (double*)dls_workspace;
+  DISPATCH_GAUSS_A(act_dim,
+                   hipLaunchKernelGGL(ppo_gauss_loss_kernel<A>, dim3(nb), dim3(kBlock), 0, stream, mu, log_std, value, idx, act,
+                                      logp_old, adv, ret, adv_moments, B, cfg, dmu_out, dvalue_out, dls_parts, parts);
+                   hipLaunchKernelGGL(gauss_dls_finalize_kernel<A>, dim3(1), dim3(kBlock), 0, stream, dls_parts, nseg,
+                                      dlog_std_out));
+  if (metrics_sum)
+    hipLaunchKernelGGL(metrics_finalize_kernel<5>, dim3(1), dim3(kBlock), 0, stream, parts, nb, metrics_sum);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

@@ -13,8 +13,14 @@
 //
 // The kernel is ONE template over classic_ppo_device.hpp's ClassicEnv<KIND>: the observation width, the action count, the state
 // view, the step function and the vector an observation row is stored with are the env's, everything else is shared.
+//
+// Pendulum-v1 (gymrl_rollout_pendulum) is the fourth instance: its argument block is gymrl_rollout_pendulum_args, its action is
+// the env's float torque and its pick is gauss_policy_device.hpp's gaussian_pick<1> on the actor's mean, the
+// UNCLIPPED draw goes into the float action slab, and the stored reward is the env's times reward_scale (one float32 multiply).
+#include <type_traits>
 #include "classic_ppo_device.hpp"
 #include "policy_device.hpp"
+#include "gauss_policy_device.hpp"
 
 using namespace gymrl;
 namespace M = gymrl::mlp;
@@ -27,8 +33,8 @@ constexpr int kDynFloats = M::kBufs * M::kRows * M::kStride + M::kRows * M::kInS
 constexpr int kDynBytes = 96 * 1024; // > 80 KB: one workgroup per CU (as mlp_forward_kernel)
 static_assert(kDynFloats * 4 <= kDynBytes, "LDS carve-up");
 
-template <int KIND>
-__global__ __launch_bounds__(kThreads) void rollout_classic_kernel(gymrl_rollout_lunar_args a, gymrl_mlp_desc d) {
+template <int KIND, class Args>
+__global__ __launch_bounds__(kThreads) void rollout_classic_kernel(Args a, gymrl_mlp_desc d) {
   using Env = ClassicEnv<KIND>;
   using ObsVec = typename Env::ObsVec;
   constexpr int kObs = Env::kObs, kActions = Env::kActions;
@@ -78,16 +84,28 @@ __global__ __launch_bounds__(kThreads) void rollout_classic_kernel(gymrl_rollout
           float z[kActions], lp, H;
 #pragma unroll
           for (int k = 0; k < kActions; ++k) z[k] = head[row * M::kHeadStride + k];
-          const int act = categorical_pick<kActions>(z, a.noise_exp ? a.noise_exp + o * kActions : nullptr, a.seed,
-                                                     (uint64_t)(a.env_id0 + i), a.counter0 + (uint64_t)t, 0, lp, H);
-          a.act[o] = act; a.logp[o] = lp;
-          Env::step(st, i, a.seed, a.env_id0, act, r);
-          a.rew[o] = r.reward;
+          if constexpr (std::is_same<Args, gymrl_rollout_pendulum_args>::value) {   // N(mu, exp(log_std)): gymrl_gaussian_sample's bits
+            float act[kActions];
+            gaussian_pick<kActions>(z, a.log_std, a.noise_normal ? a.noise_normal + o * kActions : nullptr, a.seed,
+                                    (uint64_t)(a.env_id0 + i), a.counter0 + (uint64_t)t, 0, act, lp, H);
+            a.act[o] = act[0]; a.logp[o] = lp;
+            Env::step(st, i, a.seed, a.env_id0, act[0], r);
+            a.rew[o] = r.reward * a.reward_scale;
+          } else {                                                                  // Categorical(logits): gymrl_categorical_sample's
+            const int act = categorical_pick<kActions>(z, a.noise_exp ? a.noise_exp + o * kActions : nullptr, a.seed,
+                                                       (uint64_t)(a.env_id0 + i), a.counter0 + (uint64_t)t, 0, lp, H);
+            a.act[o] = act; a.logp[o] = lp;
+            Env::step(st, i, a.seed, a.env_id0, act, r);
+            a.rew[o] = r.reward;
+          }
           a.done[o] = r.done;
           if (a.ep_ret && r.done) a.ep_ret[o] = (float)r.ret;
           float* on = a.obs + ((size_t)(t + 1) * N + i) * kObs;
           if constexpr (kObsVecs == 1 && sizeof(ObsVec) == 16) {
             reinterpret_cast<float4*>(on)[0] = make_float4(r.o_next[0], r.o_next[1], r.o_next[2], r.o_next[3]);
+          } else if constexpr (sizeof(ObsVec) == 4) {
+#pragma unroll
+            for (int k = 0; k < kObsVecs; ++k) on[k] = r.o_next[k];
           } else {
 #pragma unroll
             for (int k = 0; k < kObsVecs; ++k) reinterpret_cast<float2*>(on)[k] = make_float2(r.o_next[2 * k], r.o_next[2 * k + 1]);
@@ -103,25 +121,29 @@ __global__ __launch_bounds__(kThreads) void rollout_classic_kernel(gymrl_rollout
 }
 
 // what every kind's entry refuses alike, before any launch: the slabs, the step window, the GAE pair, the row's alignment, the policy
-template <int KIND>
-bool rollout_args_ok(const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc* policy) {
+template <int KIND, class Args>
+bool rollout_args_ok(const Args* a, const gymrl_mlp_desc* policy) {
   using Env = ClassicEnv<KIND>;
   if (!a || !policy || !a->env_state || !a->obs || !a->act || !a->logp || !a->val || !a->rew || !a->done ||
       !a->next_value || a->n_envs <= 0 || a->T <= 0 || a->t0 < 0 || a->nsteps < 0 || a->t0 + a->nsteps > a->T)
     return false;
   if (a->gae_running && !a->gae_workspace) return false;
+  if constexpr (std::is_same<Args, gymrl_rollout_pendulum_args>::value) {
+    if (!a->log_std || !(a->reward_scale == a->reward_scale)) return false;
+    if ((reinterpret_cast<uintptr_t>(a->act) | reinterpret_cast<uintptr_t>(a->log_std) | reinterpret_cast<uintptr_t>(a->noise_normal)) & 3) return false;
+  }
   if (reinterpret_cast<uintptr_t>(a->obs) & (sizeof(typename Env::ObsVec) - 1)) return false;
   return ppo_desc_ok(policy, Env::kObs, Env::kActions);
 }
 
-template <int KIND>
-int rollout_launch(const gymrl_rollout_lunar_args* a, const gymrl_mlp_desc* policy, void* stream) {
+template <int KIND, class Args>
+int rollout_launch(const Args* a, const gymrl_mlp_desc* policy, void* stream) {
   if (!rollout_args_ok<KIND>(a, policy)) return -22;
   if (a->nsteps == 0 && a->t0 != a->T) return 0;
   static bool attr_set = false;
-  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_classic_kernel<KIND>}, kDynBytes)) return rc;
+  if (const int rc = set_max_lds_once(attr_set, {(const void*)rollout_classic_kernel<KIND, Args>}, kDynBytes)) return rc;
   const int blocks = (a->n_envs + M::kRows - 1) / M::kRows;
-  hipLaunchKernelGGL(rollout_classic_kernel<KIND>, dim3(blocks), dim3(kThreads), kDynBytes, (hipStream_t)stream, *a, *policy);
+  hipLaunchKernelGGL((rollout_classic_kernel<KIND, Args>), dim3(blocks), dim3(kThreads), kDynBytes, (hipStream_t)stream, *a, *policy);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
@@ -141,6 +163,12 @@ int gymrl_rollout_classic(int env_kind, const gymrl_rollout_lunar_args* a, const
     case GYMRL_ENV_ACROBOT: return rollout_launch<GYMRL_ENV_ACROBOT>(a, policy, stream);
     default: return -22;
   }
+}
+
+size_t gymrl_rollout_pendulum_args_bytes(void) { return sizeof(gymrl_rollout_pendulum_args); }
+
+int gymrl_rollout_pendulum(const gymrl_rollout_pendulum_args* a, const gymrl_mlp_desc* policy, void* stream) {
+  return rollout_launch<GYMRL_ENV_PENDULUM>(a, policy, stream);
 }
 
 }  // extern "C"

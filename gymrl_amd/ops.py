@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, ClassicPpoEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
-                   LunarCollectArgs, LunarEvalArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, AcrobotNetEvalArgs, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
+                   LunarCollectArgs, LunarEvalArgs, PendulumPpoEvalArgs, RolloutPendulumArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, AcrobotNetEvalArgs, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
                    Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
@@ -136,6 +136,52 @@ def categorical_sample(logits, value=None, noise_exp=None, seed=0, counter=0, en
     return act_out, logp_out, ent_out, value_out
 
 
+GAUSS_MAX_ACT = 8              # gymrl_gaussian_sample / gymrl_ppo_gauss_loss_fwd_bwd: 1 <= A <= 8
+
+
+def _need_dev(who, **tensors):
+    """The Gaussian entry points' wrappers: a CPU tensor is refused before any pointer is read."""
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"{who}: {name} is a CPU tensor; gymrl_amd ops run on the MI355X only (no CPU fallback)")
+
+
+def gaussian_sample_shape_ok(N, A):
+    """What gymrl_gaussian_sample takes: N >= 0 rows of 1..8 action components."""
+    return N >= 0 and 1 <= A <= GAUSS_MAX_ACT
+
+
+def gaussian_sample(mu, log_std, value=None, noise_normal=None, seed=0, counter=0, env_id0=0, deterministic=False, act_out=None,
+                    logp_out=None, ent_out=None, value_out=None, online=None):
+    """The Gaussian policy's draw (include/gymrl.h "Gaussian policy"): mu f32[N, A], log_std f32[A] -> (action f32[N, A], logp,
+    entropy, value_out).  noise_normal f32[N, A]: explicit N(0, 1) draws (parity mode)."""
+    if mu.dim() != 2 or not gaussian_sample_shape_ok(*mu.shape):
+        raise ValueError(f"gaussian_sample: mu is f32[N, A] with 1 <= A <= {GAUSS_MAX_ACT}, not {tuple(mu.shape)}")
+    n, A = mu.shape
+    if tuple(log_std.shape) != (A,):
+        raise ValueError(f"gaussian_sample: log_std is f32[A] = {(A,)}, not {tuple(log_std.shape)}")
+    for name, t, shape in (("value", value, (n,)), ("noise_normal", noise_normal, (n, A)), ("act_out", act_out, (n, A)),
+                           ("logp_out", logp_out, (n,)), ("ent_out", ent_out, (n,)), ("value_out", value_out, (n,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"gaussian_sample: {name} is {shape}, not {tuple(t.shape)}")
+    if online is not None and value is None:
+        raise ValueError("gaussian_sample: the online GAE composition needs the values")
+    _need_dev("gaussian_sample", mu=mu, log_std=log_std, value=value, noise_normal=noise_normal, act_out=act_out, logp_out=logp_out,
+              ent_out=ent_out, value_out=value_out)
+    dev = mu.device
+    act_out = torch.empty(n, A, dtype=torch.float32, device=dev) if act_out is None else act_out
+    logp_out = torch.empty(n, dtype=torch.float32, device=dev) if logp_out is None else logp_out
+    ent_out = torch.empty(n, dtype=torch.float32, device=dev) if ent_out is None else ent_out
+    if value is not None and value_out is None:
+        value_out = torch.empty(n, dtype=torch.float32, device=dev)
+    check(lib().gymrl_gaussian_sample(_ptr(mu, torch.float32), _ptr(log_std, torch.float32), _ptr(value, torch.float32, True),
+                                      _ptr(noise_normal, torch.float32, True), seed, counter, env_id0, n, A, int(deterministic),
+                                      _ptr(act_out, torch.float32), _ptr(logp_out, torch.float32), _ptr(ent_out, torch.float32, True),
+                                      _ptr(value_out, torch.float32, True), C.byref(online) if online is not None else None, _stream()),
+          "gymrl_gaussian_sample")
+    return act_out, logp_out, ent_out, value_out
+
+
 # --------------------------------------------------------------- PPO loss ---
 _ws_cache = {}
 
@@ -161,6 +207,64 @@ def ppo_loss_fwd_bwd(logits, value, act, logp_old, adv, ret, cfg, idx=None, adv_
                                        _ptr(adv_moments, torch.float64, True), B, A, C.byref(c), _ptr(dlogits_out), _ptr(dvalue_out),
                                        _ptr(metrics_sum, torch.float64, True), _ptr(workspace, None, True), _stream()), "gymrl_ppo_loss_fwd_bwd")
     return dlogits_out, dvalue_out
+
+
+def ppo_gauss_loss_shape_ok(B, A):
+    """What gymrl_ppo_gauss_loss_fwd_bwd takes: B >= 0 rows of 1..8 action components."""
+    return B >= 0 and 1 <= A <= GAUSS_MAX_ACT
+
+
+def ppo_gauss_loss_workspace(B, A, device):
+    """The float64 segment table of the log_std gradient, f64[ceil(B / 256), A] (gymrl_ppo_gauss_loss_workspace_bytes)."""
+    return torch.empty(max(int(lib().gymrl_ppo_gauss_loss_workspace_bytes(B, A)) // 8, 1), dtype=torch.float64, device=device)
+
+
+def ppo_gauss_loss_fwd_bwd(mu, log_std, value, act, logp_old, adv, ret, cfg, idx=None, adv_moments=None, dmu_out=None, dvalue_out=None,
+                           dlog_std_out=None, metrics_sum=None, workspace=None, dls_workspace=None, grid_blocks=0):
+    """L1 under the Gaussian policy (include/gymrl.h): mu f32[B, A], log_std f32[A], value f32[B]; act f32[M, A], logp_old / adv /
+    ret f32[M] read at idx[b] (or at b: M >= B) -> (dmu f32[B, A], dvalue f32[B], dlog_std f32[A]).  cfg = (clip_eps, dual_clip,
+    value_coef, entropy_coef).  grid_blocks: 0 = the default grid; dlog_std carries the same bits under every grid."""
+    if mu.dim() != 2 or not ppo_gauss_loss_shape_ok(*mu.shape):
+        raise ValueError(f"ppo_gauss_loss_fwd_bwd: mu is f32[B, A] with 1 <= A <= {GAUSS_MAX_ACT}, not {tuple(mu.shape)}")
+    B, A = mu.shape
+    if tuple(log_std.shape) != (A,) or tuple(value.shape) != (B,):
+        raise ValueError(f"ppo_gauss_loss_fwd_bwd: log_std is f32[{A}] and value f32[{B}], not {tuple(log_std.shape)} and {tuple(value.shape)}")
+    if act.dim() != 2 or act.shape[1] != A:
+        raise ValueError(f"ppo_gauss_loss_fwd_bwd: act is f32[M, {A}], not {tuple(act.shape)}")
+    M = act.shape[0]
+    for name, t in (("logp_old", logp_old), ("adv", adv), ("ret", ret)):
+        if tuple(t.shape) != (M,):
+            raise ValueError(f"ppo_gauss_loss_fwd_bwd: {name} is f32[M] = {(M,)}, not {tuple(t.shape)}")
+    if (idx is None and M < B) or (idx is not None and tuple(idx.shape) != (B,)):
+        raise ValueError("ppo_gauss_loss_fwd_bwd: idx is i32[B], and without it the stored rows are at least B")
+    for name, t, shape in (("adv_moments", adv_moments, (3,)), ("dmu_out", dmu_out, (B, A)), ("dvalue_out", dvalue_out, (B,)),
+                           ("dlog_std_out", dlog_std_out, (A,)), ("metrics_sum", metrics_sum, (5,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"ppo_gauss_loss_fwd_bwd: {name} is {shape}, not {tuple(t.shape)}")
+    if grid_blocks < 0 or (grid_blocks and workspace is not None and metrics_sum is None):
+        raise ValueError("ppo_gauss_loss_fwd_bwd: grid_blocks is >= 0, and 0 where `workspace` is the caller's table of metric partials")
+    if dls_workspace is not None and dls_workspace.numel() * dls_workspace.element_size() < int(lib().gymrl_ppo_gauss_loss_workspace_bytes(B, A)):
+        raise ValueError("ppo_gauss_loss_fwd_bwd: dls_workspace is smaller than gymrl_ppo_gauss_loss_workspace_bytes(B, A)")
+    _need_dev("ppo_gauss_loss_fwd_bwd", mu=mu, log_std=log_std, value=value, act=act, logp_old=logp_old, adv=adv, ret=ret, idx=idx,
+              adv_moments=adv_moments, dmu_out=dmu_out, dvalue_out=dvalue_out, dlog_std_out=dlog_std_out, metrics_sum=metrics_sum,
+              workspace=workspace, dls_workspace=dls_workspace)
+    dev = mu.device
+    dmu_out = torch.empty_like(mu) if dmu_out is None else dmu_out
+    dvalue_out = torch.empty(B, dtype=torch.float32, device=dev) if dvalue_out is None else dvalue_out
+    dlog_std_out = torch.empty(A, dtype=torch.float32, device=dev) if dlog_std_out is None else dlog_std_out
+    if metrics_sum is not None and workspace is None:
+        workspace = _reduce_ws(dev)
+    if dls_workspace is None:
+        dls_workspace = ppo_gauss_loss_workspace(B, A, dev)
+    c = PPOCfg(*cfg)
+    check(lib().gymrl_ppo_gauss_loss_fwd_bwd(_ptr(mu, torch.float32), _ptr(log_std, torch.float32), _ptr(value, torch.float32),
+                                             _ptr(idx, torch.int32, True), _ptr(act, torch.float32), _ptr(logp_old, torch.float32),
+                                             _ptr(adv, torch.float32), _ptr(ret, torch.float32), _ptr(adv_moments, torch.float64, True), B, A,
+                                             C.byref(c), _ptr(dmu_out, torch.float32), _ptr(dvalue_out, torch.float32),
+                                             _ptr(dlog_std_out, torch.float32), _ptr(metrics_sum, torch.float64, True),
+                                             _ptr(workspace, None, True), _ptr(dls_workspace), int(grid_blocks), _stream()),
+          "gymrl_ppo_gauss_loss_fwd_bwd")
+    return dmu_out, dvalue_out, dlog_std_out
 
 
 def ppo_full_loss_fwd_bwd(logits, value, act, logp_old, ent_old, adv, ret, cfg, idx=None, dlogits_out=None,
@@ -1072,6 +1176,43 @@ def classic_ppo_eval(kind, policy, n_episodes, seed, stream_id0, cap=None, want_
     return returns, lengths, terminated, final
 
 
+PENDULUM_MAX_STEPS = EPISODE_ENVS[PENDULUM][4]
+
+
+def pendulum_ppo_eval_shape_ok(P, n_episodes, cap):
+    """What gymrl_pendulum_ppo_eval takes: P >= 1 policies x E >= 1 episodes with P * E below 2^31, 1 <= cap <= 200."""
+    return P >= 1 and n_episodes >= 1 and P * n_episodes <= 0x7FFFFFFF and 1 <= cap <= PENDULUM_MAX_STEPS
+
+
+def pendulum_ppo_eval(policy, n_episodes, seed, stream_id0, cap=None, want_final_obs=False, device=None):
+    """n_episodes whole Pendulum-v1 episodes per policy under the Gaussian actor-critic's mean (a = mu), in ONE launch
+    (include/gymrl.h gymrl_pendulum_ppo_eval) -> (returns f64, lengths i32, terminated u8, final_obs f32[..., 3] | None), each
+    [P, n_episodes].  policy: a nn.FusedMLP (mean [1] then value [1]; P = 1) or a LunarPolicyStack of such networks."""
+    if isinstance(policy, LunarPolicyStack):
+        P, stride, desc, dev = policy.P, policy.stride, policy.desc, policy.buffer.device
+    else:
+        dev = torch.device(device) if device is not None else policy.stages[0][0].weight.device
+        P, stride = 1, 0
+    n_episodes, cap = int(n_episodes), PENDULUM_MAX_STEPS if cap is None else int(cap)
+    if not pendulum_ppo_eval_shape_ok(P, n_episodes, cap) or stream_id0 < 0:
+        raise ValueError(f"pendulum_ppo_eval: P >= 1, episodes >= 1, 1 <= cap <= {PENDULUM_MAX_STEPS}, stream_id0 >= 0: got "
+                         f"{(P, n_episodes, cap, stream_id0)}")
+    if dev.type != "cuda":
+        raise RuntimeError("pendulum_ppo_eval: the policy lives on the CPU; gymrl_amd ops run on the MI355X only (no CPU fallback)")
+    if not isinstance(policy, LunarPolicyStack):
+        desc = policy.descriptor(16, dev)
+    returns = torch.empty(P, n_episodes, dtype=torch.float64, device=dev)
+    lengths = torch.empty(P, n_episodes, dtype=torch.int32, device=dev)
+    terminated = torch.empty(P, n_episodes, dtype=torch.uint8, device=dev)
+    final = torch.empty(P, n_episodes, 3, dtype=torch.float32, device=dev) if want_final_obs else None
+    a = PendulumPpoEvalArgs()
+    a.P, a.E, a.cap, a.seed, a.stream_id0, a.policy_stride = P, n_episodes, cap, seed, stream_id0, stride
+    a.returns, a.lengths, a.terminated = _ptr(returns), _ptr(lengths), _ptr(terminated)
+    a.final_obs = _ptr(final, torch.float32, True)
+    check(lib().gymrl_pendulum_ppo_eval(C.byref(a), C.byref(desc), _stream()), "gymrl_pendulum_ppo_eval")
+    return returns, lengths, terminated, final
+
+
 def lunar_mhc_eval(policy_desc, n_episodes, seed, stream_id0, cap=LUNAR_MAX_STEPS, want_terminal_obs=True, device=None):
     """lunar_policy_eval for PPO-full's mHC network: policy_desc is a filled _lib.MhcPolicy (its `image` as the caller left it:
     None reads the parameters in place), one policy."""
@@ -1814,6 +1955,49 @@ def rollout_classic(kind, env_state, n_envs, seed, env_id0, counter0, obs, act, 
     a = _rollout_classic_args("rollout_classic", kind, env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done,
                               ep_ret, next_value, T, t0, nsteps, gamma, lam, noise_exp, gae_running, gae_workspace, ep_stats)
     check(lib().gymrl_rollout_classic(kind, C.byref(a), C.byref(policy_desc), _stream()), "gymrl_rollout_classic")
+
+
+def rollout_pendulum_shape_ok(n_envs, T, t0, nsteps):
+    """What gymrl_rollout_pendulum takes: N >= 1 envs, T >= 1 and a step window inside [0, T]."""
+    return n_envs >= 1 and T >= 1 and t0 >= 0 and nsteps >= 0 and t0 + nsteps <= T
+
+
+def rollout_pendulum(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, policy_desc,
+                     log_std, T, t0, nsteps, gamma, lam, reward_scale=1.0, noise_normal=None, gae_running=None, gae_workspace=None,
+                     ep_stats=None):
+    """gymrl_rollout_pendulum: the persistent rollout for PPO on Pendulum-v1 under the Gaussian policy (obs [T+1, N, 3], act
+    f32[T, N] the unclipped draw, log_std f32[1], noise_normal f32[T, N, 1]); rew holds reward * reward_scale."""
+    what = "rollout_pendulum"
+    if not rollout_pendulum_shape_ok(n_envs, T, t0, nsteps):
+        raise ValueError(f"{what}: N >= 1, T >= 1 and 0 <= t0 <= t0 + nsteps <= T, got {(n_envs, T, t0, nsteps)}")
+    if tuple(obs.shape) != (T + 1, n_envs, 3):
+        raise ValueError(f"{what}: obs is f32[T + 1, N, 3] = {(T + 1, n_envs, 3)}, not {tuple(obs.shape)}")
+    for name, t in (("act", act), ("logp", logp), ("val", val), ("rew", rew), ("done", done), ("ep_ret", ep_ret)):
+        if t is not None and tuple(t.shape) != (T, n_envs):
+            raise ValueError(f"{what}: {name} is [T, N] = {(T, n_envs)}, not {tuple(t.shape)}")
+    if next_value.numel() != n_envs:
+        raise ValueError(f"{what}: next_value is f32[N] = {n_envs}, not {tuple(next_value.shape)}")
+    if tuple(log_std.shape) != (1,):
+        raise ValueError(f"{what}: log_std is f32[1], not {tuple(log_std.shape)}")
+    if noise_normal is not None and tuple(noise_normal.shape) != (T, n_envs, 1):
+        raise ValueError(f"{what}: noise_normal is f32[T, N, 1] = {(T, n_envs, 1)}, not {tuple(noise_normal.shape)}")
+    if gae_running is not None and (tuple(gae_running.shape) != (2, n_envs) or gae_workspace is None):
+        raise ValueError(f"{what}: gae_running is f64[2, N] = {(2, n_envs)} and comes with gae_workspace")
+    _need_dev(what, env_state=env_state, obs=obs, act=act, logp=logp, val=val, rew=rew, done=done, ep_ret=ep_ret, next_value=next_value,
+              log_std=log_std, noise_normal=noise_normal, gae_running=gae_running, gae_workspace=gae_workspace, ep_stats=ep_stats)
+    if env_state.numel() * env_state.element_size() < int(lib().gymrl_env_state_bytes(PENDULUM, n_envs)):
+        raise ValueError(f"{what}: env_state is smaller than gymrl_env_state_bytes({PENDULUM}, {n_envs})")
+    a = RolloutPendulumArgs()
+    a.env_state, a.n_envs, a.seed, a.env_id0, a.counter0 = _ptr(env_state).value, n_envs, seed, env_id0, counter0
+    a.obs, a.act, a.logp = _ptr(obs, torch.float32).value, _ptr(act, torch.float32).value, _ptr(logp, torch.float32).value
+    a.val, a.rew, a.done = _ptr(val, torch.float32).value, _ptr(rew, torch.float32).value, _ptr(done, torch.uint8).value
+    a.ep_ret, a.next_value = _ptr(ep_ret, torch.float32, True).value, _ptr(next_value, torch.float32).value
+    a.log_std, a.noise_normal = _ptr(log_std, torch.float32).value, _ptr(noise_normal, torch.float32, True).value
+    a.reward_scale = float(reward_scale)
+    a.gae_running, a.gae_workspace = _ptr(gae_running, torch.float64, True).value, _ptr(gae_workspace, None, True).value
+    a.gamma, a.lam, a.ep_stats = gamma, lam, _ptr(ep_stats, torch.float64, True).value
+    a.T, a.t0, a.nsteps = T, t0, nsteps
+    check(lib().gymrl_rollout_pendulum(C.byref(a), C.byref(policy_desc), _stream()), "gymrl_rollout_pendulum")
 
 
 def rollout_lunar_mhc(env_state, n_envs, seed, env_id0, counter0, obs, act, logp, val, rew, done, ep_ret, next_value, policy_desc,

@@ -240,13 +240,13 @@ class PPOTrainer:
         self.env = VecEnv(config.env_name, N, device=self.device, seed=self.base_seed, env_id0=self.rank * N)
 
         state_dim = self.env.observation_space.shape[0]
-        action_dim = self.env.action_space.n
+        action_dim = self._action_dim()
         self.action_dim = action_dim
 
         # identical initial parameters on every rank: CPU init under a fixed torch seed
         gen_state = torch.random.get_rng_state()
         torch.manual_seed(self.base_seed)
-        self.model = ActorCritic(state_dim, action_dim, config.hidden_dim)
+        self.model = self._build_model(state_dim, action_dim)
         torch.random.set_rng_state(gen_state)
         self.flat_params, self.flat_grads = flatten_module(self.model, self.device, order=ppo_net.LAYOUT)
         self._fused_update = None      # built on first update() when cfg.fused_update and the shape allows it
@@ -255,7 +255,7 @@ class PPOTrainer:
                                    max_grad_norm=config.max_grad_norm)
 
         T = int(config.update_freq)
-        self.buffer = RolloutBuffer(T, N, state_dim, self.device)
+        self.buffer = self._build_buffer(T, N, state_dim)
         self.step_count = 0
         self.rollout_count = 0
         self.episode_rewards = deque(maxlen=100)
@@ -285,6 +285,48 @@ class PPOTrainer:
             print(f"Device: {self.device} x{self.world_size} | envs/GPU: {N} | rollout T: {T}")
             print(f"State dim: {state_dim}, Action dim: {action_dim}")
             print(f"Model parameters: {sum(p.numel() for p in self.model.parameters()):,}")
+
+    # ---- what a policy head other than the categorical one replaces (ppo_pendulum.PPOTrainer: the Gaussian head) ----
+    def _action_dim(self):
+        return self.env.action_space.n
+
+    def _build_model(self, state_dim, action_dim):
+        return ActorCritic(state_dim, action_dim, self.cfg.hidden_dim)
+
+    def _build_buffer(self, T, N, state_dim):
+        return RolloutBuffer(T, N, state_dim, self.device)
+
+    def _sample_step(self, t, head, value, noise, counter0, online):
+        """One vector step's draw of the step-by-step rollout: the actor's output `head` -> rows t of the action, log-probability and
+        value slabs (and the online GAE composition of step t - 1)."""
+        b, env = self.buffer, self.env
+        ops.categorical_sample(head, value=value.view(-1), noise_exp=None if noise is None else noise[t],
+                               seed=env.seed, counter=counter0 + t,
+                               env_id0=env.env_id0, act_out=b.actions[t], logp_out=b.log_probs[t],
+                               ent_out=None, value_out=b.values[t], online=online)
+
+    def _stored_step(self, t):
+        """After env.step() filled rows t of the reward / done slabs (the Gaussian trainer scales the stored reward here)."""
+
+    def _packed_actions(self):
+        """The action slab as gymrl_pack_rollout's i32[T * N] (a float action travels through the records as its bits)."""
+        return self.buffer.actions.view(-1)
+
+    def _loss_backward(self, mb_obs, mb_act, mb_lp, mb_adv, mb_ret, row, tm):
+        """The autograd update of one minibatch: torch's layers forward, the loss kernel's gradients to the heads, backward."""
+        B = mb_obs.shape[0]
+        logits, values = self.model(mb_obs)
+        values = values.view(-1)
+        dlogits = torch.empty_like(logits)
+        dvalues = torch.empty_like(values)
+        if tm is not None:
+            tm.start("ppo_loss_fwd_bwd")
+        ops.ppo_loss_fwd_bwd(logits, values, mb_act, mb_lp, mb_adv, mb_ret, self._loss_cfg,
+                             adv_moments=self._moments, dlogits_out=dlogits, dvalue_out=dvalues,
+                             workspace=self._metric_parts[row])
+        if tm is not None:
+            tm.stop("ppo_loss_fwd_bwd", B)
+        torch.autograd.backward([logits, values], [dlogits, dvalues])
 
     # ------------------------------------------------------------------ GAE --
     def compute_gae(self, next_value=None):
@@ -357,12 +399,10 @@ class PPOTrainer:
             # while sampling step t, fold step t-1 (whose delta needs V_t) into its GAE chunk map
             online = (ops.gae_online(b.rewards[t - 1], b.dones[t - 1], b.values[t - 1], self._gae_running,
                                      self._gae_ws, t - 1, b.T, cfg.gamma, cfg.gae_lambda) if fuse_gae and t > 0 else None)
-            ops.categorical_sample(logits, value=value.view(-1), noise_exp=None if noise is None else noise[t],
-                                   seed=env.seed, counter=counter0 + t,
-                                   env_id0=env.env_id0, act_out=b.actions[t], logp_out=b.log_probs[t],
-                                   ent_out=None, value_out=b.values[t], online=online)
+            self._sample_step(t, logits, value, noise, counter0, online)
             env.step(b.actions[t], b.states[t + 1], b.rewards[t], done_out=b.dones[t],
                      ep_ret_out=b.ep_returns[t])
+            self._stored_step(t)
             if tm is not None and t % 64 == 0:
                 tm.stop("env_step+sample", b.N)
         b.pos = b.T
@@ -464,7 +504,7 @@ class PPOTrainer:
         obs_dim = b.states.shape[-1]
         tm = self._timers
         # P6: one 64-B record per transition so that a shuffled minibatch is one random line per sample
-        self._packed = ops.pack_rollout(b.states[:b.T].reshape(total, obs_dim), b.actions.view(-1),
+        self._packed = ops.pack_rollout(b.states[:b.T].reshape(total, obs_dim), self._packed_actions(),
                                         b.log_probs.view(-1), b.advantages.view(-1), b.returns.view(-1),
                                         self._packed)
         fu = None
@@ -558,18 +598,7 @@ class PPOTrainer:
                 fu.step(mb_obs, mb_act, mb_lp, mb_adv, mb_ret, self._loss_cfg, self._moments, self._metric_parts[row],
                         reducer=red)
             else:                                     # shapes ppo_net does not cover (or cfg.fused_update = False): autograd
-                logits, values = self.model(mb_obs)
-                values = values.view(-1)
-                dlogits = torch.empty_like(logits)
-                dvalues = torch.empty_like(values)
-                if tm is not None:
-                    tm.start("ppo_loss_fwd_bwd")
-                ops.ppo_loss_fwd_bwd(logits, values, mb_act, mb_lp, mb_adv, mb_ret, self._loss_cfg,
-                                     adv_moments=self._moments, dlogits_out=dlogits, dvalue_out=dvalues,
-                                     workspace=self._metric_parts[row])
-                if tm is not None:
-                    tm.stop("ppo_loss_fwd_bwd", B)
-                torch.autograd.backward([logits, values], [dlogits, dvalues])
+                self._loss_backward(mb_obs, mb_act, mb_lp, mb_adv, mb_ret, row, tm)
                 if red is not None:
                     red.launch(0)
             # the next minibatch's rows do not depend on the parameters: gathered while the last bucket is in flight

@@ -1,0 +1,164 @@
+"""PPO with a diagonal-Gaussian policy on Pendulum-v1 — the continuous-action sibling of ppo_lunarlander.PPOTrainer.
+
+The reference tree has no continuous-action PPO script; the policy rule is this project's own and is written out in
+include/gymrl.h ("Gaussian policy"): the actor's last layer is the mean (not squashed), `log_std` is a state-independent
+parameter, the UNCLIPPED draw is stored and the env clips the torque it applies.  Everything else is ppo_lunarlander's: the
+buffers, GAE, the epoch shuffle, clip-norm + Adam on one flat buffer, checkpoints, the train() loop.
+
+What runs where:
+  * rollout   one launch per chunk (gymrl_rollout_pendulum; Config.persistent_rollout), or the three-launch step loop
+              gymrl_mlp_forward -> gymrl_gaussian_sample -> gymrl_env_step; both write the same bits
+  * update    the two MLPs through torch autograd; gymrl_ppo_gauss_loss_fwd_bwd supplies d(loss) / d(mean, value, log_std)
+              (the fused update of ppo_net covers the categorical head only)
+  * eval      whole deterministic episodes (a = mean) in one launch (gymrl_pendulum_ppo_eval; Config.fused_eval), or the loop
+"""
+import torch
+import torch.nn as nn
+
+from . import ops
+from . import ppo_lunarlander as base
+from .envs import VecEnv
+
+
+class Config(base.Config):
+    def __init__(self):
+        super().__init__()
+        self.env_name = "Pendulum-v1"
+        self.max_train_steps = 2_000_000
+        self.num_envs = 64
+        self.update_freq = 200           # steps per env per rollout: every rollout starts with a reset (as the reference's PPO loop
+                                         # does), so a rollout is one whole 200-step episode per env
+        self.num_epochs = 10
+        self.num_minibatches = 8
+        self.gamma = 0.95
+        self.gae_lambda = 0.95
+        self.entropy_coef = 0.0
+        self.lr = 1e-3
+        self.hidden_dim = 64
+        self.log_std_init = 0.0          # log_std's initial value (std 1)
+        self.reward_scale = 0.1          # the STORED reward is the env's times this (one float32 multiply, in the rollout kernel
+                                         # and in the step loop alike); episode returns and evaluation stay unscaled
+        self.fused_eval = True           # eval() as one launch (gymrl_pendulum_ppo_eval); the loop acts on the same forward
+        self.solved_reward = -200.0
+
+
+class GaussianActorCritic(base.ActorCritic):
+    """ppo_lunarlander.ActorCritic whose actor head is the Gaussian's mean, plus the state-independent log_std."""
+
+    def __init__(self, state_dim, action_dim, hidden_dim=64, log_std_init=0.0):
+        super().__init__(state_dim, action_dim, hidden_dim)
+        self.log_std = nn.Parameter(torch.full((action_dim,), float(log_std_init)))
+
+    @torch.no_grad()
+    def get_action(self, state, deterministic=False, seed=0, counter=0, env_id0=0, noise_normal=None):
+        """state [N, obs] -> (action f32[N, A], logp[N], value[N]) on act_forward's mean: the forward the rollout and the
+        one-launch evaluation act on, so that a deterministic episode is the same bits on either path."""
+        mu, value = self.act_forward(state)
+        act, logp, _, val = ops.gaussian_sample(mu, self.log_std.detach(), value=value.view(-1), noise_normal=noise_normal, seed=seed,
+                                                counter=counter, env_id0=env_id0, deterministic=deterministic)
+        return act, logp, val
+
+
+class RolloutBuffer(base.RolloutBuffer):
+    """The slab with a float action row per step (one torque per env)."""
+
+    def __init__(self, T, N, obs_dim, device):
+        super().__init__(T, N, obs_dim, device)
+        self.actions = torch.zeros(T, N, dtype=torch.float32, device=device)
+
+
+class PPOTrainer(base.PPOTrainer):
+    _EVAL_KINDS = {ops.PENDULUM: 1}
+
+    def __init__(self, config):
+        if ops.ENV_KINDS.get(config.env_name) != ops.PENDULUM:
+            raise ValueError("ppo_pendulum.PPOTrainer runs Pendulum-v1 (the discrete envs are ppo_lunarlander.PPOTrainer's)")
+        super().__init__(config)
+        if not self._persistent_ok() and self.buffer.N % 4:
+            raise ValueError("ppo_pendulum.PPOTrainer: the step loop needs num_envs % 4 == 0 (gymrl_env_step stores an observation row of "
+                             "the slab on 16 bytes, and a row of N envs is 12 N bytes); the one-launch rollout takes any num_envs")
+        self._reward_scale = torch.tensor(float(config.reward_scale), dtype=torch.float32, device=self.device)
+        self._reward_scale_host = float(self._reward_scale)         # the float32 value, read back once
+        self._dlog_std = self.model.log_std.grad                    # a view of the flat gradient: the loss kernel writes it
+        self._dls_ws = None                                         # (_parity_noise: f32[rollouts, T, N, 1] N(0, 1) draws here)
+
+    # ------------------------------------------------------------ the head --
+    def _action_dim(self):
+        return self.env.action_space.shape[0]
+
+    def _build_model(self, state_dim, action_dim):
+        return GaussianActorCritic(state_dim, action_dim, self.cfg.hidden_dim, self.cfg.log_std_init)
+
+    def _build_buffer(self, T, N, state_dim):
+        return RolloutBuffer(T, N, state_dim, self.device)
+
+    def _sample_step(self, t, head, value, noise, counter0, online):
+        b, env = self.buffer, self.env
+        ops.gaussian_sample(head, self.model.log_std.detach(), value=value.view(-1), noise_normal=None if noise is None else noise[t],
+                            seed=env.seed, counter=counter0 + t, env_id0=env.env_id0, act_out=b.actions[t].view(-1, 1),
+                            logp_out=b.log_probs[t], value_out=b.values[t], online=online)
+
+    def _stored_step(self, t):
+        r = self.buffer.rewards[t]
+        torch.mul(r, self._reward_scale, out=r)                     # float32 x float32, as the rollout kernel multiplies
+
+    def _packed_actions(self):
+        return self.buffer.actions.view(torch.int32).view(-1)
+
+    def _loss_backward(self, mb_obs, mb_act, mb_lp, mb_adv, mb_ret, row, tm):
+        B = mb_obs.shape[0]
+        mu, values = self.model(mb_obs)
+        values = values.view(-1)
+        dmu, dvalues = torch.empty_like(mu), torch.empty_like(values)
+        if self._dls_ws is None or self._dls_ws.numel() * 8 < ops.lib().gymrl_ppo_gauss_loss_workspace_bytes(B, 1):
+            self._dls_ws = ops.ppo_gauss_loss_workspace(B, 1, self.device)
+        if tm is not None:
+            tm.start("ppo_gauss_loss_fwd_bwd")
+        ops.ppo_gauss_loss_fwd_bwd(mu, self.model.log_std.detach(), values, mb_act.view(torch.float32).view(-1, 1), mb_lp, mb_adv,
+                                   mb_ret, self._loss_cfg, adv_moments=self._moments, dmu_out=dmu, dvalue_out=dvalues,
+                                   dlog_std_out=self._dlog_std, workspace=self._metric_parts[row], dls_workspace=self._dls_ws)
+        if tm is not None:
+            tm.stop("ppo_gauss_loss_fwd_bwd", B)
+        torch.autograd.backward([mu, values], [dmu, dvalues])       # (log_std is not on the graph: its gradient is already in place)
+
+    # ------------------------------------------------------------- rollout --
+    def _persistent_ok(self):
+        cfg, env = self.cfg, self.env
+        return (cfg.persistent_rollout and cfg.fused_policy_forward and isinstance(env, VecEnv) and env.kind == ops.PENDULUM
+                and self.action_dim == 1 and bool(self.model._act_net()))
+
+    def _collect_rollout_persistent(self, counter0, noise, fuse_gae):
+        cfg, b, env = self.cfg, self.buffer, self.env
+        net = self.model._act_net()
+        net.refresh()
+        desc = net.descriptor(b.N, self.device)
+        tm = self._timers
+        chunk = int(cfg.rollout_chunk) if int(cfg.rollout_chunk) > 0 else b.T
+        for t0 in range(0, b.T, chunk):
+            n = min(chunk, b.T - t0)
+            if tm is not None:
+                tm.start("rollout_chunk")
+            ops.rollout_pendulum(env.state, b.N, env.seed, env.env_id0, counter0, b.states, b.actions, b.log_probs, b.values, b.rewards,
+                                 b.dones, b.ep_returns, self._next_value, desc, self.model.log_std.detach(), b.T, t0, n, cfg.gamma,
+                                 cfg.gae_lambda, reward_scale=self._reward_scale_host, noise_normal=noise,
+                                 gae_running=self._gae_running if fuse_gae else None, gae_workspace=self._gae_ws if fuse_gae else None,
+                                 ep_stats=env.ep_stats)
+            if tm is not None:
+                tm.stop("rollout_chunk", n * b.N)
+        b.pos = b.T
+        self.step_count += b.T * b.N
+        self.rollout_count += 1
+        self._agg_ready = bool(fuse_gae)
+        self._carry_ready = False
+        self._finished = True
+        return self._next_value
+
+    # ---------------------------------------------------------------- eval --
+    def _eval_launch(self, policy, num_episodes, stream_offset=0):
+        return ops.pendulum_ppo_eval(policy, num_episodes, self.base_seed + self.EVAL_SEED_OFFSET, self.EVAL_ENV_ID0 + stream_offset,
+                                     device=self.device)
+
+
+if __name__ == "__main__":       # python -m gymrl_amd.ppo_pendulum [--<Config attribute> <value> ...]
+    from .utils.cli import run_script
+    run_script(Config, PPOTrainer)

@@ -178,6 +178,36 @@ int gymrl_categorical_sample(const float* logits, const float* value_in,
                              int64_t env_id0, int n, int n_actions, int deterministic,
                              int32_t* act_out, float* logp_out, float* ent_out,
                              float* value_out, const gymrl_gae_online* online, void* stream);
+/*
+ * Gaussian policy — the diagonal-Gaussian head PPO uses on a continuous action (gymrl_amd/ppo_pendulum.py).  The reference tree
+ * has no continuous-action PPO script: this rule is the project's own, restated on the host in tests/gauss_policy_ref.py
+ * (float32 throughout, no contraction into fma, the grouping as written, every sum over k ascending from 0.0f).
+ *   network   ActorCritic(state_dim, A): the actor's last layer is the mean mu[A], not squashed; log_std f32[A] is a
+ *             state-independent parameter vector in device memory; the critic is the categorical head's.
+ *   draw      eps_k ~ N(0, 1): Philox4x32-10 keyed as gymrl_categorical_sample keys its words — key = seed, counter words
+ *             (env id low, env id high, counter low, RNG_POLICY | (counter high & 0x3FFFFF) << 2 | block) — with block = k / 2;
+ *             words (x, y) give eps_{2 block}, (z, w) give eps_{2 block + 1}, each by Box-Muller:
+ *             u1 = ((w0 >> 8) + 1) * 2^-24, u2 = (w1 >> 8) * 2^-24, eps = sqrtf(-2.0f * det_logf(u1)) * det_cosf(6.2831855f * u2).
+ *             noise_normal f32[...][A] replaces the draw when given (parity mode, as noise_exp is for the categorical).
+ *             a_k = mu_k + det_expf(log_std_k) * eps_k.  deterministic != 0: a = mu, eps = 0.
+ *             The action is NOT clipped: the slab holds the draw, the env clips the torque it applies.
+ *   logp      at the draw: sum_k ((-0.5f * (eps_k * eps_k) - log_std_k) - 0.918938533f)
+ *             at the update, for a stored action a: the same with z_k = (a_k - mu_k) * det_expf(-log_std_k) in place of eps_k
+ *   entropy   sum_k (1.418938533f + log_std_k)
+ *   loss      gymrl_ppo_loss_fwd_bwd's terms, clip / dual-clip and tie rules, metrics and gymrl_ppo_cfg with this logp / entropy;
+ *             with g_lp = dL/dlogp and g_H = -entropy_coef / B of a row:
+ *             dmu_k = g_lp * (z_k * det_expf(-log_std_k)),  dvalue as L1,
+ *             dlog_std_k = sum over rows of (g_lp * (z_k * z_k - 1.0f) + g_H), each row's float32 term added in float64.
+ *
+ * gymrl_gaussian_sample: mu f32[N, A], log_std f32[A], value_in f32[N] or NULL (copied to value_out), noise_normal f32[N, A] or
+ * NULL -> act_out f32[N, A], logp_out f32[N], ent_out f32[N] or NULL.  `online`: gymrl_categorical_sample's producer side of GAE
+ * (the same composition; the decoupled-lambda pair running2 / lam2 is refused).  1 <= A <= 8.
+ */
+int gymrl_gaussian_sample(const float* mu, const float* log_std, const float* value_in,
+                          const float* noise_normal, uint64_t seed, uint64_t counter,
+                          int64_t env_id0, int n, int act_dim, int deterministic,
+                          float* act_out, float* logp_out, float* ent_out,
+                          float* value_out, const gymrl_gae_online* online, void* stream);
 /* Last step of a rollout: composes step T-1 with val_cur = the bootstrap value V_T. */
 int gymrl_gae_online_flush(const gymrl_gae_online* online, const float* val_cur, int N,
                            void* stream);
@@ -278,6 +308,25 @@ int gymrl_ppo_loss_fwd_bwd(const float* logits, const float* value, const int32_
                            const gymrl_ppo_cfg* cfg_host, float* dlogits_out,
                            float* dvalue_out, double* metrics_sum, void* workspace,
                            void* stream);
+/*
+ * L1 under the Gaussian policy above: gymrl_ppo_loss_fwd_bwd's interface (idx, adv_moments, metrics_sum and `workspace` mean what
+ * they mean there) with mu f32[B, A] in place of the logits, log_std f32[A], act f32[*, A] the stored actions ->
+ * dmu_out f32[B, A], dvalue_out f32[B], dlog_std_out f32[A] (written, not accumulated).  One row per lane, one launch plus the
+ * finalising pass(es); no host synchronisation, no float atomics, capturable in a hipGraph.
+ * dlog_std is a fixed-order reduction whose order depends on B alone: rows [256 j, 256 j + 256) are segment j, a segment's terms
+ * are added in float64 (a wave's lanes by shuffle, the four waves in order) into dls_workspace f64[ceil(B / 256)][A]
+ * (gymrl_ppo_gauss_loss_workspace_bytes(B, A) bytes, 8-byte aligned, required), and the finalising pass adds the segments — the
+ * same bits from run to run and for every grid.  grid_blocks: 0 = min(ceil(B / 256), 1024) workgroups (gymrl_loss_blocks(B), the
+ * rows of the metric partials); a smaller positive value narrows the grid (tests; refused where `workspace` is a caller's
+ * partials table, i.e. without metrics_sum).  1 <= A <= 8.  A NaN advantage yields NaN metrics and gradients.
+ */
+size_t gymrl_ppo_gauss_loss_workspace_bytes(int B, int A);
+int gymrl_ppo_gauss_loss_fwd_bwd(const float* mu, const float* log_std, const float* value, const int32_t* idx,
+                                 const float* act, const float* logp_old, const float* adv,
+                                 const float* ret, const double* adv_moments, int B, int A,
+                                 const gymrl_ppo_cfg* cfg_host, float* dmu_out, float* dvalue_out,
+                                 float* dlog_std_out, double* metrics_sum, void* workspace,
+                                 void* dls_workspace, int grid_blocks, void* stream);
 
 int gymrl_loss_blocks(int B);
 /* out[r][k] = sum over b < blocks_per_row of partials[r][b][k]  (f64, fixed order) */
@@ -708,6 +757,40 @@ int gymrl_rollout_cartpole(const gymrl_rollout_lunar_args* args, const gymrl_mlp
  * kind, a descriptor whose input width is not D or whose logit width is not A, and an `obs` that is not aligned to the store of
  * an observation row: 16 bytes (CartPole-v1: one float4) or 8 bytes (the other two: one and three float2). */
 int gymrl_rollout_classic(int env_kind, const gymrl_rollout_lunar_args* args, const gymrl_mlp_desc* policy, void* stream);
+/* The same rollout for PPO on Pendulum-v1 under the Gaussian policy (gymrl_gaussian_sample above; csrc/rollout_classic.hip, the
+ * fourth instance of its kernel template): obs f32[T+1][N][3], act f32[T][N] the UNCLIPPED draw (the stepper clips the torque to
+ * +-2), the policy's two dst == -1 stages are the mean [1] then the value [1], log_std f32[1], noise_normal f32[T][N][1] or NULL,
+ * env_state is gymrl_env_state_bytes(GYMRL_ENV_PENDULUM, n_envs).  rew holds the env's reward times reward_scale (one float32
+ * multiply); ep_ret and ep_stats stay unscaled.  The other members are gymrl_rollout_lunar_args'.  Bit-identical to
+ * gymrl_mlp_forward -> gymrl_gaussian_sample -> gymrl_env_step (-> rew * reward_scale).  An observation row is 12 bytes: it is
+ * stored as three floats, and `obs`, `act`, `log_std` and `noise_normal` are 4-byte aligned.  -EINVAL before any launch: a NULL
+ * block, policy, env_state, slab, next_value or log_std, n_envs <= 0, T <= 0, a window outside [0, T], gae_running without
+ * gae_workspace, a NaN reward_scale, a misaligned pointer, and a descriptor that is not (3 -> ... -> 1, 1). */
+typedef struct {
+  void* env_state;
+  int n_envs;
+  uint64_t seed;
+  int64_t env_id0;
+  uint64_t counter0;
+  float* obs;
+  float* act;
+  float* logp;
+  float* val;
+  float* rew;
+  uint8_t* done;
+  float* ep_ret;
+  float* next_value;
+  const float* log_std;
+  const float* noise_normal;
+  float reward_scale;
+  double* gae_running;
+  void* gae_workspace;
+  double gamma, lam;
+  double* ep_stats;
+  int T, t0, nsteps;
+} gymrl_rollout_pendulum_args;
+size_t gymrl_rollout_pendulum_args_bytes(void);  /* sizeof(gymrl_rollout_pendulum_args) */
+int gymrl_rollout_pendulum(const gymrl_rollout_pendulum_args* args, const gymrl_mlp_desc* policy, void* stream);
 /* The same persistent rollout for PPO-full (ppo_full_lunarlander.py collect_experience :440-505): the policy is the mHC network
  * (gymrl_mhc_policy, declared with gymrl_mhc_policy_forward below; obs_dim 8, n_act 4), `ent` receives the behaviour policy's
  * entropy, and with gae_running2 / lam2 both decoupled-lambda chunk maps are composed (the actor's with `lam`, then the critic's).
@@ -841,6 +924,19 @@ typedef struct {
 } gymrl_classic_ppo_eval_args;
 size_t gymrl_classic_ppo_eval_args_bytes(void);  /* sizeof(gymrl_classic_ppo_eval_args) */
 int gymrl_classic_ppo_eval(const gymrl_classic_ppo_eval_args* args, const gymrl_mlp_desc* policy, void* stream);
+/* gymrl_classic_ppo_eval's contract and kernel for Pendulum-v1 under the Gaussian policy: the policy is gymrl_rollout_pendulum's
+ * descriptor, the action is the actor's mean (a = mu: no draw, log_std is not read), an episode ends with terminated = 0 when its
+ * length reaches cap <= 200.  final_obs f32[P * E][3] (4-byte aligned).  Bit-identical to gymrl_mlp_forward ->
+ * gymrl_gaussian_sample(deterministic) -> gymrl_env_step; the return is the float64 sum the stepper keeps (ep_ret). */
+typedef struct {
+  int P, E, cap;
+  uint64_t seed; int64_t stream_id0;
+  int64_t policy_stride;                   /* floats between consecutive policies' tensors; 0 with P == 1 */
+  double* returns; int32_t* lengths; uint8_t* terminated;
+  float* final_obs;                        /* f32[P * E][3] or NULL */
+} gymrl_pendulum_ppo_eval_args;
+size_t gymrl_pendulum_ppo_eval_args_bytes(void);  /* sizeof(gymrl_pendulum_ppo_eval_args) */
+int gymrl_pendulum_ppo_eval(const gymrl_pendulum_ppo_eval_args* args, const gymrl_mlp_desc* policy, void* stream);
 
 /* ================================================ low-latency Linear layers == */
 /*
