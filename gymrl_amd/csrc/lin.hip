@@ -24,8 +24,22 @@
 // Accumulation order (documented for the tests; all sums are f32 fma chains inside the MFMA unit):
 //   lin_fwd:        for k0 = 0, 16, ...: for e = 0..3: the MFMA adds the four products k = k0 + 4 q + e, q = 0..3 in order
 //   lin_bwd_input:  the same with n in place of k
-//   lin_bwd_weight: for b0 = lo, lo + 16, ...: for e = 0..3: rows b = b0 + 4 e + q, q = 0..3; B > 512 rows are cut into
-//                   slices whose partial tiles are added in slice order by a second launch (fixed order, no atomics)
+//   lin_bwd_weight: for b0 = lo, lo + 16, ...: for e = 0..3: rows b = b0 + 4 e + q, q = 0..3 — the rows of a slice ascending, one
+//                   chain from +0 (the 64 x 64-block kernels walk b = b0 + 4 s + q, s = 0..3: the same ascending chain, so a big
+//                   shape and its fallback to the 16 x 16 tiles give the same bits).  B > 512 rows are cut into `slices` slices of
+//                   rows_per_slice rows (lin_device.hpp bwd_weight_slices); a second launch, lin_slice_reduce_kernel, adds their
+//                   partial tiles in a fixed order, no atomics: NOT plain slice order but eight groups of ceil(slices / 8)
+//                   consecutive slices, each group summed ascending in f32 from 0 (a group may be short or empty), then group 0's
+//                   sum + group 1's + ... + group 7's.  One slice: no reduce.  accumulate: old value + result, one f32 add.
+//   db:             per slice and column, lane group q sums the rows congruent to q modulo 4 (counted from the slice's first row)
+//                   serially in f32 from 0; the four sums are combined (q0 + q1) + (q2 + q3); slices reduce like the tiles of dW.
+//   lin_bwd_input_skinny_kernel (N <= 16, more than 8192 rows, one input block): on the VALU, n ascending, s = s + dz * w — a
+//                   multiply and then an add, no fma.  By design its last bits differ from the MFMA kernel's on the same shape:
+//                   the dispatch is by shape alone, so a given launch is still reproducible.
+//   dz = dy * act'(y) is formed in f32 before the chain (tanh: 1 - y * y, two roundings).  The tanh forward epilogue is
+//   train_tanhf (hardware exp2 and rcp) and SiLU uses the device's expf: the pre-activation acc + bias is reproducible on the
+//   host bit for bit, these two activations of it are not.  The test suite's CPU checker restates all of the above in plain C
+//   and tests/test_lin_seams_gpu.py holds the kernels to it with exact equality.
 #include "lin_device.hpp"
 
 namespace {

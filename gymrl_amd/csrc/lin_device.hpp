@@ -437,7 +437,8 @@ __device__ __forceinline__ f32x4 tile_bwd_weight(const float* __restrict__ dZ, i
 // gymrl_lin_bwd_weight's cut of the batch reduction (lin.hip): one chain up to 512 rows; above that `slices` slices of
 // rows_per_slice rows (a multiple of 32) whose partial tiles lin_slice_reduce_kernel adds in eight groups — group g the slices
 // g * each .. (g + 1) * each - 1 one after another from +0, then the groups in turn.  B >= 16384 on 64-aligned shapes takes the
-// 64 x 64-block kernels (another order: not restated here, the fused step stops at 8192 rows).  The fused step's weight-gradient
+// 64 x 64-block kernels (another cut — the slice count below — but per slice the same ascending chain and db order; the fused step
+// stops at 8192 rows).  The fused step's weight-gradient
 // tiles (slab_step_device.hpp sac_dw_body) follow the same cut: one wave per slice, the last one to arrive adds them in this order.
 __host__ __device__ __forceinline__ bool bwd_weight_big_shape(int B, int N, int K) { return B >= 16384 && N % 64 == 0 && K % 64 == 0; }
 __host__ __device__ __forceinline__ int bwd_weight_slices(int B, int N, int K) {

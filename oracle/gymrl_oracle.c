@@ -280,6 +280,123 @@ void orc_linear_bwd_bias(const float* dY, int64_t B, int N, int slices, int64_t 
   }
 }
 
+/* ------------------------------------------------- low-latency Linear layers ---
+ * The backward launches of gymrl_amd/csrc/lin.hip (gymrl_lin_bwd_input / _bwd_weight) in the accumulation order
+ * that file's header documents.  The forward is orc_linear_act (k0 = 0, 16, ...; e; q: k = k0 + 4q + e).
+ * act: include/gymrl.h's codes, 0 none, 1 tanh, 2 relu, 3 clamp; the derivative is a function of the saved OUTPUT y
+ * (lin_device.hpp act_bwd). */
+static float lin_act_bwd(float y, int act, float lo, float hi) {
+  if (act == 2) return y > 0.0f ? 1.0f : 0.0f;
+  if (act == 1) return 1.0f - y * y;
+  if (act == 3) return (y > lo && y < hi) ? 1.0f : 0.0f;
+  return 1.0f;
+}
+
+/* dz = dy * act'(y) of one row in f32; act none: dy itself */
+static void lin_dz_row(const float* dy, const float* y, int N, int act, float lo, float hi, float* dz) {
+  for (int n = 0; n < N; ++n) dz[n] = act == 0 ? dy[n] : dy[n] * lin_act_bwd(y[n], act, lo, hi);
+}
+
+/* dX [B, K] (+)= sum over items of (dY_i * act_i'(Y_i)) W_i: ONE fmaf chain per output from +0, per item
+ * n0 = 0, 16, ...; e = 0..3; q = 0..3: n = n0 + 4q + e (terms past N are exact zeros in the kernel: skipped); the items'
+ * chains run on into one another (sum_items).  accumulate: old value + chain, one f32 add.  Y[i] may be NULL where act[i] == 0. */
+void orc_lin_bwd_input(const float* const* dY, const float* const* Y, const float* const* W, const int* act, const float* lo,
+                       const float* hi, int n_items, int64_t B, int N, int K, int accumulate, float* dX) {
+  int* order = (int*)malloc(sizeof(int) * (size_t)N);
+  float* dz = (float*)malloc(sizeof(float) * (size_t)N * (size_t)n_items);
+  int cnt = 0;
+  for (int n0 = 0; n0 < N; n0 += 16)
+    for (int e = 0; e < 4; ++e)
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + 4 * q + e;
+        if (n < N) order[cnt++] = n;
+      }
+  for (int64_t r = 0; r < B; ++r) {
+    for (int i = 0; i < n_items; ++i)
+      lin_dz_row(dY[i] + (size_t)r * N, Y[i] ? Y[i] + (size_t)r * N : NULL, N, act[i], lo[i], hi[i], dz + (size_t)i * N);
+    for (int k = 0; k < K; ++k) {
+      float acc = 0.0f;
+      for (int i = 0; i < n_items; ++i)
+        for (int j = 0; j < N; ++j) {
+          const int n = order[j];
+          acc = fmaf(dz[(size_t)i * N + n], W[i][(size_t)n * K + k], acc);
+        }
+      float* dst = dX + (size_t)r * K + k;
+      *dst = accumulate ? *dst + acc : acc;
+    }
+  }
+  free(order);
+  free(dz);
+}
+
+/* lin_bwd_input_skinny_kernel (N <= 16, more than 8192 rows): on the VALU, n ascending, s = s + dz * w — a multiply and then
+ * an add, no fma; accumulate: chain + old value.  By design not the MFMA kernel's bits. */
+void orc_lin_bwd_input_skinny(const float* dY, const float* Y, const float* W, int act, float lo, float hi, int64_t B, int N,
+                              int K, int accumulate, float* dX) {
+  float* dz = (float*)malloc(sizeof(float) * (size_t)N);
+  for (int64_t r = 0; r < B; ++r) {
+    lin_dz_row(dY + (size_t)r * N, Y ? Y + (size_t)r * N : NULL, N, act, lo, hi, dz);
+    for (int k = 0; k < K; ++k) {
+      float s = 0.0f;
+      for (int n = 0; n < N; ++n) {
+        const float p = dz[n] * W[(size_t)n * K + k];
+        s = s + p;
+      }
+      float* dst = dX + (size_t)r * K + k;
+      *dst = accumulate ? s + *dst : s;
+    }
+  }
+  free(dz);
+}
+
+/* dW [N, K] (+)= (dY * act'(Y))^T X and db [N] (+)= its column sums (db NULL: skipped) for rows cut into `slices` slices of
+ * `rps` rows.  Per slice: an fmaf chain over the slice's rows ascending from +0 per element of dW; db from four serial f32
+ * sums of the rows congruent to q (mod 4) counted from the slice's first row, combined (q0 + q1) + (q2 + q3).  One slice:
+ * that is the result.  More: lin_slice_reduce_kernel — eight groups of ceil(slices / 8) consecutive slices, each summed
+ * ascending in f32 from 0, then group 0's sum + group 1's + ... + group 7's.  accumulate: old value + result, one f32 add. */
+void orc_lin_bwd_weight(const float* dY, const float* Y, const float* X, int act, float lo, float hi, int64_t B, int N, int K,
+                        int slices, int64_t rps, int accumulate, float* dW, float* db) {
+  const size_t wk = (size_t)N * K, per = wk + (size_t)N;
+  float* part = (float*)malloc(sizeof(float) * per);
+  float* grp = (float*)calloc(8 * per, sizeof(float));
+  float* col = (float*)malloc(sizeof(float) * 4 * (size_t)N);
+  float* dz = (float*)malloc(sizeof(float) * (size_t)N);
+  const int each = (slices + 7) / 8;
+  for (int s = 0; s < slices; ++s) {
+    const int64_t m0 = (int64_t)s * rps, m1 = m0 + rps < B ? m0 + rps : B;
+    for (size_t i = 0; i < wk; ++i) part[i] = 0.0f;
+    for (int i = 0; i < 4 * N; ++i) col[i] = 0.0f;
+    for (int64_t m = m0; m < m1; ++m) {
+      lin_dz_row(dY + (size_t)m * N, Y ? Y + (size_t)m * N : NULL, N, act, lo, hi, dz);
+      const float* x = X + (size_t)m * K;
+      float* c = col + (size_t)((m - m0) & 3) * N;
+      for (int n = 0; n < N; ++n) {
+        const float d = dz[n];
+        float* p = part + (size_t)n * K;
+        c[n] = c[n] + d;
+        for (int k = 0; k < K; ++k) p[k] = fmaf(d, x[k], p[k]);
+      }
+    }
+    for (int n = 0; n < N; ++n) part[wk + n] = (col[n] + col[N + n]) + (col[2 * N + n] + col[3 * N + n]);
+    if (slices == 1) break;
+    float* g = grp + (size_t)(s / each) * per;
+    for (size_t i = 0; i < per; ++i) g[i] = g[i] + part[i];
+  }
+  for (size_t i = 0; i < per; ++i) {
+    float v = part[i];
+    if (slices > 1) {
+      v = grp[i];
+      for (int k = 1; k < 8; ++k) v = v + grp[(size_t)k * per + i];
+    }
+    float* dst = i < wk ? dW + i : (db ? db + (i - wk) : NULL);
+    if (dst) *dst = accumulate ? *dst + v : v;
+  }
+  free(part);
+  free(grp);
+  free(col);
+  free(dz);
+}
+
 /* ============================================================== Philox ==== */
 /* Philox4x32-10 (Salmon et al. 2011), the build's own counter-based env/policy
  * stream; integer only. */

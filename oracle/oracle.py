@@ -140,6 +140,55 @@ def linear_bwd_bias(dy, slices, rows_per_slice):
     return db
 
 
+def _items(v, n):
+    return list(v) if isinstance(v, (list, tuple)) else [v] * n
+
+
+def lin_bwd_input(dy, y, W, act=0, lo=0.0, hi=0.0, old=None, skinny=False):
+    """gymrl_lin_bwd_input's dX [B, K] = (dy * act'(y)) W in lin.hip's documented order.  Lists: the items' chains run on
+    into one another (sum_items).  old: accumulate on top of it (one f32 add).  skinny: the VALU kernel's order instead
+    (one item).  y may be None where act is 0."""
+    multi = isinstance(W, (list, tuple))
+    n = len(W) if multi else 1
+    dys, Ws = [_f32(a) for a in _items(dy, n)], [_f32(a) for a in _items(W, n)]
+    ys = [None if a is None else _f32(a) for a in _items(y, n)]
+    acts, los, his = [int(a) for a in _items(act, n)], _items(lo, n), _items(hi, n)
+    B, N = dys[0].shape
+    K = Ws[0].shape[1]
+    assert all(a.shape == (B, N) for a in dys) and all(a.shape == (N, K) for a in Ws)
+    assert all(a == 0 or t is not None for a, t in zip(acts, ys))
+    dx = np.empty((B, K), np.float32) if old is None else _f32(old).copy()
+    assert dx.shape == (B, K)
+    if skinny:
+        assert n == 1
+        lib().orc_lin_bwd_input_skinny(_p(dys[0]), _p(ys[0]), _p(Ws[0]), acts[0], C.c_float(los[0]), C.c_float(his[0]),
+                                       C.c_int64(B), N, K, int(old is not None), _p(dx))
+        return dx
+    vp = lambda ts: (C.c_void_p * n)(*[None if t is None else t.ctypes.data for t in ts])   # noqa: E731
+    lib().orc_lin_bwd_input(vp(dys), vp(ys), vp(Ws), (C.c_int * n)(*acts), (C.c_float * n)(*los), (C.c_float * n)(*his), n,
+                            C.c_int64(B), N, K, int(old is not None), _p(dx))
+    return dx
+
+
+def lin_bwd_weight(dy, y, x, slices, rows_per_slice, act=0, lo=0.0, hi=0.0, old_dw=None, old_db=None, want_db=True):
+    """gymrl_lin_bwd_weight's (dW [N, K], db [N] | None) for the given cut of the rows, in lin.hip's documented order
+    (x: the concatenated input).  old_dw / old_db: accumulate on top of them."""
+    dy, x = _f32(dy), _f32(x)
+    y = None if y is None else _f32(y)
+    B, N = dy.shape
+    K = x.shape[1]
+    assert x.shape[0] == B and (int(act) == 0 or y is not None)
+    acc = old_dw is not None
+    dW = _f32(old_dw).copy() if acc else np.empty((N, K), np.float32)
+    db = None
+    if want_db:
+        db = _f32(old_db).copy() if acc else np.empty(N, np.float32)
+    assert dW.shape == (N, K) and (db is None or db.shape == (N,))
+    lib().orc_lin_bwd_weight(_p(dy), _p(y), _p(x), int(act), C.c_float(lo), C.c_float(hi), C.c_int64(B), N, K, int(slices),
+                             C.c_int64(int(rows_per_slice)), int(acc), _p(dW), _p(db))
+    return dW, db
+
+
 def mlp_forward(x, stages):
     """stages: list of (W, b, act, src, dst); src -1 = x, dst -1 = network output.  Returns the list of
     outputs of the dst == -1 stages in order (include/gymrl.h gymrl_mlp_forward)."""
