@@ -594,6 +594,10 @@ SIGNATURES = {
     "gymrl_ppo_update_shape_ok": (_i, [_i, _i, _i]),
     "gymrl_heads_loss_fwd_bwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PPOCfg), _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp]),
+    "gymrl_ppo_gauss_update_shape_ok": (_i, [_i, _i, _i]),
+    "gymrl_gauss_heads_loss_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "gymrl_gauss_heads_loss_fwd_bwd": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PPOCfg), _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "gymrl_gemm_workspace_bytes": (_sz, []),
     "gymrl_linear_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "gymrl_linear_bwd_input": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),

@@ -25,6 +25,7 @@
 #include "train_device.hpp"
 #include "finalize_device.hpp"
 #include "policy_device.hpp"
+#include "gauss_policy_device.hpp"
 #include "../../include/gymrl.h"
 
 namespace {
@@ -633,6 +634,233 @@ __global__ __launch_bounds__(kTB) void heads_loss_kernel(float* Zac, int64_t B, 
   }
 }
 
+// ------------------------------------------------------------------ F3+L1g+B4 -
+// heads_loss_kernel's pass under the Gaussian head (include/gymrl.h "Gaussian policy"): the actor head is the mean, the loss
+// of a row is ppo_gauss_loss_row<A> (gauss_policy_device.hpp, the bits of ppo_gauss_loss_kernel), the stored action is f32[B, A]
+// and log_std f32[A] comes from device memory.  Layout, batch, butterfly, the move to one row per lane, the fetch of dmu / dv
+// (v_readlane at C = 256, ds_bpermute below), dZac in place, block_colsum and met_parts are heads_loss_kernel's, restated here
+// so that its instances keep their listing.  The gradient to log_std is a sum over the batch that training reads: a live
+// lane's dls[k] (float32) is widened to float64, a batch's lanes are added by wave_sum (fixed lane order), and the sum lands in
+// dls_parts[bt][A] — indexed by the batch, not by the wave or workgroup that happened to walk it — for
+// gauss_dls_batches_kernel.  Rows past B in the last batch are loaded from row B - 1 and add nothing to any sum.
+// The batches are dealt to nblocks = heads_loss_grid(B, C) VIRTUAL workgroups as heads_loss_kernel deals them to its grid, and
+// workgroup b of the launch runs virtual workgroups b, b + gridDim.x, ... one after the other, each from zeroed accumulators to
+// its own partial row and metric row: every output carries the same bits under every grid (gridDim.x == nblocks is one trip).
+template <int A, int C>
+__global__ __launch_bounds__(kTB) void gauss_heads_loss_kernel(float* Zac, int64_t B, const float* __restrict__ bac,
+                                                               const float* __restrict__ Wa2, const float* __restrict__ ba2,
+                                                               const float* __restrict__ Wc2, const float* __restrict__ bc2,
+                                                               const float* __restrict__ log_std, const float* __restrict__ act,
+                                                               const float* __restrict__ logp_old, const float* __restrict__ adv,
+                                                               const float* __restrict__ ret, const double* __restrict__ adv_moments,
+                                                               gymrl_ppo_cfg cfg, int nblocks, float* __restrict__ partials,
+                                                               double* __restrict__ met_parts, double* __restrict__ dls_parts) {
+  static_assert(C == 64 || C == 128 || C == 256, "a row is 16, 32 or 64 lanes");
+  constexpr int lpr = C / 4, rpw = 64 / lpr, kBatch = kRB * rpw;
+  extern __shared__ float sm[];
+  __shared__ double s_norm[2];
+  __shared__ double s_met[5][kTB / 64];
+  if (threadIdx.x == 0) {
+    double mean = 0.0, sd = 1.0;
+    if (adv_moments) {      // whole-rollout advantage normalisation, as heads_loss_kernel
+      const double cnt = adv_moments[0];
+      mean = adv_moments[1] / cnt;
+      double var = adv_moments[2] / cnt - mean * mean;
+      var = var > 0.0 ? var : 0.0;
+      sd = sqrt(var) + 1e-8;
+    }
+    s_norm[0] = mean; s_norm[1] = sd;
+  }
+  __syncthreads();
+  const RowMap m(C, threadIdx.x & 63);               // C = 256: c4 = lane, one row per wave-load
+  const int lane = threadIdx.x & 63;
+  float wa[A][4], wc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    wc[j] = Wc2[4 * m.c4 + j];
+#pragma unroll
+    for (int a = 0; a < A; ++a) wa[a][j] = Wa2[(size_t)a * C + 4 * m.c4 + j];
+  }
+  float hb[A + 1], ls[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) { hb[a] = ba2 ? ba2[a] : 0.0f; ls[a] = log_std[a]; }
+  hb[A] = bc2 ? bc2[0] : 0.0f;
+  f32x4 pa = {0.0f, 0.0f, 0.0f, 0.0f}, pc = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (bac) {
+    pa = *reinterpret_cast<const f32x4*>(bac + 4 * m.c4);
+    pc = *reinterpret_cast<const f32x4*>(bac + C + 4 * m.c4);
+  }
+  constexpr int NACC = 8 + 4 * A + 4 + 4 * ((A + 1 + 3) / 4);
+  const float invB = 1.0f / (float)B;
+  const int64_t nbatch = (B + kBatch - 1) / kBatch;
+  // vb is the same for the whole workgroup, so its barriers are reached by all 256 lanes; bt is wave-uniform, its trip count
+  // differs between the waves of a workgroup, and no barrier stands inside that loop
+  for (int vb = blockIdx.x; vb < nblocks; vb += gridDim.x) {
+    float acc[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = 0.0f;
+    double met[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t bt = (int64_t)vb * (kTB / 64) + (threadIdx.x >> 6); bt < nbatch; bt += (int64_t)nblocks * (kTB / 64)) {
+      const int64_t r0 = bt * kBatch;
+      f32x4 ha[kRB], hc[kRB];
+#pragma unroll
+      for (int k = 0; k < kRB; ++k) {
+        const int64_t row = r0 + k * rpw + m.r_in;
+        const int64_t rr = row < B ? row : B - 1;
+        const size_t o = (size_t)rr * 2 * C + 4 * m.c4;
+        ha[k] = *reinterpret_cast<const f32x4*>(Zac + o);
+        hc[k] = *reinterpret_cast<const f32x4*>(Zac + o + C);
+      }
+      // the loss inputs of row r0 + lane (lanes >= kBatch and rows past the end: a valid row, results unused)
+      const bool live = lane < kBatch && r0 + lane < B;
+      const int64_t rl = live ? r0 + lane : r0;
+      float a_r[A];
+#pragma unroll
+      for (int a = 0; a < A; ++a) a_r[a] = act[(size_t)rl * A + a];
+      const float lpo = logp_old[rl], rt = ret[rl];
+      float ad = adv[rl];
+      float mu[A], v = 0.0f;
+#pragma unroll
+      for (int a = 0; a < A; ++a) mu[a] = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kRB; ++k) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { ha[k][j] = train_tanhf(ha[k][j] + pa[j]); hc[k][j] = train_tanhf(hc[k][j] + pc[j]); }
+        float p[A + 1];
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+          float s = 0.0f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) s = fmaf(ha[k][j], wa[a][j], s);
+          p[a] = s;
+        }
+        {
+          float s = 0.0f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) s = fmaf(hc[k][j], wc[j], s);
+          p[A] = s;
+        }
+        for (int off = lpr / 2; off > 0; off >>= 1) {
+#pragma unroll
+          for (int a = 0; a <= A; ++a) p[a] += __shfl_xor(p[a], off, 64);
+        }
+        // every lane of the row holds the sums: C = 256 keeps row k in lane k; narrower, the row's lane c4 == k keeps it
+        // (lane r_in * lpr + k) and one permute after the loop moves the batch to lanes k * rpw + r_in
+        if (m.c4 == k) {
+#pragma unroll
+          for (int a = 0; a < A; ++a) mu[a] = p[a] + hb[a];
+          v = p[A] + hb[A];
+        }
+      }
+      if constexpr (rpw > 1) {
+        const int src = (lane % rpw) * lpr + lane / rpw;      // lanes >= kBatch read past the kept lanes: results unused
+#pragma unroll
+        for (int a = 0; a < A; ++a) mu[a] = __shfl(mu[a], src, 64);
+        v = __shfl(v, src, 64);
+      }
+      float dl[A], dls[A], dvr, m_obj, m_val, m_ent, m_clip, m_kl;
+      if (adv_moments) ad = (float)(((double)ad - s_norm[0]) / s_norm[1]);
+      ppo_gauss_loss_row<A>(mu, ls, v, a_r, lpo, ad, rt, invB, cfg, dl, dls, dvr, m_obj, m_val, m_ent, m_clip, m_kl);
+      if (live) {
+        met[0] += -(double)m_obj; met[1] += (double)m_val; met[2] += (double)m_ent;
+        met[3] += (double)m_clip; met[4] += (double)m_kl;
+      }
+#pragma unroll
+      for (int a = 0; a < A; ++a) {            // all 64 lanes take part in the shuffles; a lane that is not live adds 0.0
+        const double s = wave_sum(live ? (double)dls[a] : 0.0);
+        if (lane == 0) dls_parts[(size_t)bt * A + a] = s;
+      }
+#pragma unroll
+      for (int k = 0; k < kRB; ++k) {
+        float dk[A], dvk;
+        if constexpr (rpw > 1) {               // all lanes take part in the permute, live or not
+#pragma unroll
+          for (int a = 0; a < A; ++a) dk[a] = __shfl(dl[a], k * rpw + m.r_in, 64);
+          dvk = __shfl(dvr, k * rpw + m.r_in, 64);
+        }
+        if (r0 + k * rpw + m.r_in < B) {       // per row group; C = 256: wave-uniform
+          if constexpr (rpw == 1) {
+#pragma unroll
+            for (int a = 0; a < A; ++a) dk[a] = lane_bcast(dl[a], k);
+            dvk = lane_bcast(dvr, k);
+          }
+          f32x4 za, zc;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float s = 0.0f;
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+              s = fmaf(dk[a], wa[a][j], s);
+              acc[8 + 4 * a + j] = fmaf(dk[a], ha[k][j], acc[8 + 4 * a + j]);
+            }
+            za[j] = s * (1.0f - ha[k][j] * ha[k][j]);
+            zc[j] = (dvk * wc[j]) * (1.0f - hc[k][j] * hc[k][j]);
+            acc[j] += za[j];
+            acc[4 + j] += zc[j];
+            acc[8 + 4 * A + j] = fmaf(dvk, hc[k][j], acc[8 + 4 * A + j]);
+          }
+#pragma unroll
+          for (int a = 0; a < A; ++a) acc[12 + 4 * A + a] += dk[a];
+          acc[12 + 4 * A + A] += dvk;
+          const size_t o = (size_t)(r0 + k * rpw + m.r_in) * 2 * C + 4 * m.c4;
+          *reinterpret_cast<f32x4*>(Zac + o) = za;
+          *reinterpret_cast<f32x4*>(Zac + o + C) = zc;
+        }
+      }
+    }
+    if (m.c4 != 0) {
+#pragma unroll
+      for (int i = 12 + 4 * A; i < NACC; ++i) acc[i] = 0.0f;
+    }
+    // metrics: wave sums -> LDS -> one f64 row per workgroup
+    {
+      const int wid = threadIdx.x >> 6;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const double s = wave_sum(met[k]);
+        if (lane == 0) s_met[k][wid] = s;
+      }
+    }
+    // block_colsum stores row blockIdx.x of what it is handed: handed the table from row vb - blockIdx.x on, it stores row vb
+    block_colsum<NACC>(acc, C, m, sm, partials + (size_t)(vb - (int)blockIdx.x) * (NACC / 4) * C);   // (its barrier also publishes s_met)
+    if (threadIdx.x < 5) {
+      double s = 0.0;
+#pragma unroll
+      for (int w = 0; w < kTB / 64; ++w) s += s_met[threadIdx.x][w];
+      met_parts[(size_t)vb * 5 + threadIdx.x] = s;
+    }
+    __syncthreads();                                      // sm and s_met are free for the next virtual workgroup
+  }
+}
+
+// dlog_std_out[k] = (float) sum over batches of dls_parts[bt][k], ONE workgroup: thread t adds batches t, t + 256, ... in
+// ascending order (float64), the 64 threads of a wave are added by wave_sum, the four waves in order.
+template <int A>
+__global__ __launch_bounds__(kTB) void gauss_dls_batches_kernel(const double* __restrict__ dls_parts, int64_t nbatch,
+                                                                float* __restrict__ dlog_std_out) {
+  __shared__ double s_dls[A][kTB / 64];
+  double v[A];
+#pragma unroll
+  for (int k = 0; k < A; ++k) v[k] = 0.0;
+  for (int64_t j = threadIdx.x; j < nbatch; j += kTB) {
+#pragma unroll
+    for (int k = 0; k < A; ++k) v[k] += dls_parts[(size_t)j * A + k];
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < A; ++k) {
+    const double s = wave_sum(v[k]);
+    if (lane == 0) s_dls[k][wid] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kTB / 64; ++w) s += s_dls[threadIdx.x][w];
+    dlog_std_out[threadIdx.x] = (float)s;
+  }
+}
+
 inline bool pow2_cols(int C) { return C >= 16 && C <= 256 && (C & (C - 1)) == 0; }
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline size_t sm_bytes(int C, int nv4) { return sizeof(float) * (size_t)(kTB / 64) * (64 / (C / 4)) * nv4 * C; }
@@ -695,6 +923,37 @@ void launch_heads_loss(dim3 grid, int C, hipStream_t s, bool parts_only, float* 
   if (!parts_only)
     hipLaunchKernelGGL(heads_finalize_kernel<A>, dim3((NV * C + kFinE - 1) / kFinE), block, 0, s, parts, (int)grid.x, C, dbac, dWa2,
                        dWc2, dba2, dbc2);
+}
+
+// the Gaussian head's fused update: the widths and first layers of the categorical one, a single mean
+inline bool gauss_update_actions(int A) { return A == 1; }
+inline int64_t gauss_heads_loss_batches(int64_t B, int C) {
+  const int batch = kRB * (64 / (C / 4));
+  return (B + batch - 1) / batch;
+}
+
+template <int A>
+void launch_gauss_heads_loss(dim3 grid, int C, hipStream_t s, float* Zac, int64_t B, const float* bac, const float* Wa2,
+                             const float* ba2, const float* Wc2, const float* bc2, const float* log_std, const float* act,
+                             const float* logp_old, const float* adv, const float* ret, const double* adv_moments,
+                             const gymrl_ppo_cfg& cfg, float* parts, double* metric_parts, double* dls_parts, float* dbac,
+                             float* dWa2, float* dba2, float* dWc2, float* dbc2, float* dlog_std_out) {
+  constexpr int NV = (8 + 4 * A + 4 + 4 * ((A + 1 + 3) / 4)) / 4;
+  const dim3 block(kTB);
+  const size_t lds = sm_bytes(C, NV);
+  const int nblocks = heads_loss_grid(B, C);          // the virtual workgroups: the partial rows and metric rows written
+  if (C == 256)
+    hipLaunchKernelGGL((gauss_heads_loss_kernel<A, 256>), grid, block, lds, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, log_std, act, logp_old,
+                       adv, ret, adv_moments, cfg, nblocks, parts, metric_parts, dls_parts);
+  else if (C == 128)
+    hipLaunchKernelGGL((gauss_heads_loss_kernel<A, 128>), grid, block, lds, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, log_std, act, logp_old,
+                       adv, ret, adv_moments, cfg, nblocks, parts, metric_parts, dls_parts);
+  else
+    hipLaunchKernelGGL((gauss_heads_loss_kernel<A, 64>), grid, block, lds, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, log_std, act, logp_old,
+                       adv, ret, adv_moments, cfg, nblocks, parts, metric_parts, dls_parts);
+  hipLaunchKernelGGL(heads_finalize_kernel<A>, dim3((NV * C + kFinE - 1) / kFinE), block, 0, s, parts, nblocks, C, dbac, dWa2,
+                     dWc2, dba2, dbc2);
+  hipLaunchKernelGGL(gauss_dls_batches_kernel<A>, dim3(1), block, 0, s, dls_parts, gauss_heads_loss_batches(B, C), dlog_std_out);
 }
 
 }  // namespace
@@ -865,6 +1124,36 @@ int gymrl_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* b
   else
     launch_heads_loss<2>(grid, C, s, parts_only, Zac, B, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, adv_moments, *cfg, parts,
                          metric_parts, dbac, dWa2, dba2, dWc2, dbc2);
+  GYMRL_CHECK_LAUNCH();
+  return 0;
+}
+
+int gymrl_ppo_gauss_update_shape_ok(int C, int D, int A) {
+  return heads_loss_cols(C) && update_obs(D) && gauss_update_actions(A) ? 1 : 0;
+}
+
+size_t gymrl_gauss_heads_loss_workspace_bytes(int64_t B, int C, int A) {
+  if (B <= 0 || !heads_loss_cols(C) || !gauss_update_actions(A)) return 0;
+  return (size_t)gauss_heads_loss_batches(B, C) * (size_t)A * sizeof(double);
+}
+
+int gymrl_gauss_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* bac, const float* Wa2, const float* ba2,
+                                   const float* Wc2, const float* bc2, const float* log_std, const float* act,
+                                   const float* logp_old, const float* adv, const float* ret, const double* adv_moments,
+                                   const gymrl_ppo_cfg* cfg, float* dbac, float* dWa2, float* dba2, float* dWc2, float* dbc2,
+                                   float* dlog_std_out, double* metric_parts, void* workspace, void* dls_workspace,
+                                   int grid_blocks, void* stream) {
+  // (no "block partials only" mode: gymrl_update_finalize stays the categorical head's)
+  if (!Zac || !Wa2 || !Wc2 || !log_std || !act || !logp_old || !adv || !ret || !cfg || !dbac || !dWa2 || !dba2 || !dWc2 ||
+      !dbc2 || !dlog_std_out || !metric_parts || !workspace || !dls_workspace || B <= 0 || !heads_loss_cols(C) ||
+      !gauss_update_actions(A) || grid_blocks < 0 || !al16(Zac) || (bac && !al16(bac)) ||
+      (reinterpret_cast<uintptr_t>(metric_parts) & 7) || (reinterpret_cast<uintptr_t>(dls_workspace) & 7))
+    return -22;
+  hipStream_t s = (hipStream_t)stream;
+  int nb = heads_loss_grid(B, C);                     // == gymrl_heads_loss_blocks(B, C) <= kMaxBlocks rows of `workspace`
+  if (grid_blocks > 0 && grid_blocks < nb) nb = grid_blocks;
+  launch_gauss_heads_loss<1>(dim3(nb), C, s, Zac, B, bac, Wa2, ba2, Wc2, bc2, log_std, act, logp_old, adv, ret, adv_moments, *cfg,
+                             (float*)workspace, metric_parts, (double*)dls_workspace, dbac, dWa2, dba2, dWc2, dbc2, dlog_std_out);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

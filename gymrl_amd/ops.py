@@ -1799,6 +1799,80 @@ def heads_loss_fwd_bwd(Zac, bac, Wa2, ba2, Wc2, bc2, act, logp_old, adv, ret, cf
           "gymrl_heads_loss_fwd_bwd")
 
 
+GAUSS_UPDATE_WIDTHS, GAUSS_UPDATE_OBS, GAUSS_UPDATE_ACT = (64, 128, 256), (2, 3, 4, 6, 8), (1,)
+
+
+def ppo_gauss_update_shape_ok(C_, D, A):
+    """gymrl_ppo_gauss_update_shape_ok: the (hidden, obs_dim, action components) the Gaussian head's fused PPO update covers.
+    Host only."""
+    for name, v in (("C", C_), ("D", D), ("A", A)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"ppo_gauss_update_shape_ok: {name} is an int, not {type(v).__name__}")
+    return bool(lib().gymrl_ppo_gauss_update_shape_ok(C_, D, A))
+
+
+def gauss_heads_loss_workspace(B, C_, A, device):
+    """The float64 batch table of the log_std gradient, f64[ceil(B / (8 * 256 / C)), A] (gymrl_gauss_heads_loss_workspace_bytes)."""
+    n = int(lib().gymrl_gauss_heads_loss_workspace_bytes(B, C_, A))
+    if n <= 0:
+        raise ValueError(f"gauss_heads_loss_workspace: no table for B = {B}, C = {C_}, A = {A}")
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+def gauss_heads_loss_fwd_bwd(Zac, bac, Wa2, ba2, Wc2, bc2, log_std, act, logp_old, adv, ret, cfg, adv_moments, dbac, dWa2, dba2,
+                             dWc2, dbc2, dlog_std_out, metric_parts, workspace, dls_workspace, grid_blocks=0):
+    """Heads forward + the Gaussian policy's PPO loss + heads backward in one pass; dZac overwrites Zac (include/gymrl.h
+    gymrl_gauss_heads_loss_fwd_bwd).  act f32[B, A] are the minibatch's stored actions; the five head gradients and dlog_std_out
+    f32[A] are written.  grid_blocks: 0 = the default grid; every output carries the same bits under every grid."""
+    who = "gauss_heads_loss_fwd_bwd"
+    if Zac.dim() != 2 or Zac.shape[0] < 1 or Zac.shape[1] % 2 or Zac.shape[1] // 2 not in GAUSS_UPDATE_WIDTHS:
+        raise ValueError(f"{who}: Zac is f32[B >= 1, 2C] with C in {GAUSS_UPDATE_WIDTHS}, not {tuple(Zac.shape)}")
+    B, Cc = Zac.shape[0], Zac.shape[1] // 2
+    if Wa2.dim() != 2 or Wa2.shape[0] not in GAUSS_UPDATE_ACT or Wa2.shape[1] != Cc:
+        raise ValueError(f"{who}: Wa2 is f32[A, {Cc}] with A in {GAUSS_UPDATE_ACT}, not {tuple(Wa2.shape)}")
+    A = Wa2.shape[0]
+    f32, f64 = torch.float32, torch.float64
+    for name, t, shape, dt, opt in (
+            ("Zac", Zac, (B, 2 * Cc), f32, False), ("bac", bac, (2 * Cc,), f32, True), ("Wa2", Wa2, (A, Cc), f32, False),
+            ("ba2", ba2, (A,), f32, True), ("Wc2", Wc2, (1, Cc), f32, False), ("bc2", bc2, (1,), f32, True),
+            ("log_std", log_std, (A,), f32, False), ("act", act, (B, A), f32, False), ("logp_old", logp_old, (B,), f32, False),
+            ("adv", adv, (B,), f32, False), ("ret", ret, (B,), f32, False), ("adv_moments", adv_moments, (3,), f64, True),
+            ("dbac", dbac, (2 * Cc,), f32, False), ("dWa2", dWa2, (A, Cc), f32, False), ("dba2", dba2, (A,), f32, False),
+            ("dWc2", dWc2, (1, Cc), f32, False), ("dbc2", dbc2, (1,), f32, False), ("dlog_std_out", dlog_std_out, (A,), f32, False)):
+        if t is None:
+            if opt:
+                continue
+            raise ValueError(f"{who}: {name} is required")
+        if tuple(t.shape) != shape and not (shape == (1, Cc) and tuple(t.shape) == (Cc,)):
+            raise ValueError(f"{who}: {name} is {shape}, not {tuple(t.shape)}")
+        if t.dtype != dt:
+            raise ValueError(f"{who}: {name} is {dt}, not {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+    if metric_parts is None or metric_parts.dtype != f64 or metric_parts.dim() != 2 or metric_parts.shape[1] != 5 \
+            or not metric_parts.is_contiguous():
+        raise ValueError(f"{who}: metric_parts is a contiguous f64[heads_loss_blocks(B, C), 5]")
+    if isinstance(grid_blocks, bool) or not isinstance(grid_blocks, int) or grid_blocks < 0:
+        raise ValueError(f"{who}: grid_blocks is an int >= 0")
+    if workspace is None or dls_workspace is None:
+        raise ValueError(f"{who}: workspace (mlp_train_workspace) and dls_workspace (gauss_heads_loss_workspace) are required")
+    if metric_parts.shape[0] < heads_loss_blocks(B, Cc):
+        raise ValueError(f"{who}: metric_parts has {metric_parts.shape[0]} rows, heads_loss_blocks(B, C) = {heads_loss_blocks(B, Cc)}")
+    if dls_workspace.numel() * dls_workspace.element_size() < int(lib().gymrl_gauss_heads_loss_workspace_bytes(B, Cc, A)):
+        raise ValueError(f"{who}: dls_workspace is smaller than gymrl_gauss_heads_loss_workspace_bytes(B, C, A)")
+    if workspace.numel() * workspace.element_size() < int(lib().gymrl_mlp_train_workspace_bytes(Cc, 0, A)):
+        raise ValueError(f"{who}: workspace is smaller than gymrl_mlp_train_workspace_bytes(C, 0, A)")
+    _need_dev(who, Zac=Zac, bac=bac, Wa2=Wa2, ba2=ba2, Wc2=Wc2, bc2=bc2, log_std=log_std, act=act, logp_old=logp_old, adv=adv, ret=ret,
+              adv_moments=adv_moments, dbac=dbac, dWa2=dWa2, dba2=dba2, dWc2=dWc2, dbc2=dbc2, dlog_std_out=dlog_std_out,
+              metric_parts=metric_parts, workspace=workspace, dls_workspace=dls_workspace)
+    c = PPOCfg(*[float(v) for v in cfg])
+    check(lib().gymrl_gauss_heads_loss_fwd_bwd(_ptr(Zac), B, Cc, A, _ptr(bac, None, True), _ptr(Wa2), _ptr(ba2, None, True), _ptr(Wc2),
+                                               _ptr(bc2, None, True), _ptr(log_std), _ptr(act), _ptr(logp_old), _ptr(adv), _ptr(ret),
+                                               _ptr(adv_moments, None, True), C.byref(c), _ptr(dbac), _ptr(dWa2), _ptr(dba2), _ptr(dWc2),
+                                               _ptr(dbc2), _ptr(dlog_std_out), _ptr(metric_parts), _ptr(workspace), _ptr(dls_workspace),
+                                               grid_blocks, _stream()), "gymrl_gauss_heads_loss_fwd_bwd")
+
+
 # ------------------------------------------------------ update-path GEMMs ---
 def gemm_workspace(device):
     return torch.empty(int(lib().gymrl_gemm_workspace_bytes()), dtype=torch.uint8, device=device)

@@ -308,6 +308,18 @@ class PPOTrainer:
     def _stored_step(self, t):
         """After env.step() filled rows t of the reward / done slabs (the Gaussian trainer scales the stored reward here)."""
 
+    def _fused_update_for(self, mb):
+        """The hand-scheduled update object for minibatches of up to `mb` rows (built on first use, rebuilt when they grow), or None
+        where update() goes through autograd's _loss_backward."""
+        cfg, tm = self.cfg, self._timers
+        fu = None
+        if cfg.fused_update and ppo_net.supported(self.model):
+            if self._fused_update is None or self._fused_update.R < mb:
+                self._fused_update = ppo_net.FusedActorCriticUpdate(self.model, mb)
+            fu = self._fused_update
+            fu.timers = tm
+        return fu
+
     def _packed_actions(self):
         """The action slab as gymrl_pack_rollout's i32[T * N] (a float action travels through the records as its bits)."""
         return self.buffer.actions.view(-1)
@@ -507,12 +519,7 @@ class PPOTrainer:
         self._packed = ops.pack_rollout(b.states[:b.T].reshape(total, obs_dim), self._packed_actions(),
                                         b.log_probs.view(-1), b.advantages.view(-1), b.returns.view(-1),
                                         self._packed)
-        fu = None
-        if cfg.fused_update and ppo_net.supported(self.model):
-            if self._fused_update is None or self._fused_update.R < mb:
-                self._fused_update = ppo_net.FusedActorCriticUpdate(self.model, mb)
-            fu = self._fused_update
-            fu.timers = tm
+        fu = self._fused_update_for(mb)
         one_pass = fu is not None
         # block partials of every minibatch's 5 metric sums; reduced by ONE launch after the last step
         nblk = fu.metric_blocks(mb) if one_pass else ops.loss_blocks(mb)

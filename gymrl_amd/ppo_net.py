@@ -12,7 +12,9 @@ the GEMM libraries are not on this path.
                                                       gymrl_heads_loss_fwd_bwd, ONE pass over Zac;
                                                       hidden 64 / 128 with 2 or 4 actions: gymrl_heads_fwd_tanh ->
                                                       gymrl_ppo_loss_fwd_bwd -> gymrl_heads_bwd (the same per-row
-                                                      arithmetic as three passes; gymrl_heads_bwd takes no A = 3)
+                                                      arithmetic as three passes; gymrl_heads_bwd takes no A = 3);
+                                                      FusedGaussianUpdate (the Gaussian head, one mean): always
+                                                      gymrl_gauss_heads_loss_fwd_bwd, ONE pass that also writes dlog_std
     backward  d[Wa1;Wc1] = dZac^T H2                  gymrl_linear_bwd_weight (hidden 256) / gymrl_lin_bwd_weight
               dZ2 = (dZac [Wa1;Wc1]) (1 - H2^2)       gymrl_linear_bwd_input, tanh' in the epilogue
               dW2 = dZ2^T H1, db2 = colsum dZ2        gymrl_linear_bwd_weight / gymrl_lin_bwd_weight (+ bias gradient)
@@ -50,9 +52,22 @@ def supported(model):
             and model.critic[0].out_features == H)
 
 
+def gauss_supported(model):
+    """supported() for the Gaussian head (ppo_pendulum.GaussianActorCritic): the library's own gate
+    (gymrl_ppo_gauss_update_shape_ok: H in {64, 128, 256}, D in {2, 3, 4, 6, 8}, A == 1), the same widths, and a log_std."""
+    H = model.shared[0].out_features
+    D = model.shared[0].in_features
+    A = model.actor[2].out_features
+    return (ops.ppo_gauss_update_shape_ok(H, D, A)
+            and model.shared[2].out_features == H and model.actor[0].out_features == H
+            and model.critic[0].out_features == H and hasattr(model, "log_std"))
+
+
 class FusedActorCriticUpdate:
+    _covers = staticmethod(supported)      # the shapes this schedule takes (FusedGaussianUpdate: gauss_supported)
+
     def __init__(self, model, max_rows):
-        if not supported(model):
+        if not self._covers(model):
             raise ValueError("unsupported ActorCritic shape for the fused update path")
         self.m = model
         W1 = model.shared[0].weight
@@ -84,13 +99,13 @@ class FusedActorCriticUpdate:
         # two independent choices.  The heads: gymrl_heads_loss_fwd_bwd (one pass) at hidden 256 and wherever A = 3, which
         # gymrl_heads_bwd does not take.  The weight gradients: the 256-deep GEMM (gemm_ws) at hidden 256, the narrow
         # kernels of lin.hip (lin_ws) below it.
-        self.one_pass_heads = H == 256 or self.A == 3
+        self.one_pass_heads, defer = self._schedule()
         self.gemm_ws = ops.gemm_workspace(dev) if H == 256 else None
         # the five batch reductions' second halves as ONE launch at the end of step() (gymrl_update_finalize) instead of five
         # behind their producers: every producer then keeps its partials in a workspace of its own until that launch
-        self.defer_finalize = H == 256
-        self.gemm_ws2 = ops.gemm_workspace(dev) if H == 256 else None
-        self.ws2 = ops.mlp_train_workspace(H, self.D, self.A, dev) if H == 256 else None
+        self.defer_finalize = defer
+        self.gemm_ws2 = ops.gemm_workspace(dev) if defer else None
+        self.ws2 = ops.mlp_train_workspace(H, self.D, self.A, dev) if defer else None
         if not self.one_pass_heads:
             self.logits = torch.empty(R, self.A, device=dev)
             self.value = torch.empty(R, 1, device=dev)
@@ -98,6 +113,15 @@ class FusedActorCriticUpdate:
             self.dvalue = torch.empty(R, device=dev)
         if H != 256:
             self.lin_ws = ops.lin_workspace(R, 2 * H, H, 1, dev) if R > 512 else None
+
+    def _schedule(self):
+        """(one-pass heads, deferred finalize) for this shape."""
+        return self.H == 256 or self.A == 3, self.H == 256
+
+    def _heads_one_pass(self, t, sfx, B, Zac, heads, act, logp_old, adv, ret, loss_cfg, adv_moments, dbac, hg, metric_parts):
+        """The one pass over Zac: loss, dZac in place, the heads' gradients (or their block partials) and the metric partials."""
+        t("heads_loss_fwd_bwd" + sfx, B, ops.heads_loss_fwd_bwd, Zac, None, *heads, act, logp_old, adv, ret, loss_cfg, adv_moments,
+          dbac, *hg, metric_parts, self.ws)
 
     def _timed(self, name, units, fn, *args, **kw):
         tm = self.timers
@@ -135,8 +159,7 @@ class FusedActorCriticUpdate:
         defer = self.defer_finalize and self.one_pass_heads and wide and reducer is None
         if self.one_pass_heads:
             dbac, hg = (None, (None,) * 4) if defer else (self.dbac, hgrads)
-            t("heads_loss_fwd_bwd" + sfx, B, ops.heads_loss_fwd_bwd, Zac, None, *heads, act, logp_old, adv, ret, loss_cfg, adv_moments,
-              dbac, *hg, metric_parts, self.ws)
+            self._heads_one_pass(t, sfx, B, Zac, heads, act, logp_old, adv, ret, loss_cfg, adv_moments, dbac, hg, metric_parts)
         else:
             logits, value, dl, dv = self.logits[:B], self.value[:B], self.dlogits[:B], self.dvalue[:B]
             # the GEMM added [ba1;bc1]: the heads read pre-activations, recompute their tanh in backward, write dZac in place
@@ -169,3 +192,27 @@ class FusedActorCriticUpdate:
               self.ws)
         if reducer is not None:
             reducer.launch(0)
+
+
+class FusedGaussianUpdate(FusedActorCriticUpdate):
+    """FusedActorCriticUpdate.step() for ppo_pendulum.GaussianActorCritic: the same launches around the heads, and the heads as
+    gymrl_gauss_heads_loss_fwd_bwd — always the one pass, never the deferred finalize (gymrl_update_finalize is the categorical
+    head's; hidden 256 takes step()'s non-deferred calls).  `act` arrives as the minibatch's packed int32 column and is read as
+    the float32 bits it holds; d(loss) / d(log_std) goes straight into model.log_std.grad's view of the flat gradient."""
+    _covers = staticmethod(gauss_supported)
+
+    def __init__(self, model, max_rows):
+        super().__init__(model, max_rows)
+        self.log_std = model.log_std.detach()          # the parameter's view of the flat buffer
+        self.dlog_std = model.log_std.grad             # ... and of the flat gradient
+        if self.dlog_std is None or self.dlog_std.untyped_storage().data_ptr() != model._flat_grads.untyped_storage().data_ptr():
+            raise ValueError("log_std.grad is not a view of the flat gradient: flatten_module(model, device, order=ppo_net.LAYOUT)")
+        self.dls_ws = ops.gauss_heads_loss_workspace(self.R, self.H, self.A, model.shared[0].weight.device)
+
+    def _schedule(self):
+        return True, False
+
+    def _heads_one_pass(self, t, sfx, B, Zac, heads, act, logp_old, adv, ret, loss_cfg, adv_moments, dbac, hg, metric_parts):
+        t("gauss_heads_loss_fwd_bwd" + sfx, B, ops.gauss_heads_loss_fwd_bwd, Zac, None, *heads, self.log_std,
+          act.view(torch.float32).view(-1, self.A), logp_old, adv, ret, loss_cfg, adv_moments, dbac, *hg, self.dlog_std, metric_parts,
+          self.ws, self.dls_ws)

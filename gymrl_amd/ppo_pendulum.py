@@ -8,14 +8,16 @@ buffers, GAE, the epoch shuffle, clip-norm + Adam on one flat buffer, checkpoint
 What runs where:
   * rollout   one launch per chunk (gymrl_rollout_pendulum; Config.persistent_rollout), or the three-launch step loop
               gymrl_mlp_forward -> gymrl_gaussian_sample -> gymrl_env_step; both write the same bits
-  * update    the two MLPs through torch autograd; gymrl_ppo_gauss_loss_fwd_bwd supplies d(loss) / d(mean, value, log_std)
-              (the fused update of ppo_net covers the categorical head only)
+  * update    ppo_net.FusedGaussianUpdate.step() (Config.fused_update): the categorical trainer's hand-scheduled minibatch with the
+              heads as ONE pass, gymrl_gauss_heads_loss_fwd_bwd, which also leaves d(loss) / d(log_std) in the flat gradient;
+              or the two MLPs through torch autograd with gymrl_ppo_gauss_loss_fwd_bwd's d(loss) / d(mean, value, log_std)
+              (fused_update = False, several ranks, or a shape gymrl_ppo_gauss_update_shape_ok does not cover)
   * eval      whole deterministic episodes (a = mean) in one launch (gymrl_pendulum_ppo_eval; Config.fused_eval), or the loop
 """
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, ppo_net
 from . import ppo_lunarlander as base
 from .envs import VecEnv
 
@@ -104,6 +106,16 @@ class PPOTrainer(base.PPOTrainer):
 
     def _packed_actions(self):
         return self.buffer.actions.view(torch.int32).view(-1)
+
+    def _fused_update_for(self, mb):
+        cfg = self.cfg
+        if not (cfg.fused_update and ppo_net.gauss_supported(self.model)) or self.collective:
+            return None                                             # autograd's _loss_backward below (multi-rank included)
+        if self._fused_update is None or self._fused_update.R < mb:
+            self._fused_update = ppo_net.FusedGaussianUpdate(self.model, mb)
+        fu = self._fused_update
+        fu.timers = self._timers
+        return fu
 
     def _loss_backward(self, mb_obs, mb_act, mb_lp, mb_adv, mb_ret, row, tm):
         B = mb_obs.shape[0]

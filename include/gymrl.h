@@ -198,6 +198,9 @@ int gymrl_categorical_sample(const float* logits, const float* value_in,
  *             with g_lp = dL/dlogp and g_H = -entropy_coef / B of a row:
  *             dmu_k = g_lp * (z_k * det_expf(-log_std_k)),  dvalue as L1,
  *             dlog_std_k = sum over rows of (g_lp * (z_k * z_k - 1.0f) + g_H), each row's float32 term added in float64.
+ *   update    the two MLPs through torch autograd around gymrl_ppo_gauss_loss_fwd_bwd, or the hand-scheduled minibatch of
+ *             ppo_net.FusedGaussianUpdate with the heads, this loss and dlog_std as ONE pass over the pre-activations:
+ *             gymrl_gauss_heads_loss_fwd_bwd below (A == 1, gated by gymrl_ppo_gauss_update_shape_ok); the same row arithmetic.
  *
  * gymrl_gaussian_sample: mu f32[N, A], log_std f32[A], value_in f32[N] or NULL (copied to value_out), noise_normal f32[N, A] or
  * NULL -> act_out f32[N, A], logp_out f32[N], ent_out f32[N] or NULL.  `online`: gymrl_categorical_sample's producer side of GAE
@@ -1247,6 +1250,42 @@ int gymrl_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* b
                              const double* adv_moments, const gymrl_ppo_cfg* cfg, float* dbac, float* dWa2,
                              float* dba2, float* dWc2, float* dbc2, double* metric_parts, void* workspace,
                              void* stream);
+/*
+ * The same ONE pass under the Gaussian policy ("Gaussian policy" above; ppo_net.FusedGaussianUpdate): the actor head's A sums
+ * plus ba2 are the mean mu[A], log_std f32[A] is read from device memory, act f32[B, A] holds the minibatch's stored actions in
+ * order, and a row's loss and gradients are gymrl_ppo_gauss_loss_fwd_bwd's, bit for bit (one shared device function).  Layout,
+ * the advantage normalisation from adv_moments, dZac in place, the five head gradients, `workspace`
+ * (gymrl_mlp_train_workspace_bytes(C, D, A)) and metric_parts f64[gymrl_heads_loss_blocks(B, C)][5] are
+ * gymrl_heads_loss_fwd_bwd's.  The five head gradients and dlog_std_out f32[A] are all required (written, not accumulated):
+ * there is no "block partials only" mode, gymrl_update_finalize stays the categorical head's.  No host synchronisation, no
+ * float atomics, capturable in a hipGraph.
+ * dlog_std is a fixed-order reduction whose order depends on B and C alone.  With rpw = 256 / C rows per wave-load, rows
+ * [8 rpw j, 8 rpw j + 8 rpw) are batch j (32 / 16 / 8 rows at C = 64 / 128 / 256) and row 8 rpw j + l sits in lane l of the wave
+ * that walks the batch.  A row's float32 term (g_lp * (z_k * z_k - 1.0f) + g_H) is widened to float64; lanes without a row hold
+ * 0.0; the wave's 64 lanes are added by the halving tree v[l] += v[l + off], off = 32, 16, .. 1, and lane 0's sum is stored to
+ * dls_workspace f64[ceil(B / (8 rpw))][A] (gymrl_gauss_heads_loss_workspace_bytes(B, C, A) bytes, 8-byte aligned) at row j —
+ * by the batch's number, whichever wave of whichever workgroup walked it.  A second launch of ONE workgroup then adds the
+ * batches: thread t of 256 adds batches t, t + 256, t + 512, .. in ascending order, a wave's 64 threads are added by the same
+ * halving tree, the four waves' sums are added in order 0, 1, 2, 3, and the result is rounded to float32 once.
+ * grid_blocks: 0 = gymrl_heads_loss_blocks(B, C) workgroups; a smaller positive value narrows the grid (tests; a larger one is
+ * the default).  The batches are dealt to gymrl_heads_loss_blocks(B, C) virtual workgroups whatever the grid, and a workgroup of
+ * a narrower grid runs several of them one after the other, each to its own partial row and metric row: dZac, the six
+ * gradients and every row of metric_parts carry the same bits under every grid.
+ * -22 before any launch: C not in {64, 128, 256}, A != 1, B <= 0, grid_blocks < 0, Zac (or a given bac) off 16 bytes,
+ * metric_parts or dls_workspace off 8 bytes, or a NULL among Zac, Wa2, Wc2, log_std, act, logp_old, adv, ret, cfg, the six
+ * gradient outputs, metric_parts, workspace, dls_workspace (bac, ba2, bc2 and adv_moments may be NULL).
+ * gymrl_ppo_gauss_update_shape_ok: 1 where that update covers a GaussianActorCritic of hidden width C, observation width D and
+ * A action components: C in {64, 128, 256}, D in {2, 3, 4, 6, 8}, A == 1; 0 otherwise.  Host only.  gymrl_ppo_update_shape_ok and
+ * the categorical entry points answer A = 1 as they always did.
+ */
+int gymrl_ppo_gauss_update_shape_ok(int C, int D, int A);
+size_t gymrl_gauss_heads_loss_workspace_bytes(int64_t B, int C, int A);
+int gymrl_gauss_heads_loss_fwd_bwd(float* Zac, int64_t B, int C, int A, const float* bac, const float* Wa2,
+                                   const float* ba2, const float* Wc2, const float* bc2, const float* log_std,
+                                   const float* act, const float* logp_old, const float* adv, const float* ret,
+                                   const double* adv_moments, const gymrl_ppo_cfg* cfg, float* dbac, float* dWa2,
+                                   float* dba2, float* dWc2, float* dbc2, float* dlog_std_out, double* metric_parts,
+                                   void* workspace, void* dls_workspace, int grid_blocks, void* stream);
 
 /* ===================================================== update-path GEMMs === */
 /*
