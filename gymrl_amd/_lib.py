@@ -397,6 +397,15 @@ class EsShapeGradArgs(C.Structure):
                 ("generation", C.c_uint64), ("returns", C.c_void_p), ("grad", C.c_void_p), ("weights", C.c_void_p)]
 
 
+class TabularTrainArgs(C.Structure):
+    _c_name_ = "gymrl_tabular_train_args"
+    _fields_ = [("rule", C.c_int), ("env_kind", C.c_int), ("is_slippery", C.c_int), ("shaped", C.c_int), ("Q", C.c_void_p),
+                ("state", C.c_void_p), ("n_runs", C.c_int), ("restart", C.c_int), ("seed", C.c_uint64), ("run_id0", C.c_int64),
+                ("eps_table", C.c_void_p), ("max_episodes", C.c_int), ("max_steps", C.c_int), ("max_iters", C.c_int),
+                ("lr", C.c_double), ("gamma", C.c_double), ("episode_rewards", C.c_void_p), ("episode_lengths", C.c_void_p),
+                ("k_out", C.c_void_p), ("episodes_out", C.c_void_p), ("Q2", C.c_void_p), ("eps_len", C.c_int64)]
+
+
 class SnesPerturbArgs(C.Structure):
     _c_name_ = "gymrl_snes_perturb_args"
     _fields_ = [("n", C.c_int), ("P", C.c_int), ("stride", C.c_int64), ("seed", C.c_uint64), ("generation", C.c_uint64),
@@ -669,6 +678,9 @@ SIGNATURES = {
     "gymrl_qlearn_state_bytes": (_sz, [_i]),
     "gymrl_qlearn_train": (_i, [_i, _i, _i, _vp, _vp, _i, _i, _u64, _i64, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_qlearn_eval": (_i, [_i, _i, _vp, _i, _i, _u64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "gymrl_tabular_state_bytes": (_sz, [_i, _i]),
+    "gymrl_tabular_args_bytes": (_sz, []),
+    "gymrl_tabular_train": (_i, [_P(TabularTrainArgs), _vp]),
     "gymrl_snes_perturb_args_bytes": (_sz, []),
     "gymrl_snes_tell_args_bytes": (_sz, []),
     "gymrl_snes_perturb": (_i, [_P(SnesPerturbArgs), _vp]),

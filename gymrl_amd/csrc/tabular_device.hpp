@@ -82,6 +82,10 @@ __device__ __forceinline__ double max4(double q0, double q1, double q2, double q
   m = q1 > m ? q1 : m; m = q2 > m ? q2 : m; m = q3 > m ? q3 : m;
   return m;
 }
+// entry a of a row held in four registers, by selects (a runtime-indexed register array would go to scratch)
+__device__ __forceinline__ double pick4(int a, double q0, double q1, double q2, double q3) {
+  return a == 0 ? q0 : (a == 1 ? q1 : (a == 2 ? q2 : q3));
+}
 
 constexpr int kActions = 4;
 
@@ -96,6 +100,17 @@ struct RunState {
   __host__ __device__ RunState(void* buf, int n) {
     Carver c(buf, n);
     ep_ret = c.take<double>(); state = c.take<int32_t>(); episode = c.take<int32_t>(); step = c.take<int32_t>(); k = c.take<int32_t>();
+    bytes = c.off;
+  }
+};
+// gymrl_tabular_train's record: RunState (so rule 0 hands it to the Q-learning kernel as it is) and, behind it, SARSA's pending
+// action — the one select(s) drew for the step not yet taken, -1 where the next iteration draws afresh
+struct TdRunState : RunState {
+  int32_t* pending;
+  __host__ __device__ TdRunState(void* buf, int n) : RunState(buf, n) {
+    Carver c(buf, n);
+    c.off = bytes;
+    pending = c.take<int32_t>();
     bytes = c.off;
   }
 };

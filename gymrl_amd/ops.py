@@ -11,7 +11,7 @@ import torch
 
 from ._lib import (ACT_NONE, ACT_RELU, ACT_TANH, MLP_MAX_INPUT, MLP_MAX_STAGES, MLP_MAX_WIDTH, ClassicDuelEvalArgs, ClassicEvalArgs, ClassicPpoEvalArgs, DdqnUpdateArgs, EsNoiseArgs, EsPerturbArgs, EsShapeGradArgs, SnesPerturbArgs, SnesTellArgs, DqnActArgs, NdqnActArgs, NdqnCombineArgs, NdqnUpdateArgs, DqnUpdateArgs, DsacActArgs, DsacUpdateArgs, GaeOnline,
                    LunarCollectArgs, LunarEvalArgs, PendulumPpoEvalArgs, RolloutPendulumArgs, MlpDesc, MlpPackStackArgs, MlprnnParams, AcrobotNetEvalArgs, MountainCarEvalArgs, MountainCarNetEvalArgs, PPOCfg, PPOFullCfg, RainbowActArgs, RainbowUpdateArgs, RolloutLunarArgs, SacActArgs, SacUpdateArgs,
-                   Td3ActArgs, Td3UpdateArgs, check, lib)
+                   TabularTrainArgs, Td3ActArgs, Td3UpdateArgs, check, lib)
 
 _vp = C.c_void_p
 
@@ -834,6 +834,44 @@ def qlearn_eval(kind, Q, n_episodes, seed, stream_id0, cap, is_slippery=False):
     check(lib().gymrl_qlearn_eval(kind, int(bool(is_slippery)), _ptr(Q, torch.float64), R, n_episodes, seed, stream_id0, cap,
                                   _ptr(returns), _ptr(lengths), _ptr(flags), _stream()), "gymrl_qlearn_eval")
     return returns, lengths, flags
+
+
+TABULAR_RULES = {"qlearning": 0, "sarsa": 1, "expected_sarsa": 2, "double_q": 3}     # GYMRL_TABULAR_RULE_*
+
+
+def tabular_draws(rule, max_episodes, max_steps):
+    """Draws one run can take = the entries of the epsilon table: SARSA's episode that runs out has drawn one action more."""
+    return max_episodes * (max_steps + (1 if rule == TABULAR_RULES["sarsa"] else 0))
+
+
+def tabular_state_bytes(rule, n_runs):
+    return int(lib().gymrl_tabular_state_bytes(rule, n_runs))
+
+
+def tabular_train(rule, kind, Q, state, eps_table, seed, run_id0, max_episodes, max_steps, max_iters, lr, gamma, episode_rewards,
+                  episode_lengths, k_out, episodes_out, Q2=None, is_slippery=False, shaped=False, restart=False):
+    """qlearn_train under one of TABULAR_RULES' values (include/gymrl.h states the loops): at most max_iters draws of every run in
+    ONE launch.  Q2 f64[R, S, 4] is Double Q-learning's second table (None otherwise); eps_table has tabular_draws(...) entries;
+    `state` holds tabular_state_bytes(rule, R) bytes."""
+    R = Q.shape[0]
+    shape = (R, TABULAR_STATES.get(kind, -1), TABULAR_ACTIONS)
+    if tuple(Q.shape) != shape or (Q2 is not None and tuple(Q2.shape) != shape):
+        raise ValueError(f"Q is {tuple(Q.shape)}, env kind {kind} needs [R, {TABULAR_STATES.get(kind)}, {TABULAR_ACTIONS}]")
+    if rule not in TABULAR_RULES.values() or (Q2 is not None) != (rule == TABULAR_RULES["double_q"]):
+        raise ValueError(f"tabular_train: rule {rule} with{'out' if Q2 is None else ''} a second table")
+    if eps_table.numel() != tabular_draws(rule, max_episodes, max_steps) or tuple(episode_rewards.shape) != (R, max_episodes) or \
+            tuple(episode_lengths.shape) != (R, max_episodes) or k_out.numel() != R or episodes_out.numel() != R or \
+            state.numel() < tabular_state_bytes(rule, R):
+        raise ValueError("tabular_train: a buffer does not have the size its rule, run count and episode budget ask for")
+    a = TabularTrainArgs()
+    a.rule, a.env_kind, a.is_slippery, a.shaped = rule, kind, int(bool(is_slippery)), int(bool(shaped))
+    a.Q, a.state, a.n_runs, a.restart = _ptr(Q, torch.float64), _ptr(state, torch.uint8), R, int(bool(restart))
+    a.seed, a.run_id0, a.eps_table, a.eps_len = seed, run_id0, _ptr(eps_table, torch.float64), eps_table.numel()
+    a.max_episodes, a.max_steps, a.max_iters, a.lr, a.gamma = max_episodes, max_steps, max_iters, lr, gamma
+    a.episode_rewards, a.episode_lengths = _ptr(episode_rewards, torch.float64), _ptr(episode_lengths, torch.int32)
+    a.k_out, a.episodes_out = _ptr(k_out, torch.int32), _ptr(episodes_out, torch.int32)
+    a.Q2 = None if Q2 is None else _ptr(Q2, torch.float64)
+    check(lib().gymrl_tabular_train(C.byref(a), _stream()), "gymrl_tabular_train")
 
 
 # ------------------------------------------- MountainCar-v0 rule baseline ---

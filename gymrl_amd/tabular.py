@@ -4,6 +4,8 @@ runs behind the reference's QLearningTrainer surface (qlearning_frozenlake.py:36
 train() is csrc/tabular.hip's gymrl_qlearn_train: one lane per run, every run's table in LDS, `steps_per_launch` steps of
 every run per launch and nothing but the launches in between.  eval() / test() are gymrl_qlearn_eval.  select_action() and
 update() are the reference's two methods restated on the host in float64 for one run; they are not on the hot path.
+TabularTD (below) is the same population under SARSA, Expected SARSA or Double Q-learning: sarsa_frozenlake.py /
+sarsa_cliffwalking.py.
 """
 import math
 
@@ -92,25 +94,39 @@ class TabularQLearning:
     def _flags(self):
         return dict(is_slippery=bool(getattr(self.cfg, "is_slippery", False)), shaped=bool(getattr(self.cfg, "use_reward_shaping", False)))
 
-    def _tables(self):
-        return torch.from_numpy(np.ascontiguousarray(self.Q, np.float64).reshape(self.num_runs, self.n_states, self.n_actions)).to(self.device)
+    def _tables(self, Q):
+        return torch.from_numpy(np.ascontiguousarray(Q, np.float64).reshape(self.num_runs, self.n_states, self.n_actions)).to(self.device)
+
+    # what a rule other than Q-learning changes about train() and _evaluate() (TabularTD below)
+    def _draw_budget(self):
+        return self.cfg.max_episodes * self.cfg.max_steps
+
+    def _state_bytes(self):
+        return ops.qlearn_state_bytes(self.num_runs)
+
+    def _launch(self, Q, state, eps, chunk, rew, length, k_dev, done_dev, restart):
+        cfg = self.cfg
+        ops.qlearn_train(self.kind, Q, state, eps, cfg.seed, cfg.run_id0, cfg.max_episodes, cfg.max_steps, chunk, cfg.lr, cfg.gamma,
+                         rew, length, k_dev, done_dev, restart=restart, **self._flags())
+
+    def _greedy_table(self):
+        return self.Q
 
     def train(self):
         print("Starting training...")
         cfg, R, dev = self.cfg, self.num_runs, self.device
-        total = cfg.max_episodes * cfg.max_steps
+        total = self._draw_budget()
         chunk = int(cfg.steps_per_launch) if cfg.steps_per_launch else total
         eps = torch.tensor([self._epsilon_at(k) for k in range(1, total + 1)], dtype=torch.float64).to(dev)
-        Q = self._tables()
-        state = torch.zeros(ops.qlearn_state_bytes(R), dtype=torch.uint8, device=dev)
+        Q = self._tables(self.Q)
+        state = torch.zeros(self._state_bytes(), dtype=torch.uint8, device=dev)
         rew = torch.zeros(R, cfg.max_episodes, dtype=torch.float64, device=dev)
         length = torch.zeros(R, cfg.max_episodes, dtype=torch.int32, device=dev)
         k_dev = torch.zeros(R, dtype=torch.int32, device=dev)
         done_dev = torch.zeros(R, dtype=torch.int32, device=dev)
         reported, launched = 0, 0
         while True:
-            ops.qlearn_train(self.kind, Q, state, eps, cfg.seed, cfg.run_id0, cfg.max_episodes, cfg.max_steps, chunk, cfg.lr, cfg.gamma,
-                             rew, length, k_dev, done_dev, restart=launched == 0, **self._flags())
+            self._launch(Q, state, eps, chunk, rew, length, k_dev, done_dev, restart=launched == 0)
             launched += chunk
             finished = int(done_dev.min().item())              # episodes every run has behind it
             if finished // self.report_every > reported // self.report_every:
@@ -141,5 +157,80 @@ class TabularQLearning:
         """(returns, lengths, reached) of num_episodes greedy episodes per run, numpy [R, num_episodes].  stream_offset moves the
         env draws to another block of streams: test()'s extra episode uses VISUAL_STREAM_OFFSET, so it is not eval()'s first."""
         stream0 = EVAL_STREAM0 + stream_offset + self.cfg.run_id0 * num_episodes
-        out = ops.qlearn_eval(self.kind, self._tables(), num_episodes, self.cfg.seed, stream0, cap, is_slippery=self._flags()["is_slippery"])
+        out = ops.qlearn_eval(self.kind, self._tables(self._greedy_table()), num_episodes, self.cfg.seed, stream0, cap, is_slippery=self._flags()["is_slippery"])
         return tuple(t.cpu().numpy() for t in out)
+
+
+def step_coin(seed, stream, k):
+    """Double Q-learning's coin of (stream, k): the low bit of the word whose top bits are the exploring action."""
+    return philox4x32(seed, stream & 0xFFFFFFFF, stream >> 32, k, RNG_TABULAR)[2] & 1
+
+
+class TabularTD(TabularQLearning):
+    """The same population under Config.rule: "sarsa", "expected_sarsa", "double_q" or "qlearning" (include/gymrl.h states
+    the loops; csrc/tabular.hip's gymrl_tabular_train runs them).  Double Q-learning keeps its second table in self.Q2 and acts
+    and evaluates on Q + Q2.  select_action() / update() restate the rule on the host for one run: SARSA's update takes the
+    next action, Expected SARSA's uses the epsilon select_action drew with, Double Q-learning's the coin of that draw."""
+
+    def __init__(self, config):
+        if config.rule not in ops.TABULAR_RULES:
+            raise ValueError(f"rule is {config.rule!r}: one of {sorted(ops.TABULAR_RULES)}")
+        super().__init__(config)
+        self.rule = ops.TABULAR_RULES[config.rule]
+        self.Q2 = np.zeros_like(self.Q) if config.rule == "double_q" else None
+        print(f"Rule: {config.rule}")
+
+    def _greedy_table(self):
+        return self.Q if self.Q2 is None else self.Q + self.Q2
+
+    def select_action(self, state, deterministic=False):
+        self._one_run("select_action")
+        if not deterministic:
+            eps = self._get_epsilon()
+            u, explore, _ = step_draw(self.cfg.seed, self.cfg.run_id0, self.sample_count, self.n_actions)
+            if u < eps:
+                return int(explore)
+        return int(np.argmax(self._greedy_table()[state, :]))
+
+    def update(self, state, action, reward, next_state, done, next_action=None):
+        self._one_run("update")
+        cfg, rule, Q = self.cfg, self.cfg.rule, self.Q
+        if rule == "double_q" and step_coin(cfg.seed, cfg.run_id0, self.sample_count):
+            Q, other = self.Q2, self.Q
+        elif rule == "double_q":
+            other = self.Q2
+        if done:
+            target = reward
+        elif rule == "sarsa":
+            if next_action is None:
+                raise ValueError("SARSA's update needs the action select_action chose in next_state")
+            target = reward + cfg.gamma * Q[next_state, next_action]
+        elif rule == "expected_sarsa":
+            q0, q1, q2, q3 = Q[next_state, :]
+            eps = self.epsilon
+            target = reward + cfg.gamma * (eps * 0.25 * (((q0 + q1) + q2) + q3) + (1.0 - eps) * max(q0, q1, q2, q3))
+        elif rule == "double_q":
+            target = reward + cfg.gamma * other[next_state, int(np.argmax(Q[next_state, :]))]
+        else:
+            target = reward + cfg.gamma * np.max(Q[next_state, :])
+        predict = Q[state, action]
+        Q[state, action] = predict + cfg.lr * (target - predict)
+
+    # ---- the population on the device ----
+    def _draw_budget(self):
+        return ops.tabular_draws(self.rule, self.cfg.max_episodes, self.cfg.max_steps)
+
+    def _state_bytes(self):
+        return ops.tabular_state_bytes(self.rule, self.num_runs)
+
+    def _launch(self, Q, state, eps, chunk, rew, length, k_dev, done_dev, restart):
+        cfg = self.cfg
+        ops.tabular_train(self.rule, self.kind, Q, state, eps, cfg.seed, cfg.run_id0, cfg.max_episodes, cfg.max_steps, chunk, cfg.lr,
+                          cfg.gamma, rew, length, k_dev, done_dev, Q2=self._Q2_dev, restart=restart, **self._flags())
+
+    def train(self):
+        self._Q2_dev = None if self.Q2 is None else self._tables(self.Q2)
+        super().train()
+        if self.Q2 is not None:
+            self.Q2 = self._Q2_dev.cpu().numpy().reshape(self.Q2.shape)
+        self._Q2_dev = None

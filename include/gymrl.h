@@ -1961,6 +1961,57 @@ int gymrl_qlearn_train(int env_kind, int is_slippery, int shaped, double* Q, voi
                        void* stream);
 int gymrl_qlearn_eval(int env_kind, int is_slippery, const double* Q, int n_runs, int n_episodes, uint64_t seed,
                       int64_t stream_id0, int cap, double* returns, int32_t* lengths, uint8_t* flags, void* stream);
+/* Three more temporal-difference control rules on the same envs, draws and layout (csrc/tabular.hip: td_train_kernel; no reference
+ * script).  select(s): k += 1; (u, explore, _) = the draw of (seed, stream, k); explore if u < eps_k, else the FIRST maximum of
+ * the row the rule acts on.  Float64, every operation one rounding in the order written, no fused multiply-add.
+ *   GYMRL_TABULAR_RULE_SARSA
+ *     s = start; a = select(s)
+ *     for step in range(max_steps):
+ *         s2, r, done = env.step(a)              (slip word: the draw of the k that chose a)
+ *         if done: target = r
+ *         else:    a2 = select(s2); target = r + gamma * Q[s2, a2]
+ *         Q[s, a] = Q[s, a] + lr * (target - Q[s, a])
+ *         if done: break
+ *         s, a = s2, a2
+ *     a2 is chosen from the table BEFORE this step's write (it matters when s2 == s).  When the loop runs out at max_steps
+ *     without done, the last a2 has been drawn and k has advanced; it is dropped and the next episode draws afresh.  An episode
+ *     takes up to max_steps + 1 draws: eps_table needs max_episodes * (max_steps + 1) entries, and that product is the one
+ *     held below 2^31.  One iteration of the kernel is one draw, so max_iters counts draws here.
+ *   GYMRL_TABULAR_RULE_EXPECTED_SARSA
+ *     Q-learning's loop (one select per step) with, for eps = the eps_k that select used for this step and q0..q3 = Q[s2, :]
+ *     before the write,
+ *         target = r + gamma * (eps * 0.25 * (((q0 + q1) + q2) + q3) + (1.0 - eps) * max(q0..q3))
+ *   GYMRL_TABULAR_RULE_DOUBLE_Q
+ *     Q-learning's loop on two tables.  select acts on the row QA[s, j] + QB[s, j] (one add per action, first maximum).  The
+ *     coin is word 2 of the step's draw & 1; the exploring action keeps that word's top bits, (w * 4) >> 32.
+ *         coin 0: a* = first maximum of QA[s2, :], target = r + gamma * QB[s2, a*], QA[s, a] = QA[s, a] + lr * (target - QA[s, a])
+ *         coin 1: the same with QA and QB exchanged
+ *     done gives target = r.  Greedy evaluation: gymrl_qlearn_eval on the elementwise float64 sum QA + QB, formed by the caller.
+ * gymrl_tabular_train is gymrl_qlearn_train behind one struct: `rule` in front of that call's arguments, behind them Q2 (QB:
+ * f64[n_runs, S, 4] for DOUBLE_Q, NULL for every other rule) and eps_len, the entries of eps_table (at least max_episodes *
+ * max_steps; SARSA: max_episodes * (max_steps + 1)).  `state` holds gymrl_tabular_state_bytes(rule, n_runs) bytes (0 for an
+ * unknown rule or n_runs <= 0): gymrl_qlearn_train's record and SARSA's pending action behind it, so a call continues the one
+ * before it bit for bit wherever max_iters cut it.  GYMRL_TABULAR_RULE_QLEARNING writes gymrl_qlearn_train's bits.  -22 before
+ * anything is launched: NULL args, what gymrl_qlearn_train refuses, an unknown rule, Q2 present or absent against the rule or
+ * misaligned, eps_len shorter than the rule needs, SARSA's max_episodes * (max_steps + 1) >= 2^31.  max_iters == 0 without
+ * restart: 0, nothing launched. */
+enum { GYMRL_TABULAR_RULE_QLEARNING = 0, GYMRL_TABULAR_RULE_SARSA = 1, GYMRL_TABULAR_RULE_EXPECTED_SARSA = 2, GYMRL_TABULAR_RULE_DOUBLE_Q = 3 };
+typedef struct {
+  int rule;                                /* GYMRL_TABULAR_RULE_* */
+  int env_kind, is_slippery, shaped;
+  double* Q; void* state;
+  int n_runs, restart;
+  uint64_t seed; int64_t run_id0;
+  const double* eps_table;
+  int max_episodes, max_steps, max_iters;
+  double lr, gamma;
+  double* episode_rewards; int32_t* episode_lengths; int32_t* k_out; int32_t* episodes_out;
+  double* Q2;                              /* DOUBLE_Q: QB in / out; NULL otherwise */
+  int64_t eps_len;                         /* entries of eps_table */
+} gymrl_tabular_train_args;
+size_t gymrl_tabular_state_bytes(int rule, int n_runs);
+size_t gymrl_tabular_args_bytes(void);       /* sizeof(gymrl_tabular_train_args) */
+int gymrl_tabular_train(const gymrl_tabular_train_args* args, void* stream);
 
 /* ---- separable NES on the population evaluators (csrc/es.hip; no reference script) ------------------------------------------
  * The second learner on the evolution-strategies block's noise, ranks and summation contract (above the tabular runs; tests pin
