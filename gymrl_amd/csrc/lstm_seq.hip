@@ -372,6 +372,9 @@ inline int grid_for(int64_t work) {
 }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// T = 0 or B = 0 leaves the [T,B,*] arrays without an element, and an allocator hands out NULL for those
+inline bool seq_elems(int T, int B) { return T > 0 && B > 0; }
+
 inline bool lens_ok(const int32_t* len, int B, int T) {
   for (int b = 0; b < B; ++b)
     if (len[b] < 0 || len[b] > T) return false;
@@ -409,7 +412,8 @@ int gymrl_lstm_cell_bwd(const float* gi, const float* gh, const float* c, const 
 int gymrl_lstm_seq_fwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const float* c0,
                        const int32_t* len, int T, int B, int H, float* h_seq, float* c_seq, float* h_last, float* c_last,
                        void* stream) {
-  if (!gi || !W_hh || !b_hh || !len || !h_seq || !c_seq || T < 0 || B < 0) return -22;
+  if (!W_hh || !b_hh || !len || T < 0 || B < 0) return -22;
+  if (seq_elems(T, B) && (!gi || !h_seq || !c_seq)) return -22;       // an empty [T,B,*] array may be NULL
   if (H != 16 && H != 32 && H != 48 && H != 64) return -22;
   if (!aligned16(W_hh) || !aligned16(h_seq) || (h0 && !aligned16(h0))) return -22;
   if (!lens_ok(len, B, T)) return -22;
@@ -438,7 +442,8 @@ int gymrl_lstm_seq_bwd(const float* gi, const float* W_hh, const float* b_hh, co
                        const float* h_seq, const float* c_seq, const float* d_hseq, const float* d_hlast,
                        const float* d_clast, const int32_t* len, int T, int B, int H, float* dgates, float* dh0, float* dc0,
                        void* stream) {
-  if (!gi || !W_hh || !b_hh || !h_seq || !c_seq || !len || !dgates || T < 0 || B < 0) return -22;
+  if (!W_hh || !b_hh || !len || T < 0 || B < 0) return -22;
+  if (seq_elems(T, B) && (!gi || !h_seq || !c_seq || !dgates)) return -22;   // an empty [T,B,*] array may be NULL
   if (H != 16 && H != 32 && H != 48 && H != 64) return -22;
   if (!aligned16(W_hh) || !aligned16(h_seq) || (h0 && !aligned16(h0))) return -22;
   if (!lens_ok(len, B, T)) return -22;

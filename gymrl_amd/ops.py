@@ -367,19 +367,26 @@ def gru_seq_fwd(gi, W_hh, b_hh, lengths, h0=None, h_seq=None, h_last=None):
     return h_seq, h_last
 
 
-def gru_seq_bwd(gi, W_hh, b_hh, h_seq, lengths, d_hseq=None, d_hlast=None, h0=None, need_dh0=True):
-    """Reverse recurrence of gru_seq_fwd (gymrl_gru_seq_bwd).  Returns (dgi, dgh f32[T,B,3H], dh0 f32[B,H] or None)."""
+def gru_seq_bwd(gi, W_hh, b_hh, h_seq, lengths, d_hseq=None, d_hlast=None, h0=None, need_dh0=True, dgi=None, dgh=None,
+                dh0=None):
+    """Reverse recurrence of gru_seq_fwd (gymrl_gru_seq_bwd).  Returns (dgi, dgh f32[T,B,3H], dh0 f32[B,H] or None);
+    dgi, dgh, dh0: the caller's buffers to write them into."""
     T, B, H3 = gi.shape
     H = H3 // 3
     lens, nb = _host_i32(lengths)
+    if dh0 is not None and not need_dh0:
+        raise ValueError("dh0 given with need_dh0=False")
     _gru_seq_shapes(gi, W_hh, b_hh, h0, nb, T, B, H, h_seq=(h_seq, (T, B, H)), d_hseq=(d_hseq, (T, B, H)),
-                    d_hlast=(d_hlast, (B, H)))
-    dgi, dgh = torch.empty_like(gi), torch.empty_like(gi)
-    dh0 = torch.empty(B, H, dtype=torch.float32, device=gi.device) if need_dh0 else None
+                    d_hlast=(d_hlast, (B, H)), dgi=(dgi, (T, B, H3)), dgh=(dgh, (T, B, H3)), dh0=(dh0, (B, H)))
+    dgi = torch.empty_like(gi) if dgi is None else dgi
+    dgh = torch.empty_like(gi) if dgh is None else dgh
+    if need_dh0 and dh0 is None:
+        dh0 = torch.empty(B, H, dtype=torch.float32, device=gi.device)
     check(lib().gymrl_gru_seq_bwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
                                   _ptr(h0, torch.float32, True), _ptr(h_seq, torch.float32),
                                   _ptr(d_hseq, torch.float32, True), _ptr(d_hlast, torch.float32, True), lens, T, B, H,
-                                  _ptr(dgi), _ptr(dgh), _ptr(dh0, torch.float32, True), _stream()), "gymrl_gru_seq_bwd")
+                                  _ptr(dgi, torch.float32), _ptr(dgh, torch.float32), _ptr(dh0, torch.float32, True), _stream()),
+          "gymrl_gru_seq_bwd")
     return dgi, dgh, dh0
 
 
@@ -421,42 +428,49 @@ def _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, lens_len, T, B, H, **more):
         _need_shape(t, shape, name)
 
 
-def lstm_seq_fwd(gi, W_hh, b_hh, lengths, h0=None, c0=None):
+def lstm_seq_fwd(gi, W_hh, b_hh, lengths, h0=None, c0=None, h_seq=None, c_seq=None, h_last=None, c_last=None):
     """The LSTM recurrence in one launch (gymrl_lstm_seq_fwd).  gi f32[T,B,4H] time-major, lengths: host ints [B].
-    Returns (h_seq, c_seq f32[T,B,H], zero past each length; h_last, c_last f32[B,H])."""
-    if gi.dim() != 3:
-        raise ValueError(f"gi: expected [T, B, 4H], got {tuple(gi.shape)}")
-    T, B, H4 = gi.shape
-    H = H4 // 4
-    lens, nb = _host_i32(lengths)
-    _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, nb, T, B, H)
-    h_seq, c_seq = (torch.empty(T, B, H, dtype=torch.float32, device=gi.device) for _ in range(2))
-    h_last, c_last = (torch.empty(B, H, dtype=torch.float32, device=gi.device) for _ in range(2))
-    check(lib().gymrl_lstm_seq_fwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
-                                   _ptr(h0, torch.float32, True), _ptr(c0, torch.float32, True), lens, T, B, H, _ptr(h_seq),
-                                   _ptr(c_seq), _ptr(h_last), _ptr(c_last), _stream()), "gymrl_lstm_seq_fwd")
-    return h_seq, c_seq, h_last, c_last
-
-
-def lstm_seq_bwd(gi, W_hh, b_hh, h_seq, c_seq, lengths, d_hseq=None, d_hlast=None, d_clast=None, h0=None, c0=None,
-                 need_d0=True):
-    """Reverse recurrence of lstm_seq_fwd (gymrl_lstm_seq_bwd).  Returns (dgates f32[T,B,4H] = dgi = dgh, dh0, dc0
-    f32[B,H] or None)."""
+    Returns (h_seq, c_seq f32[T,B,H], zero past each length; h_last, c_last f32[B,H]); each may be given as the caller's
+    buffer to write into."""
     if gi.dim() != 3:
         raise ValueError(f"gi: expected [T, B, 4H], got {tuple(gi.shape)}")
     T, B, H4 = gi.shape
     H = H4 // 4
     lens, nb = _host_i32(lengths)
     _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, nb, T, B, H, h_seq=(h_seq, (T, B, H)), c_seq=(c_seq, (T, B, H)),
-                     d_hseq=(d_hseq, (T, B, H)), d_hlast=(d_hlast, (B, H)), d_clast=(d_clast, (B, H)))
-    dgates = torch.empty_like(gi)
-    dh0, dc0 = ((torch.empty(B, H, dtype=torch.float32, device=gi.device) for _ in range(2)) if need_d0 else (None, None))
+                     h_last=(h_last, (B, H)), c_last=(c_last, (B, H)))
+    h_seq, c_seq = (torch.empty(T, B, H, dtype=torch.float32, device=gi.device) if t is None else t for t in (h_seq, c_seq))
+    h_last, c_last = (torch.empty(B, H, dtype=torch.float32, device=gi.device) if t is None else t for t in (h_last, c_last))
+    check(lib().gymrl_lstm_seq_fwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
+                                   _ptr(h0, torch.float32, True), _ptr(c0, torch.float32, True), lens, T, B, H,
+                                   _ptr(h_seq, torch.float32), _ptr(c_seq, torch.float32), _ptr(h_last, torch.float32),
+                                   _ptr(c_last, torch.float32), _stream()), "gymrl_lstm_seq_fwd")
+    return h_seq, c_seq, h_last, c_last
+
+
+def lstm_seq_bwd(gi, W_hh, b_hh, h_seq, c_seq, lengths, d_hseq=None, d_hlast=None, d_clast=None, h0=None, c0=None,
+                 need_d0=True, dgates=None, dh0=None, dc0=None):
+    """Reverse recurrence of lstm_seq_fwd (gymrl_lstm_seq_bwd).  Returns (dgates f32[T,B,4H] = dgi = dgh, dh0, dc0
+    f32[B,H] or None); dgates, dh0, dc0: the caller's buffers to write them into."""
+    if gi.dim() != 3:
+        raise ValueError(f"gi: expected [T, B, 4H], got {tuple(gi.shape)}")
+    T, B, H4 = gi.shape
+    H = H4 // 4
+    lens, nb = _host_i32(lengths)
+    if not need_d0 and (dh0 is not None or dc0 is not None):
+        raise ValueError("dh0 / dc0 given with need_d0=False")
+    _lstm_seq_shapes(gi, W_hh, b_hh, h0, c0, nb, T, B, H, h_seq=(h_seq, (T, B, H)), c_seq=(c_seq, (T, B, H)),
+                     d_hseq=(d_hseq, (T, B, H)), d_hlast=(d_hlast, (B, H)), d_clast=(d_clast, (B, H)),
+                     dgates=(dgates, (T, B, H4)), dh0=(dh0, (B, H)), dc0=(dc0, (B, H)))
+    dgates = torch.empty_like(gi) if dgates is None else dgates
+    if need_d0:
+        dh0, dc0 = (torch.empty(B, H, dtype=torch.float32, device=gi.device) if t is None else t for t in (dh0, dc0))
     check(lib().gymrl_lstm_seq_bwd(_ptr(gi, torch.float32), _ptr(W_hh, torch.float32), _ptr(b_hh, torch.float32),
                                    _ptr(h0, torch.float32, True), _ptr(c0, torch.float32, True), _ptr(h_seq, torch.float32),
                                    _ptr(c_seq, torch.float32), _ptr(d_hseq, torch.float32, True),
                                    _ptr(d_hlast, torch.float32, True), _ptr(d_clast, torch.float32, True), lens, T, B, H,
-                                   _ptr(dgates), _ptr(dh0, torch.float32, True), _ptr(dc0, torch.float32, True), _stream()),
-          "gymrl_lstm_seq_bwd")
+                                   _ptr(dgates, torch.float32), _ptr(dh0, torch.float32, True), _ptr(dc0, torch.float32, True),
+                                   _stream()), "gymrl_lstm_seq_bwd")
     return dgates, dh0, dc0
 
 

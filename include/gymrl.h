@@ -403,7 +403,8 @@ int gymrl_rnd_reward(const float* predict, const float* target, int B, int E, fl
  * are the incoming gradients (either may be NULL = zeros); it writes dgi, dgh f32[T,B,3H] (zero for t >= len[b]) and
  * dh0 f32[B,H] (may be NULL).  dW_hh = sum_t dgh_t^T h_{t-1}, db_hh, dW_ih and dx are the caller's GEMMs over the
  * flattened rows.  One launch per 768 episodes, all T steps inside; H in {16, 32, 48, 64}; W_hh, h0, h_seq 16-byte
- * aligned.  -22 on anything else, before any HIP call. */
+ * aligned.  With T == 0 or B == 0 the [T,B,*] arrays have no element and may be NULL (h_last too when B == 0); T == 0
+ * still writes h_last = h0 and dh0 = d_hlast.  -22 on anything else, before any HIP call. */
 int gymrl_gru_seq_fwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const int32_t* len,
                       int T, int B, int H, float* h_seq, float* h_last, void* stream);
 int gymrl_gru_seq_bwd(const float* gi, const float* W_hh, const float* b_hh, const float* h0, const float* h_seq,

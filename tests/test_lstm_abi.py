@@ -83,6 +83,9 @@ def test_lstm_seq_validates_arguments_without_gpu():
     for lens in (_lens(3, 5), _lens(-1, 2)):
         assert fwd(lens=lens) == -22 and bwd(lens=lens) == -22            # len out of [0, T]
     assert fwd(T=-1) == -22 and fwd(B=-2) == -22 and bwd(T=-1) == -22 and bwd(B=-2) == -22
+    # T = 0 or B = 0: the [T,B,*] arrays have no element, and NULL is what an allocator hands out for them
+    assert fwd(gi=null, h_seq=null, c_seq=null, B=0) == 0 and bwd(gi=null, h_seq=null, c_seq=null, dgates=null, B=0) == 0
+    assert fwd(W=null, B=0) == -22 and bwd(b=null, B=0) == -22
 
 
 def test_ops_wrappers_refuse_cpu_tensors_and_wrong_shapes():
@@ -105,6 +108,19 @@ def test_ops_wrappers_refuse_cpu_tensors_and_wrong_shapes():
         ops.lstm_seq_bwd(gi, W, b, torch.zeros(T, B, H), torch.zeros(T, B, H + 4), [T] * B)
     with pytest.raises(ValueError, match="gh"):
         ops.lstm_cell_bwd(gi[0], torch.zeros(B, 3 * H), torch.zeros(B, H), torch.zeros(B, H))
+    seq, row = torch.zeros(T, B, H), torch.zeros(B, H)                 # caller-owned outputs of the wrong shape
+    for name, bad in (("h_seq", torch.zeros(T, B + 1, H)), ("c_seq", torch.zeros(T + 1, B, H)), ("h_last", torch.zeros(B, H + 1)),
+                      ("c_last", torch.zeros(B + 1, H))):
+        with pytest.raises(ValueError, match=name):
+            ops.lstm_seq_fwd(gi, W, b, [T] * B, **{name: bad})
+    for name, bad in (("dgates", torch.zeros(T, B, 3 * H)), ("dh0", torch.zeros(B, H + 1)), ("dc0", torch.zeros(H, B))):
+        with pytest.raises(ValueError, match=name):
+            ops.lstm_seq_bwd(gi, W, b, seq, seq, [T] * B, **{name: bad})
+    for kw in ({"dh0": row}, {"dc0": row}, {"dh0": row, "dc0": row}):
+        with pytest.raises(ValueError, match="need_d0"):
+            ops.lstm_seq_bwd(gi, W, b, seq, seq, [T] * B, need_d0=False, **kw)
+    with pytest.raises(RuntimeError, match="MI355X"):                  # well-shaped outputs pass the shape checks
+        ops.lstm_seq_bwd(gi, W, b, seq, seq, [T] * B, dgates=torch.zeros_like(gi), dh0=row, dc0=row.clone())
 
 
 def test_urnn_accepts_gru_and_lstm_only():

@@ -44,6 +44,11 @@ def test_gru_seq_validates_arguments_without_gpu():
     assert bwd(ok, 4, 40) == -22 and bwd(_lens(3, 9), 4, 64) == -22 and bwd(ok, 4, 64, dgi=null) == -22
     assert L.gymrl_gru_seq_bwd(fake, fake, fake, null, null, null, null, ok, 4, 2, 64, fake, fake, null, null) == -22  # NULL h_seq
     assert L.gymrl_gru_seq_bwd(fake, fake, fake, null, fake, null, null, ok, 4, 0, 64, fake, fake, null, null) == 0
+    # B = 0: the [T,B,*] arrays and h_last have no element, and NULL is what an allocator hands out for them
+    assert L.gymrl_gru_seq_fwd(null, fake, fake, null, ok, 4, 0, 64, null, null, null) == 0
+    assert L.gymrl_gru_seq_bwd(null, fake, fake, null, null, null, null, ok, 4, 0, 64, null, null, null, null) == 0
+    assert L.gymrl_gru_seq_fwd(null, null, fake, null, ok, 4, 0, 64, null, null, null) == -22      # W_hh is never empty
+    assert L.gymrl_gru_seq_fwd(fake, fake, fake, null, _lens(0, 0), 0, 2, 64, null, null, null) == -22   # T = 0, B > 0: h_last
 
 
 def test_episode_gae_validates_offsets_without_gpu():
@@ -147,3 +152,13 @@ def test_ops_wrappers_check_offsets_and_shapes_before_launch():
     with pytest.raises(ValueError, match="d_hseq"):
         ops.gru_seq_bwd(gi, torch.zeros(192, 64), torch.zeros(192), torch.zeros(4, 2, 64), [4, 2],
                         d_hseq=torch.zeros(4, 3, 64))
+    W, b, seq = torch.zeros(192, 64), torch.zeros(192), torch.zeros(4, 2, 64)      # caller-owned outputs of the wrong shape
+    for name, bad in (("dgi", torch.zeros(4, 2, 128)), ("dgh", torch.zeros(3, 2, 192)), ("dh0", torch.zeros(2, 63))):
+        with pytest.raises(ValueError, match=name):
+            ops.gru_seq_bwd(gi, W, b, seq, [4, 2], **{name: bad})
+    with pytest.raises(ValueError, match="need_dh0"):
+        ops.gru_seq_bwd(gi, W, b, seq, [4, 2], need_dh0=False, dh0=torch.zeros(2, 64))
+    with pytest.raises(ValueError, match="h_last"):
+        ops.gru_seq_fwd(gi, W, b, [4, 2], h_last=torch.zeros(2, 65))
+    with pytest.raises(RuntimeError, match="no CPU fallback"):                     # well-shaped outputs pass the shape checks
+        ops.gru_seq_bwd(gi, W, b, seq, [4, 2], dgi=torch.zeros_like(gi), dgh=torch.zeros_like(gi), dh0=torch.zeros(2, 64))
