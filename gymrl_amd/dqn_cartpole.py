@@ -187,6 +187,10 @@ class DQNTrainer(WeightImages, PolicyEval):
             return None
         return layers, self.flat_params, ops.CLASSIC_HEAD_ARGMAX, 0.0
 
+    def _q_values(self, state):
+        """f32[N, A] that select_action is greedy on (c51_cartpole.py: the expected values of a categorical head)."""
+        return self.policy_net(state)
+
     def get_epsilon(self):
         """:117-122 — advanced once per (vector) action selection."""
         self.sample_count += 1
@@ -199,7 +203,7 @@ class DQNTrainer(WeightImages, PolicyEval):
         """:124-133 for a batch of states [N, D] -> i32[N] (device in, device out).  The reference's scalar surface: ONE host
         observation (np.ndarray [D]) in -> python int out, as `select_action(state) -> int` at :124-133."""
         state, kind = scalar.obs_batch(state, self.device)
-        q = self.policy_net(state)
+        q = self._q_values(state)
         if deterministic:       # eval(): greedy, and the exploration stream must not move (bit-exact resume / replay)
             return scalar.discrete_out(ops.epsilon_greedy(q, 0.0, u=u, seed=self.base_seed, counter=0, env_id0=self.env.env_id0), kind)
         eps = self.get_epsilon()

@@ -1541,6 +1541,64 @@ def dqn_td_loss(q, q_next_target, act, rew, flag, gamma_n, q_next_online=None, w
     return td, dq
 
 
+C51_MAX_ACTIONS, C51_MAX_ATOMS = 8, 64          # gymrl_c51_q / gymrl_c51_loss: 1 <= A <= 8, 2 <= M <= 64
+
+
+def c51_shape_ok(B, A, M, vmin, vmax):
+    """What gymrl_c51_q / gymrl_c51_loss take: B >= 0 rows of 1..8 actions x 2..64 atoms on a support vmin < vmax."""
+    return B >= 0 and 1 <= A <= C51_MAX_ACTIONS and 2 <= M <= C51_MAX_ATOMS and vmax > vmin and 0.0 < (vmax - vmin) / (M - 1) < 3.4e38
+
+
+def _c51_rows(who, logits, A, M, vmin, vmax):
+    if logits.dim() == 3 and tuple(logits.shape[1:]) == (A, M):
+        logits = logits.reshape(logits.shape[0], A * M)
+    if logits.dim() != 2 or logits.shape[1] != A * M or not c51_shape_ok(logits.shape[0], A, M, vmin, vmax):
+        raise ValueError(f"{who}: logits are f32[B, A * M] with 1 <= A <= {C51_MAX_ACTIONS}, 2 <= M <= {C51_MAX_ATOMS} and "
+                         f"vmin < vmax, not {tuple(logits.shape)} with A = {A}, M = {M}, support [{vmin}, {vmax}]")
+    return logits
+
+
+def c51_q(logits, A, M, vmin, vmax, argmax=False):
+    """gymrl_c51_q: logits f32[B, A * M] (or [B, A, M]) of a categorical head -> q f32[B, A], the expected value of every
+    action's softmax over the support z_j = vmin + j (vmax - vmin) / (M - 1); argmax=True: (q, i32[B] first maximum)."""
+    logits = _c51_rows("c51_q", logits, A, M, vmin, vmax)
+    _need_dev("c51_q", logits=logits)
+    B = logits.shape[0]
+    q = torch.empty(B, A, dtype=torch.float32, device=logits.device)
+    arg = torch.empty(B, dtype=torch.int32, device=logits.device) if argmax else None
+    if B == 0:                      # (an empty tensor has no data pointer to hand over; the entry point would launch nothing)
+        return (q, arg) if argmax else q
+    check(lib().gymrl_c51_q(_ptr(logits, torch.float32), B, A, M, vmin, vmax, _ptr(q), _ptr(arg, torch.int32, True), _stream()),
+          "gymrl_c51_q")
+    return (q, arg) if argmax else q
+
+
+def c51_loss(logits, next_target, act, rew, flag, gamma_n, vmin, vmax, next_online=None, w=None, loss_sum=None):
+    """gymrl_c51_loss: the projected cross-entropy of C51, forward and backward.  logits, next_target (and next_online: the
+    double-Q selector) f32[B, A, M]; act i32[B]; rew, flag (and w: importance weights) f32[B] -> (row_loss f32[B], unweighted,
+    dlogits f32[B, A, M] = d mean_b(w_b row_loss_b) / d logits, every entry written); loss_sum f64[1] += sum_b w_b row_loss_b."""
+    if logits.dim() != 3 or not c51_shape_ok(*logits.shape, vmin, vmax):
+        raise ValueError(f"c51_loss: logits are f32[B, A, M] with 1 <= A <= {C51_MAX_ACTIONS}, 2 <= M <= {C51_MAX_ATOMS} and "
+                         f"vmin < vmax, not {tuple(logits.shape)} on the support [{vmin}, {vmax}]")
+    B, A, M = logits.shape
+    for name, t, shape in (("next_target", next_target, (B, A, M)), ("next_online", next_online, (B, A, M)), ("act", act, (B,)),
+                           ("rew", rew, (B,)), ("flag", flag, (B,)), ("w", w, (B,)), ("loss_sum", loss_sum, (1,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"c51_loss: {name} is {shape}, not {tuple(t.shape)}")
+    _need_dev("c51_loss", logits=logits, next_target=next_target, act=act, rew=rew, flag=flag, next_online=next_online, w=w,
+              loss_sum=loss_sum)
+    row_loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    if B == 0:
+        return row_loss, dlogits
+    ws = _reduce_ws(logits.device) if loss_sum is not None else None
+    check(lib().gymrl_c51_loss(_ptr(logits, torch.float32), _ptr(next_online, torch.float32, True), _ptr(next_target, torch.float32),
+                               _ptr(act, torch.int32), _ptr(rew, torch.float32), _ptr(flag, torch.float32), _ptr(w, torch.float32, True),
+                               B, A, M, vmin, vmax, gamma_n, _ptr(row_loss), _ptr(dlogits), _ptr(loss_sum, torch.float64, True),
+                               _ptr(ws, None, True), _stream()), "gymrl_c51_loss")
+    return row_loss, dlogits
+
+
 def noisy_action(mu, std, bound, eps=None, mode=0, noise_clip=0.0, seed=0, counter=0, out=None):
     """gymrl_noisy_action: Gaussian exploration noise (mode 0, numpy-float64 semantics) or TD3 target-policy
     smoothing (mode 1, torch-float32 semantics) on an action tensor; eps = explicit f64 N(0,1) draws."""

@@ -1479,6 +1479,39 @@ int gymrl_dqn_td_loss(const float* q, const float* q_next_online, const float* q
                       double* loss_sum, void* workspace, void* stream);
 
 /*
+ * C51: the categorical value head (Bellemare et al. 2017) — csrc/c51.hip, arithmetic in csrc/c51_device.hpp.
+ * logits f32[B][A][M]: a Linear(H, A * M) head, atom j of action a at a * M + j.  Support z_j = vmin + j * dz,
+ * dz = (vmax - vmin) / (M - 1), float32.  Shapes: 1 <= A <= 8, 2 <= M <= 64 (one atom per lane of a wave64), vmax > vmin with
+ * a finite dz > 0, B >= 0; anything else is -22 before any HIP call, B == 0 returns 0 without a launch.
+ *   softmax   e_j = det_expf(x_j - max_j x_j),  s = sum_j e_j,  p_j = e_j / s
+ * Sums over a row's atoms (s, q, the cross-entropy) run as the halving tree over 64 slots (slots >= M hold +0):
+ * v[0:off] + v[off:2 off] for off = 32 ... 1.  No order depends on B or the grid.
+ *
+ * gymrl_c51_q: q_out f32[B][A] = sum_j p_j z_j per (row, action); argmax_out i32[B] (may be NULL) = the FIRST maximum over the
+ * actions (torch.argmax's tie rule).  Acting: q_out feeds gymrl_epsilon_greedy.
+ *
+ * gymrl_c51_loss, per row b (next_online, next_target f32[B][A][M]; act i32[B]; rew, flag f32[B]; w f32[B] or NULL = 1):
+ *   1. a* = first maximum over a of the expected value of next_online[b] (double-Q; NULL: of next_target[b])
+ *   2. p* = softmax(next_target[b, a*, :])
+ *   3. Tz_j = clamp(rew + gamma_n (1 - flag) z_j, vmin, vmax),  b_j = (Tz_j - vmin) / dz,
+ *      m_i = sum_j p*_j max(0, 1 - |b_j - i|), j ascending from +0: the gather form of the floor / ceil scatter — no atomics,
+ *      and a b_j that lands on an atom gives that atom weight 1 (the textbook scatter's l == u case)
+ *   4. logp_i = (x_i - max) - det_logf(s) on x = logits[b, act_b, :];  row_loss_out[b] = -sum_i m_i logp_i (unweighted: the
+ *      priority error of a PER trainer)
+ *   5. dlogits_out[b, act_b, i] = (w_b * (1 / B)) * (p_i - m_i); every other action's atoms are written 0, so the caller
+ *      needs no memset.  An act_b outside [0, A) touches nothing out of range: row_loss_out[b] = NaN, the row's gradient 0
+ *   6. loss_sum f64[1] (may be NULL) += sum_b (double)(row_loss_b * w_b) in gymrl_dqn_td_loss's reduction (one workgroup of
+ *      four rows adds to loss_sum itself, more go through workspace >= gymrl_reduce_workspace_bytes(), required with loss_sum,
+ *      and a finalize launch)
+ */
+int gymrl_c51_q(const float* logits, int B, int A, int M, float vmin, float vmax, float* q_out,
+                int32_t* argmax_out, void* stream);
+int gymrl_c51_loss(const float* logits, const float* next_online, const float* next_target,
+                   const int32_t* act, const float* rew, const float* flag, const float* w, int B, int A,
+                   int M, float vmin, float vmax, double gamma_n, float* row_loss_out,
+                   float* dlogits_out, double* loss_sum, void* workspace, void* stream);
+
+/*
  * A1: Actor.sample — sac_pendulum.py:76-87 — forward and backward.
  *   x = mean + exp(log_std)*eps; a = tanh(x)*bound;
  *   logp = sum_j [ Normal(mean,std).log_prob(x) - log(bound*(1 - tanh(x)^2) + 1e-6) ]
