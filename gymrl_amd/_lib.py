@@ -631,6 +631,8 @@ SIGNATURES = {
     "gymrl_dqn_td_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_c51_q": (_i, [_vp, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     "gymrl_c51_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _d, _vp, _vp, _vp, _vp, _vp]),
+    "gymrl_qr_q": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gymrl_qr_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _d, _vp, _vp, _vp, _vp, _vp]),
     "gymrl_sac_sample_fwd": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "gymrl_sac_sample_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "gymrl_sac_target": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _vp, _vp]),

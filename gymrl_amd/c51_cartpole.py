@@ -33,38 +33,53 @@ class Config(_DQNConfig):
         self.double_q = False                # a* from the online net's expected values (the target net's when off)
 
 
-class C51Head:
-    """What the categorical head changes in a DQNTrainer-family trainer: the network's width, the values acting is greedy on,
-    and the refusal of the fused paths, which know scalar Q heads only."""
+class DistributionalHead:
+    """What a head of K values per action (C51's atoms, qrdqn_cartpole.py's quantiles) changes in a DQNTrainer-family trainer:
+    the network's width, the values acting is greedy on (_q_values, the subclass's), and the refusal of the fused paths, which
+    know scalar Q heads only.  A subclass names itself (head_name), its width (_per_action), its action limit, and refuses a bad
+    Config in _check_head."""
+    head_name, max_actions = None, 8
 
     def __init__(self, config):
-        M = config.num_atoms
-        if not ops.c51_shape_ok(0, 1, M, config.v_min, config.v_max):
-            raise ValueError(f"{type(self).__name__}: num_atoms in 2..{ops.C51_MAX_ATOMS} and v_min < v_max, not {M} atoms on "
-                             f"[{config.v_min}, {config.v_max}]")
+        self._check_head(config)
         if getattr(config, "fused_step", False):
-            raise ValueError(f"{type(self).__name__}: there is no fused vector step for the categorical head "
+            raise ValueError(f"{type(self).__name__}: there is no fused vector step for the {self.head_name} head "
                              "(Config.fused_step must stay False)")
         super().__init__(config)
-        if self.action_dim > ops.C51_MAX_ACTIONS:
-            raise ValueError(f"{type(self).__name__}: at most {ops.C51_MAX_ACTIONS} actions, {config.env_name} has {self.action_dim}")
+        if self.action_dim > self.max_actions:
+            raise ValueError(f"{type(self).__name__}: at most {self.max_actions} actions, {config.env_name} has {self.action_dim}")
 
     def _make_network(self, state_dim, action_dim, hidden_dim):
-        return QNetwork(state_dim, action_dim * self.cfg.num_atoms, hidden_dim)
+        return QNetwork(state_dim, action_dim * self._per_action(self.cfg), hidden_dim)
 
-    def _head(self, logits):
-        """f32[N, A * M] off the last layer -> f32[N, A, M] (a view)."""
-        return logits.view(logits.shape[0], self.action_dim, self.cfg.num_atoms)
-
-    def _q_values(self, state):
-        cfg = self.cfg
-        return ops.c51_q(self.policy_net(state), self.action_dim, cfg.num_atoms, cfg.v_min, cfg.v_max)
+    def _head(self, out):
+        """f32[N, A * K] off the last layer -> f32[N, A, K] (a view)."""
+        return out.view(out.shape[0], self.action_dim, self._per_action(self.cfg))
 
     def _fused_update_ok(self):
         return False
 
     def _eval_policy(self):
         return None
+
+
+class C51Head(DistributionalHead):
+    """The categorical head: M atoms per action on [v_min, v_max], acting on their expected values (gymrl_c51_q)."""
+    head_name, max_actions = "categorical", ops.C51_MAX_ACTIONS
+
+    def _check_head(self, config):
+        M = config.num_atoms
+        if not ops.c51_shape_ok(0, 1, M, config.v_min, config.v_max):
+            raise ValueError(f"{type(self).__name__}: num_atoms in 2..{ops.C51_MAX_ATOMS} and v_min < v_max, not {M} atoms on "
+                             f"[{config.v_min}, {config.v_max}]")
+
+    @staticmethod
+    def _per_action(config):
+        return config.num_atoms
+
+    def _q_values(self, state):
+        cfg = self.cfg
+        return ops.c51_q(self.policy_net(state), self.action_dim, cfg.num_atoms, cfg.v_min, cfg.v_max)
 
 
 class C51Trainer(C51Head, DQNTrainer):

@@ -15,7 +15,7 @@
 // broadcasts (every lane the same address), M^2 multiply-adds per row.
 // The loss sum is the float64 reduction of the other loss kernels (offpolicy.hip): lane 0 of a row's wave carries
 // (double)(row_loss_b * w_b), a workgroup adds its four waves ascending, one workgroup adds to loss_sum itself, more write
-// partials that finalize sums in a fixed order.
+// partials that finalize sums in a fixed order (row_loss_device.hpp, shared with qrdqn.hip).
 #include "c51_device.hpp"
 #include "../../include/gymrl.h"
 
@@ -23,46 +23,10 @@ using namespace gymrl;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kRows = kBlock / GYMRL_WAVE;      // rows per workgroup and grid-stride step
-constexpr int kMaxBlocks = 4096;                // <= gymrl_reduce_workspace_bytes() / sizeof(double)
-inline int grid_for(int B) {
-  const int64_t nb = ((int64_t)B + kRows - 1) / kRows;
-  return nb < 1 ? 1 : (nb > kMaxBlocks ? kMaxBlocks : (int)nb);
-}
-
-// offpolicy.hip's block_partials<1> / finalize_kernel<1>: the same loads and float64 sums in the same order
-__device__ __forceinline__ void block_partial(double v, double* __restrict__ partials, double* __restrict__ direct) {
-  __shared__ double sm[kRows];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const double s = wave_sum(v);
-  if (lane == 0) sm[wid] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kRows; ++w) t += sm[w];
-    if (direct) direct[0] += t;
-    else partials[blockIdx.x] = t;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void c51_finalize_kernel(const double* __restrict__ partials, int nblocks,
-                                                              double* __restrict__ out) {
-  __shared__ double sm[kRows];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += kBlock) v += partials[i];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const double s = wave_sum(v);
-  if (lane == 0) sm[wid] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kRows; ++w) t += sm[w];
-    out[0] += t;
-  }
-}
+using rowloss::kBlock;
+using rowloss::kRows;
+using rowloss::grid_for;
+using rowloss::block_partial;
 
 __global__ __launch_bounds__(kBlock) void c51_q_kernel(const float* __restrict__ logits, int B, int A, int M, float vmin,
                                                        float dz, float* __restrict__ q_out,
@@ -156,7 +120,7 @@ int gymrl_c51_loss(const float* logits, const float* next_online, const float* n
   hipLaunchKernelGGL(c51_loss_kernel, dim3(nb), dim3(kBlock), 0, stream, logits, next_online, next_target, act, rew, flag, w,
                      B, A, M, vmin, vmax, dz, (float)gamma_n, row_loss_out, dlogits_out, parts,
                      (loss_sum && nb == 1) ? loss_sum : nullptr);
-  if (loss_sum && nb > 1) hipLaunchKernelGGL(c51_finalize_kernel, dim3(1), dim3(kBlock), 0, stream, parts, nb, loss_sum);
+  if (loss_sum && nb > 1) hipLaunchKernelGGL(rowloss::finalize_kernel, dim3(1), dim3(kBlock), 0, stream, parts, nb, loss_sum);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

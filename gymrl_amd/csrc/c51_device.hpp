@@ -11,6 +11,7 @@
 //   * the projection m_i = sum_j p*_j max(0, 1 - |b_j - i|) is a serial sum over j = 0 ... M - 1 ascending, starting from +0.
 #pragma once
 #include "gymrl_device.hpp"
+#include "row_loss_device.hpp"
 #include "softmax_device.hpp"
 
 namespace gymrl {
@@ -19,11 +20,7 @@ namespace c51 {
 constexpr int kMaxAtoms = GYMRL_WAVE;          // one atom per lane
 constexpr int kMaxActions = kSoftmaxMaxA;      // 8
 
-__device__ __forceinline__ float wave_allsum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+using rowloss::wave_allsum;                    // the butterfly of the header above
 __device__ __forceinline__ float wave_allmax(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

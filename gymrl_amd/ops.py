@@ -1599,6 +1599,64 @@ def c51_loss(logits, next_target, act, rew, flag, gamma_n, vmin, vmax, next_onli
     return row_loss, dlogits
 
 
+QR_MAX_ACTIONS, QR_MAX_QUANTILES = 8, 64        # gymrl_qr_q / gymrl_qr_loss: 1 <= A <= 8, 1 <= N <= 64
+
+
+def qr_shape_ok(B, A, N, kappa=1.0):
+    """What gymrl_qr_q / gymrl_qr_loss take: B >= 0 rows of 1..8 actions x 1..64 quantiles, a Huber threshold that is finite and
+    > 0 as a float32 (NaN compares false)."""
+    return B >= 0 and 1 <= A <= QR_MAX_ACTIONS and 1 <= N <= QR_MAX_QUANTILES and 0.0 < C.c_float(kappa).value < float("inf")
+
+
+def _qr_rows(who, quant, A, N):
+    if quant.dim() == 3 and tuple(quant.shape[1:]) == (A, N):
+        quant = quant.reshape(quant.shape[0], A * N)
+    if quant.dim() != 2 or quant.shape[1] != A * N or not qr_shape_ok(quant.shape[0], A, N):
+        raise ValueError(f"{who}: quant is f32[B, A * N] with 1 <= A <= {QR_MAX_ACTIONS} and 1 <= N <= {QR_MAX_QUANTILES}, "
+                         f"not {tuple(quant.shape)} with A = {A}, N = {N}")
+    return quant
+
+
+def qr_q(quant, A, N, argmax=False):
+    """gymrl_qr_q: quant f32[B, A * N] (or [B, A, N]) of a quantile head -> q f32[B, A], the mean of every action's N quantiles;
+    argmax=True: (q, i32[B] first maximum)."""
+    quant = _qr_rows("qr_q", quant, A, N)
+    _need_dev("qr_q", quant=quant)
+    B = quant.shape[0]
+    q = torch.empty(B, A, dtype=torch.float32, device=quant.device)
+    arg = torch.empty(B, dtype=torch.int32, device=quant.device) if argmax else None
+    if B == 0:                      # (an empty tensor has no data pointer to hand over; the entry point would launch nothing)
+        return (q, arg) if argmax else q
+    check(lib().gymrl_qr_q(_ptr(quant, torch.float32), B, A, N, _ptr(q), _ptr(arg, torch.int32, True), _stream()), "gymrl_qr_q")
+    return (q, arg) if argmax else q
+
+
+def qr_loss(quant, next_target, act, rew, flag, gamma_n, kappa=1.0, next_online=None, w=None, loss_sum=None):
+    """gymrl_qr_loss: the quantile-Huber loss of QR-DQN, forward and backward.  quant, next_target (and next_online: the
+    double-Q selector) f32[B, A, N]; act i32[B]; rew, flag (and w: importance weights) f32[B] -> (row_loss f32[B], unweighted,
+    dquant f32[B, A, N] = d mean_b(w_b row_loss_b) / d quant, every entry written); loss_sum f64[1] += sum_b w_b row_loss_b."""
+    if quant.dim() != 3 or not qr_shape_ok(*quant.shape, kappa):
+        raise ValueError(f"qr_loss: quant is f32[B, A, N] with 1 <= A <= {QR_MAX_ACTIONS}, 1 <= N <= {QR_MAX_QUANTILES} and a "
+                         f"finite kappa > 0, not {tuple(quant.shape)} with kappa = {kappa}")
+    B, A, N = quant.shape
+    for name, t, shape in (("next_target", next_target, (B, A, N)), ("next_online", next_online, (B, A, N)), ("act", act, (B,)),
+                           ("rew", rew, (B,)), ("flag", flag, (B,)), ("w", w, (B,)), ("loss_sum", loss_sum, (1,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"qr_loss: {name} is {shape}, not {tuple(t.shape)}")
+    _need_dev("qr_loss", quant=quant, next_target=next_target, act=act, rew=rew, flag=flag, next_online=next_online, w=w,
+              loss_sum=loss_sum)
+    row_loss = torch.empty(B, dtype=torch.float32, device=quant.device)
+    dquant = torch.empty_like(quant)
+    if B == 0:
+        return row_loss, dquant
+    ws = _reduce_ws(quant.device) if loss_sum is not None else None
+    check(lib().gymrl_qr_loss(_ptr(quant, torch.float32), _ptr(next_online, torch.float32, True), _ptr(next_target, torch.float32),
+                              _ptr(act, torch.int32), _ptr(rew, torch.float32), _ptr(flag, torch.float32), _ptr(w, torch.float32, True),
+                              B, A, N, kappa, gamma_n, _ptr(row_loss), _ptr(dquant), _ptr(loss_sum, torch.float64, True),
+                              _ptr(ws, None, True), _stream()), "gymrl_qr_loss")
+    return row_loss, dquant
+
+
 def noisy_action(mu, std, bound, eps=None, mode=0, noise_clip=0.0, seed=0, counter=0, out=None):
     """gymrl_noisy_action: Gaussian exploration noise (mode 0, numpy-float64 semantics) or TD3 target-policy
     smoothing (mode 1, torch-float32 semantics) on an action tensor; eps = explicit f64 N(0,1) draws."""

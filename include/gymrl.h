@@ -1512,6 +1512,39 @@ int gymrl_c51_loss(const float* logits, const float* next_online, const float* n
                    float* dlogits_out, double* loss_sum, void* workspace, void* stream);
 
 /*
+ * QR-DQN: the quantile-regression value head (Dabney et al. 2018) — csrc/qrdqn.hip, arithmetic in csrc/qrdqn_device.hpp.
+ * quant f32[B][A][N]: a Linear(H, A * N) head, quantile i of action a at a * N + i, for the fixed midpoints
+ * tau_i = (2 i + 1) / (2 N).  There is no support, no projection and no clamp.  Shapes: 1 <= A <= 8, 1 <= N <= 64 (one quantile
+ * per lane of a wave64), B >= 0, kappa finite and > 0; anything else, a NULL required pointer, or loss_sum without workspace is
+ * -22 before any HIP call, B == 0 returns 0 without a launch.  float32 throughout, +, -, *, / and comparisons only.
+ * Sums over a row's quantiles (the mean, the row's loss) run as the halving tree over 64 slots (slots >= N hold +0):
+ * v[0:off] + v[off:2 off] for off = 32 ... 1; the sum over the target samples j is serial, j ascending from +0.  No order
+ * depends on B or the grid.
+ *
+ * gymrl_qr_q: q_out f32[B][A] = (sum_i quant[b][a][i]) / N; argmax_out i32[B] (may be NULL: untouched) = the FIRST maximum over
+ * the actions (torch.argmax's tie rule).  Acting: q_out feeds gymrl_epsilon_greedy.
+ *
+ * gymrl_qr_loss, per row b (next_online, next_target f32[B][A][N]; act i32[B]; rew, flag f32[B]; w f32[B] or NULL = 1):
+ *   1. a* = first maximum over a of the mean quantile of next_online[b] (double-Q; NULL: of next_target[b])
+ *   2. g = (float)gamma_n * (1 - flag_b),  T_j = rew_b + g * next_target[b][a*][j]
+ *   3. with theta_i = quant[b][act_b][i], u_ij = T_j - theta_i and wt_ij = |tau_i - 1{u_ij < 0}| (tau_i, or 1 - tau_i below 0):
+ *        H(u) = 0.5 u^2 if |u| <= kappa, else kappa (|u| - 0.5 kappa)
+ *        l_i = sum_j wt_ij H(u_ij),   g_i = sum_j wt_ij clamp(u_ij, -kappa, kappa)
+ *      row_loss_out[b] = sum_i (l_i / kappa) / N (unweighted: the priority error of a PER trainer)
+ *   4. dquant_out[b][act_b][i] = (w_b * (1 / B)) * -((g_i / kappa) / N); every other action's quantiles are written 0, so the
+ *      caller needs no memset.  An act_b outside [0, A) touches nothing out of range: row_loss_out[b] = NaN, the row's gradient 0
+ *   5. loss_sum f64[1] (may be NULL) += sum_b (double)(row_loss_b * w_b) in gymrl_c51_loss's reduction (one workgroup of four
+ *      rows adds to loss_sum itself, more go through workspace >= gymrl_reduce_workspace_bytes(), required with loss_sum, and a
+ *      finalize launch)
+ * At u == 0 the indicator is 0 and both terms are 0; at |u| == kappa the two branches of H agree.
+ */
+int gymrl_qr_q(const float* quant, int B, int A, int N, float* q_out, int32_t* argmax_out, void* stream);
+int gymrl_qr_loss(const float* quant, const float* next_online, const float* next_target,
+                  const int32_t* act, const float* rew, const float* flag, const float* w, int B, int A,
+                  int N, float kappa, double gamma_n, float* row_loss_out, float* dquant_out,
+                  double* loss_sum, void* workspace, void* stream);
+
+/*
  * A1: Actor.sample — sac_pendulum.py:76-87 — forward and backward.
  *   x = mean + exp(log_std)*eps; a = tanh(x)*bound;
  *   logp = sum_j [ Normal(mean,std).log_prob(x) - log(bound*(1 - tanh(x)^2) + 1e-6) ]
