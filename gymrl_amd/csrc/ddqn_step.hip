@@ -22,9 +22,7 @@
 // heads as two items of one stage per chain, the combine q = v + (a - mean a) and its backward per row, ONE dX stage.  LDS: three
 // slabs (P1, N1, T1; N1 and T1 are dead after the heads and take the two heads' input gradients): 54,016 B at H = 256.  No
 // H x H layer, so no weight images.  duel_combine below states the arithmetic order.
-#include "duel_device.hpp"
-#include "policy_device.hpp"
-#include "slab_step_device.hpp"
+#include "value_step_device.hpp"
 
 namespace {
 
@@ -33,46 +31,10 @@ using namespace gymrl::slab;
 
 constexpr int kDdqnMaxBatch = 256;     // (ops.DDQN_FUSED_MAX_BATCH) one grid of at most 16 slabs in the row phase: the loss sum is one block's
 constexpr int kDdqnSlabs = 6;
-struct DdqnImages {                    // gymrl_ddqn_update_args.images, f32[3][H*H]: gymrl_dqn_update_args.images' layout
-  const float *pf, *tf, *pb;
-  __host__ __device__ DdqnImages(const float* base, int H) {
-    const ImageSlots at(base, H);
-    pf = at(0); tf = at(1); pb = at(2);
-  }
-  static constexpr int kCount = 3;
-  static PackTable sources(const gymrl_ddqn_update_args& a) {
-    return PackTable{{a.policy.w[1], a.target.w[1], a.policy.w[1], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 2};
-  }
-};
-
-// hand-off between the row phase and the tile phase (caller-owned workspace)
-struct DdqnWs {
-  float* s;                            // [B][D]: the gathered states
-  float *H1, *Z1, *H2, *Z2, *dq;       // the policy net's activations on s and dL/dz per layer ([B][H]; dq [B][A])
-  double* terms;                       // [B][3]: the row's td^2 * w in column 0 (sac_dw_body's row pitch)
-  __host__ __device__ static size_t carve(DdqnWs* w, void* base, int B, int D, int A, int H) {
-    carve_taker take{base};
-    float* s = take((size_t)B * D);
-    float* h[4];
-    for (int i = 0; i < 4; ++i) h[i] = take((size_t)B * H);
-    float* dq = take((size_t)B * A);
-    double* terms = reinterpret_cast<double*>(take((size_t)B * 6));
-    if (w) { w->s = s; w->H1 = h[0]; w->Z1 = h[1]; w->H2 = h[2]; w->Z2 = h[3]; w->dq = dq; w->terms = terms; }
-    return take.off;
-  }
-};
-
-
-// The ring row of batch element b, or -1: beyond the batch, or an index outside [0, cap) — such a row is never read: it enters
-// the batch as zeros with weight 0 (td_out = -y of a zero row, no gradient), instead of a read outside the ring.
-__device__ __forceinline__ int64_t ddqn_row(const gymrl_ddqn_update_args& a, int b, bool in_batch) {
-  if (!in_batch) return -1;
-  const int64_t row = (int64_t)a.idx[b];
-  return (row >= 0 && row < a.cap) ? row : -1;
-}
+// (gymrl_ddqn_update_args.images — gymrl_dqn_update_args.images' layout — and the workspace: QNet3Images / QNet3Ws)
 
 template <int HC>
-__global__ __launch_bounds__(kThreads) void ddqn_r1_kernel(const gymrl_ddqn_update_args a, const DdqnWs ws) {
+__global__ __launch_bounds__(kThreads) void ddqn_r1_kernel(const gymrl_ddqn_update_args a, const QNet3Ws ws) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds L;
   const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
@@ -81,12 +43,14 @@ __global__ __launch_bounds__(kThreads) void ddqn_r1_kernel(const gymrl_ddqn_upda
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
   const int t = threadIdx.x;
   const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
-  const DdqnImages im(a.images, H);
+  const QNet3Images im(a.images, H);
   const gymrl_td3_actor_params &p = a.policy, &tg = a.target;
-  // ---- ring gather by the sampled rows: one thread per row, rows beyond the batch are zero (weight 0) ----
+  // ---- ring gather by the sampled rows: one thread per row, rows beyond the batch are zero (weight 0).  (The text of
+  // gather_ring_row and, below, of td_row<false>, kept in place: called from here they left this kernel's registers different
+  // and the Acrobot N = 64 step 1.9 % outside the parent's range — DESIGN 4m') ----
   if (t < 16) {
     const int b = row0 + t;
-    const int64_t row = ddqn_row(a, b, t < nrows);
+    const int64_t row = checked_ring_row(t < nrows, [&] { return (int64_t)a.idx[b]; }, a.cap);
     const bool ok = row >= 0;
     for (int k = 0; k < kMaxD; ++k) {
       const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
@@ -148,33 +112,22 @@ __global__ __launch_bounds__(kThreads) void ddqn_r1_kernel(const gymrl_ddqn_upda
   bwd_stage(lds, {BwdItem{Z0, ld, H, p.w[1], H, -1, nullptr, P1, ld, R, -1, 0, ws.Z1, H, im.pb}}, row0, nrows);      // (the last stage: no barrier behind it)
 }
 
-
 // ---- the dueling instance: policy.w / .b = {fc1, value_stream, advantage_stream}; ws.H2 holds dv [B], ws.dq holds da [B][A] ----
 template <int HC>
-__global__ __launch_bounds__(kThreads) void ddqn_duel_r1_kernel(const gymrl_ddqn_update_args a, const DdqnWs ws) {
+__global__ __launch_bounds__(kThreads) void ddqn_duel_r1_kernel(const gymrl_ddqn_update_args a, const QNet3Ws ws) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds L;
   const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
   const int P1 = L.big, N1 = P1 + 16 * ld, T1 = N1 + 16 * ld;
-  const int Xv = N1, Xa = T1;             // the heads' input gradients, once policy(s') and target(s') are through their heads
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
   const int t = threadIdx.x;
-  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
+  const int R = GYMRL_ACT_RELU, kD = kMaxD;
   const gymrl_td3_actor_params &p = a.policy, &tg = a.target;
+  // ---- ring gather by the SAMPLED rows: a row beyond the batch or outside [0, cap) is a zero row of weight 0 ----
   if (t < 16) {
     const int b = row0 + t;
-    const int64_t row = ddqn_row(a, b, t < nrows);
-    const bool ok = row >= 0;
-    for (int k = 0; k < kMaxD; ++k) {
-      const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
-      lds[L.S + t * kMaxD + k] = sv;
-      lds[L.S2 + t * kMaxD + k] = (ok && k < D) ? a.r_next[row * D + k] : 0.0f;
-      if (t < nrows && k < D) ws.s[(size_t)b * D + k] = sv;
-    }
-    lds[L.Misc + t * 4 + 0] = ok ? a.r_reward[row] : 0.0f;
-    lds[L.Misc + t * 4 + 1] = ok ? (float)a.r_flag[row] : 0.0f;
-    lds[L.Misc + t * 4 + 2] = ok ? __int_as_float((int)a.r_action[row]) : 0.0f;
-    lds[L.Misc + t * 4 + 3] = ok ? a.is_weight[b] : 0.0f;
+    const int64_t row = checked_ring_row(t < nrows, [&] { return (int64_t)a.idx[b]; }, a.cap);
+    gather_ring_row(a, lds, L, t, b, t < nrows, row, /*checked=*/true, ws.s, RowWeight::kGiven, a.is_weight);
   }
   __syncthreads();
   {
@@ -184,58 +137,11 @@ __global__ __launch_bounds__(kThreads) void ddqn_duel_r1_kernel(const gymrl_ddqn
     fwd_stage<3>(lds, st, row0, nrows);
   }
   __syncthreads();
-  {                                       // value (1 column) and advantage (A columns) of every chain: six items of one stage
-    const FwdItem st[6] = {fwd_item(P1, ld, -1, 0, H, H, 1, p.w[1], p.b[1], L.Cq1, 4, nullptr, 0, NA),
-                           fwd_item(P1, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Cq0, 4, nullptr, 0, NA),
-                           fwd_item(N1, ld, -1, 0, H, H, 1, p.w[1], p.b[1], L.Dq1, 4, nullptr, 0, NA),
-                           fwd_item(N1, ld, -1, 0, H, H, A, p.w[2], p.b[2], L.Q1, 4, nullptr, 0, NA),
-                           fwd_item(T1, ld, -1, 0, H, H, 1, tg.w[1], tg.b[1], L.Mean, 4, nullptr, 0, NA),
-                           fwd_item(T1, ld, -1, 0, H, H, A, tg.w[2], tg.b[2], L.Q0, 4, nullptr, 0, NA)};
-    fwd_stage<6>(lds, st, row0, nrows);
-  }
-  __syncthreads();
-  if (t < 16) {                           // the three combines, then dqn_td_kernel with qn_online and w set, then the combine's backward
-    float q[4], qo[4], qt[4];
-    duel_combine(lds + L.Cq0 + t * 4, lds[L.Cq1 + t * 4], A, q);
-    duel_combine(lds + L.Q1 + t * 4, lds[L.Dq1 + t * 4], A, qo);
-    duel_combine(lds + L.Q0 + t * 4, lds[L.Mean + t * 4], A, qt);
-    int astar = 0;
-    float best = qo[0];
-    for (int k = 1; k < A; ++k) if (qo[k] > best) { best = qo[k]; astar = k; }
-    float nq = qt[0], qa = q[0];
-    const int act = __float_as_int(lds[L.Misc + t * 4 + 2]);
-    for (int k = 1; k < A; ++k) { if (k == astar) nq = qt[k]; if (k == act) qa = q[k]; }
-    const float y = lds[L.Misc + t * 4 + 0] + a.gamma * nq * (1.0f - lds[L.Misc + t * 4 + 1]);
-    const float td = qa - y;
-    const float wb = lds[L.Misc + t * 4 + 3], invB = 1.0f / (float)a.B;
-    float dq[4], da[4], dv;
-    for (int k = 0; k < 4; ++k) dq[k] = k == act ? (2.0f * td) * wb * invB : 0.0f;
-    duel_combine_bwd(dq, A, da, dv);
-    for (int k = 0; k < 4; ++k) {
-      lds[L.Dq0 + t * 4 + k] = k < A ? da[k] : 0.0f;
-      lds[L.Dq1 + t * 4 + k] = k == 0 ? dv : 0.0f;
-      if (t < nrows && k < A) ws.dq[(size_t)(row0 + t) * A + k] = da[k];
-    }
-    if (t < nrows) {
-      ws.H2[row0 + t] = dv;
-      a.td_out[row0 + t] = td;
-      ws.terms[(size_t)(row0 + t) * 3] = (double)((td * td) * wb);
-    }
-  }
-  __syncthreads();
-  // ---- ONE dX stage: each head's input gradient on its own (two backward launches on the layer path), autograd's sum of the two,
-  // then fc1's ReLU derivative from its saved output ----
-  {
-    const BwdItem st[2] = {BwdItem{L.Dq1, 4, 1, p.w[1], H, -1, nullptr, -1, 0, NA, Xv, ld, nullptr, 0, nullptr},
-                           BwdItem{L.Dq0, 4, A, p.w[2], H, -1, nullptr, -1, 0, NA, Xa, ld, nullptr, 0, nullptr}};
-    bwd_stage<2>(lds, st, row0, nrows);
-  }
-  __syncthreads();
-  for (int e = t; e < 16 * H; e += kThreads) {
-    const int row = e / H, k = e - row * H;
-    const float g = (lds[Xv + row * ld + k] + lds[Xa + row * ld + k]) * act_bwd(lds[P1 + row * ld + k], R, 0.0f, 0.0f);
-    if (row < nrows) ws.Z1[(size_t)(row0 + row) * H + k] = g;
-  }
+  // the heads, the loss and ONE dX stage back to fc1: N1 and T1 take the heads' input gradients once policy(s') and target(s')
+  // are through their heads; dL/dz1 leaves for ws.Z1 with no further stage (Zs = -1)
+  const DuelHeads pol{p.w[1], p.b[1], p.w[2], p.b[2]}, tgt{tg.w[1], tg.b[1], tg.w[2], tg.b[2]};
+  duel_heads_segment(lds, L, A, H, ld, row0, nrows, a.gamma, a.B, {P1, N1, T1}, {pol, pol, tgt}, /*Xv=*/N1, /*Xa=*/T1, ws.H2, ws.dq, a.td_out,
+                     ws.terms, /*Zs=*/-1, ws.Z1);
 }
 
 // ---- acting with the dueling network: gymrl_dqn_act_step's kernel with the two heads and the combine in front of the choice ----
@@ -247,11 +153,7 @@ __global__ __launch_bounds__(kThreads) void ddqn_duel_act_kernel(const gymrl_dqn
   const int X0 = L.big;
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.N - row0);
   const int t = threadIdx.x;
-  if (t < 16) {
-    const int i = row0 + t;
-    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = (t < nrows && k < D) ? a.obs[(size_t)i * D + k] : 0.0f;
-  }
-  __syncthreads();
+  act_load_obs(a, lds, L, t, row0, nrows);
   const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
   fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.policy.w[0], a.policy.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);
   {
@@ -265,9 +167,7 @@ __global__ __launch_bounds__(kThreads) void ddqn_duel_act_kernel(const gymrl_dqn
     if (t < nrows) {
       float* q = lds + L.Mean + t * kMaxA;
       duel_combine(lds + L.Cq0 + t * 4, lds[L.Cq1 + t * 4], A, q);
-      const uint64_t counter = a.counter_dev ? a.counter_dev[0] : a.counter;
-      const float eps = a.epsilon_dev ? a.epsilon_dev[0] : a.epsilon;
-      act = epsilon_greedy_pick(q, A, a.u ? a.u + (size_t)(row0 + t) * 2 : nullptr, a.seed, (uint64_t)(a.env_id0 + row0 + t), counter, eps);
+      act = epsilon_greedy_lane(a, q, t, row0);
     }
     cartpole_act_tail(a, lds, L, t, row0, nrows, act);
   }
@@ -277,7 +177,7 @@ __global__ __launch_bounds__(kThreads) void ddqn_duel_act_kernel(const gymrl_dqn
 
 extern "C" {
 
-size_t gymrl_ddqn_update_workspace_bytes(int B, int D, int A, int H) { return workspace_bytes<DdqnWs>(B, D, A, H); }
+size_t gymrl_ddqn_update_workspace_bytes(int B, int D, int A, int H) { return workspace_bytes<QNet3Ws>(B, D, A, H); }
 size_t gymrl_ddqn_args_bytes(int which) { return which == 1 ? sizeof(gymrl_ddqn_update_args) : 0; }
 
 static int ddqn_set_lds_attr() {
@@ -300,7 +200,7 @@ int gymrl_ddqn_pack_images(const gymrl_ddqn_update_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_ddqn_update_args& a = *args;
   if (!pack_args_ok(a) || a.dueling || !all_set({a.policy.w[1], a.target.w[1]})) return -22;      // (the dueling net has no H x H layer)
-  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, DdqnImages::kCount), dim3(256), 0, (hipStream_t)stream_, DdqnImages::sources(a), a.images, a.H);
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, QNet3Images::kCount), dim3(256), 0, (hipStream_t)stream_, QNet3Images::sources(a), a.images, a.H);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
@@ -311,34 +211,12 @@ int gymrl_ddqn_update(const gymrl_ddqn_update_args* args, void* stream_) {
   if (!ddqn_update_args_ok(a)) return -22;
   hipStream_t stream = (hipStream_t)stream_;
   if (const int rc = ddqn_set_lds_attr()) return rc;
-  DdqnWs ws;
-  DdqnWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
-  const int B = a.B, D = a.D, A = a.A, H = a.H, slabs = (B + 15) / 16;
-  if (a.dueling) {
-    DwArgs p{};
-    DwBuilder pb{p, B};
-    pb.seg(ws.Z1, H, H, ws.s, D, nullptr, 0, D, D, a.policy.w[0], a.policy.b[0]);
-    pb.seg(ws.H2, 1, 1, ws.H1, H, nullptr, 0, H, H, a.policy.w[1], a.policy.b[1]);              // the value head: dv [B][1]
-    pb.seg(ws.dq, A, A, ws.H1, H, nullptr, 0, H, H, a.policy.w[2], a.policy.b[2]);              // the advantage head: da [B][A]
-    pb.close(a, nullptr, a.policy_p, a.policy_m, a.policy_v, a.adam_policy, a.adam_policy_dev, 0.0f, 0.0f, ws.terms, nullptr, 0, 1, a.loss_sum);
-    p.clamp_abs = a.clamp_abs;
-    hipLaunchKernelGGL(H == 256 ? ddqn_duel_r1_kernel<256> : ddqn_duel_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, 3), stream, a, ws);
-    launch_dw(p, stream);
-    GYMRL_CHECK_LAUNCH();
-    return 0;
-  }
-  const DdqnImages im(a.images, H);
-  // the policy net's tile list, as gymrl_dqn_update's: no target twins, the clamp in front of Adam's moments
-  DwArgs p{};
-  DwBuilder pb{p, B};
-  pb.seg(ws.Z1, H, H, ws.s, D, nullptr, 0, D, D, a.policy.w[0], a.policy.b[0]);
-  pb.seg(ws.Z2, H, H, ws.H1, H, nullptr, 0, H, H, a.policy.w[1], a.policy.b[1], nullptr, nullptr, im.pf, im.pb);
-  pb.seg(ws.dq, A, A, ws.H2, H, nullptr, 0, H, H, a.policy.w[2], a.policy.b[2]);
-  // (at most 256 rows: no slice partials, and the loss sum closes in this launch's last block — dqn_td_kernel's one block)
-  pb.close(a, nullptr, a.policy_p, a.policy_m, a.policy_v, a.adam_policy, a.adam_policy_dev, 0.0f, 0.0f, ws.terms, nullptr, 0, 1, a.loss_sum);
-  p.clamp_abs = a.clamp_abs;
-  hipLaunchKernelGGL(H == 256 ? ddqn_r1_kernel<256> : ddqn_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, kDdqnSlabs), stream, a, ws);
-  launch_dw(p, stream);
+  QNet3Ws ws;
+  QNet3Ws::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
+  const int H = a.H, slabs = (a.B + 15) / 16;
+  if (a.dueling) hipLaunchKernelGGL(H == 256 ? ddqn_duel_r1_kernel<256> : ddqn_duel_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, 3), stream, a, ws);
+  else hipLaunchKernelGGL(H == 256 ? ddqn_r1_kernel<256> : ddqn_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, kDdqnSlabs), stream, a, ws);
+  launch_qnet3_dw(a, ws, a.dueling != 0, stream);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

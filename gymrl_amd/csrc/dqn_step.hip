@@ -10,8 +10,7 @@
 // reference's clamp of every gradient element to +-1 (:163-165) as DwArgs.clamp_abs.  ONE workgroup carries a slab through the
 // whole row phase — policy(s) and target(s') ride along as items of the same stages — so nothing here waits for another
 // workgroup: no flag, no counter; launch order on one stream is the only ordering.
-#include "policy_device.hpp"
-#include "slab_step_device.hpp"
+#include "value_step_device.hpp"
 
 namespace {
 
@@ -19,38 +18,11 @@ using namespace gymrl;
 using namespace gymrl::slab;
 
 constexpr int kDqnMaxBatch = 256;      // (ops.DQN_FUSED_MAX_BATCH) one grid of at most 16 slabs in the row phase: the loss sum is one block's
-struct DqnImages {                     // gymrl_dqn_update_args.images, f32[3][H*H]: two forward images, then the input-gradient image
-  const float *pf, *tf, *pb;
-  __host__ __device__ DqnImages(const float* base, int H) {
-    const ImageSlots at(base, H);
-    pf = at(0); tf = at(1); pb = at(2);
-  }
-  static constexpr int kCount = 3;
-  static PackTable sources(const gymrl_dqn_update_args& a) {
-    return PackTable{{a.policy.w[1], a.target.w[1], a.policy.w[1], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 2};
-  }
-};
-
-// hand-off between the row phase and the tile phase (caller-owned workspace)
-struct DqnWs {
-  float* s;                            // [B][D]: the gathered states
-  float *H1, *Z1, *H2, *Z2, *dq;       // the policy net's activations and dL/dz per layer ([B][H]; dq [B][A])
-  double* terms;                       // [B][3]: the row's td^2 in column 0 (sac_dw_body's row pitch)
-  __host__ __device__ static size_t carve(DqnWs* w, void* base, int B, int D, int A, int H) {
-    carve_taker take{base};
-    float* s = take((size_t)B * D);
-    float* h[4];
-    for (int i = 0; i < 4; ++i) h[i] = take((size_t)B * H);
-    float* dq = take((size_t)B * A);
-    double* terms = reinterpret_cast<double*>(take((size_t)B * 6));
-    if (w) { w->s = s; w->H1 = h[0]; w->Z1 = h[1]; w->H2 = h[2]; w->Z2 = h[3]; w->dq = dq; w->terms = terms; }
-    return take.off;
-  }
-};
+// (gymrl_dqn_update_args.images and the workspace: QNet3Images / QNet3Ws of value_step_device.hpp)
 
 // ---- R1: draw + gather, policy(s) next to target(s'), the TD target and the loss gradient, the policy net's dX chain ----
 template <int HC>
-__global__ __launch_bounds__(kThreads) void dqn_r1_kernel(const gymrl_dqn_update_args a, const DqnWs ws) {
+__global__ __launch_bounds__(kThreads) void dqn_r1_kernel(const gymrl_dqn_update_args a, const QNet3Ws ws) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds L;
   const int D = a.D, A = a.A, H = HC ? HC : a.H, ld = lin::slab_ld(H);
@@ -60,22 +32,13 @@ __global__ __launch_bounds__(kThreads) void dqn_r1_kernel(const gymrl_dqn_update
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
   const int t = threadIdx.x;
   const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
-  const DqnImages im(a.images, H);
+  const QNet3Images im(a.images, H);
   const gymrl_td3_actor_params &p = a.policy, &tg = a.target;
   // ---- index draw + ring gather: one thread per row, rows beyond the batch are zero ----
   if (t < 16) {
     const int b = row0 + t;
-    const bool ok = t < nrows;
-    const int64_t row = ok ? replay_draw_row(a, b) : 0;
-    for (int k = 0; k < kMaxD; ++k) {
-      const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
-      lds[L.S + t * kMaxD + k] = sv;
-      lds[L.S2 + t * kMaxD + k] = (ok && k < D) ? a.r_next[row * D + k] : 0.0f;
-      if (ok && k < D) ws.s[(size_t)b * D + k] = sv;
-    }
-    lds[L.Misc + t * 4 + 0] = ok ? a.r_reward[row] : 0.0f;
-    lds[L.Misc + t * 4 + 1] = ok ? (float)a.r_flag[row] : 0.0f;            // dones become float32
-    lds[L.Misc + t * 4 + 2] = ok ? __int_as_float((int)a.r_action[row]) : 0.0f;
+    const int64_t row = t < nrows ? replay_draw_row(a, b) : -1;       // (not checked against the ring: `checked` below)
+    gather_ring_row(a, lds, L, t, b, t < nrows, row, /*checked=*/false, ws.s);
   }
   __syncthreads();
   // ---- policy_net(s) (:150) and target_net(s') (:154): two independent chains, layer by layer ----
@@ -98,21 +61,14 @@ __global__ __launch_bounds__(kThreads) void dqn_r1_kernel(const gymrl_dqn_update
   }
   __syncthreads();
   if (t < 16) {                           // offpolicy.hip dqn_td_kernel (:155-161) with qn_online == nullptr, w == nullptr, gamma_n = gamma
-    const float* sel = lds + L.Q0 + t * 4;
-    int astar = 0;
-    float best = sel[0];
-    for (int k = 1; k < A; ++k) if (sel[k] > best) { best = sel[k]; astar = k; }
-    const float nq = sel[astar];
-    const float y = lds[L.Misc + t * 4 + 0] + a.gamma * nq * (1.0f - lds[L.Misc + t * 4 + 1]);
-    const int act = __float_as_int(lds[L.Misc + t * 4 + 2]);
-    const float td = lds[L.Cq0 + t * 4 + act] - y;
-    const float wb = 1.0f, invB = 1.0f / (float)a.B;
+    const float* qt = lds + L.Q0 + t * 4;       // (the target row picks a* itself)
+    float td, dq[4];
+    const float term = td_row<false>(lds + L.Cq0 + t * 4, qt, qt, A, lds + L.Misc + t * 4, a.gamma, 1.0f, 1.0f / (float)a.B, td, dq);
     for (int k = 0; k < 4; ++k) {
-      const float d = k == act ? (2.0f * td) * wb * invB : 0.0f;
-      lds[L.Dq0 + t * 4 + k] = d;
-      if (t < nrows && k < A) ws.dq[(size_t)(row0 + t) * A + k] = d;
+      lds[L.Dq0 + t * 4 + k] = dq[k];
+      if (t < nrows && k < A) ws.dq[(size_t)(row0 + t) * A + k] = dq[k];
     }
-    if (t < nrows) ws.terms[(size_t)(row0 + t) * 3] = (double)((td * td) * wb);
+    if (t < nrows) ws.terms[(size_t)(row0 + t) * 3] = (double)term;
   }
   __syncthreads();
   // ---- the policy net's input-gradient chain (what backward() computes before the weight gradients) ----
@@ -130,11 +86,7 @@ __global__ __launch_bounds__(kThreads) void dqn_act_kernel(const gymrl_dqn_act_a
   const int X0 = L.big, X1 = X0 + 16 * ld;
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.N - row0);
   const int t = threadIdx.x;
-  if (t < 16) {
-    const int i = row0 + t;
-    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = (t < nrows && k < D) ? a.obs[(size_t)i * D + k] : 0.0f;
-  }
-  __syncthreads();
+  act_load_obs(a, lds, L, t, row0, nrows);
   const int R = GYMRL_ACT_RELU, kD = kMaxD, kA = kMaxA;
   const float* pf = (a.images && (H & 15) == 0) ? a.images : nullptr;
   fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.policy.w[0], a.policy.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);
@@ -143,12 +95,7 @@ __global__ __launch_bounds__(kThreads) void dqn_act_kernel(const gymrl_dqn_act_a
   // one lane per env: the choice, the env's step with auto-reset, replay row (the first wave: 16 lanes busy)
   if (t < 64) {
     int act = 0;
-    if (t < nrows) {
-      const uint64_t counter = a.counter_dev ? a.counter_dev[0] : a.counter;
-      const float eps = a.epsilon_dev ? a.epsilon_dev[0] : a.epsilon;
-      act = epsilon_greedy_pick(lds + L.Mean + t * kMaxA, A, a.u ? a.u + (size_t)(row0 + t) * 2 : nullptr, a.seed,
-                                (uint64_t)(a.env_id0 + row0 + t), counter, eps);
-    }
+    if (t < nrows) act = epsilon_greedy_lane(a, lds + L.Mean + t * kMaxA, t, row0);
     classic_act_tail<KIND>(a, lds, L, t, row0, nrows, act);
   }
 }
@@ -169,7 +116,7 @@ DqnActKernel dqn_act_pick(int env_kind, bool wide) {
 
 extern "C" {
 
-size_t gymrl_dqn_update_workspace_bytes(int B, int D, int A, int H) { return workspace_bytes<DqnWs>(B, D, A, H); }
+size_t gymrl_dqn_update_workspace_bytes(int B, int D, int A, int H) { return workspace_bytes<QNet3Ws>(B, D, A, H); }
 size_t gymrl_dqn_args_bytes(int which) { return which == 0 ? sizeof(gymrl_dqn_act_args) : which == 1 ? sizeof(gymrl_dqn_update_args) : 0; }
 
 static int dqn_set_lds_attr() {
@@ -219,7 +166,7 @@ int gymrl_dqn_pack_images(const gymrl_dqn_update_args* args, void* stream_) {
   if (!args) return -22;
   const gymrl_dqn_update_args& a = *args;
   if (!pack_args_ok(a) || !all_set({a.policy.w[1], a.target.w[1]})) return -22;
-  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, DqnImages::kCount), dim3(256), 0, (hipStream_t)stream_, DqnImages::sources(a), a.images, a.H);
+  hipLaunchKernelGGL(pack_images_kernel, dim3((a.H * a.H + 255) / 256, QNet3Images::kCount), dim3(256), 0, (hipStream_t)stream_, QNet3Images::sources(a), a.images, a.H);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }
@@ -230,21 +177,10 @@ int gymrl_dqn_update(const gymrl_dqn_update_args* args, void* stream_) {
   if (!dqn_update_args_ok(a)) return -22;
   hipStream_t stream = (hipStream_t)stream_;
   if (const int rc = dqn_set_lds_attr()) return rc;
-  DqnWs ws;
-  DqnWs::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
-  const int B = a.B, D = a.D, A = a.A, H = a.H, slabs = (B + 15) / 16;
-  const DqnImages im(a.images, H);
-  // the policy net's tile list: no target twins (the hard copy is the caller's), the clamp in front of Adam's moments
-  DwArgs p{};
-  DwBuilder pb{p, B};
-  pb.seg(ws.Z1, H, H, ws.s, D, nullptr, 0, D, D, a.policy.w[0], a.policy.b[0]);
-  pb.seg(ws.Z2, H, H, ws.H1, H, nullptr, 0, H, H, a.policy.w[1], a.policy.b[1], nullptr, nullptr, im.pf, im.pb);
-  pb.seg(ws.dq, A, A, ws.H2, H, nullptr, 0, H, H, a.policy.w[2], a.policy.b[2]);
-  // (at most 256 rows: no slice partials, and the loss sum closes in this launch's last block — dqn_td_kernel's one block)
-  pb.close(a, nullptr, a.policy_p, a.policy_m, a.policy_v, a.adam_policy, a.adam_policy_dev, 0.0f, 0.0f, ws.terms, nullptr, 0, 1, a.loss_sum);
-  p.clamp_abs = a.clamp_abs;
-  hipLaunchKernelGGL(H == 256 ? dqn_r1_kernel<256> : dqn_r1_kernel<0>, dim3(slabs), dim3(kThreads), lds_bytes(H, 4), stream, a, ws);
-  launch_dw(p, stream);
+  QNet3Ws ws;
+  QNet3Ws::carve(&ws, align256(a.workspace), a.B, a.D, a.A, a.H);
+  hipLaunchKernelGGL(a.H == 256 ? dqn_r1_kernel<256> : dqn_r1_kernel<0>, dim3((a.B + 15) / 16), dim3(kThreads), lds_bytes(a.H, 4), stream, a, ws);
+  launch_qnet3_dw(a, ws, /*dueling=*/false, stream);
   GYMRL_CHECK_LAUNCH();
   return 0;
 }

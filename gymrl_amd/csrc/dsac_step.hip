@@ -11,9 +11,8 @@
 // expressions) in place of a sampled action, twin critics that are separate modules with separate optimisers, no actor
 // target, and the actor phase on every step.  ONE workgroup carries a slab through a whole row phase — the independent
 // chains ride along as items of the same stages — so nothing here waits for another workgroup: no flag, no counter.
-#include "policy_device.hpp"
-#include "slab_step_device.hpp"
 #include "softmax_device.hpp"
+#include "value_step_device.hpp"
 
 namespace {
 
@@ -73,6 +72,8 @@ __global__ __launch_bounds__(kThreads) void dsac_r1_kernel(const gymrl_dsac_upda
   const DsacImages im(a.images, H);
   const gymrl_td3_actor_params &p = a.actor, &c1 = a.critic1, &c2 = a.critic2, &t1 = a.critic1_target, &t2 = a.critic2_target;
   // ---- index draw + ring gather: one thread per row, rows beyond the batch are zero ----
+  // (value_step_device.hpp gather_ring_row with an unchecked row and no weight is this text; called from here this kernel's
+  // registers came out differently and the N = 64 step measured 0.4 % outside the parent's range, so the text stays)
   if (t < 16) {
     const int b = row0 + t;
     const bool ok = t < nrows;
@@ -266,11 +267,7 @@ __global__ __launch_bounds__(kThreads) void dsac_act_kernel(const gymrl_dsac_act
   const int X0 = L.big, X1 = X0 + 16 * ld;
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.N - row0);
   const int t = threadIdx.x;
-  if (t < 16) {
-    const int i = row0 + t;
-    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = (t < nrows && k < D) ? a.obs[(size_t)i * D + k] : 0.0f;
-  }
-  __syncthreads();
+  act_load_obs(a, lds, L, t, row0, nrows);
   const int R = GYMRL_ACT_RELU, kD = kMaxD, kA = kMaxA;
   const float* af = (a.images && (H & 15) == 0) ? a.images : nullptr;
   fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, a.actor.w[0], a.actor.b[0], X0, ld, nullptr, 0, R)}, row0, nrows);

@@ -25,9 +25,7 @@
 // two heads' input gradients; T1 is dead after fc2 and carries dL/dz2.  At H = 64 (slab_ld = 68): 6 * 16 * 68 * 4 = 26,112 B +
 // 4,096 B = 30,208 B; at H = 256: 103,936 B (one workgroup per compute unit; the grid is at most 16 workgroups).
 // ndqn_act_kernel: two slabs, 12,800 B at H = 64.  fc2 is read from the combine's workspace: no weight images here.
-#include "duel_device.hpp"
-#include "policy_device.hpp"
-#include "slab_step_device.hpp"
+#include "value_step_device.hpp"
 
 namespace {
 
@@ -120,11 +118,7 @@ __global__ __launch_bounds__(kThreads) void ndqn_act_kernel(const gymrl_ndqn_act
   const int X0 = L.big, X1 = X0 + 16 * ld;
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.N - row0);
   const int t = threadIdx.x;
-  if (t < 16) {
-    const int i = row0 + t;
-    for (int k = 0; k < kMaxD; ++k) lds[L.S + t * kMaxD + k] = (t < nrows && k < D) ? a.obs[(size_t)i * D + k] : 0.0f;
-  }
-  __syncthreads();
+  act_load_obs(a, lds, L, t, row0, nrows);
   const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
   fwd_one(lds, {fwd_item(L.S, kD, -1, 0, D, D, H, ws.w[0][0], ws.b[0][0], X0, ld, nullptr, 0, R)}, row0, nrows);
   fwd_one(lds, {fwd_item(X0, ld, -1, 0, H, H, H, ws.w[0][1], ws.b[0][1], X1, ld, nullptr, 0, R)}, row0, nrows);
@@ -146,39 +140,21 @@ __global__ __launch_bounds__(kThreads) void ndqn_act_kernel(const gymrl_ndqn_act
   }
 }
 
-// The ring row of batch element b, or -1: beyond the batch, or an index outside [0, cap) — such a row is never read: it enters
-// the batch as zeros and carries no gradient (ddqn_step.hip ddqn_row).
-__device__ __forceinline__ int64_t ndqn_row(const gymrl_ndqn_update_args& a, int b, bool in_batch) {
-  if (!in_batch) return -1;
-  const int64_t row = replay_draw_row(a, b);
-  return (row >= 0 && row < a.cap) ? row : -1;
-}
-
 __global__ __launch_bounds__(kThreads) void ndqn_r1_kernel(const gymrl_ndqn_update_args a, const NdqnWs ws) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const Lds L;
   const int D = a.D, A = a.A, H = a.H, ld = lin::slab_ld(H);
   const int P1 = L.big, N1 = P1 + 16 * ld, T1 = N1 + 16 * ld, P2 = T1 + 16 * ld, N2 = P2 + 16 * ld, T2 = N2 + 16 * ld;
-  const int Xv = N2, Xa = T2, Z0 = T1;
+  const int Z0 = T1;
   const int bx = blockIdx.x, row0 = bx * 16, nrows = min(16, a.B - row0);
   const int t = threadIdx.x;
-  const int R = GYMRL_ACT_RELU, NA = GYMRL_ACT_NONE, kD = kMaxD;
+  const int R = GYMRL_ACT_RELU, kD = kMaxD;
   const gymrl_ndqn_params& tg = a.target;
   // ---- index draw + ring gather: one thread per row, rows beyond the batch or outside the ring are zero ----
   if (t < 16) {
     const int b = row0 + t;
-    const int64_t row = ndqn_row(a, b, t < nrows);
-    const bool ok = row >= 0;
-    for (int k = 0; k < kMaxD; ++k) {
-      const float sv = (ok && k < D) ? a.r_state[row * D + k] : 0.0f;
-      lds[L.S + t * kMaxD + k] = sv;
-      lds[L.S2 + t * kMaxD + k] = (ok && k < D) ? a.r_next[row * D + k] : 0.0f;
-      if (t < nrows && k < D) ws.s[(size_t)b * D + k] = sv;
-    }
-    lds[L.Misc + t * 4 + 0] = ok ? a.r_reward[row] : 0.0f;
-    lds[L.Misc + t * 4 + 1] = ok ? (float)a.r_flag[row] : 0.0f;            // dones become float32
-    lds[L.Misc + t * 4 + 2] = ok ? __int_as_float((int)a.r_action[row]) : 0.0f;
-    lds[L.Misc + t * 4 + 3] = ok ? 1.0f : 0.0f;
+    const int64_t row = checked_ring_row(t < nrows, [&] { return replay_draw_row(a, b); }, a.cap);
+    gather_ring_row(a, lds, L, t, b, t < nrows, row, /*checked=*/true, ws.s, RowWeight::kUnit);
   }
   __syncthreads();
   // ---- policy_net(s) on set A, policy_net(s') on set B, target_net(s') on the target's mu: three chains, layer by layer ----
@@ -196,57 +172,12 @@ __global__ __launch_bounds__(kThreads) void ndqn_r1_kernel(const gymrl_ndqn_upda
     fwd_stage<3>(lds, st, row0, nrows);
   }
   __syncthreads();
-  {                                       // value (1 column) and advantage (A columns) of every chain: six items of one stage
-    const FwdItem st[6] = {fwd_item(P2, ld, -1, 0, H, H, 1, ws.w[1][2], ws.b[1][2], L.Cq1, 4, nullptr, 0, NA),
-                           fwd_item(P2, ld, -1, 0, H, H, A, ws.w[1][3], ws.b[1][3], L.Cq0, 4, nullptr, 0, NA),
-                           fwd_item(N2, ld, -1, 0, H, H, 1, ws.w[2][2], ws.b[2][2], L.Dq1, 4, nullptr, 0, NA),
-                           fwd_item(N2, ld, -1, 0, H, H, A, ws.w[2][3], ws.b[2][3], L.Q1, 4, nullptr, 0, NA),
-                           fwd_item(T2, ld, -1, 0, H, H, 1, tg.w_mu[2], tg.b_mu[2], L.Mean, 4, nullptr, 0, NA),
-                           fwd_item(T2, ld, -1, 0, H, H, A, tg.w_mu[3], tg.b_mu[3], L.Q0, 4, nullptr, 0, NA)};
-    fwd_stage<6>(lds, st, row0, nrows);
-  }
-  __syncthreads();
-  if (t < 16) {                           // the three combines, then dqn_td_kernel with qn_online set and no weights, then the combine's backward
-    float q[4], qo[4], qt[4];
-    duel_combine(lds + L.Cq0 + t * 4, lds[L.Cq1 + t * 4], A, q);
-    duel_combine(lds + L.Q1 + t * 4, lds[L.Dq1 + t * 4], A, qo);
-    duel_combine(lds + L.Q0 + t * 4, lds[L.Mean + t * 4], A, qt);
-    int astar = 0;
-    float best = qo[0];
-    for (int k = 1; k < A; ++k) if (qo[k] > best) { best = qo[k]; astar = k; }
-    float nq = qt[0], qa = q[0];
-    const int act = __float_as_int(lds[L.Misc + t * 4 + 2]);
-    for (int k = 1; k < A; ++k) { if (k == astar) nq = qt[k]; if (k == act) qa = q[k]; }
-    const float y = lds[L.Misc + t * 4 + 0] + a.gamma * nq * (1.0f - lds[L.Misc + t * 4 + 1]);
-    const float td = qa - y;
-    const float wb = lds[L.Misc + t * 4 + 3], invB = 1.0f / (float)a.B;
-    float dq[4], da[4], dv;
-    for (int k = 0; k < 4; ++k) dq[k] = k == act ? (2.0f * td) * wb * invB : 0.0f;
-    duel_combine_bwd(dq, A, da, dv);
-    for (int k = 0; k < 4; ++k) {
-      lds[L.Dq0 + t * 4 + k] = k < A ? da[k] : 0.0f;
-      lds[L.Dq1 + t * 4 + k] = k == 0 ? dv : 0.0f;
-      if (t < nrows && k < A) ws.da[(size_t)(row0 + t) * A + k] = da[k];
-    }
-    if (t < nrows) {
-      ws.dv[row0 + t] = dv;
-      ws.terms[(size_t)(row0 + t) * 3] = (double)((td * td) * wb);
-    }
-  }
-  __syncthreads();
-  // ---- set A's input-gradient chain: each head's dX on its own, autograd's sum of the two under fc2's ReLU derivative, then fc2's ----
-  {
-    const BwdItem st[2] = {BwdItem{L.Dq1, 4, 1, ws.w[1][2], H, -1, nullptr, -1, 0, NA, Xv, ld, nullptr, 0, nullptr},
-                           BwdItem{L.Dq0, 4, A, ws.w[1][3], H, -1, nullptr, -1, 0, NA, Xa, ld, nullptr, 0, nullptr}};
-    bwd_stage<2>(lds, st, row0, nrows);
-  }
-  __syncthreads();
-  for (int e = t; e < 16 * H; e += kThreads) {
-    const int row = e / H, k = e - row * H;
-    const float g = (lds[Xv + row * ld + k] + lds[Xa + row * ld + k]) * act_bwd(lds[P2 + row * ld + k], R, 0.0f, 0.0f);
-    lds[Z0 + row * ld + k] = g;
-    if (row < nrows) ws.Z2[(size_t)(row0 + row) * H + k] = g;
-  }
+  // the heads, the loss (dqn_td_kernel with qn_online set and no weights: a live row weighs 1) and set A's input-gradient chain:
+  // N2 and T2 take the two heads' input gradients, their sum under fc2's ReLU derivative goes to ws.Z2 and to Z0 for fc2's own dX
+  const DuelHeads hp[3] = {{ws.w[1][2], ws.b[1][2], ws.w[1][3], ws.b[1][3]}, {ws.w[2][2], ws.b[2][2], ws.w[2][3], ws.b[2][3]},
+                           {tg.w_mu[2], tg.b_mu[2], tg.w_mu[3], tg.b_mu[3]}};
+  duel_heads_segment(lds, L, A, H, ld, row0, nrows, a.gamma, a.B, {P2, N2, T2}, hp, /*Xv=*/N2, /*Xa=*/T2, ws.dv, ws.da, /*td_out=*/nullptr,
+                     ws.terms, /*Zs=*/Z0, ws.Z2);
   __syncthreads();
   bwd_stage(lds, {BwdItem{Z0, ld, H, ws.w[1][1], H, -1, nullptr, P1, ld, R, -1, 0, ws.Z1, H, nullptr}}, row0, nrows);      // (the last stage: no barrier behind it)
 }

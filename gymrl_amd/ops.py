@@ -3058,11 +3058,44 @@ def dqn_fused_shape_ok(B, D, A, H):
     return _fused_shape_ok(B, D, A, H, DQN_FUSED_MAX_BATCH, 4)
 
 
-class _QLayers:
-    """dqn_cartpole.QNetwork's three Linear layers (net.0, net.2, net.4) under the names the shared helpers read."""
+class _Layers3:
+    """Three Linear layers under the names the shared helpers read: dqn_cartpole.QNetwork's (net.0, net.2, net.4), or a tuple
+    (fc1, fc2, fc3) — the dueling net's (fc1, value_stream, advantage_stream) in gymrl_ddqn_update_args' slots."""
 
-    def __init__(self, qnet):
-        self.fc1, self.fc2, self.fc3 = qnet.net[0], qnet.net[2], qnet.net[4]
+    def __init__(self, net):
+        self.fc1, self.fc2, self.fc3 = (net.net[0], net.net[2], net.net[4]) if hasattr(net, "net") else net
+
+
+def _q_act_args(name, env, net, ring, cap, images):
+    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"{name}: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
+    a = DqnActArgs()
+    layers = _Layers3(net)
+    _set_act_env(a, env, layers, ring, cap, images)
+    _td3_actor_params(a.policy, layers)
+    return a
+
+
+def _q_update_args(make, name, B, D, A, fc1_width, opt, ring, gamma, loss_sum, workspace, td_out=None, set_cap=False):
+    """What the value learners' update blocks (gymrl_dqn / ddqn / ndqn_update_args) share: the checks — before the block is made
+    (make()) or a network is looked at (fc1_width()) —, the shapes, the ring (set_cap: its row count, where the kernel checks rows
+    against it), the policy net's optimiser and the addresses."""
+    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise ValueError(f"{name}: loss_sum must be a float64[1]")
+    if td_out is not None and (td_out.dtype != torch.float32 or td_out.numel() != B):
+        raise ValueError(f"{name}: td_out must be a float32 [{B}]")
+    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
+        raise ValueError(f"{name}: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
+    a = make()
+    a.B, a.D, a.A, a.H, a.gamma = B, D, A, fc1_width(), float(gamma)
+    if set_cap:
+        a.cap = ring[0].shape[0]
+    if td_out is not None:
+        a.td_out = _addr(td_out)
+    _set_ring(a, ring)
+    _set_optimisers(a, opt, policy=opt)
+    a.loss_sum, a.workspace = _addr(loss_sum), _addr(workspace)
+    return a
 
 
 def dqn_update_workspace(B, D, A, H, device):
@@ -3081,13 +3114,7 @@ def dqn_pack_images(a):
 
 def dqn_act_args(env, policy, ring, cap, images=None):
     """A gymrl_dqn_act_args with everything that does not change from step to step filled in."""
-    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
-        raise ValueError(f"dqn_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
-    a = DqnActArgs()
-    layers = _QLayers(policy)
-    _set_act_env(a, env, layers, ring, cap, images)
-    _td3_actor_params(a.policy, layers)
-    return a
+    return _q_act_args("dqn_act_args", env, policy, ring, cap, images)
 
 
 def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, cursor_dev=None, u=None, seed=0, counter=0,
@@ -3114,20 +3141,11 @@ def dqn_act_step(a, env, obs, obs_out, epsilon=0.0, epsilon_dev=None, cursor=0, 
 def dqn_update_args(B, D, A, policy, target, opt, ring, gamma, loss_sum, workspace, images=None):
     """A gymrl_dqn_update_args with the per-trainer constants filled in.  opt: the policy net's FusedAdam (its clamp_abs is the
     update's); loss_sum: f64[1] (sum of td^2)."""
-    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
-        raise ValueError("dqn_update_args: loss_sum must be a float64[1]")
-    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
-        raise ValueError(f"dqn_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
-    a = DqnUpdateArgs()
-    p, t = _QLayers(policy), _QLayers(target)
-    a.B, a.D, a.A, a.H = B, D, A, p.fc1.weight.shape[0]
-    a.gamma = float(gamma)
-    _set_ring(a, ring)
-    _td3_actor_params(a.policy, p)
-    _td3_actor_params(a.target, t)
-    _set_optimisers(a, opt, policy=opt)
-    a.clamp_abs = float(opt.clamp_abs)
-    a.loss_sum, a.workspace, a.images = _addr(loss_sum), _addr(workspace), _addr(images)
+    a = _q_update_args(DqnUpdateArgs, "dqn_update_args", B, D, A, lambda: _Layers3(policy).fc1.weight.shape[0], opt, ring, gamma, loss_sum,
+                       workspace)
+    _td3_actor_params(a.policy, _Layers3(policy))
+    _td3_actor_params(a.target, _Layers3(target))
+    a.clamp_abs, a.images = float(opt.clamp_abs), _addr(images)
     return a
 
 
@@ -3160,24 +3178,10 @@ def ddqn_pack_images(a):
     check(lib().gymrl_ddqn_pack_images(C.byref(a), _stream()), "gymrl_ddqn_pack_images")
 
 
-class _Layers3:
-    """Three Linear layers under the names the shared helpers read: (fc1, fc2, fc3), or the dueling net's (fc1, value_stream,
-    advantage_stream) in gymrl_ddqn_update_args' slots."""
-
-    def __init__(self, layers):
-        self.fc1, self.fc2, self.fc3 = layers
-
-
 def ddqn_act_args(env, layers, ring, cap, images=None):
     """A gymrl_dqn_act_args for gymrl_dqn_act_step (layers = fc1, fc2, fc3) or gymrl_ddqn_duel_act_step (fc1, value_stream,
     advantage_stream; no images)."""
-    if tuple(ring[0].shape[1:]) != (env.obs_dim,) or tuple(ring[1].shape[1:]) != (1,):
-        raise ValueError(f"ddqn_act_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)} do not fit the env")
-    a = DqnActArgs()
-    layers = _Layers3(layers)
-    _set_act_env(a, env, layers, ring, cap, images)
-    _td3_actor_params(a.policy, layers)
-    return a
+    return _q_act_args("ddqn_act_args", env, layers, ring, cap, images)
 
 
 def ddqn_duel_act_step(a, env, obs, obs_out, **kw):
@@ -3189,22 +3193,11 @@ def ddqn_update_args(B, D, A, policy_layers, target_layers, opt, ring, gamma, td
     """A gymrl_ddqn_update_args with the per-trainer constants filled in.  policy_layers / target_layers: (fc1, fc2, fc3), or
     with dueling (fc1, value_stream, advantage_stream); opt: the policy net's FusedAdam (its clamp_abs is the update's);
     td_out: f32[B]; loss_sum: f64[1] (sum of td^2 * w)."""
-    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
-        raise ValueError("ddqn_update_args: loss_sum must be a float64[1]")
-    if td_out.dtype != torch.float32 or td_out.numel() != B:
-        raise ValueError(f"ddqn_update_args: td_out must be a float32 [{B}]")
-    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
-        raise ValueError(f"ddqn_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
-    a = DdqnUpdateArgs()
-    p, t = _Layers3(policy_layers), _Layers3(target_layers)
-    a.B, a.D, a.A, a.H, a.dueling = B, D, A, p.fc1.weight.shape[0], int(dueling)
-    a.gamma, a.cap = float(gamma), ring[0].shape[0]
-    _set_ring(a, ring)
-    _td3_actor_params(a.policy, p)
-    _td3_actor_params(a.target, t)
-    _set_optimisers(a, opt, policy=opt)
-    a.clamp_abs = float(opt.clamp_abs)
-    a.td_out, a.loss_sum, a.workspace, a.images = _addr(td_out), _addr(loss_sum), _addr(workspace), _addr(None if dueling else images)
+    a = _q_update_args(DdqnUpdateArgs, "ddqn_update_args", B, D, A, lambda: _Layers3(policy_layers).fc1.weight.shape[0], opt, ring, gamma,
+                       loss_sum, workspace, td_out=td_out, set_cap=True)
+    _td3_actor_params(a.policy, _Layers3(policy_layers))
+    _td3_actor_params(a.target, _Layers3(target_layers))
+    a.dueling, a.clamp_abs, a.images = int(dueling), float(opt.clamp_abs), _addr(None if dueling else images)
     return a
 
 
@@ -3367,18 +3360,10 @@ def ndqn_act_step(a, env, obs, obs_out, cursor=0, cursor_dev=None, action_out=No
 
 def ndqn_update_args(B, D, A, policy, target, opt, ring, gamma, loss_sum, workspace):
     """A gymrl_ndqn_update_args with the per-trainer constants filled in.  opt: the policy net's FusedAdam; loss_sum: f64[1]."""
-    if loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
-        raise ValueError("ndqn_update_args: loss_sum must be a float64[1]")
-    if tuple(ring[0].shape[1:]) != (D,) or tuple(ring[1].shape[1:]) != (1,):
-        raise ValueError(f"ndqn_update_args: ring rows {tuple(ring[0].shape)} / {tuple(ring[1].shape)}, expected [.., {D}] / [.., 1]")
-    a = NdqnUpdateArgs()
-    a.B, a.D, a.A, a.H = B, D, A, policy.fc1.out_features
-    a.gamma, a.cap = float(gamma), ring[0].shape[0]
-    _set_ring(a, ring)
+    a = _q_update_args(NdqnUpdateArgs, "ndqn_update_args", B, D, A, lambda: policy.fc1.out_features, opt, ring, gamma, loss_sum, workspace,
+                       set_cap=True)
     _ndqn_params(a.policy, policy)
     _ndqn_params(a.target, target)
-    _set_optimisers(a, opt, policy=opt)
-    a.loss_sum, a.workspace = _addr(loss_sum), _addr(workspace)
     return a
 
 

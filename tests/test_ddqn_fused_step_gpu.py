@@ -227,3 +227,48 @@ def test_images_change_where_a_value_is_read_not_the_value():
     ops.ddqn_pack_images(b._fused[1])
     torch.cuda.synchronize()
     assert torch.equal(before, b._fused[4]) and before.abs().sum().item() > 0
+
+
+@pytest.mark.parametrize("duel", [False, True])
+def test_a_row_outside_the_ring_is_a_zero_row_of_weight_zero(duel):
+    """ops.ddqn_update's "a row outside the ring is not read: it counts as a zero row of weight 0", which the trainer never
+    reaches (it refuses such rows on the host).  Update X carries idx = cap, -1 and 2^31 - 1 under weight 0.7; update Y, from
+    the same parameters, moments and target, carries at those places a ring row that IS all zeros, under weight 0: parameters,
+    moments, td_out and the loss sum equal bit for bit.  B = 17: two slabs, the second with one live row (an outside one)."""
+    from gymrl_amd import ops
+    B, H, D, A, cap, r0 = 17, 32, 4, 2, 64, 41
+    tr = _trainer(16, B, H, cap, True, duel=duel)
+    dev = tr.device
+    g = torch.Generator(device="cuda").manual_seed(23)
+    rnd = lambda *shape: torch.randn(*shape, generator=g, device=dev)  # noqa: E731
+    state, action, reward, nxt, flag = tr.memory.ring
+    state.copy_(rnd(cap, D)), nxt.copy_(rnd(cap, D)), reward.copy_(rnd(cap))
+    action.copy_((rnd(cap, 1) > 0).to(action.dtype)), flag.copy_((rnd(cap) > 1).to(flag.dtype))
+    for t in (state, action, reward, nxt, flag):
+        t[r0] = 0
+    tr.target_flat.add_(0.05 * rnd(tr.target_flat.numel()))
+    tr.optimizer.m.copy_(0.01 * rnd(tr.optimizer.m.numel())), tr.optimizer.v.copy_((0.01 * rnd(tr.optimizer.v.numel())) ** 2)
+    start = [t.clone() for t in (tr.flat_params, tr.target_flat, tr.optimizer.m, tr.optimizer.v)]
+    rows = torch.randint(0, cap, (B,), generator=g, device=dev, dtype=torch.int32)
+    weight = 0.5 + torch.rand(B, generator=g, device=dev)
+    outside = {3: cap, 16: -1, 9: 2 ** 31 - 1}
+
+    def update(values, w):
+        for dst, src in zip((tr.flat_params, tr.target_flat, tr.optimizer.m, tr.optimizer.v), start):
+            dst.copy_(src)
+        idx, isw = rows.clone(), weight.clone()
+        for b, row in values.items():
+            idx[b], isw[b] = row, w
+        td, loss = torch.full((B,), 9.0, device=dev), torch.full((1,), 9.0, dtype=torch.float64, device=dev)
+        ws = ops.ddqn_update_workspace(B, D, A, H, dev)
+        a = ops.ddqn_update_args(B, D, A, tr._layers(tr.policy_net), tr._layers(tr.target_net), tr.optimizer, tr.memory.ring, 0.9, td,
+                                 loss, ws, dueling=duel)
+        ops.ddqn_update(a, idx, isw, adam_policy=ops.adam_bias(1e-3, 0.9, 0.999, 1))
+        torch.cuda.synchronize()
+        return [tr.flat_params.clone(), tr.optimizer.m.clone(), tr.optimizer.v.clone(), td, loss]
+
+    x, y = update(outside, 0.7), update({b: r0 for b in outside}, 0.0)
+    for name, p, q in zip(("parameters", "m", "v", "td_out", "loss_sum"), x, y):
+        assert torch.equal(p, q), (name, p, q)
+    assert not torch.equal(x[0], start[0]) and bool((x[3] != 0).any()) and float(x[4]) > 0.0
+    assert torch.equal(tr.target_flat, start[1])
